@@ -1,6 +1,6 @@
 """Headline benchmark: output MPix/s of the FreqFusion x4 full 3-expert forward on 256x256 LR tiles.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either the driver launches one rank per GPU (torch.distributed.run: RANK / WORLD_SIZE set), or -- when called plainly --
 this script starts N fresh child ranks of itself before touching any GPU and relays rank 0's JSON line.
@@ -11,6 +11,10 @@ shard them with NO data-path collective (weak scaling).  The only collective is 
 broadcast of the frozen weights from rank 0.  The steady state is replayed from a HIP graph (the
 eager Python launch loop is captured once), inputs are resident in HBM before the timed region.
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.
+--dump-outputs DIR: after the timed steps, the SR output of the last timed step (what a caller of the timed path receives) is
+written as DIR/sr.npy, float32 [1, 3, 4*tile, 4*tile] (12 MiB at the default tile; DIR/sr_rank<r>.npy per rank when N > 1).
+Above 64 MiB (--tile > 591) the file holds a fixed seeded sample of 16 Mi output values, flattened, in index order.
+Weights and tiles are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -32,6 +36,7 @@ MPIX_PER_TILE = (4 * TILE) ** 2 / 1e6
 PEAK_TF = {"f32": 157.3, "bf16": 2500.0, "bf16x2": 2500.0, "bf16x3": 2500.0}   # MI355X_MICROARCH.md dense MFMA peaks
 MFMA_PER_ALGO_FLOP = {"f32": 1, "bf16": 1, "bf16x2": 2, "bf16x3": 3}
 SEED = 1234
+DUMP_MAX_BYTES = 64 * 2 ** 20      # --dump-outputs cap
 
 
 def make_tile(seed: int, size: int = TILE) -> torch.Tensor:
@@ -261,7 +266,11 @@ def main():
                     help="contraction mode of the headline run.  BASELINE configs[1] names bf16: plain bf16 MFMA operands with fp32 "
                          "accumulation (68.8 dB against the reference's output; the line carries the PSNR-vs-ground-truth deltas); "
                          "bf16x3 = fp32-grade split-bf16 products (123 dB), the plugin's default; f32 = exact fp32 MFMA")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's SR output to DIR/sr.npy (float32; DIR/sr_rank<r>.npy per rank when --gpus > 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_spawn(args))
@@ -340,15 +349,17 @@ def main():
             lanes = 1
             torch.cuda.synchronize()
     nstep = [0]
+    last = [None]                                            # the output tensor of the latest step
 
     def step():
         if lanes == 2:                                       # step i on lane i & 1: step i+1 starts while step i drains
-            model.graphed_async(lr, nstep[0] & 1)
+            last[0] = model.graphed_async(lr, nstep[0] & 1)[0]
             nstep[0] += 1
         elif graph is not None:
             graph.replay()
+            last[0] = out
         else:
-            model(lr)
+            last[0] = model(lr)
 
     for _ in range(args.warmup):
         step()
@@ -369,6 +380,15 @@ def main():
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs:                                    # before any other pass can touch the step's output buffer
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump = os.path.join(args.dump_outputs, "sr.npy" if world == 1 else f"sr_rank{rank}.npy")
+        sr = last[0].detach().float().cpu().numpy()
+        if sr.nbytes > DUMP_MAX_BYTES:                       # large --tile: a fixed seeded sample of the output, same positions every run
+            idx = np.sort(np.random.default_rng(SEED).choice(sr.size, DUMP_MAX_BYTES // 4, replace=False))
+            sr = sr.reshape(-1)[idx]
+        np.save(dump, sr)
+        log(f"last step's output {tuple(last[0].shape)} written to {dump}")
 
     # ---- per-kernel-class accounting: one extra eager pass with HIP events around every launch ---------------
     roof, breakdown, stages = None, None, None

@@ -1,7 +1,6 @@
-"""Cached-expert feature format: files written by isr2_amd.cache against the reference's own reader
-(CachedSRDataset, loaded by file path when /root/reference is present -- build container only), and the HIP extractor against
+"""Cached-expert feature format: files written by isr2_amd.cache against what the reference's own reader
+(CachedSRDataset) was recorded to load and return (tests/golden/cache_reader_view.npz), and the HIP extractor against
 the reference's forward_all_with_hooks golden (tests/golden/hooks48.npz)."""
-import importlib.util
 import os
 
 import numpy as np
@@ -38,28 +37,45 @@ def test_cache_roundtrip_and_layout(tmp_path):
         cache.write_sample(str(tmp_path), "bad", lr, hr, {"hat": outs["hat"]}, feats)
 
 
+def _flatten(d, prefix):
+    out = {}
+    for k, v in d.items():
+        p = f"{prefix}/{k}"
+        if isinstance(v, dict):
+            out.update(_flatten(v, p))
+        else:
+            out[p] = v.numpy() if isinstance(v, torch.Tensor) else np.array(v)
+    return out
+
+
 def test_reference_reader_loads_our_files(tmp_path):
     """The reference's CachedSRDataset (src/data/cached_dataset.py) reads files written by isr2_amd.cache: same keys, shapes
-    and values.  Needs the reference tree (this container); skipped where it is absent (GPU box)."""
-    ref = os.path.join(os.environ.get("FF_REFERENCE_ROOT", "/root/reference"), "src", "data", "cached_dataset.py")
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present")
+    and values.  tests/golden/cache_reader_view.npz (tests/golden/make_golden_contracts.py) holds the part files the reference's
+    reader was seen to load and what it returned for them: the files written now must be those files, entry for entry, and
+    isr2_amd.cache.read_sample must return what the reference's reader returned."""
     from isr2_amd import cache
-    spec = importlib.util.spec_from_file_location("ref_cached_dataset", ref)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    g = np.load(os.path.join(HERE, "golden", "cache_reader_view.npz"))
     for i in range(2):
-        lr, hr, outs, feats = _fake_sample(seed=i)
-        cache.write_sample(str(tmp_path), f"img_{i:03d}", lr, hr, outs, feats)
-    import contextlib, io
-    with contextlib.redirect_stdout(io.StringIO()):
-        ds = mod.CachedSRDataset(str(tmp_path), augment=False, repeat_factor=1, load_features=True)
-    assert len(ds) == 2
-    item = ds[1]
-    lr, hr, outs, feats = _fake_sample(seed=1)
-    assert torch.equal(item["lr"], lr) and torch.equal(item["hr"], hr) and item["filename"] == "img_001"
-    for k in ("hat", "dat", "nafnet"):
-        assert torch.equal(item["expert_imgs"][k], outs[k][0]) and torch.equal(item["expert_feats"][k], feats[k][0])
+        cache.write_sample(str(tmp_path), f"img_{i:03d}", *_fake_sample(seed=i, h=4, w=3))
+    written = {}
+    for f in sorted(os.listdir(tmp_path)):
+        written.update(_flatten(torch.load(str(tmp_path / f), weights_only=True), "file/" + f))
+    assert sorted(written) == sorted(k for k in g.files if k.startswith("file/"))
+    for k, v in written.items():
+        assert v.dtype == g[k].dtype and v.shape == g[k].shape and np.array_equal(v, g[k]), k
+    stems = cache.list_stems(str(tmp_path))
+    assert len(stems) == int(g["reader/len"])
+    for i, stem in enumerate(stems):
+        got = _flatten(cache.read_sample(str(tmp_path), stem, load_features=True), f"reader/{i}")
+        assert sorted(got) == sorted(k for k in g.files if k.startswith(f"reader/{i}/"))
+        for k, v in got.items():
+            assert v.dtype == g[k].dtype and v.shape == g[k].shape and np.array_equal(v, g[k]), k
+        lr, hr, outs, feats = _fake_sample(seed=i, h=4, w=3)
+        assert stem == f"img_{i:03d}" and str(g[f"reader/{i}/filename"]) == stem
+        assert np.array_equal(g[f"reader/{i}/lr"], lr.numpy()) and np.array_equal(g[f"reader/{i}/hr"], hr.numpy())
+        for k in ("hat", "dat", "nafnet"):
+            assert np.array_equal(g[f"reader/{i}/expert_imgs/{k}"], outs[k][0].numpy())
+            assert np.array_equal(g[f"reader/{i}/expert_feats/{k}"], feats[k][0].numpy())
 
 
 def test_oracle_hook_features_match_reference_golden(synth_sd):

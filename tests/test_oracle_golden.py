@@ -14,7 +14,7 @@ TOL = 2e-4   # fp32 re-association across ~150 residual blocks; observed <= 2e-5
 @pytest.fixture(scope="module", params=["c48_u8", "c42x52_nat"])
 def case(request, synth_sd):
     g = np.load(os.path.join(HERE, "golden", request.param + ".npz"))
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    torch.set_num_threads(max(1, min(len(os.sched_getaffinity(0)), 16)))   # this process's CPU share, not the whole host's
     taps = {}
     out = O.forward(synth_sd, torch.from_numpy(g["lr"]), taps)
     taps["final"] = out

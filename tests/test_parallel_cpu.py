@@ -182,7 +182,7 @@ def test_visible_gpu_count_uses_no_gpu_call(monkeypatch):
 def test_run_sharded_checks_paths_before_spawning(tmp_path, monkeypatch, capsys):
     """A bad --model_dir fails in the parent (exit 2), before any rank is started."""
     from isr2_amd import run_sharded
-    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "0,1")
+    monkeypatch.setattr("isr2_amd.parallel.visible_gpu_count", lambda: 2)   # two GPUs whatever this machine's visibility lists say
     monkeypatch.delenv("FF_ALLOW_SYNTH", raising=False)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     (tmp_path / "in").mkdir()
