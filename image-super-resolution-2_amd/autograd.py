@@ -727,3 +727,76 @@ def planes_to_nhwc(x: Var, B: int) -> Var:
             _acc(x, ops.nhwc_to_nchw(g).reshape(BC, H, W_))
     _rec(bwd, x)
     return y
+
+
+# ======================================================================================================================
+# The reference's loss components (CombinedLoss, perceptual_loss.py:1207-1283) on csrc/sr_losses.hip.  Images are NHWC [B,H,W,3];
+# the kernels clamp the prediction themselves (train.py:325) and their gradients are w.r.t. the PRE-clamp prediction.
+LOSS_ORDER = ("l1", "charbonnier", "l2", "ssim", "edge", "fft", "swt")      # CombinedLoss.forward's order of the weighted sum
+LOSS_ID = dict(l1=0, charbonnier=1, l2=2, ssim=3, edge=4, swt=5, fft=6)      # ff_loss_workspace's component numbers
+
+
+def ssim_gauss11() -> T:
+    """SSIMLoss._create_gaussian_window's 1-D weights (perceptual_loss.py:232-243): fp32, normalised; the window is their outer product."""
+    import math
+    g = torch.tensor([math.exp(-(x - 5) ** 2 / (2 * 1.5 ** 2)) for x in range(11)], dtype=torch.float32)
+    return g / g.sum()
+
+
+class SRLoss:
+    """One loss component per call: value[0] = its unweighted value (device), dsr = / += weight * d value / d sr."""
+
+    def __init__(self, dev):
+        self.dev = torch.device(dev)
+        self.fft = FFT2(self.dev)
+        self.gauss = ssim_gauss11().to(self.dev)
+        self._work = {}
+
+    def _ws(self, name: str, B: int, H: int, W: int) -> T:
+        key = (name, B, H, W)
+        w = self._work.get(key)
+        if w is None:
+            n = int(_L().ff_loss_workspace(LOSS_ID[name], B, H, W))
+            if n <= 0:
+                raise _lib.FFError(f"ff_loss_workspace: bad shape for {name}: {(B, H, W)}")
+            w = self._work[key] = torch.empty(n, device=self.dev, dtype=torch.float32)
+        return w
+
+    def component(self, name: str, sr: T, hr: T, weight: float = 1.0, dsr: Optional[T] = None, accumulate: bool = False,
+                  value: Optional[T] = None) -> T:
+        if name not in LOSS_ID:
+            raise _lib.FFError(f"unknown loss component {name!r}; known: {', '.join(LOSS_ORDER)}")
+        if sr.dim() != 4 or sr.shape[-1] != 3 or tuple(hr.shape) != tuple(sr.shape):
+            raise _lib.FFError(f"loss {name}: expected NHWC [B,H,W,3] prediction and target of one shape, got {tuple(sr.shape)} / {tuple(hr.shape)}")
+        for t in (sr, hr) + ((dsr,) if dsr is not None else ()):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.dev:
+                raise _lib.FFError(f"loss {name}: tensors must be contiguous fp32 on {self.dev}")
+        if dsr is not None and tuple(dsr.shape) != tuple(sr.shape):
+            raise _lib.FFError(f"loss {name}: dsr shape {tuple(dsr.shape)} != {tuple(sr.shape)}")
+        B, H, W_, _ = sr.shape
+        if value is None:
+            value = torch.empty(1, device=self.dev, dtype=torch.float32)
+        work = self._ws(name, B, H, W_)
+        L = _L()
+        common = (float(weight), dsr.data_ptr() if dsr is not None else None, int(bool(accumulate)), value.data_ptr(), work.data_ptr(),
+                  work.numel(), _st())
+        if name in ("l1", "charbonnier", "l2"):
+            _lib.check(L.ff_loss_pointwise(LOSS_ID[name], sr.data_ptr(), hr.data_ptr(), B, H, W_, *common))
+        elif name == "ssim":
+            _lib.check(L.ff_loss_ssim(sr.data_ptr(), hr.data_ptr(), B, H, W_, self.gauss.data_ptr(), *common))
+        elif name == "edge":
+            _lib.check(L.ff_loss_edge(sr.data_ptr(), hr.data_ptr(), B, H, W_, *common))
+        elif name == "swt":
+            _lib.check(L.ff_loss_swt(sr.data_ptr(), hr.data_ptr(), B, H, W_, *common))
+        else:
+            (wc, ws), (hc, hs) = self.fft.tw(W_), self.fft.tw(H)
+            _lib.check(L.ff_loss_fft(sr.data_ptr(), hr.data_ptr(), B, H, W_, wc.data_ptr(), ws.data_ptr(), hc.data_ptr(), hs.data_ptr(), *common))
+        return value
+
+    def combined(self, active, sr: T, hr: T, dsr: Optional[T], values: T, weights: T, total: T) -> T:
+        """CombinedLoss.forward for the active (name, weight) pairs in LOSS_ORDER: values[k] = component k, total = sum_k w_k values[k]
+        (in order), dsr = d total / d sr.  `weights` holds the active weights on the device, in the same order."""
+        for k, (name, w) in enumerate(active):
+            self.component(name, sr, hr, w, dsr, accumulate=k > 0, value=values[k:k + 1])
+        _lib.check(_L().ff_loss_combine(values.data_ptr(), weights.data_ptr(), len(active), total.data_ptr(), _st()))
+        return total

@@ -3,11 +3,14 @@
 Drop-in for the body of the reference's `train_epoch_cached` loop (train.py:308-356) with the experts precomputed:
 
     sr   = model.forward_with_precomputed(lr, expert_imgs, expert_feats)      # TRAIN mode (enhanced_fusion.py:756-812)
-    loss = mean |clamp(sr, 0, 1) - hr|                                        # CombinedLoss, stage-1 weights {l1: 1}
+    loss = mean |clamp(sr, 0, 1) - hr|                                        # CombinedLoss, stage-1 weights {l1: 1} (default)
     loss.backward(); clip_grad_norm_(params, 1.0); AdamW.step(); ema.update() # train.py:338-351, checkpoint_manager.py:400-407
 
     tr = FusionTrainer(state_dict, "cuda:0")          # reference-keyed fusion (+ collaborative) state dict
     loss = tr.step(lr, hr, outs, feats)               # one optimizer step; returns the loss (device scalar)
+    tr.set_epoch(epoch)                               # the reference's staged loss weights (LOSS_STAGES, get_loss_stage)
+
+Loss weights other than {l1: 1} run CombinedLoss's components (l1, charbonnier, l2, ssim, edge, fft, swt) on csrc/sr_losses.hip.
 
 Train-mode semantics that differ from the eval path (fusion.py): BatchNorm uses batch statistics -- per CALL, and the shared LKA
 block is called once per band / expert (large_kernel_attention.py:236-240, 406-411) -- and updates its running statistics;
@@ -34,9 +37,43 @@ from .autograd import Var
 from .fusion import DB4_LO, DB4_HI, _dct_matrix, _zigzag_masks
 
 T = torch.Tensor
+# configs/train_config.yaml:130-170 (loss.stages), selected per epoch by train.py:98-118 get_loss_stage
+LOSS_STAGES = (
+    {"epochs": (0, 80), "name": "foundation_psnr",                                               # train_config.yaml:133-143
+     "weights": {"l1": 1.0, "charbonnier": 0.0, "swt": 0.0, "fft": 0.0, "ssim": 0.0, "vgg": 0.0}},
+    {"epochs": (80, 150), "name": "frequency_refinement",                                        # train_config.yaml:145-155
+     "weights": {"l1": 0.75, "charbonnier": 0.0, "swt": 0.20, "fft": 0.05, "ssim": 0.0, "vgg": 0.0}},
+    {"epochs": (150, 200), "name": "detail_enhancement",                                         # train_config.yaml:157-167
+     "weights": {"l1": 0.60, "charbonnier": 0.0, "swt": 0.25, "fft": 0.10, "ssim": 0.05, "vgg": 0.0}},
+)
+LOSS_KEYS = ag.LOSS_ORDER + ("vgg", "clip")                   # CombinedLoss.weights (perceptual_loss.py:1109-1119)
 HP = dict(lr=1.5e-4, betas=(0.9, 0.999), eps=1.0e-8, weight_decay=1.0e-4, clip=1.0, ema_decay=0.9995)   # configs/train_config.yaml:102-125
 DW_KEYS = ("lka.local_conv.weight", "lka.h_conv.weight", "lka.v_conv.weight")
 BN_SUFFIX = ("running_mean", "running_var", "num_batches_tracked")
+
+
+def loss_stage(epoch: int, stages=LOSS_STAGES) -> Tuple[int, Dict[str, float], str]:
+    """get_loss_stage (train.py:98-118): the stage whose [start, end) holds `epoch`, else the last one -> (number, weights, name)."""
+    for i, st in enumerate(stages):
+        if st["epochs"][0] <= epoch < st["epochs"][1]:
+            return i + 1, dict(st["weights"]), st["name"]
+    return len(stages), dict(stages[-1]["weights"]), stages[-1]["name"]
+
+
+def validate_loss_weights(w: Dict[str, float]) -> Dict[str, float]:
+    """Check a CombinedLoss weight dict; returns it with float values.  vgg / clip need pretrained networks (VGG19, CLIP) that this
+    project does not ship: a weight of 0 (every stage of the shipped YAML) is accepted, anything above is an error."""
+    out = {}
+    for k, v in dict(w).items():
+        if k not in LOSS_KEYS:
+            raise _lib.FFError(f"unknown loss weight {k!r}; known: {', '.join(LOSS_KEYS)}")
+        v = float(v)
+        if not math.isfinite(v) or v < 0.0:
+            raise _lib.FFError(f"loss weight {k} = {v}: weights must be finite and >= 0")
+        if k in ("vgg", "clip") and v > 0.0:
+            raise _lib.FFError(f"loss weight {k} = {v}: the {k.upper()} loss needs pretrained weights this project does not have")
+        out[k] = v
+    return out
 
 
 def _is_buffer(name: str) -> bool:
@@ -74,8 +111,9 @@ def trainable_names(sd: Dict[str, T]) -> List[str]:
 
 class FusionTrainer:
     def __init__(self, state_dict: Dict[str, T], device="cuda:0", hp: Optional[dict] = None, dropout: float = 0.1, seed: int = 0,
-                 gemm: Optional[str] = "f32"):
-        """gemm: contraction mode of the step's convolutions / linear layers -- "f32" (exact fp32 MFMA, the default: the reference
+                 gemm: Optional[str] = "f32", loss_weights: Optional[Dict[str, float]] = None):
+        """loss_weights: CombinedLoss weights (validate_loss_weights); None = {l1: 1}, the stage-1 loss.
+        gemm: contraction mode of the step's convolutions / linear layers -- "f32" (exact fp32 MFMA, the default: the reference
         trains in fp32, configs/train_config.yaml:100-101, and the step is not GEMM-bound: 90 vs 85 ms), "bf16x3", or None = whatever
         ops.gemm_mode() says (the weight gradients are exact fp32 MFMA in every mode)."""
         dev = torch.device(device)
@@ -121,7 +159,43 @@ class FusionTrainer:
             g = g / g.sum()
             self.gauss = (g[:, None] * g[None, :]).reshape(25, 1).repeat(1, 3).contiguous().to(dev)
             self.fft = ag.FFT2(dev)
+            self.loss_values = torch.zeros(len(ag.LOSS_ORDER), device=dev)
         self.last_grad_norm = None
+        self.srloss = None
+        self.stage = None
+        self.set_loss_weights({"l1": 1.0} if loss_weights is None else loss_weights)
+
+    # ---------------------------------------------------------------------------------------------------- loss
+    def set_loss_weights(self, w: Dict[str, float]):
+        """CombinedLoss.set_weights: the components with weight > 0 are computed, in CombinedLoss.forward's order."""
+        self.loss_weights = validate_loss_weights(w)
+        self.active_losses = [(k, self.loss_weights[k]) for k in ag.LOSS_ORDER if self.loss_weights.get(k, 0.0) > 0.0]
+        if not self.active_losses:
+            raise _lib.FFError("loss weights: at least one component must have a weight > 0")
+        self._default_loss = self.active_losses == [("l1", 1.0)]
+        with torch.cuda.device(self.dev):
+            self.active_w = torch.tensor([w_ for _, w_ in self.active_losses], dtype=torch.float32, device=self.dev)
+
+    def set_stage(self, stage: int):
+        """The weights of stage `stage` (1-based) of LOSS_STAGES; save_checkpoint records the number."""
+        if not 1 <= int(stage) <= len(LOSS_STAGES):
+            raise _lib.FFError(f"loss stage {stage}: expected 1..{len(LOSS_STAGES)}")
+        self.set_loss_weights(LOSS_STAGES[int(stage) - 1]["weights"])
+        self.stage = int(stage)
+
+    def set_epoch(self, epoch: int) -> int:
+        """train.py:294-295: the stage of `epoch` (loss_stage) and its weights; returns the stage number."""
+        num, w, _ = loss_stage(epoch)
+        self.set_loss_weights(w)
+        self.stage = num
+        return num
+
+    def last_loss_components(self) -> Dict[str, float]:
+        """The unweighted value of every active component in the last step (CombinedLoss's return_components), read on demand."""
+        if self._default_loss:
+            return {"l1": float(self.loss.cpu())}
+        vals = self.loss_values[:len(self.active_losses)].cpu().tolist()
+        return {k: float(v) for (k, _), v in zip(self.active_losses, vals)}
 
     # ---------------------------------------------------------------------------------------------------- parameters
     def _native_shape(self, k: str):
@@ -387,7 +461,7 @@ class FusionTrainer:
         return t.to(self.dev, torch.float32).contiguous()
 
     def forward_backward(self, lr: T, hr: T, outs: Dict[str, T], feats: Dict[str, T]):
-        """Zero the gradient buffer, run forward + L1 + backward.  Returns (sr NHWC tensor, loss [1] device tensor)."""
+        """Zero the gradient buffer, run forward + loss + backward.  Returns (sr NHWC tensor, loss [1] device tensor)."""
         lr, hr = self._to_dev(lr), self._to_dev(hr)
         outs = {k: self._to_dev(v) for k, v in outs.items()}
         feats = {k: self._to_dev(v) for k, v in feats.items()}
@@ -407,8 +481,13 @@ class FusionTrainer:
                 sr = self.forward(lr, outs, feats)
                 hr_nhwc = ops.nchw_to_nhwc(hr)
                 dsr = torch.empty_like(sr.data)
-                _lib.check(_lib.load().ff_l1_loss_grad(sr.data.data_ptr(), hr_nhwc.data_ptr(), dsr.data_ptr(), sr.data.numel(), self.loss.data_ptr(),
-                                                       self.work.data_ptr(), 1024, ag._st()))
+                if self._default_loss:
+                    _lib.check(_lib.load().ff_l1_loss_grad(sr.data.data_ptr(), hr_nhwc.data_ptr(), dsr.data_ptr(), sr.data.numel(),
+                                                           self.loss.data_ptr(), self.work.data_ptr(), 1024, ag._st()))
+                else:
+                    if self.srloss is None:
+                        self.srloss = ag.SRLoss(self.dev)
+                    self.srloss.combined(self.active_losses, sr.data, hr_nhwc, dsr, self.loss_values, self.active_w, self.loss)
                 sr.grad, sr.owned = dsr, True
                 tape.backward()
         self._vars = {}
@@ -526,7 +605,7 @@ def _trainer_save(self, path: str, epoch: int, metrics: Optional[dict] = None, l
     """Write a checkpoint in the reference's layout (loadable by its CheckpointManager.load_checkpoint when this trainer was built
     from a complete reference state dict; a later FusionTrainer.load_checkpoint resumes bit-exactly either way)."""
     ck = build_checkpoint(self.state_dict_in_order(), self._export(self.M), self._export(self.V), self.ema_shadow(), self.step_count, self.hp,
-                          epoch, metrics, lr_now, scheduler_state)
+                          epoch, metrics, lr_now, scheduler_state, stage=self.stage)
     ck["ff_trainer"] = {"seed": self.seed, "dropout": self.dropout, "step_count": self.step_count}
     _save_atomic(ck, path)
     return path
@@ -596,6 +675,8 @@ def _trainer_load(self, path_or_ckpt, load_optimizer: bool = True):
         self.step_count = steps.pop() if steps else 0
         g = osd["param_groups"][0]
         self.hp.update(lr=float(g.get("initial_lr", g["lr"])), betas=tuple(g["betas"]), eps=float(g["eps"]), weight_decay=float(g["weight_decay"]))
+    if "stage" in ck:                                                 # train.py:1149 extra_state={'stage': ...}
+        self.set_stage(int(ck["stage"]))
     if "ff_trainer" in ck:
         self.seed, self.dropout = int(ck["ff_trainer"]["seed"]), float(ck["ff_trainer"]["dropout"])
     return ck

@@ -458,6 +458,31 @@ int ff_grad_sqnorm(const float* g, long long n, float* out_sqnorm, float* work, 
 int ff_adamw_ema_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* ema, long long n, const float* hyper10,
                       const float* sqnorm, void* stream);
 
+/* The reference's staged training losses (csrc/sr_losses.hip; CombinedLoss, perceptual_loss.py:1207-1283).  sr (pre-clamp) and hr
+ * are NHWC [B][H][W][3]; each component writes its UNWEIGHTED value to value[0] (device) and, when dsr is not null, stores
+ * (accumulate = 0) or adds (accumulate = 1) weight * d(value)/d(sr) with the clamp mask 0 <= sr <= 1.  Fixed-order reductions:
+ * identical calls give identical bits.  Workspace in floats: ff_loss_workspace(component, B, H, W), component 0 l1, 1 charbonnier,
+ * 2 l2, 3 ssim, 4 edge, 5 swt, 6 fft.
+ *   ff_loss_pointwise  kind 0 l1, 1 charbonnier (eps 1e-6), 2 l2
+ *   ff_loss_ssim       1 - mean SSIM (gauss11: the normalised 11-tap Gaussian, sigma 1.5; zero padding 5; C1 0.01^2, C2 0.03^2)
+ *   ff_loss_edge       l1(Sobel x) + l1(Sobel y), zero padding 1
+ *   ff_loss_swt        SWTLoss('haar', 2, use_gpu_approximation=True); band weights a 0.5, h 1.5, v 1.5, d 2.0
+ *   ff_loss_fft        FFTLoss(focus_high_freq=True); tw*: the twiddle tables of ff_rfft2
+ *   ff_loss_combine    total[0] = sum_k weights[k] * values[k] (device arrays), added in order */
+long long ff_loss_workspace(int component, int B, int H, int W);
+int ff_loss_pointwise(int kind, const float* sr, const float* hr, int B, int H, int W, float weight, float* dsr, int accumulate,
+                      float* value, float* work, long long work_floats, void* stream);
+int ff_loss_ssim(const float* sr, const float* hr, int B, int H, int W, const float* gauss11, float weight, float* dsr, int accumulate,
+                 float* value, float* work, long long work_floats, void* stream);
+int ff_loss_edge(const float* sr, const float* hr, int B, int H, int W, float weight, float* dsr, int accumulate, float* value,
+                 float* work, long long work_floats, void* stream);
+int ff_loss_swt(const float* sr, const float* hr, int B, int H, int W, float weight, float* dsr, int accumulate, float* value,
+                float* work, long long work_floats, void* stream);
+int ff_loss_fft(const float* sr, const float* hr, int B, int H, int W, const float* twW_cos, const float* twW_sin, const float* twH_cos,
+                const float* twH_sin, float weight, float* dsr, int accumulate, float* value, float* work, long long work_floats,
+                void* stream);
+int ff_loss_combine(const float* values, const float* weights, int k, float* total, void* stream);
+
 /* C-level executor (csrc/ff_executor.hip): the whole forward -- models/team29_FreqFusion/io.py:221 `model(lr)` =
  * CompleteEnhancedFusionSR.forward, src/models/enhanced_fusion.py:694-754 -- for callers without Python.  A plan
  * (<stem>.ffplan, written by isr2_amd.plan.export_plan) lists every launch of one input shape with pointers expressed as
