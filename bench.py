@@ -1,6 +1,10 @@
 """Headline benchmark: output MPix/s of the FreqFusion x4 full 3-expert forward on 256x256 LR tiles.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if asked and prints the result line, nothing more.
+--full adds, after the timed steps: the per-kernel accounting pass (roofline, stage and kernel breakdowns), the other contraction
+modes with their PSNR against the reference's output, the CPU oracle baseline and the training side block (about two minutes).
 
 N > 1: either the driver launches one rank per GPU (torch.distributed.run: RANK / WORLD_SIZE set), or -- when called plainly --
 this script starts N fresh child ranks of itself before touching any GPU and relays rank 0's JSON line.
@@ -10,7 +14,7 @@ one synthetic 256x256 LR tile per GPU (BASELINE.json configs[1]); tiles are inde
 shard them with NO data-path collective (weak scaling).  The only collective is the one-off RCCL
 broadcast of the frozen weights from rank 0.  The steady state is replayed from a HIP graph (the
 eager Python launch loop is captured once), inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.
+Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for how the --full fields (roofline, cpu_baseline, ...) are defined.
 --dump-outputs DIR: after the timed steps, the SR output of the last timed step (what a caller of the timed path receives) is
 written as DIR/sr.npy, float32 [1, 3, 4*tile, 4*tile] (12 MiB at the default tile; DIR/sr_rank<r>.npy per rank when N > 1).
 Above 64 MiB (--tile > 591) the file holds a fixed seeded sample of 16 Mi output values, flattened, in index order.
@@ -258,13 +262,16 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="time the eager Python launch loop instead of HIP-graph replay")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("FF_BENCH_LANES", "2")), choices=(1, 2),
                     help="tiles in flight: 2 = consecutive steps replay on two lane streams (model.graphed_async, the plugin's tile pipeline), 1 = strictly one after the other")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the f32 / plain-bf16 side measurements")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step side block (BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-kernel accounting and roofline, "
+                         "the other contraction modes and accuracy against the reference, the CPU baseline, the training side block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other contraction modes, the accuracy block and the training side block")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training-step side block (BASELINE configs[4])")
     ap.add_argument("--tile", type=int, default=TILE)
     ap.add_argument("--dtype", default=os.environ.get("FF_GEMM", "bf16"), choices=("bf16", "bf16x3", "f32"),
                     help="contraction mode of the headline run.  BASELINE configs[1] names bf16: plain bf16 MFMA operands with fp32 "
-                         "accumulation (68.8 dB against the reference's output; the line carries the PSNR-vs-ground-truth deltas); "
+                         "accumulation (68.8 dB against the reference's output; a --full line carries the PSNR-vs-ground-truth deltas); "
                          "bf16x3 = fp32-grade split-bf16 products (123 dB), the plugin's default; f32 = exact fp32 MFMA")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's SR output to DIR/sr.npy (float32; DIR/sr_rank<r>.npy per rank when --gpus > 1)")
@@ -390,9 +397,10 @@ def main():
         np.save(dump, sr)
         log(f"last step's output {tuple(last[0].shape)} written to {dump}")
 
-    # ---- per-kernel-class accounting: one extra eager pass with HIP events around every launch ---------------
+    # ---- --full only from here on: what the headline does not need ------------------------------------------
+    # per-kernel-class accounting: one extra eager pass with HIP events around every launch
     roof, breakdown, stages = None, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         def _timed(fn):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -508,9 +516,10 @@ def main():
                        "launch": "hipGraph replay" if graph is not None else "eager",
                        "tiles_in_flight": lanes},
             "path_tflops": world * args.steps * flop_per_tile / elapsed / 1e12,
-            "roofline": roof, "stage_ms_per_tile": stages, "kernel_breakdown_ms_per_tile": breakdown,
         }
-        if world == 1 and not args.no_extra:
+        if args.full:
+            line.update({"roofline": roof, "stage_ms_per_tile": stages, "kernel_breakdown_ms_per_tile": breakdown})
+        if args.full and world == 1 and not args.no_extra:
             log("side measurements: f32 and plain-bf16 contraction modes")
             one_ms = None
             if lanes == 2:                                   # the same tile strictly one after the other (latency of one tile)
@@ -535,10 +544,10 @@ def main():
                 if mode != ops.gemm_mode():
                     extra[mode] = time_mode(mode, sd, dev, lr, max(2, min(args.steps, 5)))
             line["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log(f"cpu baseline (oracle, {tile}x{tile} tile, {host_threads()} threads)")
             line["cpu_baseline"] = cpu_baseline(sd, host_threads(), tile)
-        if world == 1 and not args.no_train and not args.no_extra:
+        if args.full and world == 1 and not args.no_train and not args.no_extra:
             log("side block: fusion-only training step (config 5)")
             del model
             torch.cuda.empty_cache()

@@ -8,20 +8,20 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/final
 rm -rf $O && mkdir -p $O && cd $R
-FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra > $O/pmc_f.json 2> $O/pmc_f.err || exit 1
+FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --full --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra > $O/pmc_f.json 2> $O/pmc_f.err || exit 1
 echo "[collect] pmc fetch done"
-FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra > $O/pmc_w.json 2> $O/pmc_w.err || exit 1
+FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --full --steps 1 --warmup 0 --no-graph --no-cpu-baseline --no-extra > $O/pmc_w.json 2> $O/pmc_w.err || exit 1
 echo "[collect] pmc write done"
 FF_GIT_HASH=${FF_GIT_HASH:-n/a} python3 tools/pmc_traffic.py $O/pmc_f $O/pmc_w $O/pmc_hbm_traffic.json || exit 1
 cp $O/pmc_hbm_traffic.json $R/profiles/r03_pmc_hbm_traffic_$V.json       # (in this box's copy: bench.py reads the newest matching file)
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 echo "[collect] bench done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ms -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $O/bench_under_rocprof.json 2> $O/stats_ms.err || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ms -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $O/bench_under_rocprof.json 2> $O/stats_ms.err || exit 1
 echo "[collect] stats (multi-stream) done"
-FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ss -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $O/bench_under_rocprof_ss.json 2> $O/stats_ss.err || exit 1
+FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ss -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $O/bench_under_rocprof_ss.json 2> $O/stats_ss.err || exit 1
 echo "[collect] stats (single stream) done"
 # the plugin's fp32-grade mode (bf16x3), single stream: the like-for-like successor of profiles/r02_*_singlestream.csv
-FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ss_x3 -- python3 bench.py --dtype bf16x3 --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $O/bench_under_rocprof_ss_bf16x3.json 2> $O/stats_ss_x3.err || exit 1
+FF_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ss_x3 -- python3 bench.py --full --dtype bf16x3 --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $O/bench_under_rocprof_ss_bf16x3.json 2> $O/stats_ss_x3.err || exit 1
 python3 tools/kernel_stats_per_forward.py $O/stats_ss_x3 $O/kernels_per_forward_singlestream_bf16x3.csv || exit 1
 echo "[collect] stats (bf16x3, single stream) done"
 # per-forward tables of the library's own kernels, setup (ATen weight preparation, runtime copies) listed apart
