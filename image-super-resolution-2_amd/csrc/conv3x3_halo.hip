@@ -10,7 +10,6 @@
 // previous tap.  Accumulators stay in registers over all chunks and taps (K = 9*Cin).
 //   LDS row (pixel or weight row) = [64 k hi | 64 k lo | 16 B pad] = 272 B = 68 dwords: conflict-free ds_read_b128.
 #include "ff_common.h"
-#include <stdlib.h>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -510,22 +509,18 @@ extern "C" long long ff_conv3x3_halo_weight_bytes(int Cout, int Cin, int bn, int
   return (long long)((Cout + bn - 1) / bn) * ((Cin + 63) / 64) * 9 * (64 / wk) * slot;
 }
 
-// number of workgroups ( = rows of pool_partials, each nblk... see below) for (B, H, W, Cout, bn): rows x row length
-// pixel rows per workgroup (the launch table below).  Plain bf16, 32 / 64 output channels, and fewer than two 16x16 tiles per CU
-// (the 256x256 token grids of HAT / DAT: 256 tiles): 8-row tiles of four waves, 46 KB of LDS, up to three workgroups per CU -- with
-// one 16-row workgroup per CU the launch is as long as ONE workgroup's serial load / taps / store sequence.
+// Plain bf16, 32 / 64 output channels, and fewer than two 16x16 tiles per CU (the 256x256 token grids of HAT / DAT: 256 tiles): with
+// one 16-row workgroup per CU the launch would be as long as ONE workgroup's serial load / taps / store sequence, so these take forms
+// of their own -- bn 64 the blocked 16-row form, bn 32 8-row tiles of four waves (46 KB of LDS, up to three workgroups per CU).
+// The launch and ff_conv3x3_halo_pool_rows both decide by this one test.
+static bool halo_small_grid(int B, int H, int W, int Cout, int bn, int nterms) {
+  const long long tiles16 = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((Cout + bn - 1) / bn);
+  return nterms == 1 && (bn == 32 || bn == 64) && tiles16 < 512;
+}
+
+// pixel rows per workgroup of the form ff_conv3x3_halo launches (its launch table below)
 static int halo_rows_per_wg(int B, int H, int W, int Cout, int bn, int nterms) {
-  if (bn == 128) return 8;
-  static const int blocked = []() { const char* e = getenv("FF_HALO_BLOCKED"); return e ? atoi(e) : 1; }();   // tuning switch
-  if (nterms == 1 && bn == 64 && blocked) {
-    const long long tiles16 = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((Cout + bn - 1) / bn);
-    if (tiles16 < 512 || blocked == 2) return 16;        // blocked 16-row form (launch table below)
-  }
-  static const int wide8 = []() { const char* e = getenv("FF_HALO_192_8ROW"); return e ? atoi(e) : 0; }();   // tuning switch: 8-row form for 192 outputs (measured 36.9 vs 35.8 us on CAB 60->180, 67.1 vs 65.7 on 180->180: off)
-  if (nterms == 1 && (bn <= 64 || (bn == 192 && wide8))) {
-    const long long tiles16 = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((Cout + bn - 1) / bn);
-    if (tiles16 < 512) return 8;
-  }
+  if (bn == 128 || (bn == 32 && halo_small_grid(B, H, W, Cout, bn, nterms))) return 8;
   return 16;
 }
 
@@ -553,30 +548,16 @@ extern "C" int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int 
   p.in = in; p.w = (const unsigned char*)w_img; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.ldi = ldi; p.Cout = Cout; p.ldo = ldo; p.ldr = ldr;
   p.nchunk = (Cin + 63) / 64; p.act = act; p.alpha = alpha; p.shuffle = shuffle; p.pool_part = pool_partials; p.io_bf16 = io_bf16;
-  static const int vec_epi_on = []() { const char* e = getenv("FF_HALO_VEC_EPI"); return e ? atoi(e) : 1; }();   // tuning switch
-  p.vec_epi = vec_epi_on && shuffle == 0 && Cout % 4 == 0 && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && !(res && pool_partials) &&
+  p.vec_epi = shuffle == 0 && Cout % 4 == 0 && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && !(res && pool_partials) &&
               (!res || (ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)) && (!mul || (((uintptr_t)mul) & 15) == 0);
 #ifdef HX_TIMING
   p.dbg = g_hx_dbg;
 #endif
   hipStream_t st = (hipStream_t)stream;
-  static const int ring = []() { const char* e = getenv("FF_HALO_RING"); return e ? atoi(e) : 0; }();   // tuning switch: weight-ring slots
-  static const int blocked = []() { const char* e = getenv("FF_HALO_BLOCKED"); return e ? atoi(e) : 1; }();
-  if (nterms == 1 && bn == 64 && blocked) {
-    const long long tiles16 = (long long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((Cout + bn - 1) / bn);
-    if (tiles16 < 512 || blocked == 2) return launch_halo<8, 1, 1, 2, 64, 9, 1>(p, st);    // nine resident tap tiles, three barriers per chunk
+  if (halo_small_grid(B, H, W, Cout, bn, nterms)) {
+    if (bn == 64) return launch_halo<8, 1, 1, 2, 64, 9, 1>(p, st);     // nine resident tap tiles, three barriers per chunk
+    return launch_halo<4, 1, 1, 1, 64, 2, 1>(p, st);                   // 8x16 pixels, 4 waves
   }
-  if (nterms == 1 && bn <= 64 && halo_rows_per_wg(B, H, W, Cout, bn, nterms) == 8) {   // 8x16 pixels, 4 waves
-    if (bn == 32) return launch_halo<4, 1, 1, 1, 64, 2, 1>(p, st);
-    if (ring == 3) return launch_halo<4, 1, 1, 2, 64, 3, 1>(p, st);
-    if (ring == 4) return launch_halo<4, 1, 1, 2, 64, 4, 1>(p, st);
-    if (ring == 5) return launch_halo<4, 1, 1, 2, 64, 5, 1>(p, st);
-    return launch_halo<4, 1, 1, 2, 64, 2, 1>(p, st);
-  }
-  if (nterms == 1 && bn == 192 && halo_rows_per_wg(B, H, W, Cout, bn, nterms) == 8)
-    return launch_halo<2, 2, 2, 3, 32, 2, 1>(p, st);      // 8x16 pixels x 192, 4 waves, 58 KB: two workgroups per CU on the 256 x 256 grids
-  if (nterms == 1 && bn == 64 && ring == 3) return launch_halo<8, 1, 1, 2, 64, 3, 1>(p, st);
-  if (nterms == 1 && bn == 192 && ring >= 3) return launch_halo<4, 2, 2, 3, 32, 3, 1>(p, st);
   switch (bn) {
     // 16x16-pixel workgroups of 8 waves (two per SIMD: one wave's LDS reads and waits hide behind the
     // other's MFMAs -- measured 140 -> 121 us for 180->180 against the 4-wave form)

@@ -19,7 +19,6 @@
 //   * epilogue: 32x32 tiles are transposed through LDS so global stores / residual loads are 128-byte row segments.
 // Workgroup = 8 waves = 256 tokens: 65 536 tokens -> 256 workgroups = one per CU.
 #include "ff_common.h"
-#include <stdlib.h>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -348,7 +347,6 @@ static unsigned long long* g_tm_dbg = nullptr;
 #define TM_T(i) do { } while (0)
 #endif
 
-template <int NTERMS>
 __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int W1B = W1PL * 16, W2B = W2PL * 16;
@@ -452,10 +450,8 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
         fx[st & 1] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * (st + 2));
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (NTERMS == 3) {
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, oacc[n], 0, 0, 0);
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], oacc[n], 0, 0, 0);
-      }
+      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, oacc[n], 0, 0, 0);
+      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], oacc[n], 0, 0, 0);
       oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], oacc[n], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -567,10 +563,8 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
           fx[st & 1] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * (st + 2));
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (NTERMS == 3) {
-          hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, hacc, 0, 0, 0);
-          hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], hacc, 0, 0, 0);
-        }
+        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, hacc, 0, 0, 0);
+        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], hacc, 0, 0, 0);
         hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], hacc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -607,10 +601,8 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
           fl[u & 1] = *reinterpret_cast<const bf16x8*>(ap + ((u + 2) >> 1) * 32 * W2ROWB + 32 * ((u + 2) & 1) + W2B);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (NTERMS == 3) {
-          oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl[s2], oacc[n], 0, 0, 0);
-          oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh[s2], oacc[n], 0, 0, 0);
-        }
+        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl[s2], oacc[n], 0, 0, 0);
+        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh[s2], oacc[n], 0, 0, 0);
         oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh[s2], oacc[n], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -987,15 +979,11 @@ extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int l
   FF_CHECK_ARG(M * (long long)(ldx > ldc ? ldx : ldc) < (1LL << 31), "ff_token_projmlp: too many tokens for 32-bit row offsets");
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_projmlp_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_projmlp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_projmlp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { ff_set_error("ff_token_projmlp: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
     attr_set = true;
   }
-  static int v2 = -1;
-  if (v2 < 0) { const char* e = getenv("FF_PM_V2"); v2 = (e && e[0] == '0') ? 0 : 1; }
-  FF_CHECK_ARG(io_bf16 == 0 || v2, "ff_token_projmlp: bf16 att / c2 rows need the bf16 kernel (FF_PM_V2)");
-  if (nterms == 1 && v2) {
+  if (nterms == 1) {
     const size_t lds2 = (size_t)PM_OFF_VEC + (size_t)(2 * TM_KP + hidden_tiles * 32) * 4;
     FF_CHECK_ARG(lds2 <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
     static bool attr2 = false;
@@ -1005,8 +993,7 @@ extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int l
       attr2 = true;
     }
     hipLaunchKernelGGL(token_projmlp_bf16_kernel, dim3((unsigned)nblk), dim3(512), lds2, (hipStream_t)stream, p);
-  } else if (nterms == 3) hipLaunchKernelGGL(token_projmlp_kernel<3>, dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(token_projmlp_kernel<1>, dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
+  } else hipLaunchKernelGGL(token_projmlp_kernel, dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_token_projmlp");
   return FF_OK;
 }

@@ -51,11 +51,10 @@ def _tl(blk: dict, key: str) -> dict:
     return pk
 
 
-# plain bf16: intermediates that are consumed only as bf16 MFMA operands live in HBM as bf16 (needs the v2 attention / proj + MLP kernels)
-_BF16_ROWS = (os.environ.get("FF_BF16_ROWS", "1") != "0" and os.environ.get("FF_WF_V2", "1") != "0" and os.environ.get("FF_PM_V2", "1") != "0")
+# plain bf16: intermediates that are consumed only as bf16 MFMA operands live in HBM as bf16
+_BF16_ROWS = os.environ.get("FF_BF16_ROWS", "1") != "0"
 _OCAB_V2 = os.environ.get("FF_OCAB_V2", "1") != "0"          # plain bf16: HAT's overlapping cross-attention in the persistent per-window kernel
 _SGFN_TAIL = os.environ.get("FF_SGFN_TAIL", "1") != "0"      # plain bf16: DAT's SpatialGate + fc2 + residual in one launch
-_CAB_FUSED = os.environ.get("FF_CAB_FUSED", "0") == "1"        # opt-in: HAT's conv branch in one launch (csrc/cab_fused.hip); bit-identical to the two launches, measured no faster
 
 
 def _fast() -> bool:
@@ -184,7 +183,7 @@ class HatHIP:
         d = C // self.heads
         # plain bf16: att, the normalised rows and conv1's output are consumed only as MFMA operands (rounded to bf16 there), so they are
         # stored as bf16 -- bit-identical results, half the bytes; conv2's output enters x1 times conv_scale = 0.01 and goes the same way
-        b16 = (_BF16_ROWS and ops.gemm_mode() == "bf16" and _fast() and _WIN_FUSED and _PROJ_MLP and not _CAB_FUSED and x.shape[0] == 1
+        b16 = (_BF16_ROWS and ops.gemm_mode() == "bf16" and _fast() and _WIN_FUSED and _PROJ_MLP and x.shape[0] == 1
                and H * W >= 1024 and C % 4 == 0)
         att = ops.empty_rows_bf16(tuple(x.shape), x.device) if b16 else ops.empty_like_rows(x)
         s = blk["shift"]
@@ -202,11 +201,8 @@ class HatHIP:
             ops.window_attn(qkv, att, blk["bias"], q_off=0, k_off=C, v_off=2 * C, o_off=0, H=H, W=W, Hp=H, Wp=W, win=(self.ws, self.ws),
                             kwin=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, heads=self.heads, d=d, scale=d ** -0.5,
                             rel_table=blk["rel"] if _REL_BIAS else None)
-        if _CAB_FUSED and ops.gemm_mode() == "bf16" and blk["cab0"][0].shape[0] <= 64 and C <= 192 and x.shape[0] == 1:
-            c2, c2mean = ops.cab_fused(xn, blk["cab0"][0], blk["cab0"][1], blk["cab2"][0], blk["cab2"][1], partials=True)   # conv -> GELU -> conv + pool, one launch
-        else:
-            c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16)
-            c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=b16)   # pool partials from the conv epilogue
+        c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16)
+        c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=b16)   # pool partials from the conv epilogue
         gate = ops.vec_mlp(c2mean, *blk["ca1"], "relu", *blk["ca2"], "sigmoid", post=self.conv_scale)
         if _fast() and _PROJ_MLP:                                  # proj + both residuals + norm2 + MLP: x1 never reaches memory
             return ops.token_projmlp(att, x, _pm(blk), blk["n2"][0], blk["n2"][1], c2=c2, c2_scale=gate.reshape(-1))

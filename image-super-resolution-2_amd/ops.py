@@ -105,7 +105,6 @@ def gemm_mode() -> str:
 
 
 _SMALL = _os.environ.get("FF_SMALL_CONV", "1") != "0"     # fp32 VALU kernel for 3x3 convolutions with Cout <= 16, Cin <= 64
-_HALO_ALL = _os.environ.get("FF_HALO", "1") == "2"          # tuning aid: every eligible 3x3 through the halo kernel
 _HALO = _os.environ.get("FF_HALO", "1") != "0"     # LDS-resident 3x3 convolution (csrc/conv3x3_halo.hip); 0 = generic implicit GEMM
 
 
@@ -371,7 +370,8 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
     op, ldo, *_ = _nhwc(out, "conv2d.out|bf16ok" if out_bf16 else "conv2d.out")
     halo_ok = (_HALO and _GEMM_MODE in ("bf16x3", "bf16") and (KH, KW) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1)
                and not dynamic_w and Cin >= 32 and Cin % 4 == 0 and ldi % 4 == 0 and xp % 16 == 0
-               and (Cout <= 64 or Cin >= 128 or 128 < Cout <= 192 or _HALO_ALL) and H * W >= 1024 and xp != op and B * H * W * ldi < 2 ** 31)
+               and (Cout <= 64 or Cin >= 128 or 128 < Cout <= 192)   # measured (profiles/r01_conv3x3_halo_vs_igemm.txt); 64 -> 256 ties
+               and H * W >= 1024 and xp != op and B * H * W * ldi < 2 ** 31)
     if (in_bf16 or out_bf16) and not (halo_ok and _GEMM_MODE == "bf16" and shuffle == 0 and res is None):
         raise _lib.FFError("conv2d: bf16 input / output rows exist for the LDS-resident 3x3 kernel in plain-bf16 mode only")
     rp, ldr = None, 0
@@ -392,10 +392,7 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
         _lib.check(_L().ff_conv2d(xp, w.data_ptr(), _ptr(bias), _ptr(mul), rp, op, B, H, W, Cin, ldi, Ho, Wo, Cout, ldo, ldr,
                                   KH, KW, stride[0], stride[1], pad[0], pad[1], ACT[act], float(alpha), shuffle, tile_hint,
                                   _stream()))
-    elif (_HALO and _GEMM_MODE in ("bf16x3", "bf16") and (KH, KW) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1)
-          and not dynamic_w and Cin >= 32 and Cin % 4 == 0 and ldi % 4 == 0 and xp % 16 == 0
-          and (Cout <= 64 or Cin >= 128 or 128 < Cout <= 192 or _HALO_ALL)   # measured (profiles/r01_conv3x3_halo_vs_igemm.txt); 64 -> 256 ties
-          and H * W >= 1024 and xp != op and B * H * W * ldi < 2 ** 31):
+    elif halo_ok:
         from . import prep as _prep
 
         nt_ = _nterms()
@@ -426,29 +423,6 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
     if want_pool:
         return out, pool_mean(out)
     return out
-
-
-def cab_fused(x: T, w1: T, b1: T, w2: T, b2: T, partials: bool = False):
-    """HAT's CAB in one launch (plain bf16 only): conv3x3(x, w1) + b1 -> GELU -> conv3x3(., w2) + b2 and the global average pool of the
-    result.  x [1,H,W,Cin] rows view, w1 / w2 packed [Cmid, 9*Cin] / [Cout, 9*Cmid] -> (out [1,H,W,Cout], pooled [1,Cout])."""
-    if _GEMM_MODE != "bf16":
-        raise _lib.FFError("cab_fused exists for the plain-bf16 contraction mode only")
-    xp, ldi, B, H, W, Cin = _nhwc(x, "cab_fused.x")
-    Cmid, Cout = w1.shape[0], w2.shape[0]
-    if B != 1 or w1.shape[1] != 9 * Cin or w2.shape[1] != 9 * Cmid:
-        raise _lib.FFError("cab_fused: expects one image and packed 3x3 weights [Cmid, 9*Cin], [Cout, 9*Cmid]")
-    from . import prep as _prep
-    i1 = PREPARED.get(w1, "cab1", lambda: _prep.pack_conv3x3_halo(w1, Cin, 64, 1))
-    i2 = PREPARED.get(w2, "cab2", lambda: _prep.pack_conv3x3_halo(w2, Cmid, 192, 1))
-    out = empty_rows((1, H, W, Cout), x.device)
-    op, ldo, *_ = _nhwc(out, "cab_fused.out")
-    prow = int(_L().ff_cab_fused_pool_rows(H, W))
-    part = torch.empty((prow, 192), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_cab_fused(xp, ldi, i1.data_ptr(), b1.data_ptr(), i2.data_ptr(), b2.data_ptr(), op, ldo, H, W, Cin, Cmid, Cout,
-                                 part.data_ptr(), _stream()))
-    pp = PoolPartials(part, Cout, 1.0 / float(H * W))
-    _note(2.0 * H * W * 9 * (Cmid * Cin + Cout * Cmid), 4.0 * H * W * (Cin + Cout))
-    return out, (pp if partials else pp.mean())
 
 
 def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] = None, mul: Optional[T] = None,
@@ -1151,7 +1125,7 @@ def tile_normalize(acc: T, wsum: T):
     _lib.check(_L().ff_tile_normalize(acc.data_ptr(), wsum.data_ptr(), C, H, W, _stream()))
 
 
-for _n in ("conv2d", "cab_fused", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
+for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):
     globals()[_n] = _instrument(globals()[_n])

@@ -6,7 +6,7 @@ import os
 import pytest
 
 
-def test_library_builds_and_exports_header_symbols():
+def test_library_builds_at_abi_7_and_exports_header_symbols():
     from isr2_amd.build import build
     from isr2_amd import lib as L
     path = build()
@@ -17,7 +17,7 @@ def test_library_builds_and_exports_header_symbols():
     for name in protos:
         assert hasattr(handle, name), f"{name} declared in include/ff_kernels.h but not exported"
     lib = L.load()
-    assert lib.ff_abi_version() == 6
+    assert lib.ff_abi_version() == 7
     assert lib.ff_last_error() is not None
 
 
