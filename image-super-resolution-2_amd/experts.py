@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .prep import (pack_conv, pack_dw, bn_scale_shift, fold_bn_after_conv, pack_token_mlp, pack_token_linear, pack_naf_ffn,
+from .prep import (pack_conv, pack_dw, bn_scale_shift, fold_bn_after_conv, pack_token_mlp, pack_token_linear, pack_naf_ffn, pack_naf_tail,
                    pack_win_attn, pack_win_rel, pack_token_projmlp, pack_chan_qkv, pack_token_linear_gated, pack_rel_overlap)
 
 T = torch.Tensor
@@ -530,6 +530,10 @@ class NafnetHIP:
                 t = ops.linear(ops.layernorm(x, *k["n1"], eps=1e-6), *k["c1"])
             g, pooled = ops.dwconv3_gate_pool(t, *k["c2"])                   # conv2 + SimpleGate + SCA pool sums
         sca = ops.vec_mlp(pooled, *k["sca"], None)                           # [1,c]
+        if flash and ops.gemm_mode() == "bf16":                              # plain bf16: conv3 + the gated FFN in one launch, y stays on chip
+            if "tail_pk" not in k:
+                k["tail_pk"] = pack_naf_tail(*k["c3"], *k["c4"], *k["c5"])
+            return ops.naf_tail(g, x, k["tail_pk"], sca.reshape(-1), k["beta"], k["n2"][0], k["n2"][1], k["gamma"])
         nf = ops.gemm_mode() != "f32"                                        # the split-bf16 GEMM carries both NAFBlock fusions
         if nf:                                                               # conv3(g * sca): the scale rides on the A operand
             y = ops.linear(g, *k["c3"], res=x, mul=k["beta"], kmul=sca.reshape(-1))

@@ -688,6 +688,28 @@ def naf_ffn(y: T, pk: dict, ln_g: T, ln_b: T, out_scale: T, eps: float = 1e-6) -
     return out
 
 
+def naf_tail(g: T, x: T, pk: dict, sca: T, beta: T, ln_g: T, ln_b: T, gamma: T, eps: float = 1e-6) -> T:
+    """The NAFBlock tail in one launch (C = 64 / 128, plain bf16 only): y = x + beta * conv3(g * sca), then
+    y + gamma * conv5(SimpleGate(conv4(LayerNorm(y)))); bit-equal to linear(g, W3, b3, res=x, mul=beta, kmul=sca) followed by
+    naf_ffn.  g, x: rows views; pk from prep.pack_naf_tail."""
+    if _GEMM_MODE != "bf16":
+        raise _lib.FFError(f"naf_tail exists for the plain-bf16 contraction mode only, not {_GEMM_MODE!r}")
+    gp, ldg, rows, C = rows_view(g, "naf_tail.g")
+    xp, ldx, xr, xc = rows_view(x, "naf_tail.x")
+    if C != pk["C"] or xr != rows or xc != C or tuple(x.shape) != tuple(g.shape):
+        raise _lib.FFError("naf_tail: shape mismatch")
+    for t_, n_ in ((sca, "sca"), (beta, "beta"), (ln_g, "ln_g"), (ln_b, "ln_b"), (gamma, "gamma")):
+        _chk(t_, "naf_tail." + n_)
+        if t_.numel() != C or not t_.is_contiguous():
+            raise _lib.FFError(f"naf_tail: {n_} must be a contiguous [{C}] vector")
+    out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+    _lib.check(_L().ff_naf_tail(gp, ldg, xp, ldx, out.data_ptr(), C, rows, C, sca.data_ptr(), pk["b3"].data_ptr(), beta.data_ptr(),
+                                ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b4"].data_ptr(),
+                                pk["b5"].data_ptr(), gamma.data_ptr(), _stream()))
+    _note(2.0 * rows * C * 4 * C, 12.0 * rows * C)
+    return out
+
+
 def layernorm(x: T, gamma: T, beta: T, eps: float = 1e-5, out: Optional[T] = None) -> T:
     xp, ldi, rows, C = rows_view(x, "layernorm.x")
     if out is None:
@@ -1125,7 +1147,7 @@ def tile_normalize(acc: T, wsum: T):
     _lib.check(_L().ff_tile_normalize(acc.data_ptr(), wsum.data_ptr(), C, H, W, _stream()))
 
 
-for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
+for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):
     globals()[_n] = _instrument(globals()[_n])

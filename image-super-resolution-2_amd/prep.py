@@ -166,6 +166,27 @@ def pack_naf_ffn(w4: T, b4: T, w5: T, b5: T) -> dict:
     return dict(C=C, w=torch.stack(recs).contiguous(), b4=b4.contiguous(), b5=b5.contiguous())
 
 
+def pack_naf_tail(w3: T, b3: T, w4: T, b4: T, w5: T, b5: T) -> dict:
+    """Weights of ff_naf_tail (plain bf16: hi plane only): conv3 [C, C], conv4 [2C, C], conv5 [C, C] as MFMA A fragments
+    [fragment][lane = 32 hh + l31][8] = w[row0 + l31][k0 + 8 hh + j], in the order the kernel walks them:
+    W3 (32-row tile n, k-step st), W4 (gated tile g, half a / b = rows 32g.. / C + 32g.., k-step st), W5 (g, 32-row tile n,
+    k-step s of the 32 columns 32g.., permuted as in pack_naf_ffn).  4 C^2 bf16 in all: the kernel's whole LDS weight image."""
+    C = w5.shape[0]
+    assert C in (64, 128) and tuple(w3.shape) == (C, C) and tuple(w4.shape) == (2 * C, C) and tuple(w5.shape) == (C, C)
+    pos = torch.arange(32)
+    src = ((pos & ~12) | ((pos & 4) << 1) | ((pos & 8) >> 1)).to(w4.device)
+
+    def frags(w):                                        # [R, K] -> [R/32][K/16][hh][l31][8]
+        r, k = w.shape
+        return w.reshape(r // 32, 32, k // 16, 2, 8).permute(0, 2, 3, 1, 4).reshape(-1)
+
+    f4 = torch.stack([torch.stack((w4[32 * g:32 * g + 32], w4[C + 32 * g:C + 32 * g + 32])) for g in range(C // 32)])   # [g][half][32][C]
+    f5 = torch.stack([w5[:, 32 * g:32 * g + 32][:, src] for g in range(C // 32)])                                     # [g][C][32]
+    img = torch.cat([frags(w3), frags(f4.reshape(-1, C)), frags(f5.reshape(-1, 32))]).to(torch.bfloat16).contiguous()
+    assert img.numel() == 4 * C * C
+    return dict(C=C, w=img, b3=b3.contiguous(), b4=b4.contiguous(), b5=b5.contiguous())
+
+
 def win_rel_stride(ww: int) -> int:
     """Row stride of the compact bias table of ff_win_attn_fused (>= 2 ww - 1, == ww mod 32: bank-conflict free gathers)."""
     return {8: 40, 16: 48, 32: 64}[ww]

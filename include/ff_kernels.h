@@ -210,6 +210,16 @@ int ff_naf_front(const float* x, int ldx, int H, int W, int C, const float* ln_g
 int ff_naf_ffn(const float* y, int ldy, float* out, int ldo, long long M, int C, const float* gamma_ln, const float* beta_ln,
                float eps, const void* w_tiles, const float* b4, const float* b5, const float* out_scale, int nterms, void* stream);
 
+/* NAFBlock tail in one launch (csrc/naf_tail.hip; nafnet_arch.py:118-131), plain bf16 (one MFMA term) only, C = 64 / 128:
+ *   y = x + beta[n] * (W3 . (g * sca) + b3),   out = y + out_scale[n] * (W5 . SimpleGate(W4 . LayerNorm(y) + b4) + b5).
+ * Bit-equal to ff_conv2d_bf16s(1x1, kmul = sca, mul = beta, res = x, nterms = 1) followed by ff_naf_ffn(nterms = 1); y never
+ * reaches memory.  g, x [M][ldg / ldx] (16-byte aligned rows, ld % 4 == 0), out [M][ldo] must not alias them; sca, b3, beta,
+ * gamma_ln, beta_ln, b5, out_scale [C], b4 [2C]; w_frags = prep.pack_naf_tail (W3 | W4 | W5 in MFMA fragment order, 4 C^2 bf16).
+ * Added under ABI version 7 (an additive entry point: no existing prototype changed). */
+int ff_naf_tail(const float* g, int ldg, const float* x, int ldx, float* out, int ldo, long long M, int C, const float* sca,
+                const float* b3, const float* beta, const float* gamma_ln, const float* beta_ln, float eps, const void* w_frags,
+                const float* b4, const float* b5, const float* out_scale, void* stream);
+
 /* LayerNorm over the last axis of [rows][C] (nn.LayerNorm and NAFNet LayerNorm2d in NHWC):
  * hat_arch.py:272,307,397,437,964; dat_arch.py:117,734-735,931,1003; nafnet_arch.py:35-41. */
 int ff_layernorm(const float* in, int ldi, float* out, int ldo, long long rows, int C, const float* gamma,
