@@ -1,0 +1,100 @@
+// Paired training augmentation on the device: the eight symmetries of the square (D4) applied per SAMPLE to a planar batch.
+// The reference augments each sample on the host before collation (src/data/cached_dataset.py:240-268):
+//   hflip = flip(dims=[-1]) (p 0.5), then vflip = flip(dims=[-2]) (p 0.5), then rot90(k, dims=[-2,-1]) with k in 0..3,
+// the same transform for lr, hr, the three expert images and the three feature maps.  Here the loader uploads the batch as read and
+// ONE launch per tensor permutes it: codes[b] = bit 0 hflip | bit 1 vflip | bits 2-3 k.
+//
+// Composition, as an index map (out is [Ho][Wo], Ho = H and Wo = W; odd k needs H == W so that a batch keeps one shape):
+//   rot90 k=1: r[i][j] = t[j][W-1-i]    k=2: r[i][j] = t[H-1-i][W-1-j]    k=3: r[i][j] = t[H-1-j][i]
+//   t = vflip(hflip(in)): t[y][x] = in[v ? H-1-y : y][h ? W-1-x : x]
+// so even k is a copy with rows and / or columns reversed (revY = v ^ (k==2), revX = h ^ (k==2)) and odd k is a transpose with
+// reversals: out[yo][xo] = in[ry ? N-1-xo : xo][rx ? N-1-yo : yo], k=1: ry = v, rx = !h;  k=3: ry = !v, rx = h.
+//
+// A pure permutation, HBM-bound.  One block moves one 64 x 64 tile of one plane:
+//   even k: each thread moves float4s of a row (a reversed row reads the mirrored float4 and swaps its lanes), so both sides are
+//           16-byte accesses of whole 256-byte row segments; W % 4 != 0 or unaligned bases take the dword form of the same loop.
+//   odd k:  the input tile is read by rows (a wave = one 256-byte row segment), parked in LDS with a pitch of 65 dwords and read back
+//           by columns: lane l of a wave reads dword 65 l + c, bank (l + c) mod 64 -- all 64 banks, no conflict -- and the output is
+//           written by rows again.
+// The code of a block is uniform (one sample per plane), so there is no divergence inside a block.
+#include "ff_common.h"
+
+#define D4_TILE 64
+#define D4_PITCH 65
+
+__global__ __launch_bounds__(256) void d4_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int H, int W,
+                                                      const int* __restrict__ codes, int tiles_x, int tiles_per_plane, int vec4) {
+  __shared__ float tile[D4_TILE * D4_PITCH];
+  const int plane = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane * tiles_per_plane;
+  const int ty0 = (t / tiles_x) * D4_TILE, tx0 = (t - (t / tiles_x) * tiles_x) * D4_TILE;      // origin of the OUTPUT tile
+  int code = codes[plane / C] & 15;
+  if (H != W) code &= ~4;                                    // odd k on a non-square plane is refused by the host; never index outside
+  const int h = code & 1, v = (code >> 1) & 1, k = code >> 2;
+  const float* src = in + (long long)plane * H * W;
+  float* dst = out + (long long)plane * H * W;
+  const int tid = threadIdx.x;
+  if ((k & 1) == 0) {
+    const int revY = v ^ (k >> 1), revX = h ^ (k >> 1);
+    if (vec4) {
+      const int q = tid & 15, r0 = tid >> 4;                 // 16 float4 per 64-wide row, 16 rows per pass
+      const int xo = tx0 + 4 * q;
+      if (xo < W) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int yo = ty0 + r0 + 16 * p;
+          if (yo < H) {
+            const int yi = revY ? H - 1 - yo : yo;
+            f32x4 a = *reinterpret_cast<const f32x4*>(src + (long long)yi * W + (revX ? W - 4 - xo : xo));
+            if (revX) a = (f32x4){a[3], a[2], a[1], a[0]};
+            *reinterpret_cast<f32x4*>(dst + (long long)yo * W + xo) = a;
+          }
+        }
+      }
+    } else {
+      const int xo = tx0 + (tid & 63), r0 = tid >> 6;
+      if (xo < W) {
+        for (int p = 0; p < 16; ++p) {
+          const int yo = ty0 + r0 + 4 * p;
+          if (yo < H) dst[(long long)yo * W + xo] = src[(long long)(revY ? H - 1 - yo : yo) * W + (revX ? W - 1 - xo : xo)];
+        }
+      }
+    }
+    return;
+  }
+  // odd k (H == W = N): out[yo][xo] = in[ry ? N-1-xo : xo][rx ? N-1-yo : yo]
+  const int N = H;
+  const int ry = (k == 1) ? v : !v, rx = (k == 1) ? !h : h;
+  const int nx = min(D4_TILE, N - tx0), ny = min(D4_TILE, N - ty0);       // valid extent of the output tile
+  // the input rows this tile needs are the images of its output COLUMNS and vice versa; both ranges are contiguous
+  const int iy0 = ry ? N - tx0 - nx : tx0, ix0 = rx ? N - ty0 - ny : ty0;
+  const int lx = tid & 63, lr0 = tid >> 6;
+#pragma unroll 4
+  for (int p = 0; p < 16; ++p) {
+    const int r = lr0 + 4 * p;                                            // input row iy0 + r (r < nx), input column ix0 + lx (lx < ny)
+    if (r < nx && lx < ny) tile[r * D4_PITCH + lx] = src[(long long)(iy0 + r) * N + ix0 + lx];
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int p = 0; p < 16; ++p) {
+    const int r = lr0 + 4 * p;                                            // output row ty0 + r, output column tx0 + lx
+    if (r < ny && lx < nx) {
+      const int sy = ry ? nx - 1 - lx : lx;                               // input row of output column tx0 + lx, relative to iy0
+      const int sx = rx ? ny - 1 - r : r;                                 // input column of output row ty0 + r, relative to ix0
+      dst[(long long)(ty0 + r) * N + tx0 + lx] = tile[sy * D4_PITCH + sx];
+    }
+  }
+}
+
+extern "C" int ff_d4_nchw(const float* in, float* out, int B, int C, int H, int W, const int* codes, void* stream) {
+  FF_CHECK_ARG(in && out && codes, "ff_d4_nchw: null pointer");
+  FF_CHECK_ARG(in != out, "ff_d4_nchw: the permutation is not in place (in == out)");
+  FF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "ff_d4_nchw: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+  const int tiles_x = ff_cdiv(W, D4_TILE), tiles_y = ff_cdiv(H, D4_TILE);
+  const long long blocks = (long long)B * C * tiles_x * tiles_y;
+  FF_CHECK_ARG(blocks < (1ll << 31), "ff_d4_nchw: %lld tiles exceed the grid limit", blocks);
+  const int vec4 = (W % 4 == 0) && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+  hipLaunchKernelGGL(d4_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, out, C, H, W, codes, tiles_x,
+                     tiles_x * tiles_y, vec4);
+  FF_LAUNCH_CHECK("ff_d4_nchw");
+  return FF_OK;
+}

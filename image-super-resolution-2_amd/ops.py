@@ -1147,6 +1147,48 @@ def tile_normalize(acc: T, wsum: T):
     _lib.check(_L().ff_tile_normalize(acc.data_ptr(), wsum.data_ptr(), C, H, W, _stream()))
 
 
+
+D4_CODES = 16
+
+
+def d4_check_codes(codes, H: int, W: int):
+    """Host-side validation of augmentation codes (bit 0 hflip, bit 1 vflip, bits 2-3 k of rot90) for planes of H x W -> list of ints.
+    Odd k swaps H and W: a batch must come out with one shape, so it needs square planes."""
+    cl = [int(c) for c in codes]
+    for c in cl:
+        if not 0 <= c < D4_CODES:
+            raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+        if (c >> 2) & 1 and H != W:
+            raise _lib.FFError(f"d4 code {c} rotates by an odd quarter turn, which needs square planes, got {H}x{W}")
+    return cl
+
+
+def d4_nchw(x: T, codes, out: Optional[T] = None, codes_dev: Optional[T] = None) -> T:
+    """The reference's paired augmentation (cached_dataset.py:240-268) of a planar batch [B,C,H,W]: sample b takes the symmetry
+    codes[b] = hflip | vflip << 1 | k << 2, applied as flip(-1), flip(-2), rot90(k, (-2, -1)).  `codes` is a host sequence (checked
+    here, before any launch); codes_dev, when given, is the same list already on the device (int32 [B]) so that the eight tensors
+    of a micro-batch share one upload."""
+    _chk(x, "d4_nchw.x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise _lib.FFError("d4_nchw: expected a contiguous [B,C,H,W] tensor")
+    B, C, H, W = x.shape
+    cl = d4_check_codes(codes, H, W)
+    if len(cl) != B:
+        raise _lib.FFError(f"d4_nchw: {len(cl)} codes for a batch of {B}")
+    if codes_dev is None:
+        codes_dev = torch.tensor(cl, dtype=torch.int32).to(x.device)
+    elif codes_dev.dtype != torch.int32 or not codes_dev.is_cuda or codes_dev.numel() != B or not codes_dev.is_contiguous():
+        raise _lib.FFError("d4_nchw: codes_dev must be a contiguous int32 device tensor of B elements")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _chk(out, "d4_nchw.out")
+        if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+            raise _lib.FFError("d4_nchw: out must be a distinct contiguous tensor of x's shape")
+    _lib.check(_L().ff_d4_nchw(x.data_ptr(), out.data_ptr(), B, C, H, W, codes_dev.data_ptr(), _stream()))
+    return out
+
+
 for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):

@@ -29,7 +29,7 @@ from . import lib as _lib
 MAGIC_PLAN, MAGIC_WTS = b"FFPLAN3\0", b"FFWTS01\0"
 FID_MARK = 0xFFFF
 K_INT, K_FLT, K_NULL, K_WEIGHT, K_WORK, K_INPUT, K_OUTPUT, K_STREAM = range(8)
-_PTR_TYPES = ("const float*", "float*", "void*", "const void*", "const unsigned char*", "unsigned char*", "double*", "const double*")
+_PTR_TYPES = ("const float*", "float*", "void*", "const void*", "const unsigned char*", "unsigned char*", "double*", "const double*", "const int*")
 ALIGN = 256
 
 

@@ -8,7 +8,13 @@ Drop-in for the body of the reference's `train_epoch_cached` loop (train.py:308-
 
     tr = FusionTrainer(state_dict, "cuda:0")          # reference-keyed fusion (+ collaborative) state dict
     loss = tr.step(lr, hr, outs, feats)               # one optimizer step; returns the loss (device scalar)
+    losses = tr.accumulate([mb0, mb1])                # accumulation_steps = 2: one optimizer step on the mean gradient of two micro-batches
     tr.set_epoch(epoch)                               # the reference's staged loss weights (LOSS_STAGES, get_loss_stage)
+
+Gradient accumulation (train.py:306-356 with accumulation_steps = A): every micro-batch of a window back-propagates (1/A) dloss/dsr
+into the SAME flat gradient buffer, which is zeroed only before the first one; BatchNorm statistics advance on every micro-batch;
+clip + AdamW + EMA run once per window and `step_count` counts optimizer steps; the reported losses stay unscaled.  Whole epochs
+(loader, augmentation, schedule, validation) are isr2_amd.epoch.
 
 Loss weights other than {l1: 1} run CombinedLoss's components (l1, charbonnier, l2, ssim, edge, fft, swt) on csrc/sr_losses.hip.
 
@@ -125,6 +131,8 @@ class FusionTrainer:
         self.dev, self.hp, self.dropout, self.seed = dev, dict(HP, **(hp or {})), float(dropout), int(seed)
         self.gemm = gemm
         self.step_count = 0
+        self.micro_index = 0                                          # position of the running micro-batch in its accumulation window
+        self.window_open = False                                      # an accumulation window holds gradients no optimizer step has used
         self.key_order = list(state_dict.keys())
         self.names = trainable_names(state_dict)
         self.ref_shape = {k: tuple(state_dict[k].shape) for k in self.names}
@@ -280,7 +288,8 @@ class FusionTrainer:
         """norm -> nn.MultiheadAttention(self-attention over ntok tokens per pixel) ; returns the attention output (no residual)."""
         tn = ag.layernorm(tok, self.p(norm + ".weight"), self.p(norm + ".bias"))
         qkv = ag.conv2d(tn, self.p(attn + ".in_proj_weight"), self.p(attn + ".in_proj_bias"))
-        seed = (self.seed * 1000003 + self.step_count) * 16 + layer
+        # micro-batches of one window share step_count: the golden-ratio stride keeps their mask streams apart (micro_index 0 = no offset)
+        seed = ((self.seed * 1000003 + self.step_count) * 16 + layer + self.micro_index * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
         a = ag.band_mha(qkv, P, ntok, heads, self.dropout, seed)
         return ag.conv2d(a, self.p(attn + ".out_proj.weight"), self.p(attn + ".out_proj.bias"))
 
@@ -460,8 +469,16 @@ class FusionTrainer:
     def _to_dev(self, t):
         return t.to(self.dev, torch.float32).contiguous()
 
-    def forward_backward(self, lr: T, hr: T, outs: Dict[str, T], feats: Dict[str, T]):
-        """Zero the gradient buffer, run forward + loss + backward.  Returns (sr NHWC tensor, loss [1] device tensor)."""
+    def forward_backward(self, lr: T, hr: T, outs: Dict[str, T], feats: Dict[str, T], *, zero_grad: bool = True, loss_scale: float = 1.0,
+                         micro_index: int = 0):
+        """Run forward + loss + backward.  Returns (sr NHWC tensor, loss [1] device tensor).
+        zero_grad: zero the flat gradient buffer first (False for every micro-batch of an accumulation window but the first: the
+        parameter gradients add into it).  loss_scale: factor on the gradient that enters the tape, 1 / accumulation_steps
+        (train.py:330-331); the returned loss and last_loss_components() stay UNSCALED (train.py:359).  micro_index: position in the
+        window, mixed into the attention-dropout seed so that the micro-batches of one window draw different masks."""
+        loss_scale, micro_index = float(loss_scale), int(micro_index)
+        if not (math.isfinite(loss_scale) and loss_scale > 0.0) or micro_index < 0:
+            raise _lib.FFError(f"forward_backward: loss_scale {loss_scale} must be finite and > 0, micro_index {micro_index} >= 0")
         lr, hr = self._to_dev(lr), self._to_dev(hr)
         outs = {k: self._to_dev(v) for k, v in outs.items()}
         feats = {k: self._to_dev(v) for k, v in feats.items()}
@@ -470,24 +487,33 @@ class FusionTrainer:
         if self.gemm is not None:
             ops.set_gemm_mode(self.gemm)
         try:
-            return self._forward_backward(lr, hr, outs, feats)
+            self.micro_index = micro_index
+            res = self._forward_backward(lr, hr, outs, feats, zero_grad, loss_scale)
+            self.window_open = not (zero_grad and loss_scale == 1.0 and micro_index == 0)
+            return res
         finally:
+            self.micro_index = 0
             ops.set_gemm_mode(old_mode)
 
-    def _forward_backward(self, lr, hr, outs, feats):
+    def _forward_backward(self, lr, hr, outs, feats, zero_grad=True, loss_scale=1.0):
         with torch.cuda.device(self.dev):
-            self.G.zero_()
+            if zero_grad:
+                self.G.zero_()
             with ag.Tape() as tape:
                 sr = self.forward(lr, outs, feats)
                 hr_nhwc = ops.nchw_to_nhwc(hr)
                 dsr = torch.empty_like(sr.data)
-                if self._default_loss:
+                if self._default_loss and loss_scale == 1.0:
                     _lib.check(_lib.load().ff_l1_loss_grad(sr.data.data_ptr(), hr_nhwc.data_ptr(), dsr.data_ptr(), sr.data.numel(),
                                                            self.loss.data_ptr(), self.work.data_ptr(), 1024, ag._st()))
                 else:
                     if self.srloss is None:
                         self.srloss = ag.SRLoss(self.dev)
-                    self.srloss.combined(self.active_losses, sr.data, hr_nhwc, dsr, self.loss_values, self.active_w, self.loss)
+                    if self._default_loss:                            # the L1 value unweighted, its gradient times loss_scale
+                        self.srloss.component("l1", sr.data, hr_nhwc, loss_scale, dsr, value=self.loss)
+                    else:                                             # gradient weights w_k * loss_scale; the total keeps the plain w_k
+                        scaled = [(k, w * loss_scale) for k, w in self.active_losses]
+                        self.srloss.combined(scaled, sr.data, hr_nhwc, dsr, self.loss_values, self.active_w, self.loss)
                 sr.grad, sr.owned = dsr, True
                 tape.backward()
         self._vars = {}
@@ -497,6 +523,7 @@ class FusionTrainer:
         """clip_grad_norm_(max_norm) + AdamW + EMA over the flat buffers: two launches."""
         hp = self.hp
         self.step_count += 1
+        self.window_open = False
         t = self.step_count
         lr_now = hp["lr"] if lr_now is None else lr_now
         b1, b2 = hp["betas"]
@@ -516,6 +543,28 @@ class FusionTrainer:
             grad_hook(self.G)
         self.optimizer_step(lr_now)
         return loss
+
+    def accumulate(self, micro_batches, lr_now: Optional[float] = None, grad_hook=None) -> List[float]:
+        """One optimizer step on the mean gradient of A = len(micro_batches) micro-batches, each (lr, hr, outs, feats): the window of
+        train.py:308-356 with accumulation_steps = A.  grad_hook (the multi-GPU all-reduce) runs once, after the last micro-batch.
+        Returns the unscaled loss of every micro-batch.  A = 1 is step() bit for bit."""
+        A = len(micro_batches)
+        if A < 1:
+            raise _lib.FFError("accumulate: no micro-batches")
+        losses = []
+        for i, (lr, hr, outs, feats) in enumerate(micro_batches):
+            _, loss = self.forward_backward(lr, hr, outs, feats, zero_grad=i == 0, loss_scale=1.0 / A, micro_index=i)
+            losses.append(loss.clone())                               # self.loss is overwritten by the next micro-batch
+        if grad_hook is not None:
+            grad_hook(self.G)
+        self.optimizer_step(lr_now)
+        return [float(v) for v in torch.cat(losses).cpu()]
+
+    def discard_window(self):
+        """Drop the gradients of an incomplete window (the reference's optimizer.zero_grad() at the top of the next epoch,
+        train.py:306); the BatchNorm statistics its micro-batches advanced stay."""
+        self.G.zero_()
+        self.window_open = False
 
     # ---------------------------------------------------------------------------------------------------- state
     def _export(self, flat: T) -> "OrderedDict[str, T]":
@@ -604,6 +653,9 @@ def _trainer_save(self, path: str, epoch: int, metrics: Optional[dict] = None, l
                   scheduler_state: Optional[dict] = None) -> str:
     """Write a checkpoint in the reference's layout (loadable by its CheckpointManager.load_checkpoint when this trainer was built
     from a complete reference state dict; a later FusionTrainer.load_checkpoint resumes bit-exactly either way)."""
+    if self.window_open:
+        raise _lib.FFError("save_checkpoint inside an open accumulation window: checkpoints are written at window boundaries "
+                           "(finish the window with optimizer_step() or drop it with discard_window())")
     ck = build_checkpoint(self.state_dict_in_order(), self._export(self.M), self._export(self.V), self.ema_shadow(), self.step_count, self.hp,
                           epoch, metrics, lr_now, scheduler_state, stage=self.stage)
     ck["ff_trainer"] = {"seed": self.seed, "dropout": self.dropout, "step_count": self.step_count}
@@ -707,3 +759,8 @@ def distributed_step(tr: "FusionTrainer", lr, hr, outs, feats, world: int, lr_no
     """One data-parallel step: local forward/backward on this rank's shard, all-reduce(mean) of the flat gradient, identical
     optimizer step on every rank (parameters stay bit-identical across ranks: same averaged gradient, same deterministic kernels)."""
     return tr.step(lr, hr, outs, feats, lr_now, grad_hook=lambda g: allreduce_mean_(g, world))
+
+
+def distributed_accumulate(tr: "FusionTrainer", micro_batches, world: int, lr_now: Optional[float] = None) -> List[float]:
+    """distributed_step with gradient accumulation: every rank accumulates its own window, ONE all-reduce after its last micro-batch."""
+    return tr.accumulate(micro_batches, lr_now, grad_hook=lambda g: allreduce_mean_(g, world))

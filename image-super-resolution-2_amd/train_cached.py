@@ -1,0 +1,61 @@
+"""Fine-tune the fusion stack from a cached-expert directory with the reference's shipped configuration (configs/train_config.yaml:
+AdamW 1.5e-4, warm-up 5 epochs + cosine restarts, batch 14, accumulation_steps 2, repeat_factor 20, EMA 0.9995, staged losses):
+
+    python -m isr2_amd.train_cached --cache DIR --val-cache DIR --out DIR --epochs N [--resume PATH] [--weights PATH]
+                                    [--batch 14] [--accum 2] [--repeat 20] [--validate-every 1] [--seed 0] [--no-augment]
+                                    [--dropout 0.1] [--gemm f32]
+
+The cache directories hold the two part files per sample that isr2_amd.cache.write_sample / extract (or the reference's own feature
+extraction) write.  --weights: a reference-keyed fusion (+ collaborative) state dict, bare or under `model_state_dict`; without it
+the seeded synthetic weights are used (smoke runs).  One JSON line per epoch on stdout; DIR/latest.pth after every
+epoch, DIR/best.pth on a new best validation PSNR (EMA weights).  --resume continues at the checkpoint's epoch + 1."""
+from __future__ import annotations
+
+import argparse
+import sys
+
+import torch
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m isr2_amd.train_cached", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--cache", required=True)
+    ap.add_argument("--val-cache", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--epochs", type=int, required=True)
+    ap.add_argument("--resume")
+    ap.add_argument("--weights")
+    ap.add_argument("--batch", type=int, default=14)
+    ap.add_argument("--accum", type=int, default=2)
+    ap.add_argument("--repeat", type=int, default=20)
+    ap.add_argument("--validate-every", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--no-augment", action="store_true")
+    ap.add_argument("--dropout", type=float, default=0.1)
+    ap.add_argument("--gemm", default="f32", choices=("f32", "bf16x3"))
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+
+    from . import epoch as E
+    from .train import FusionTrainer
+    from .weights import synth_state_dict
+    if a.weights:
+        ck = torch.load(a.weights, map_location="cpu", weights_only=True)
+        sd = ck.get("model_state_dict", ck) if isinstance(ck, dict) else ck
+        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
+    else:
+        sd = synth_state_dict(1234, parts=("fusion", "collab"))
+    tr = FusionTrainer(sd, a.device, dropout=a.dropout, seed=a.seed, gemm=a.gemm)
+    start, best = 0, float("-inf")
+    if a.resume:
+        ck = tr.load_checkpoint(a.resume)
+        start = int(ck["epoch"]) + 1
+        best = float(ck.get("metrics", {}).get("best_psnr", best))
+    data = E.CachedEpoch(a.cache, a.batch, a.repeat, augment=not a.no_augment, seed=a.seed, device=a.device)
+    E.fit(tr, data, lambda: E.read_samples(a.val_cache), a.out, a.epochs, start, a.accum, a.validate_every, best,
+          log=lambda line: print(line, flush=True))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -483,6 +483,13 @@ int ff_loss_fft(const float* sr, const float* hr, int B, int H, int W, const flo
                 void* stream);
 int ff_loss_combine(const float* values, const float* weights, int k, float* total, void* stream);
 
+/* Paired training augmentation (csrc/augment.hip; CachedSRDataset._apply_augmentation, src/data/cached_dataset.py:240-268): every
+ * sample b of a planar batch in [B][C][H][W] -> out [B][C][H][W] takes its own symmetry of the square, codes[b] (DEVICE ints) =
+ * bit 0 hflip | bit 1 vflip | bits 2-3 k, applied in the reference's order flip(-1), flip(-2), rot90(k, dims (-2, -1)).  Odd k
+ * transposes, so it needs H == W (on a non-square batch the bit is ignored: the host wrapper refuses such codes before any launch).
+ * A pure permutation, not in place; one launch per tensor per batch. */
+int ff_d4_nchw(const float* in, float* out, int B, int C, int H, int W, const int* codes, void* stream);
+
 /* C-level executor (csrc/ff_executor.hip): the whole forward -- models/team29_FreqFusion/io.py:221 `model(lr)` =
  * CompleteEnhancedFusionSR.forward, src/models/enhanced_fusion.py:694-754 -- for callers without Python.  A plan
  * (<stem>.ffplan, written by isr2_amd.plan.export_plan) lists every launch of one input shape with pointers expressed as
