@@ -8,13 +8,12 @@ step is a libff_hip.so kernel (ops.py), PyTorch only allocates.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional
 
 import torch
 
 from . import ops
-from .prep import (pack_conv, pack_dw, bn_scale_shift, fold_bn_after_conv, pack_token_mlp, pack_token_linear, pack_naf_ffn, pack_naf_tail,
+from .prep import (pack_conv, pack_dw, bn_scale_shift, fold_bn_after_conv, pack_token_linear, pack_naf_ffn, pack_naf_tail,
                    pack_win_attn, pack_win_rel, pack_token_projmlp, pack_chan_qkv, pack_token_linear_gated, pack_rel_overlap)
 
 T = torch.Tensor
@@ -51,31 +50,6 @@ def _tl(blk: dict, key: str) -> dict:
     return pk
 
 
-# plain bf16: intermediates that are consumed only as bf16 MFMA operands live in HBM as bf16
-_BF16_ROWS = os.environ.get("FF_BF16_ROWS", "1") != "0"
-_OCAB_V2 = os.environ.get("FF_OCAB_V2", "1") != "0"          # plain bf16: HAT's overlapping cross-attention in the persistent per-window kernel
-_SGFN_TAIL = os.environ.get("FF_SGFN_TAIL", "1") != "0"      # plain bf16: DAT's SpatialGate + fc2 + residual in one launch
-
-
-def _fast() -> bool:
-    """The token-stationary fused kernels exist for the default split-bf16 contraction only."""
-    return ops.fused_modes()
-
-
-# Window-resident attention block (LayerNorm + qkv + attention in one launch, csrc/win_attn_fused.hip); FF_WIN_FUSED=0 keeps
-# the two-stage form (token_linear qkv -> window_attn) for A/B measurements.
-_WIN_FUSED = os.environ.get("FF_WIN_FUSED", "1") != "0"
-# Attention projection + residuals + norm2 + MLP in one launch (csrc/token_mlp.hip: token_projmlp_kernel); 0 = two launches
-_PROJ_MLP = os.environ.get("FF_PROJ_MLP", "1") != "0"
-# DAT SpatialGate: LayerNorm statistics from the fc1 epilogue, normalisation on load in the depth-wise conv: 101 us against
-# 45 + 72 us for the separate LayerNorm pass + plain strip kernel (tools/block_timeline.py).  FF_LN_ON_LOAD=0 restores those.
-_LN_ON_LOAD = os.environ.get("FF_LN_ON_LOAD", "1") != "0"
-# DAT channel attention: LayerNorm + qkv + gram / norms in one launch (csrc/chan_qkv.hip); 0 = token_linear qkv + VALU gram kernel
-_CHAN_FUSED = os.environ.get("FF_CHAN_FUSED", "1") != "0"
-# DAT: spatial gate + channel gate + mix + projection + residual in one launch (ff_token_linear_gated); 0 = pixel_mlp, mix2, token_linear
-_GATED_PROJ = os.environ.get("FF_GATED_PROJ", "1") != "0"
-
-
 def _pm(blk: dict) -> dict:
     pk = blk.get("projmlp_pk")
     if pk is None:
@@ -93,17 +67,6 @@ def _wf(blk: dict, heads: int, d: int) -> dict:
 
 
 # =============================================================================================== HAT
-# Gathering the attention bias from the compact relative-position table in LDS removes the 400 MB / launch bias stream but
-# measured SLOWER on MI355X (120 vs 108 us per launch: the kernel is issue / LDS bound, not bandwidth bound), so the
-# expanded quad-interleaved table stays the default; FF_REL_BIAS=1 selects the gather.
-_REL_BIAS = os.environ.get("FF_REL_BIAS", "0") == "1"
-_NAF_FRONT = os.environ.get("FF_NAF_FRONT", "1") == "1"      # NAFBlock front half (norm1 + conv1 + conv2 + gate + pool) in one launch at C = 64 / 128
-# OCAB (576 keys per window): FF_REL_OCAB=1 gathers the bias from the rotated compact table in LDS instead of streaming the expanded
-# one (3.5 MB per head).  Bit-identical, 430 MB less traffic per launch, but 314 vs 207 us on MI355X (two dependent LDS reads per score):
-# the expanded table stays the default.
-_REL_OCAB = os.environ.get("FF_REL_OCAB", "0") == "1"
-
-
 def _rel_index_sa(ws: int) -> T:
     ys, xs = torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")
     yy, xx = ys.reshape(-1), xs.reshape(-1)
@@ -170,10 +133,7 @@ class HatHIP:
 
     # -- blocks -------------------------------------------------------------------------------
     def _mlp(self, x: T, blk: dict) -> T:
-        if ops.fused_modes():                                # fused LN + fc1 + GELU + fc2 + residual, hidden stays on chip
-            if "mlp_pk" not in blk:
-                blk["mlp_pk"] = pack_token_mlp(blk["fc1"][0], blk["fc1"][1], blk["fc2"][0], blk["fc2"][1])
-            return ops.token_mlp(x, blk["n2"][0], blk["n2"][1], blk["mlp_pk"])
+        """x + MLP(norm2(x)) of the f32 route; the fused modes run it inside token_projmlp."""
         xn = ops.layernorm(x, *blk["n2"])
         h = ops.linear(xn, *blk["fc1"], act="gelu")
         return ops.linear(h, *blk["fc2"], res=x)
@@ -181,57 +141,56 @@ class HatHIP:
     def hab(self, x: T, blk: dict) -> T:
         _, H, W, C = x.shape
         d = C // self.heads
+        fused = ops.fused_modes()
         # plain bf16: att, the normalised rows and conv1's output are consumed only as MFMA operands (rounded to bf16 there), so they are
         # stored as bf16 -- bit-identical results, half the bytes; conv2's output enters x1 times conv_scale = 0.01 and goes the same way
-        b16 = (_BF16_ROWS and ops.gemm_mode() == "bf16" and _fast() and _WIN_FUSED and _PROJ_MLP and x.shape[0] == 1
-               and H * W >= 1024 and C % 4 == 0)
+        b16 = ops.gemm_mode() == "bf16" and x.shape[0] == 1 and H * W >= 1024 and C % 4 == 0
         att = ops.empty_rows_bf16(tuple(x.shape), x.device) if b16 else ops.empty_like_rows(x)
         s = blk["shift"]
-        if _fast() and _WIN_FUSED:                                 # norm1 + qkv + (S)W-MSA of all six heads in one launch
+        if fused:                                                  # norm1 + qkv + (S)W-MSA of all six heads in one launch (csrc/win_attn_fused.hip)
             if "relp" not in blk:
                 blk["relp"] = pack_win_rel(blk["rel"], self.ws, self.ws)
             _, xn = ops.win_attn_fused(x, att, _wf(blk, self.heads, d), blk["relp"], gamma=blk["n1"][0], beta=blk["n1"][1], H=H, W=W,
                                        Hp=H, Wp=W, win=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, want_xn="bf16" if b16 else True)
         else:
-            if _fast():                                            # LayerNorm inside the qkv launch; xn (conv branch) is its side output
-                qkv, xn = ops.token_linear(x, _tl(blk, "qkv"), gamma=blk["n1"][0], beta=blk["n1"][1], want_xn=True)
-            else:
-                xn = ops.layernorm(x, *blk["n1"])
-                qkv = ops.linear(xn, *blk["qkv"])
+            xn = ops.layernorm(x, *blk["n1"])
+            qkv = ops.linear(xn, *blk["qkv"])
+            # the bias streams from the expanded quad-interleaved table: gathering it from the compact relative-position table in LDS
+            # removes the 400 MB / launch bias stream but measured SLOWER on MI355X (120 vs 108 us per launch: the kernel is issue /
+            # LDS bound, not bandwidth bound)
             ops.window_attn(qkv, att, blk["bias"], q_off=0, k_off=C, v_off=2 * C, o_off=0, H=H, W=W, Hp=H, Wp=W, win=(self.ws, self.ws),
-                            kwin=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, heads=self.heads, d=d, scale=d ** -0.5,
-                            rel_table=blk["rel"] if _REL_BIAS else None)
+                            kwin=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, heads=self.heads, d=d, scale=d ** -0.5)
         c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16)
         c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=b16)   # pool partials from the conv epilogue
         gate = ops.vec_mlp(c2mean, *blk["ca1"], "relu", *blk["ca2"], "sigmoid", post=self.conv_scale)
-        if _fast() and _PROJ_MLP:                                  # proj + both residuals + norm2 + MLP: x1 never reaches memory
+        if fused:                                                  # proj + both residuals + norm2 + MLP: x1 never reaches memory
             return ops.token_projmlp(att, x, _pm(blk), blk["n2"][0], blk["n2"][1], c2=c2, c2_scale=gate.reshape(-1))
-        if _fast():                                                # shortcut + conv_x*conv_scale + proj(attention), one launch
-            x = ops.token_linear(att, _tl(blk, "proj"), res=x, res2=c2, res2_scale=gate.reshape(-1))
-        else:
-            t = ops.mix2(x, c2, cb=gate)
-            x = ops.linear(att, *blk["proj"], res=t)
+        t = ops.mix2(x, c2, cb=gate)
+        x = ops.linear(att, *blk["proj"], res=t)
         return self._mlp(x, blk)
 
     def ocab_block(self, x: T, blk: dict) -> T:
         _, H, W, C = x.shape
         d = C // self.heads
-        if _fast():
+        fused = ops.fused_modes()
+        if fused:
             qkv = ops.token_linear(x, _tl(blk, "qkv"), gamma=blk["n1"][0], beta=blk["n1"][1])      # LayerNorm fused
         else:
             qkv = ops.linear(ops.layernorm(x, *blk["n1"]), *blk["qkv"])
-        ocab_v2 = _OCAB_V2 and ops.gemm_mode() == "bf16" and (self.ws, self.ows, d) == (16, 24, 30) and H % 16 == 0 and W % 16 == 0
-        att = ops.empty_rows_bf16(tuple(x.shape), x.device) if (ocab_v2 and _BF16_ROWS and _fast() and _PROJ_MLP) else ops.empty_like_rows(x)
-        if ocab_v2:
+        if ops.gemm_mode() == "bf16" and (self.ws, self.ows, d) == (16, 24, 30) and H % 16 == 0 and W % 16 == 0:
+            att = ops.empty_rows_bf16(tuple(x.shape), x.device)    # consumed only as an MFMA operand, as in hab
             ops.ocab_attn(qkv, att, blk["rel"], q_off=0, k_off=C, v_off=2 * C, H=H, W=W, heads=self.heads, d=d, ws=self.ws, ows=self.ows,
                           scale=d ** -0.5)                 # persistent per-window kernel, compact bias table in LDS (csrc/ocab_attn.hip)
         else:
+            # 576 keys per window, the bias streams from the expanded table (3.5 MB per head): gathering it in window_attn from the
+            # rotated compact table in LDS is bit-identical and 430 MB less traffic per launch, but 314 vs 207 us on MI355X (two
+            # dependent LDS reads per score)
+            att = ops.empty_like_rows(x)
             ops.window_attn(qkv, att, blk["bias"], q_off=0, k_off=C, v_off=2 * C, o_off=0, H=H, W=W, Hp=H, Wp=W, win=(self.ws, self.ws),
-                            kwin=(self.ows, self.ows), shift=(0, 0), use_mask=False, heads=self.heads, d=d, scale=d ** -0.5,
-                            rel_table=blk["rel"] if _REL_OCAB else None)
-        if _fast() and _PROJ_MLP:
+                            kwin=(self.ows, self.ows), shift=(0, 0), use_mask=False, heads=self.heads, d=d, scale=d ** -0.5)
+        if fused:
             return ops.token_projmlp(att, x, _pm(blk), blk["n2"][0], blk["n2"][1])
-        x = ops.token_linear(att, _tl(blk, "proj"), res=x) if _fast() else ops.linear(att, *blk["proj"], res=x)
+        x = ops.linear(att, *blk["proj"], res=x)
         return self._mlp(x, blk)
 
     def group(self, x: T, g: int) -> T:
@@ -360,12 +319,13 @@ class DatHIP:
         _, H, W, C = x.shape
         half, hh = C // 2, self.heads // 2
         d = half // hh
-        fused = blk["spatial"] and _fast() and _WIN_FUSED
-        if fused:
-            # norm1 + qkv + both window-attention branches: two launches (head groups 0-2 on 8x32 windows, 3-5 on 32x8), each
-            # also writes its half of v for the depth-wise conv branch (dat_arch.py:524); q and k never reach memory
+        fused = ops.fused_modes()
+        if blk["spatial"]:
             m = max(self.split)
             Hp, Wp = _ceil_to(H, m), _ceil_to(W, m)
+        if fused and blk["spatial"]:
+            # norm1 + qkv + both window-attention branches: two launches (head groups 0-2 on 8x32 windows, 3-5 on 32x8), each
+            # also writes its half of v for the depth-wise conv branch (dat_arch.py:524); q and k never reach memory
             att = ops.empty_like_rows(x)
             v = ops.empty_like_rows(x)
             pk = _wf(blk, self.heads, d)
@@ -382,70 +342,58 @@ class DatHIP:
                 ops.win_attn_fused(x, att, pk, blk["relp"][br], gamma=blk["n1"][0], beta=blk["n1"][1], H=H, W=W, Hp=Hp, Wp=Wp,
                                    win=(wh, ww), shift=sh, use_mask=blk["shifted"], head0=hh * br, nheads=hh, zero_pad=True,
                                    v_out=v, v_off=0)
-        elif not blk["spatial"] and _fast() and _CHAN_FUSED:
+        elif fused:
             # norm1 + qkv + per-head gram / norms over all tokens in one launch: only v reaches memory (dat_arch.py:617-641)
             if "cq_pk" not in blk:
                 blk["cq_pk"] = pack_chan_qkv(blk["qkv"][0], blk["qkv"][1], self.heads, C // self.heads)
             v, wbd = ops.chan_qkv_attn(x, blk["cq_pk"], blk["n1"][0], blk["n1"][1], blk["temp"])
-            qkv = None
         else:
-            if _fast():
-                qkv = ops.token_linear(x, _tl(blk, "qkv"), gamma=blk["n1"][0], beta=blk["n1"][1])   # LayerNorm fused
-            else:
-                qkv = ops.linear(ops.layernorm(x, *blk["n1"]), *blk["qkv"])          # [1,H,W,3C] = q | k | v
+            qkv = ops.linear(ops.layernorm(x, *blk["n1"]), *blk["qkv"])              # [1,H,W,3C] = q | k | v
             v = qkv[..., 2 * C:]
         conv_x = ops.dwconv2d(v, blk["dw"][0], blk["dw"][1], post_scale=blk["dw"][2], post_shift=blk["dw"][3], act="gelu")
         if blk["spatial"]:
             if not fused:
-                m = max(self.split)
-                Hp, Wp = _ceil_to(H, m), _ceil_to(W, m)
                 att = ops.empty_like_rows(x)
                 for br in range(2):
                     wh, ww = (self.split[0], self.split[1]) if br == 0 else (self.split[1], self.split[0])
                     sh = (wh // 2, ww // 2) if blk["shifted"] else (0, 0)
                     ops.window_attn(qkv, att, blk["bias"][br], q_off=br * half, k_off=C + br * half, v_off=2 * C + br * half,
                                     o_off=br * half, H=H, W=W, Hp=Hp, Wp=Wp, win=(wh, ww), kwin=(wh, ww), shift=sh,
-                                    use_mask=blk["shifted"], heads=hh, d=d, scale=d ** -0.5,
-                                    rel_table=blk["rel"][br] if _REL_BIAS else None)
+                                    use_mask=blk["shifted"], heads=hh, d=d, scale=d ** -0.5)
             ch_in, sp_in = conv_x, att
         else:
-            if qkv is not None:
+            if not fused:
                 wbd = ops.chan_attn_weights(qkv, 0, C, blk["temp"])
             att = ops.linear(v, wbd, dynamic_w=True)
             ch_in, sp_in = att, conv_x
         cm = ops.vec_mlp(ops.pool_partials(ch_in), *blk["ci1"], "gelu", *blk["ci4"], "sigmoid")          # [1,C]; pool finish inside the MLP launch
-        if _fast() and _GATED_PROJ:
+        if fused:
             # spatial gate (from sp_in, applied to ch_in) + channel gate (applied to sp_in) + projection + residual in one launch
             if "gp_pk" not in blk:
                 blk["gp_pk"] = pack_token_linear_gated(blk["proj"][0], blk["proj"][1], blk["si0"][0], blk["si0"][1], blk["si3"][0])
             x = ops.token_linear_gated(sp_in, ch_in, blk["gp_pk"], cm.reshape(-1), blk["si3b"], res=x)
             return self._sgfn(x, blk)
-        if _fast():                                                # 180 -> 11 -> 1 per pixel in one pass (fp32)
-            sm = ops.pixel_mlp(sp_in, blk["si0"][0], blk["si0"][1], "gelu", blk["si3"][0], blk["si3b"], "sigmoid")
-        else:
-            sm = ops.linear(ops.linear(sp_in, *blk["si0"], act="gelu"), *blk["si3"], act="sigmoid")      # [1,H,W,1]
+        sm = ops.linear(ops.linear(sp_in, *blk["si0"], act="gelu"), *blk["si3"], act="sigmoid")          # [1,H,W,1]
         if blk["spatial"]:
-            fused = ops.mix2(att, conv_x, ca=cm, pb=sm)
+            mixed = ops.mix2(att, conv_x, ca=cm, pb=sm)
         else:
-            fused = ops.mix2(att, conv_x, pa=sm, cb=cm)
-        x = ops.token_linear(fused, _tl(blk, "proj"), res=x) if _fast() else ops.linear(fused, *blk["proj"], res=x)
+            mixed = ops.mix2(att, conv_x, pa=sm, cb=cm)
+        x = ops.linear(mixed, *blk["proj"], res=x)
         return self._sgfn(x, blk)
 
     def _sgfn(self, x: T, blk: dict) -> T:
         """x + SGFN(norm2(x)) (dat_arch.py:155-170, :736)."""
-        if _fast() and _LN_ON_LOAD:
-            # fc1 + GELU also emits the SpatialGate LayerNorm statistics of its upper half; the depth-wise conv normalises on load
+        if ops.fused_modes():
+            # fc1 + GELU also emits the SpatialGate LayerNorm statistics of its upper half; the depth-wise conv normalises on load:
+            # 101 us against 45 + 72 us for a separate LayerNorm pass + the plain strip kernel (tools/block_timeline.py)
             c2 = blk["fc1"][0].shape[0] // 2
             y, stats = ops.token_linear(x, _tl(blk, "fc1"), gamma=blk["n2"][0], beta=blk["n2"][1], act="gelu", stats_range=(c2, 2 * c2))
-            if _SGFN_TAIL and ops.gemm_mode() == "bf16" and blk["fc2"][0].shape[0] <= 192 and c2 % 4 == 0 and c2 <= 512:
+            if ops.gemm_mode() == "bf16" and blk["fc2"][0].shape[0] <= 192 and c2 % 4 == 0 and c2 <= 512:
                 # SpatialGate + fc2 + residual in one launch: the gate product never reaches memory (csrc/sgfn_tail.hip)
                 return ops.sgfn_tail(y, c2, blk["sgc"][0], blk["sgc"][1], stats, blk["sgn"][0], blk["sgn"][1], blk["fc2"][0], blk["fc2"][1], res=x)
             z = ops.dwconv3x3_ln(y[..., c2:], blk["sgc"][0], blk["sgc"][1], stats, blk["sgn"][0], blk["sgn"][1], mul_in=y[..., :c2])
             return ops.linear(z, *blk["fc2"], res=x)
-        if _fast():
-            y = ops.token_linear(x, _tl(blk, "fc1"), gamma=blk["n2"][0], beta=blk["n2"][1], act="gelu")
-        else:
-            y = ops.linear(ops.layernorm(x, *blk["n2"]), *blk["fc1"], act="gelu")
+        y = ops.linear(ops.layernorm(x, *blk["n2"]), *blk["fc1"], act="gelu")
         c2 = y.shape[-1] // 2
         gte = ops.layernorm(y[..., c2:], *blk["sgn"])
         z = ops.dwconv2d(gte, *blk["sgc"], mul_in=y[..., :c2])                     # dw3x3(LN(x2)) * x1 in one pass
@@ -519,8 +467,8 @@ class NafnetHIP:
 
     def block(self, x: T, k: dict) -> T:
         c = x.shape[-1]
-        flash = _fast() and c in (64, 128)                                   # HR levels: the bandwidth-bound ones
-        if flash and _NAF_FRONT and c == 64:                                 # LayerNorm2d + conv1 + conv2 + SimpleGate + pool sums: one launch (313 vs 381 us at
+        flash = ops.fused_modes() and c in (64, 128)                         # HR levels: the bandwidth-bound ones
+        if flash and c == 64:                                                # LayerNorm2d + conv1 + conv2 + SimpleGate + pool sums: one launch (313 vs 381 us at
                                                                              # 1024 x 1024; the 128-channel form fits one workgroup per CU only and ties: 222 vs 217)
             g, pooled = ops.naf_front(x, _tl(k, "c1"), k["n1"][0], k["n1"][1], *k["c2"])
         else:

@@ -104,19 +104,12 @@ def gemm_mode() -> str:
     return _GEMM_MODE
 
 
-_SMALL = _os.environ.get("FF_SMALL_CONV", "1") != "0"     # fp32 VALU kernel for 3x3 convolutions with Cout <= 16, Cin <= 64
-_HALO = _os.environ.get("FF_HALO", "1") != "0"     # LDS-resident 3x3 convolution (csrc/conv3x3_halo.hip); 0 = generic implicit GEMM
+_HALO = True     # LDS-resident 3x3 convolution (csrc/conv3x3_halo.hip); False = generic implicit GEMM, also the fallback for shapes it does not take
 
 
 def set_halo(on: bool) -> None:
     global _HALO
     _HALO = bool(on)
-
-
-_PAD_PITCH = _os.environ.get("FF_PAD_PITCH", "1") != "0"
-
-
-_PAD_ROWS = _os.environ.get("FF_PAD_ROWS", "1") != "0"
 
 
 def empty_rows_bf16(shape, device) -> T:
@@ -127,11 +120,11 @@ def empty_rows_bf16(shape, device) -> T:
 
 
 def empty_rows(shape, device) -> T:
-    """fp32 activation buffer [..., C].  The row pitch is rounded up (FF_PAD_ROWS=0 disables) to a multiple of 32 floats when C is
-    not one already (180 -> 192, 60 -> 64, 720 -> 736): every 32-channel segment a GEMM epilogue stores is then a whole
-    128-byte line instead of straddling two.  Kernels take the pitch as their ld argument; the padding is never touched."""
+    """fp32 activation buffer [..., C].  The row pitch is rounded up to a multiple of 32 floats when C is not one already
+    (180 -> 192, 60 -> 64, 720 -> 736): every 32-channel segment a GEMM epilogue stores is then a whole 128-byte line
+    instead of straddling two.  Kernels take the pitch as their ld argument; the padding is never touched."""
     C = int(shape[-1])
-    if _PAD_ROWS and C >= 48 and C % 32 != 0:
+    if C >= 48 and C % 32 != 0:
         return torch.empty(tuple(shape[:-1]) + ((C + 31) // 32 * 32,), device=device, dtype=torch.float32)[..., :C]
     return torch.empty(tuple(shape), device=device, dtype=torch.float32)
 
@@ -163,9 +156,6 @@ def set_lane(k: int) -> None:
 _CAPTURE_KEY = None
 _PERSIST_GRAPH: Dict[tuple, Dict[tuple, T]] = {}
 _PERSIST_EAGER: Dict[tuple, T] = {}
-
-
-_POOL_MLP = _os.environ.get("FF_POOL_MLP", "1") != "0"     # pool finish + channel-attention MLP in one launch
 
 
 def set_capture_key(key) -> None:
@@ -379,7 +369,7 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
         if tuple(res.shape) != oshape:
             raise _lib.FFError(f"conv2d: res shape {tuple(res.shape)} != {oshape}")
         rp, ldr, *_ = _nhwc(res, "conv2d.res")
-    if (_SMALL and _GEMM_MODE != "f32" and (KH, KW) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1) and Cout <= 16
+    if (_GEMM_MODE != "f32" and (KH, KW) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1) and Cout <= 16
             and Cin * (1 if Cout == 1 else (4 if Cout <= 4 else 16)) <= 128 and shuffle == 0 and mul is None and not dynamic_w and H * W >= 4096 and xp != op):
         # small-channel tail convolutions: exact fp32 on the VALU from an LDS halo tile (csrc/conv3x3_small.hip).  Measured on
         # MI355X at 1024 x 1024: 16->3 205 -> <70 us, 8->1 160 -> <70, 16->1 204 -> <70, 32->3 166 -> 95, 6->16 173 -> 126; but
@@ -610,10 +600,10 @@ def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T]
     if K != pk["K"]:
         raise _lib.FFError("token_linear: K mismatch")
     N = pk["N"]
-    # wide outputs (qkv, fc1) get a row pitch that is a multiple of 32 floats: every 32-column store segment of the kernel
-    # is then one whole 128-byte line (no partial-line writes); consumers take the pitch as their ld argument
-    ldo = (N + 31) // 32 * 32 if ((_PAD_PITCH and N > 192) or (_PAD_ROWS and N >= 48)) else N
-    out = torch.empty(tuple(x.shape[:-1]) + (ldo,), device=x.device, dtype=torch.float32)[..., :N]
+    # the padded row pitch of empty_rows makes every 32-column store segment of the kernel one whole 128-byte line (no
+    # partial-line writes); consumers take the pitch as their ld argument
+    out = empty_rows(tuple(x.shape[:-1]) + (N,), x.device)
+    op, ldo, _, _ = rows_view(out, "token_linear.out")
     rp, ldr, r2p, ldr2 = None, 0, None, 0
     if res is not None:
         rp, ldr, rr, rc = rows_view(res, "token_linear.res")
@@ -634,7 +624,7 @@ def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T]
         slo, shi = stats_range
         stats = torch.empty((rows, 2), device=x.device, dtype=torch.float32)
         sp = stats.data_ptr()
-    _lib.check(_L().ff_token_linear(xp, ldx, out.data_ptr(), ldo, rows, K, pk["kpad"], N, pk["nt"], _ptr(gamma), _ptr(beta), float(eps),
+    _lib.check(_L().ff_token_linear(xp, ldx, op, ldo, rows, K, pk["kpad"], N, pk["nt"], _ptr(gamma), _ptr(beta), float(eps),
                                     pk["w"].data_ptr(), _ptr(pk["b"]), ACT[act], rp, ldr, r2p, ldr2, _ptr(res2_scale), xnp, ldxn,
                                     sp, slo, shi, float(stats_eps), _nterms(), _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K * (2 if want_xn else 1) + rows * N * (1 + (res is not None) + (res2 is not None))))
@@ -725,7 +715,7 @@ def layernorm(x: T, gamma: T, beta: T, eps: float = 1e-5, out: Optional[T] = Non
 def pool_partials(x: T):
     """First stage of the global average pool of one image [1,H,W,C] -> PoolPartials (vec_mlp finishes them in its own launch)."""
     xp, ld, B, H, W, C = _nhwc(x, "pool_partials.x")
-    if B != 1 or not _POOL_MLP:
+    if B != 1:
         return pool_mean(x)
     P = H * W
     rows = int(_L().ff_pool_partial_rows(P))
@@ -751,7 +741,7 @@ def vec_mlp(v, W1: T, b1: Optional[T], act1, W2: Optional[T] = None, b2: Optiona
     """act2(W2 . act1(W1 . v + b1) + b2) * post per row of v [B, Cin] (W2 None: one layer).  v may be a PoolPartials: the pool is
     then finished inside the same launch (two-layer form with a hidden width <= 64), otherwise finished first."""
     if isinstance(v, PoolPartials):
-        if W2 is not None and W1.shape[0] <= 64 and v.C <= 512 and _POOL_MLP:
+        if W2 is not None and W1.shape[0] <= 64 and v.C <= 512:
             if W1.shape[1] != v.C or W2.shape[1] != W1.shape[0]:
                 raise _lib.FFError("vec_mlp: weight shape mismatch")
             out = torch.empty((1, W2.shape[0]), device=v.part.device, dtype=torch.float32)
