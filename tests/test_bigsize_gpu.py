@@ -187,12 +187,12 @@ def model_bf16(synth_sd):
     ops.set_gemm_mode(old)
 
 
-@pytest.mark.parametrize("case", ["c48_u8", "c42x52_nat", "t256_nat"])
-def test_plain_bf16_mode_against_reference_goldens(model_bf16, case):
+def _check_lowprec_golden(model, case, label):
+    """One reference golden through a model built in a low-precision mode: every tap and the final image's PSNR at BF16_BAR."""
     g = np.load(os.path.join(GOLD, case + ".npz"))
     lr = torch.from_numpy(g["lr"]).cuda()
     taps = {}
-    out = model_bf16(lr, taps)
+    out = model(lr, taps)
     taps["final"] = out
     tol, min_psnr = BF16_BAR
     worst = {}
@@ -203,15 +203,21 @@ def test_plain_bf16_mode_against_reference_goldens(model_bf16, case):
         ref = torch.from_numpy(g[f"tap/{n}/val"])
         got = t.reshape(-1)[torch.from_numpy(g[f"tap/{n}/idx"])]
         worst[n] = (got - ref).abs().max().item() / max(1.0, float(ref.abs().max()))
-    print(case, "bf16 worst taps:", sorted(worst.items(), key=lambda kv: -kv[1])[:8])
+    print(case, label, "worst taps:", sorted(worst.items(), key=lambda kv: -kv[1])[:8])
     bad = {k: v for k, v in worst.items() if not v < tol}
     assert not bad, bad
     if f"full/final" in g.files:
         psnr = _psnr_from_samples(out.cpu().reshape(-1), torch.from_numpy(g["full/final"]).reshape(-1))
     else:
         psnr = _psnr_from_samples(out.cpu().reshape(-1)[torch.from_numpy(g["big/final/idx"])], torch.from_numpy(g["big/final/val"]))
-    print(case, "bf16 PSNR(hip, reference) =", psnr)
+    print(case, label, "PSNR(hip, reference) =", psnr)
     assert psnr >= min_psnr
+    return g, out
+
+
+@pytest.mark.parametrize("case", ["c48_u8", "c42x52_nat", "t256_nat"])
+def test_plain_bf16_mode_against_reference_goldens(model_bf16, case):
+    g, out = _check_lowprec_golden(model_bf16, case, "bf16")
     if case == "t256_nat":
         # the north-star bar itself, |PSNR(build, GT) - PSNR(reference, GT)| <= 0.01 dB, at synthesised ground truths that put the
         # reference at 25 / 30 / 35 / 40 dB (bench.delta_psnr_vs_ground_truth: the evidence the bench line carries for its bf16 headline)
@@ -220,6 +226,21 @@ def test_plain_bf16_mode_against_reference_goldens(model_bf16, case):
         rep = bench.delta_psnr_vs_ground_truth(got, g["big/final/val"].astype(np.float64))
         print("bf16 delta PSNR vs synthesised ground truth:", {k: round(v["delta_dB"], 5) for k, v in rep["points"].items()})
         assert rep["worst_abs_delta_dB"] <= 0.01, rep
+
+
+def test_bf16x2_mode_against_reference_golden(synth_sd):
+    """'bf16x2' (exact activations x bf16 weights, one of ops.GEMM_MODES) end to end on c48_u8 against the reference's golden.  It is
+    strictly more precise than plain bf16 -- only the weights are rounded -- so plain bf16's own bar applies unchanged."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from isr2_amd import ops
+    from isr2_amd.model import FreqFusionHIP
+    old = ops.gemm_mode()
+    ops.set_gemm_mode("bf16x2")
+    try:
+        _check_lowprec_golden(FreqFusionHIP(synth_sd, "cuda:0"), "c48_u8", "bf16x2")
+    finally:
+        ops.set_gemm_mode(old)
 
 
 def test_whole_image_510x339_against_reference_golden(model):
