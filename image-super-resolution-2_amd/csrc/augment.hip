@@ -98,3 +98,108 @@ extern "C" int ff_d4_nchw(const float* in, float* out, int B, int C, int H, int 
   FF_LAUNCH_CHECK("ff_d4_nchw");
   return FF_OK;
 }
+
+// ---- one symmetry on RECTANGULAR planes, with fused accumulation (geometric self-ensemble, model.FreqFusionHIP.self_ensemble) ----
+// ONE code for the whole launch, any Hs x Ws: even k keeps the plane's shape, odd k writes [Ws][Hs].  With src [Hs][Ws], dst [Hd][Wd]:
+//   even k: dst[yo][xo] = src[revY ? Hs-1-yo : yo][revX ? Ws-1-xo : xo]                  (Hd, Wd) = (Hs, Ws)
+//   odd k:  dst[yo][xo] = src[ry ? Hs-1-xo : xo][rx ? Ws-1-yo : yo]                      (Hd, Wd) = (Ws, Hs), ry / rx as above
+// The blocks tile the OUTPUT plane; the two axes of a ragged odd-k tile are clipped independently (ny against Hd, nx against Wd) and
+// the input tile they select -- nx rows of ny columns -- is addressed with the input's own stride Ws, the output with Wd.
+// t = the permuted value:  accum 0: dst = t * scale;  accum 1: dst = (dst + t) * scale -- dst is read at the address, and with the
+// width, of the store that follows it; the add is rounded before the multiply (no fma can form from add-then-multiply, and the
+// contraction pragma keeps it so), hence scale == 1 leaves the sum's bits alone and a power-of-two scale is exact.
+__device__ __forceinline__ float d4_emit(float t, float old, int accum, float scale) {
+#pragma clang fp contract(off)
+  const float s = accum ? old + t : t;
+  return s * scale;
+}
+
+__global__ __launch_bounds__(256) void d4_rect_kernel(const float* __restrict__ in, float* __restrict__ out, int Hs, int Ws, int code,
+                                                      int accum, float scale, int tiles_x, int tiles_per_plane, int vec4) {
+  __shared__ float tile[D4_TILE * D4_PITCH];
+  const int plane = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane * tiles_per_plane;
+  const int ty0 = (t / tiles_x) * D4_TILE, tx0 = (t - (t / tiles_x) * tiles_x) * D4_TILE;      // origin of the OUTPUT tile
+  const int h = code & 1, v = (code >> 1) & 1, k = (code >> 2) & 3;
+  const float* src = in + (long long)plane * Hs * Ws;
+  float* dst = out + (long long)plane * Hs * Ws;
+  const int tid = threadIdx.x;
+  if ((k & 1) == 0) {
+    const int H = Hs, W = Ws;
+    const int revY = v ^ (k >> 1), revX = h ^ (k >> 1);
+    if (vec4) {
+      const int q = tid & 15, r0 = tid >> 4;                 // 16 float4 per 64-wide row, 16 rows per pass
+      const int xo = tx0 + 4 * q;
+      if (xo < W) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int yo = ty0 + r0 + 16 * p;
+          if (yo < H) {
+            const int yi = revY ? H - 1 - yo : yo;
+            f32x4 a = *reinterpret_cast<const f32x4*>(src + (long long)yi * W + (revX ? W - 4 - xo : xo));
+            if (revX) a = (f32x4){a[3], a[2], a[1], a[0]};
+            f32x4* d = reinterpret_cast<f32x4*>(dst + (long long)yo * W + xo);
+            f32x4 o = {0.f, 0.f, 0.f, 0.f};
+            if (accum) o = *d;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a[e] = d4_emit(a[e], o[e], accum, scale);
+            *d = a;
+          }
+        }
+      }
+    } else {
+      const int xo = tx0 + (tid & 63), r0 = tid >> 6;
+      if (xo < W) {
+        for (int p = 0; p < 16; ++p) {
+          const int yo = ty0 + r0 + 4 * p;
+          if (yo < H) {
+            float* d = dst + (long long)yo * W + xo;
+            const float a = src[(long long)(revY ? H - 1 - yo : yo) * W + (revX ? W - 1 - xo : xo)];
+            *d = d4_emit(a, accum ? *d : 0.f, accum, scale);
+          }
+        }
+      }
+    }
+    return;
+  }
+  const int Hd = Ws, Wd = Hs;
+  const int ry = (k == 1) ? v : !v, rx = (k == 1) ? !h : h;
+  const int nx = min(D4_TILE, Wd - tx0), ny = min(D4_TILE, Hd - ty0);     // valid extent of the output tile, each axis on its own
+  // input rows = images of the tile's output COLUMNS (nx of them, out of Hs), input columns = images of its ROWS (ny, out of Ws)
+  const int iy0 = ry ? Hs - tx0 - nx : tx0, ix0 = rx ? Ws - ty0 - ny : ty0;
+  const int lx = tid & 63, lr0 = tid >> 6;
+#pragma unroll 4
+  for (int p = 0; p < 16; ++p) {
+    const int r = lr0 + 4 * p;                                            // input row iy0 + r (r < nx), input column ix0 + lx (lx < ny)
+    if (r < nx && lx < ny) tile[r * D4_PITCH + lx] = src[(long long)(iy0 + r) * Ws + ix0 + lx];
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int p = 0; p < 16; ++p) {
+    const int r = lr0 + 4 * p;                                            // output row ty0 + r, output column tx0 + lx
+    if (r < ny && lx < nx) {
+      const int sy = ry ? nx - 1 - lx : lx;                               // input row of output column tx0 + lx, relative to iy0
+      const int sx = rx ? ny - 1 - r : r;                                 // input column of output row ty0 + r, relative to ix0
+      float* d = dst + (long long)(ty0 + r) * Wd + tx0 + lx;
+      *d = d4_emit(tile[sy * D4_PITCH + sx], accum ? *d : 0.f, accum, scale);
+    }
+  }
+}
+
+extern "C" int ff_d4_rect_nchw(const float* src, float* dst, int B, int C, int Hs, int Ws, int code, int accum, float scale,
+                               void* stream) {
+  FF_CHECK_ARG(src && dst, "ff_d4_rect_nchw: null pointer");
+  FF_CHECK_ARG(src != dst, "ff_d4_rect_nchw: the permutation is not in place (src == dst)");
+  FF_CHECK_ARG(B > 0 && C > 0 && Hs > 0 && Ws > 0, "ff_d4_rect_nchw: bad shape B=%d C=%d Hs=%d Ws=%d", B, C, Hs, Ws);
+  FF_CHECK_ARG(code >= 0 && code < 16, "ff_d4_rect_nchw: code %d outside 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)", code);
+  FF_CHECK_ARG(accum == 0 || accum == 1, "ff_d4_rect_nchw: accum must be 0 or 1, got %d", accum);
+  const int odd = (code >> 2) & 1;
+  const int Hd = odd ? Ws : Hs, Wd = odd ? Hs : Ws;
+  const int tiles_x = ff_cdiv(Wd, D4_TILE), tiles_y = ff_cdiv(Hd, D4_TILE);
+  const long long blocks = (long long)B * C * tiles_x * tiles_y;
+  FF_CHECK_ARG(blocks < (1ll << 31), "ff_d4_rect_nchw: %lld tiles exceed the grid limit", blocks);
+  const int vec4 = (Ws % 4 == 0) && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  hipLaunchKernelGGL(d4_rect_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, dst, Hs, Ws, code, accum, scale,
+                     tiles_x, tiles_x * tiles_y, vec4);
+  FF_LAUNCH_CHECK("ff_d4_rect_nchw");
+  return FF_OK;
+}

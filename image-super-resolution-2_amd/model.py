@@ -4,6 +4,7 @@
     model = FreqFusionHIP(state_dict, device)     # reference-keyed state dict (real or synthetic)
     sr = model(lr)                                # lr [B,3,h,w] fp32 in [0,1] on the GPU -> [B,3,4h,4w]
     sr = model.graphed(lr)                        # same, replayed from a HIP graph cached per input shape
+    sr = model.self_ensemble(lr)                  # x8 geometric self-ensemble: the mean over the eight symmetries of the square
 
 There is deliberately no CPU / PyTorch compute path: without a GPU or without libff_hip.so the
 constructor raises.
@@ -16,6 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import lib as _lib
+from . import ops
 from .experts import HatHIP, DatHIP, NafnetHIP
 from .fusion import FusionHIP
 
@@ -206,3 +208,71 @@ class FreqFusionHIP:
             ev = torch.cuda.Event()
             ev.record(ls)
         return static_out, ev
+
+    @torch.no_grad()
+    def self_ensemble(self, lr: T, run=None, run_async=None, codes=ops.D4_ENSEMBLE, out: Optional[T] = None) -> T:
+        """Geometric self-ensemble (the "x8" / forward_x8 test-time pass of HAT's and EDSR's test code): the model runs on the
+        symmetries `codes` of lr [B,3,h,w], every output is mapped back and the results are averaged.  Pinned bit for bit:
+
+            acc = inv_0(run(T_0(lr)))
+            acc = acc + inv_i(run(T_i(lr)))     i = 1 .. n-1 in the order of `codes`, fp32, one rounding per add
+            out = acc * (1 / n)                 fused into the last accumulation (n = 8: an exact power-of-two scale)
+
+        with T_i = ops.d4_rect(., codes[i]) and inv_i = ops.d4_rect(., ops.d4_inverse_code(codes[i]), out=acc, accum=i > 0, ...)
+        (csrc/augment.hip: ff_d4_rect_nchw): two permutation launches per variant around the forward, no other glue.  A variant with
+        an odd quarter turn is [B,3,w,h]; its output comes back as [B,3,4h,4w].
+
+        run(x) -> [B,3,4H,4W] defaults to self.forward.  A run that returns a static graph buffer (self.graphed) is safe: the
+        accumulate launch that reads the buffer is stream-ordered before the next replay that overwrites it.  run_async(x, lane)
+        -> (output, event) (self.graphed_async) is used when every variant has lr's shape (h == w): the variants alternate over the
+        two lanes exactly as the tiles of io._tiled_forward do, and their outputs are consumed in code order on the current stream,
+        so the result is bit-identical to the sequential loop.  A non-square lr ignores run_async.
+
+        Empty codes, a code outside 0..15 and two codes that name the same symmetry raise FFError before any launch."""
+        if not isinstance(lr, torch.Tensor) or lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3 or lr.shape[2] < 1 or lr.shape[3] < 1:
+            raise _lib.FFError(f"self_ensemble: expected lr of shape [B,3,h,w], got {tuple(getattr(lr, 'shape', ()))}")
+        cl = [int(c) for c in codes]
+        if not cl:
+            raise _lib.FFError("self_ensemble: no symmetry codes given")
+        inv = [ops.d4_inverse_code(c) for c in cl]                       # raises on a code outside 0..15
+        canon = [ops.d4_canonical_code(c) for c in cl]
+        if len(set(canon)) != len(cl):
+            raise _lib.FFError(f"self_ensemble: codes {cl} name a symmetry twice (codes 8..15 repeat 0..7)")
+        B, _, h, w = lr.shape
+        oshape = (B, 3, 4 * h, 4 * w)
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != oshape or out.dtype != torch.float32
+                                or out.device != self.dev or not out.is_contiguous()):
+            raise _lib.FFError(f"self_ensemble: out must be a contiguous float32 {list(oshape)} tensor on {self.dev}")
+        lr = lr.to(self.dev, torch.float32).contiguous()
+        if run is None:
+            run = self.forward
+        if h != w:
+            run_async = None
+        n = len(cl)
+        with torch.cuda.device(self.dev):
+            acc = out if out is not None else torch.empty(oshape, device=self.dev, dtype=torch.float32)
+
+            def fold(sr, i):                                   # d4_rect refuses an sr whose mapped-back shape is not acc's
+                ops.d4_rect(sr.contiguous(), inv[i], out=acc, accum=i > 0, scale=1.0 / n if i == n - 1 else 1.0)
+
+            if run_async is None:
+                for i, c in enumerate(cl):
+                    fold(run(ops.d4_rect(lr, c)), i)
+                return acc
+            pend = [None, None]
+
+            def consume(lane):
+                if pend[lane] is not None:
+                    sr, ev, i = pend[lane]
+                    torch.cuda.current_stream().wait_event(ev)
+                    fold(sr, i)
+                    pend[lane] = None
+
+            for i, c in enumerate(cl):
+                lane = i & 1
+                consume(lane)                                  # variant i-2: its output buffer is about to be overwritten
+                sr, ev = run_async(ops.d4_rect(lr, c), lane)
+                pend[lane] = (sr, ev, i)
+            consume(n & 1)
+            consume((n + 1) & 1)
+            return acc

@@ -1179,6 +1179,59 @@ def d4_nchw(x: T, codes, out: Optional[T] = None, codes_dev: Optional[T] = None)
     return out
 
 
+# The eight distinct symmetries of the square as d4 codes: k in {0, 1} times the four flip combinations (codes 8..15 repeat them:
+# rot90(2) is both flips, rot90(3) is rot90(1) after both flips).
+D4_ENSEMBLE = (0, 1, 2, 3, 4, 5, 6, 7)
+
+
+def d4_inverse_code(code: int) -> int:
+    """The d4 code whose transform undoes `code` (both read as flip(-1), flip(-2), rot90(k), in that order).  rot^k after exactly one
+    flip is a reflection of the square, hence its own inverse; with none or both flips set (both = a half turn) the transform is a
+    rotation, and its inverse keeps the flips and turns back: k' = (4 - k) % 4."""
+    c = int(code)
+    if not 0 <= c < D4_CODES:
+        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    if (c & 1) != ((c >> 1) & 1):
+        return c
+    return (c & 3) | (((4 - (c >> 2)) % 4) << 2)
+
+
+def d4_canonical_code(code: int) -> int:
+    """The code in 0..7 (D4_ENSEMBLE) that names the same symmetry as `code`: a half turn is both flips, so k >= 2 toggles both flip
+    bits and keeps k - 2."""
+    c = int(code)
+    if not 0 <= c < D4_CODES:
+        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    return c if c < 8 else ((c & 3) ^ 3) | ((c >> 2) - 2) << 2
+
+
+def d4_rect(x: T, code: int, out: Optional[T] = None, accum: bool = False, scale: float = 1.0) -> T:
+    """ONE symmetry (`code` as in d4_nchw: flip(-1), flip(-2), rot90(k, (-2, -1))) of a planar [B,C,H,W] tensor of any H, W: the result
+    is [B,C,H,W] for even k and [B,C,W,H] for odd k.  accum=False: out = t * scale; accum=True: out = (out + t) * scale, the add
+    rounded before the multiply.  Everything is checked here, before the launch; `out` must not overlap x."""
+    _chk(x, "d4_rect.x")
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise _lib.FFError("d4_rect: expected a non-empty contiguous [B,C,H,W] tensor")
+    c = int(code)
+    if not 0 <= c < D4_CODES:
+        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    B, C, H, W = x.shape
+    oshape = (B, C, W, H) if (c >> 2) & 1 else (B, C, H, W)
+    if out is None:
+        if accum:
+            raise _lib.FFError("d4_rect: accum=True needs the tensor to accumulate into (out)")
+        out = torch.empty(oshape, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "d4_rect.out")
+        if tuple(out.shape) != oshape or not out.is_contiguous() or out.device != x.device:
+            raise _lib.FFError(f"d4_rect: out must be a contiguous {list(oshape)} tensor on x's device, got {list(out.shape)}")
+        nb = 4 * x.numel()
+        if out.data_ptr() < x.data_ptr() + nb and x.data_ptr() < out.data_ptr() + nb:
+            raise _lib.FFError("d4_rect: out overlaps x (the permutation is not in place)")
+    _lib.check(_L().ff_d4_rect_nchw(x.data_ptr(), out.data_ptr(), B, C, H, W, c, 1 if accum else 0, float(scale), _stream()))
+    return out
+
+
 for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):

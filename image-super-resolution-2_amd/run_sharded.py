@@ -1,7 +1,7 @@
 """Image-sharded multi-GPU runner of the plugin (BASELINE config 4; the reference's pattern is eval.py:162-170: the sorted
 file list is cut into contiguous shards, one worker process per GPU).
 
-    python -m isr2_amd.run_sharded --gpus 8 --input LR_DIR --output SR_DIR [--model_dir fusion.pth]
+    python -m isr2_amd.run_sharded --gpus 8 --input LR_DIR --output SR_DIR [--model_dir fusion.pth] [--self-ensemble]
 
 The parent touches no GPU: it starts one fresh child per GPU, each of which calls the plugin's
 `main(model_dir, input_path, output_path, device)` with RANK / WORLD_SIZE set.  Inside, rank 0 reads the checkpoints and the
@@ -34,8 +34,11 @@ def main(argv=None) -> int:
     ap.add_argument("--output", required=True)
     ap.add_argument("--model_dir", default=os.path.join("checkpoints", "phase5_single_gpu", "championship_sr_phase5_single_gpu",
                                                         "best_epoch0050_psnr30.05.pth"))
+    ap.add_argument("--self-ensemble", action="store_true", help="x8 geometric self-ensemble (sets FF_SELF_ENSEMBLE=1 for the ranks)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.self_ensemble:
+        os.environ["FF_SELF_ENSEMBLE"] = "1"                     # inherited by the ranks spawn_ranks starts
     if args.worker or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         worker(args)
         return 0

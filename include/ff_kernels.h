@@ -490,6 +490,14 @@ int ff_loss_combine(const float* values, const float* weights, int k, float* tot
  * A pure permutation, not in place; one launch per tensor per batch. */
 int ff_d4_nchw(const float* in, float* out, int B, int C, int H, int W, const int* codes, void* stream);
 
+/* One symmetry of the square on RECTANGULAR planes, with fused accumulation (csrc/augment.hip; the building block of the x8 geometric
+ * self-ensemble, isr2_amd.model.FreqFusionHIP.self_ensemble).  src [B][C][Hs][Ws] -> dst [B][C][Hd][Wd], both contiguous, with
+ * (Hd, Wd) = (Hs, Ws) when k = code >> 2 is even and (Ws, Hs) when it is odd; any Hs, Ws >= 1.  `code` (0..15, a HOST int, one for the
+ * whole launch) has ff_d4_nchw's meaning and order: bit 0 flip(-1), then bit 1 flip(-2), then rot90(k, dims (-2, -1)).  With t the
+ * transformed plane:  accum 0: dst = t * scale;  accum 1: dst = (dst + t) * scale -- the add is rounded first, then the multiply, no
+ * contraction (scale = 1 leaves the sum's bits untouched).  No atomics; not in place (src != dst). */
+int ff_d4_rect_nchw(const float* src, float* dst, int B, int C, int Hs, int Ws, int code, int accum, float scale, void* stream);
+
 /* C-level executor (csrc/ff_executor.hip): the whole forward -- models/team29_FreqFusion/io.py:221 `model(lr)` =
  * CompleteEnhancedFusionSR.forward, src/models/enhanced_fusion.py:694-754 -- for callers without Python.  A plan
  * (<stem>.ffplan, written by isr2_amd.plan.export_plan) lists every launch of one input shape with pointers expressed as

@@ -12,7 +12,9 @@ What this build adds around the same contract:
     built by rank 0 and sent in ONE RCCL broadcast, every rank writes its own PNGs -- no per-image collective;
   * PNG decode and encode run on host threads beside the GPU (pinned uint8 staging, only uint8 crosses PCIe); the
     compute stays on the calling thread, results and file names are exactly those of the serial loop;
-  * tiles (and repeated whole-image shapes) replay one captured HIP graph instead of re-launching ~1700 kernels.
+  * tiles (and repeated whole-image shapes) replay one captured HIP graph instead of re-launching ~1700 kernels;
+  * FF_SELF_ENSEMBLE=1 (opt-in): every image runs through the eight symmetries of the square, the outputs are mapped back and
+    averaged on the device (FreqFusionHIP.self_ensemble) -- about 8x the GPU time.
 """
 from __future__ import annotations
 
@@ -396,6 +398,27 @@ def _forward_image(model, lr_img, img_name, device, seen_shapes):
         raise
 
 
+def _self_ensemble_on() -> bool:
+    """FF_SELF_ENSEMBLE: absent, empty or 0 = one pass per image; 1 (or 8) = the x8 geometric self-ensemble.  Read by main()."""
+    v = os.environ.get("FF_SELF_ENSEMBLE", "").strip()
+    if v in ("", "0"):
+        return False
+    if v in ("1", "8"):
+        return True
+    raise ValueError(f"[team29_FreqFusion] FF_SELF_ENSEMBLE={v!r}: expected 0, 1 or 8")
+
+
+def _forward_image_x8(model, lr_img, img_name, device, seen_shapes):
+    """x8 geometric self-ensemble of one image (FreqFusionHIP.self_ensemble: the mean of the eight symmetries' outputs, mapped back
+    and added on the device).  Every variant goes through _forward_image, so each keeps the whole-image-first policy, the graph
+    replay of repeated small shapes and the fallback to 128/32 tiles.  An h x w image brings TWO shapes, h x w and w x h, four
+    variants each: both are counted in seen_shapes, so from the second variant of an orientation on its graph is replayed."""
+    h, w = lr_img.shape[-2:]
+    if seen_shapes is not None and h != w and getattr(model, "max_graphs", 2) < 2:
+        seen_shapes = None                                       # one graph slot: the two orientations would evict each other per variant
+    return model.self_ensemble(lr_img, run=lambda t: _forward_image(model, t, img_name, device, seen_shapes))
+
+
 @torch.no_grad()
 def main(model_dir: str, input_path: str, output_path: str, device=None):
     """NTIRE2026 official interface (reference io.py:188-234)."""
@@ -410,6 +433,10 @@ def main(model_dir: str, input_path: str, output_path: str, device=None):
     print(f"{tag} Device: {device}")
     own_pg = _ensure_process_group(rank, world, device) if world > 1 else False
     model = _build_and_load(model_dir, device, rank, world)
+    forward_image = _forward_image
+    if _self_ensemble_on():
+        forward_image = _forward_image_x8
+        print(f"{tag} Self-ensemble: on (8 symmetries per image, outputs mapped back and averaged; about 8x the compute)")
 
     input_imgs = sorted(glob.glob(os.path.join(input_path, "*.[pP][nN][gG]")))
     if not input_imgs:
@@ -425,7 +452,7 @@ def main(model_dir: str, input_path: str, output_path: str, device=None):
         for img_path in mine:
             img_name = os.path.basename(img_path)
             lr_img = _load_image(img_path, device)
-            sr_img = _forward_image(model, lr_img, img_name, device, None)
+            sr_img = forward_image(model, lr_img, img_name, device, None)
             _save_image(sr_img, os.path.join(output_path, img_name))
             del sr_img, lr_img
     else:
@@ -434,7 +461,7 @@ def main(model_dir: str, input_path: str, output_path: str, device=None):
         try:
             for img_path, lr_img in pipe:
                 img_name = os.path.basename(img_path)
-                sr_img = _forward_image(model, lr_img, img_name, device, seen)
+                sr_img = forward_image(model, lr_img, img_name, device, seen)
                 pipe.save(sr_img, img_name)
                 del sr_img, lr_img
         finally:

@@ -91,6 +91,9 @@ if __name__ == "__main__":
     parser.add_argument("--save_dir", default="NTIRE2026-ImageSRx4/results", type=str)
     parser.add_argument("--model_id", default=29, type=int)
     parser.add_argument("--hr_dir", default=None, type=str, help="optional ground-truth directory: report PSNR-Y / SSIM-Y (device evaluator)")
+    parser.add_argument("--self_ensemble", action="store_true", help="x8 geometric self-ensemble (sets FF_SELF_ENSEMBLE=1 for the plugin)")
     args = parser.parse_args()
+    if args.self_ensemble:
+        os.environ["FF_SELF_ENSEMBLE"] = "1"
     pprint(args)
     main(args)
