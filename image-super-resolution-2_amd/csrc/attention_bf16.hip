@@ -10,8 +10,6 @@
 // Softmax in base 2: p = exp2(fma(s, log2e, -m*log2e)) -- one v_fma + one v_exp_f32 per element.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct AttnBfParams {
   const float* qkv;
   float* out;
@@ -36,8 +34,6 @@ struct AttnBfParams {
 #define AKC 128            // keys per chunk
 #define KROWB 80           // K row: 32 bf16 + 16 B pad
 #define VROWB 272          // V^T row: 128 bf16 + 16 B pad
-
-__device__ __forceinline__ int swap23(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
 
 template <int NTERMS>
 __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
@@ -221,7 +217,7 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
       const int kk = wid * 2 + hh + 16 * i;
       const __bf16 k_h = (__bf16)kv[i], v_h = (__bf16)vv[i];
       *reinterpret_cast<__bf16*>(Kh + kk * KROWB + 2 * l31) = k_h;
-      const int vp = swap23(kk);
+      const int vp = ff_swap23(kk);
       *reinterpret_cast<__bf16*>(Vh + l31 * VROWB + 2 * vp) = v_h;
       if (NTERMS == 3) {
         *reinterpret_cast<__bf16*>(Kl + kk * KROWB + 2 * l31) = (__bf16)(kv[i] - (float)k_h);

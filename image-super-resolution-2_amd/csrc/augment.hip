@@ -22,89 +22,6 @@
 #define D4_TILE 64
 #define D4_PITCH 65
 
-__global__ __launch_bounds__(256) void d4_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int H, int W,
-                                                      const int* __restrict__ codes, int tiles_x, int tiles_per_plane, int vec4) {
-  __shared__ float tile[D4_TILE * D4_PITCH];
-  const int plane = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane * tiles_per_plane;
-  const int ty0 = (t / tiles_x) * D4_TILE, tx0 = (t - (t / tiles_x) * tiles_x) * D4_TILE;      // origin of the OUTPUT tile
-  int code = codes[plane / C] & 15;
-  if (H != W) code &= ~4;                                    // odd k on a non-square plane is refused by the host; never index outside
-  const int h = code & 1, v = (code >> 1) & 1, k = code >> 2;
-  const float* src = in + (long long)plane * H * W;
-  float* dst = out + (long long)plane * H * W;
-  const int tid = threadIdx.x;
-  if ((k & 1) == 0) {
-    const int revY = v ^ (k >> 1), revX = h ^ (k >> 1);
-    if (vec4) {
-      const int q = tid & 15, r0 = tid >> 4;                 // 16 float4 per 64-wide row, 16 rows per pass
-      const int xo = tx0 + 4 * q;
-      if (xo < W) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int yo = ty0 + r0 + 16 * p;
-          if (yo < H) {
-            const int yi = revY ? H - 1 - yo : yo;
-            f32x4 a = *reinterpret_cast<const f32x4*>(src + (long long)yi * W + (revX ? W - 4 - xo : xo));
-            if (revX) a = (f32x4){a[3], a[2], a[1], a[0]};
-            *reinterpret_cast<f32x4*>(dst + (long long)yo * W + xo) = a;
-          }
-        }
-      }
-    } else {
-      const int xo = tx0 + (tid & 63), r0 = tid >> 6;
-      if (xo < W) {
-        for (int p = 0; p < 16; ++p) {
-          const int yo = ty0 + r0 + 4 * p;
-          if (yo < H) dst[(long long)yo * W + xo] = src[(long long)(revY ? H - 1 - yo : yo) * W + (revX ? W - 1 - xo : xo)];
-        }
-      }
-    }
-    return;
-  }
-  // odd k (H == W = N): out[yo][xo] = in[ry ? N-1-xo : xo][rx ? N-1-yo : yo]
-  const int N = H;
-  const int ry = (k == 1) ? v : !v, rx = (k == 1) ? !h : h;
-  const int nx = min(D4_TILE, N - tx0), ny = min(D4_TILE, N - ty0);       // valid extent of the output tile
-  // the input rows this tile needs are the images of its output COLUMNS and vice versa; both ranges are contiguous
-  const int iy0 = ry ? N - tx0 - nx : tx0, ix0 = rx ? N - ty0 - ny : ty0;
-  const int lx = tid & 63, lr0 = tid >> 6;
-#pragma unroll 4
-  for (int p = 0; p < 16; ++p) {
-    const int r = lr0 + 4 * p;                                            // input row iy0 + r (r < nx), input column ix0 + lx (lx < ny)
-    if (r < nx && lx < ny) tile[r * D4_PITCH + lx] = src[(long long)(iy0 + r) * N + ix0 + lx];
-  }
-  __syncthreads();
-#pragma unroll 4
-  for (int p = 0; p < 16; ++p) {
-    const int r = lr0 + 4 * p;                                            // output row ty0 + r, output column tx0 + lx
-    if (r < ny && lx < nx) {
-      const int sy = ry ? nx - 1 - lx : lx;                               // input row of output column tx0 + lx, relative to iy0
-      const int sx = rx ? ny - 1 - r : r;                                 // input column of output row ty0 + r, relative to ix0
-      dst[(long long)(ty0 + r) * N + tx0 + lx] = tile[sy * D4_PITCH + sx];
-    }
-  }
-}
-
-extern "C" int ff_d4_nchw(const float* in, float* out, int B, int C, int H, int W, const int* codes, void* stream) {
-  FF_CHECK_ARG(in && out && codes, "ff_d4_nchw: null pointer");
-  FF_CHECK_ARG(in != out, "ff_d4_nchw: the permutation is not in place (in == out)");
-  FF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "ff_d4_nchw: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-  const int tiles_x = ff_cdiv(W, D4_TILE), tiles_y = ff_cdiv(H, D4_TILE);
-  const long long blocks = (long long)B * C * tiles_x * tiles_y;
-  FF_CHECK_ARG(blocks < (1ll << 31), "ff_d4_nchw: %lld tiles exceed the grid limit", blocks);
-  const int vec4 = (W % 4 == 0) && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-  hipLaunchKernelGGL(d4_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, out, C, H, W, codes, tiles_x,
-                     tiles_x * tiles_y, vec4);
-  FF_LAUNCH_CHECK("ff_d4_nchw");
-  return FF_OK;
-}
-
-// ---- one symmetry on RECTANGULAR planes, with fused accumulation (geometric self-ensemble, model.FreqFusionHIP.self_ensemble) ----
-// ONE code for the whole launch, any Hs x Ws: even k keeps the plane's shape, odd k writes [Ws][Hs].  With src [Hs][Ws], dst [Hd][Wd]:
-//   even k: dst[yo][xo] = src[revY ? Hs-1-yo : yo][revX ? Ws-1-xo : xo]                  (Hd, Wd) = (Hs, Ws)
-//   odd k:  dst[yo][xo] = src[ry ? Hs-1-xo : xo][rx ? Ws-1-yo : yo]                      (Hd, Wd) = (Ws, Hs), ry / rx as above
-// The blocks tile the OUTPUT plane; the two axes of a ragged odd-k tile are clipped independently (ny against Hd, nx against Wd) and
-// the input tile they select -- nx rows of ny columns -- is addressed with the input's own stride Ws, the output with Wd.
 // t = the permuted value:  accum 0: dst = t * scale;  accum 1: dst = (dst + t) * scale -- dst is read at the address, and with the
 // width, of the store that follows it; the add is rounded before the multiply (no fma can form from add-then-multiply, and the
 // contraction pragma keeps it so), hence scale == 1 leaves the sum's bits alone and a power-of-two scale is exact.
@@ -114,14 +31,18 @@ __device__ __forceinline__ float d4_emit(float t, float old, int accum, float sc
   return s * scale;
 }
 
-__global__ __launch_bounds__(256) void d4_rect_kernel(const float* __restrict__ in, float* __restrict__ out, int Hs, int Ws, int code,
-                                                      int accum, float scale, int tiles_x, int tiles_per_plane, int vec4) {
-  __shared__ float tile[D4_TILE * D4_PITCH];
-  const int plane = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane * tiles_per_plane;
-  const int ty0 = (t / tiles_x) * D4_TILE, tx0 = (t - (t / tiles_x) * tiles_x) * D4_TILE;      // origin of the OUTPUT tile
+// One 64 x 64 OUTPUT tile of one plane, src [Hs][Ws] -> dst [Hd][Wd] (even k: the same shape; odd k: [Ws][Hs]):
+//   even k: dst[yo][xo] = src[revY ? Hs-1-yo : yo][revX ? Ws-1-xo : xo]
+//   odd k:  dst[yo][xo] = src[ry ? Hs-1-xo : xo][rx ? Ws-1-yo : yo]
+// The two axes of a ragged odd-k tile are clipped independently (ny against Hd, nx against Wd) and the input tile they select -- nx
+// rows of ny columns -- is addressed with the input's own stride Ws, the output with Wd.
+// EMIT = false stores the permuted value as it is: a pure copy, no multiply and no add, so denormals, negative zero and NaN
+// payloads pass through untouched.  EMIT = true stores d4_emit(value, dst, accum, scale); dst is read only when accum is set, at
+// the address, and with the width, of the store that follows it.
+template <bool EMIT>
+__device__ __forceinline__ void d4_tile(const float* __restrict__ src, float* __restrict__ dst, float* tile, int Hs, int Ws, int code,
+                                        int ty0, int tx0, int vec4, int accum, float scale) {
   const int h = code & 1, v = (code >> 1) & 1, k = (code >> 2) & 3;
-  const float* src = in + (long long)plane * Hs * Ws;
-  float* dst = out + (long long)plane * Hs * Ws;
   const int tid = threadIdx.x;
   if ((k & 1) == 0) {
     const int H = Hs, W = Ws;
@@ -138,10 +59,12 @@ __global__ __launch_bounds__(256) void d4_rect_kernel(const float* __restrict__ 
             f32x4 a = *reinterpret_cast<const f32x4*>(src + (long long)yi * W + (revX ? W - 4 - xo : xo));
             if (revX) a = (f32x4){a[3], a[2], a[1], a[0]};
             f32x4* d = reinterpret_cast<f32x4*>(dst + (long long)yo * W + xo);
-            f32x4 o = {0.f, 0.f, 0.f, 0.f};
-            if (accum) o = *d;
+            if (EMIT) {
+              f32x4 o = {0.f, 0.f, 0.f, 0.f};
+              if (accum) o = *d;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) a[e] = d4_emit(a[e], o[e], accum, scale);
+              for (int e = 0; e < 4; ++e) a[e] = d4_emit(a[e], o[e], accum, scale);
+            }
             *d = a;
           }
         }
@@ -154,7 +77,7 @@ __global__ __launch_bounds__(256) void d4_rect_kernel(const float* __restrict__ 
           if (yo < H) {
             float* d = dst + (long long)yo * W + xo;
             const float a = src[(long long)(revY ? H - 1 - yo : yo) * W + (revX ? W - 1 - xo : xo)];
-            *d = d4_emit(a, accum ? *d : 0.f, accum, scale);
+            *d = EMIT ? d4_emit(a, accum ? *d : 0.f, accum, scale) : a;
           }
         }
       }
@@ -180,9 +103,46 @@ __global__ __launch_bounds__(256) void d4_rect_kernel(const float* __restrict__ 
       const int sy = ry ? nx - 1 - lx : lx;                               // input row of output column tx0 + lx, relative to iy0
       const int sx = rx ? ny - 1 - r : r;                                 // input column of output row ty0 + r, relative to ix0
       float* d = dst + (long long)(ty0 + r) * Wd + tx0 + lx;
-      *d = d4_emit(tile[sy * D4_PITCH + sx], accum ? *d : 0.f, accum, scale);
+      const float a = tile[sy * D4_PITCH + sx];
+      *d = EMIT ? d4_emit(a, accum ? *d : 0.f, accum, scale) : a;
     }
   }
+}
+
+// per-SAMPLE codes on square-or-even-k planes: the training augmentation, a pure copy (EMIT off)
+__global__ __launch_bounds__(256) void d4_nchw_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int H, int W,
+                                                      const int* __restrict__ codes, int tiles_x, int tiles_per_plane, int vec4) {
+  __shared__ float tile[D4_TILE * D4_PITCH];
+  const int plane = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane * tiles_per_plane;
+  const int ty0 = (t / tiles_x) * D4_TILE, tx0 = (t - (t / tiles_x) * tiles_x) * D4_TILE;      // origin of the OUTPUT tile
+  int code = codes[plane / C] & 15;
+  if (H != W) code &= ~4;                                    // odd k on a non-square plane is refused by the host; never index outside
+  d4_tile<false>(in + (long long)plane * H * W, out + (long long)plane * H * W, tile, H, W, code, ty0, tx0, vec4, 0, 1.f);
+}
+
+extern "C" int ff_d4_nchw(const float* in, float* out, int B, int C, int H, int W, const int* codes, void* stream) {
+  FF_CHECK_ARG(in && out && codes, "ff_d4_nchw: null pointer");
+  FF_CHECK_ARG(in != out, "ff_d4_nchw: the permutation is not in place (in == out)");
+  FF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "ff_d4_nchw: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+  const int tiles_x = ff_cdiv(W, D4_TILE), tiles_y = ff_cdiv(H, D4_TILE);
+  const long long blocks = (long long)B * C * tiles_x * tiles_y;
+  FF_CHECK_ARG(blocks < (1ll << 31), "ff_d4_nchw: %lld tiles exceed the grid limit", blocks);
+  const int vec4 = (W % 4 == 0) && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+  hipLaunchKernelGGL(d4_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, out, C, H, W, codes, tiles_x,
+                     tiles_x * tiles_y, vec4);
+  FF_LAUNCH_CHECK("ff_d4_nchw");
+  return FF_OK;
+}
+
+// ---- one symmetry on RECTANGULAR planes, with fused accumulation (geometric self-ensemble, model.FreqFusionHIP.self_ensemble) ----
+// ONE code for the whole launch, any Hs x Ws: even k keeps the plane's shape, odd k writes [Ws][Hs].  The blocks tile the OUTPUT plane;
+// d4_tile with EMIT on.
+__global__ __launch_bounds__(256) void d4_rect_kernel(const float* __restrict__ in, float* __restrict__ out, int Hs, int Ws, int code,
+                                                      int accum, float scale, int tiles_x, int tiles_per_plane, int vec4) {
+  __shared__ float tile[D4_TILE * D4_PITCH];
+  const int plane = blockIdx.x / tiles_per_plane, t = blockIdx.x - plane * tiles_per_plane;
+  const int ty0 = (t / tiles_x) * D4_TILE, tx0 = (t - (t / tiles_x) * tiles_x) * D4_TILE;      // origin of the OUTPUT tile
+  d4_tile<true>(in + (long long)plane * Hs * Ws, out + (long long)plane * Hs * Ws, tile, Hs, Ws, code, ty0, tx0, vec4, accum, scale);
 }
 
 extern "C" int ff_d4_rect_nchw(const float* src, float* dst, int B, int C, int Hs, int Ws, int code, int accum, float scale,

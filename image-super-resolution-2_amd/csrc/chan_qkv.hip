@@ -9,8 +9,6 @@
 // the layout ff_chan_attn_finish reduces.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct ChanQkvParams {
   const float* x; const float* gamma; const float* beta;
   const __bf16* w;        // [18 tiles][2 planes][32][192]: q_0, k_0, ..., q_5, k_5 (head dim padded to 32 rows), then v rows 0..191 in 6 tiles
@@ -75,6 +73,8 @@ __global__ __launch_bounds__(512) void chan_qkv_kernel(ChanQkvParams p) {
   {
     float v[CQ_KS][8];
     ff_wave_rows_to_frags<3>(p.x, p.ldx, tok0, p.M, p.K, xs, lane, v);
+    // the LayerNorm of ff_common.h (ff_frag_ln_stats / _step / ff_bf16_split), inline on purpose: through the helpers the kernel loses
+    // its 9 spilled VGPRs (256 -> 226) and is SLOWER under the bench: chan_qkv_kernel<1> 41.11 / 41.13 us -> 42.80 / 42.77 us
     float s = 0.f;
 #pragma unroll
     for (int st = 0; st < CQ_KS; ++st)

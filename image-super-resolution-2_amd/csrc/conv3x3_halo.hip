@@ -11,9 +11,6 @@
 //   LDS row (pixel or weight row) = [64 k hi | 64 k lo | 16 B pad] = 272 B = 68 dwords: conflict-free ds_read_b128.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 struct HaloParams {
   const float* in; const unsigned char* w; const float* bias; const float* mul; const float* res; float* out;
   int B, H, W, Cin, ldi, Cout, ldo, ldr, nchunk, tiles_x, tiles_y, nblk, act, shuffle;
@@ -21,16 +18,8 @@ struct HaloParams {
   float* pool_part;   // optional [workgroups][Cout padded to nblk*BN]: per-workgroup channel sums of the stored values
   int vec_epi;        // 16-byte epilogue through LDS patches (set by the launcher when the layout allows)
   int io_bf16;        // nterms == 1 only: bit 0 = input rows are bf16 (ldi in elements), bit 1 = output rows are bf16 (ldo in elements)
-#ifdef HX_TIMING
-  unsigned long long* dbg;   // tools/hx_time.cpp: [block][wave][8] wall-clock stamps (debug build only)
-#endif
+  FF_STAMP_MEMBER
 };
-#ifdef HX_TIMING
-static unsigned long long* g_hx_dbg = nullptr;
-#define HX_T(i) do { if (p.dbg && (threadIdx.x & 63) == 0) p.dbg[((long long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define HX_T(i) do { } while (0)
-#endif
 
 #define HX_ROW 272
 #define HX_W 18
@@ -115,7 +104,7 @@ void conv3x3_halo_kernel(HaloParams p) {
     }
   };
   const int ntiles = p.nchunk * 9 * NH;
-  HX_T(0);
+  FF_STAMP(8, 0);
   // Ring of NSLOT weight slots, DEPTH = NSLOT - 1 tiles in flight: tile T + DEPTH is issued at the top of tile T (into the slot tile T - 1
   // just vacated) and waited for DEPTH tiles later with a COUNTED s_waitcnt vmcnt(NPMIN * (DEPTH - 1)) (NPMIN = the fewest pieces any wave
   // issues per tile; waves that issue one more over-wait by a piece: vmcnt retires in issue order) followed by a RAW s_barrier.
@@ -182,7 +171,7 @@ void conv3x3_halo_kernel(HaloParams p) {
   };
   load_x(0);
   store_x();
-  HX_T(1);
+  FF_STAMP(8, 1);
 
   f32x16 acc[MI][NI];
 #pragma unroll
@@ -299,7 +288,7 @@ void conv3x3_halo_kernel(HaloParams p) {
       }
     }
   }
-  HX_T(2);
+  FF_STAMP(8, 2);
   // ---- vector epilogue (no pixel shuffle, Cout % 4 == 0, 16-byte aligned rows): every 32 x 32 accumulator tile goes through the wave's
   //      LDS patch so that a lane owns four consecutive channels of a pixel -- four 16-byte stores of whole 128-byte pixel segments per
   //      tile instead of sixteen 4-byte stores (tools/hx_time.cpp: the scalar epilogue was 10.7 us of CAB 60->180's 32 us and did not
@@ -464,11 +453,8 @@ void conv3x3_halo_kernel(HaloParams p) {
       }
     }
   }
-  HX_T(3);
-#ifdef HX_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  HX_T(4);
-#endif
+  FF_STAMP(8, 3);
+  FF_STAMP_DRAINED(8, 4);
 }
 
 template <int WM, int WN, int MI, int NI, int WK, int NSLOT, int NTERMS>
@@ -550,9 +536,7 @@ extern "C" int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int 
   p.nchunk = (Cin + 63) / 64; p.act = act; p.alpha = alpha; p.shuffle = shuffle; p.pool_part = pool_partials; p.io_bf16 = io_bf16;
   p.vec_epi = shuffle == 0 && Cout % 4 == 0 && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && !(res && pool_partials) &&
               (!res || (ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)) && (!mul || (((uintptr_t)mul) & 15) == 0);
-#ifdef HX_TIMING
-  p.dbg = g_hx_dbg;
-#endif
+  FF_STAMP_ARM(p);
   hipStream_t st = (hipStream_t)stream;
   if (halo_small_grid(B, H, W, Cout, bn, nterms)) {
     if (bn == 64) return launch_halo<8, 1, 1, 2, 64, 9, 1>(p, st);     // nine resident tap tiles, three barriers per chunk

@@ -21,9 +21,6 @@
 //     128x128 / 128x64 / 256x32 with 4 waves elsewhere.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 struct ConvBfParams {
   const float* in;
   const __bf16* w_hi;

@@ -90,12 +90,6 @@ extern "C" int ff_affine(float* out, int ldo, const float* in, int ldi, long lon
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect_idx(int i, int n) {   // F.pad(mode='reflect') index map
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * (n - 1) - i;
-  return i;
-}
-
 // in [B][C][H][W] -> out [B][Hp][Wp][ldo] channels [0,C): value + add[c]; pad_mode 0 zero / 1 reflect
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int C,
                                                            int H, int W, int Hp, int Wp, int ldo,
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
     float v = 0.f;
     int sy = y, sx = x;
     bool ok = y < H && x < W;
-    if (!ok && pad_mode == 1) { sy = reflect_idx(y, H); sx = reflect_idx(x, W); ok = true; }
+    if (!ok && pad_mode == 1) { sy = ff_reflect(y, H); sx = ff_reflect(x, W); ok = true; }
     if (ok) v = in[(((long long)b * C + c) * H + sy) * W + sx] + (add ? add[c] : 0.f);
     out[(((long long)b * Hp + y) * Wp + x) * ldo + c] = v;
   }

@@ -7,6 +7,9 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const float* ff_lds_cf;
 
 #define FF_OK 0
 #define FF_ERR_ARG 1
@@ -31,6 +34,31 @@ void ff_set_error(const char* fmt, ...);
       return FF_ERR_LAUNCH;                                                \
     }                                                                      \
   } while (0)
+
+// ---- phase stamps: a debug aid of tools/*_time.cpp, compiled in with -DFF_TIMING only -------------------------------------------
+// A kernel's params struct carries FF_STAMP_MEMBER, its entry point says FF_STAMP_ARM(p), and lane 0 of every wave writes
+// wall_clock64() (100 MHz) into slot i of its row of the stamp buffer [block][8 waves][per_wave] with FF_STAMP(per_wave, i);
+// FF_STAMP_DRAINED waits for the wave's outstanding stores first.  Without FF_TIMING the member expands to nothing and the others to an empty statement.
+#ifdef FF_TIMING
+static unsigned long long* g_ff_stamps = nullptr;      // set by the tool; nullptr = no stamps
+#define FF_STAMP_MEMBER unsigned long long* dbg;
+#define FF_STAMP_ARM(p) (p).dbg = g_ff_stamps
+#define FF_STAMP(per_wave, i)                                                                                             \
+  do {                                                                                                                    \
+    if (p.dbg && (threadIdx.x & 63) == 0)                                                                                 \
+      p.dbg[((long long)blockIdx.x * 8 + (threadIdx.x >> 6)) * (per_wave) + (i)] = wall_clock64();                        \
+  } while (0)
+#define FF_STAMP_DRAINED(per_wave, i)                    \
+  do {                                                   \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     \
+    FF_STAMP(per_wave, i);                               \
+  } while (0)
+#else
+#define FF_STAMP_MEMBER
+#define FF_STAMP_ARM(p) do { } while (0)
+#define FF_STAMP(per_wave, i) do { } while (0)               // (a statement: `if (ht < 3) FF_STAMP(..);` stays well formed)
+#define FF_STAMP_DRAINED(per_wave, i) do { } while (0)
+#endif
 
 // activation codes shared by every epilogue (include/ff_kernels.h FF_ACT_*)
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_LRELU = 3, ACT_SIGMOID = 4 };
@@ -134,6 +162,88 @@ __device__ __forceinline__ void ff_wave_rows_to_frags(const float* __restrict__ 
     }
   }
 }
+
+// ---- LayerNorm on MFMA B fragments (the layout ff_wave_rows_to_frags leaves: v[st][j] = x[row l31][16 st + 8 hh + j]) ----------
+// A LayerNorm or split change is made HERE -- and then carried to the sites that repeat this arithmetic inline, each for a
+// measured reason stated at the site (registers, spills or time moved when the code went through the helpers):
+//   token_linear.hip        token_linear_kernel: statistics and step (optional gamma; the statistics helper costs an occupancy step)
+//   chan_qkv.hip            chan_qkv_kernel: statistics, step and split (slower through the helpers)
+//   naf_tail.hip            naf_tail_kernel: statistics and step (slower through the helpers)
+//   naf_fused.hip           naf_ffn_kernel: statistics, step and split (through the helpers the output bits moved)
+//   naf_front.inc           naf_front_kernel: statistics, step and split (slower through the helpers)
+//   win_attn_fused_v2.inc   win_attn_fused_v2_kernel: statistics and step (slower through the statistics helper)
+//   token_mlp.hip           token_projmlp_kernel, token_projmlp_bf16_kernel: statistics in the ACCUMULATOR layout (a helper spills)
+// Callers: token_mlp_kernel (all three helpers), win_attn_fused_kernel (the statistics; its own optional-gamma step).
+// Where K is a compile-time 16 KS (NAFNet) the k < K masks and the index clamps fold away.
+// Statistics of a row over its K channels: plain sums in st-major order, the lane pair (l, l ^ 32) holds the row's two halves.
+template <int KS>
+__device__ __forceinline__ void ff_frag_ln_stats(const float (&v)[KS][8], int K, int hh, float eps, float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int st = 0; st < KS; ++st)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += v[st][j];
+  s += __shfl_xor(s, 32);
+  mean = s / (float)K;
+  float qv = 0.f;
+#pragma unroll
+  for (int st = 0; st < KS; ++st)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = (16 * st + 8 * hh + j < K) ? v[st][j] - mean : 0.f;
+      qv += d * d;
+    }
+  qv += __shfl_xor(qv, 32);
+  rstd = 1.0f / sqrtf(qv / (float)K + eps);
+}
+
+// One k-step: f[j] = (v[j] - mean) * rstd * gamma[k0 + j] + beta[k0 + j], zero beyond K (k0 = 16 st + 8 hh).  The two float4
+// loads per vector are clamped to index 0 beyond K: those values are unused.
+__device__ __forceinline__ void ff_frag_ln_step(const float (&v)[8], const float* gamma, const float* beta, int k0, int K,
+                                                float mean, float rstd, float (&f)[8]) {
+  const int ka = k0 < K ? k0 : 0, kb = k0 + 4 < K ? k0 + 4 : 0;
+  const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + ka), b0 = *reinterpret_cast<const f32x4*>(beta + ka);
+  const f32x4 g1 = *reinterpret_cast<const f32x4*>(gamma + kb), b1 = *reinterpret_cast<const f32x4*>(beta + kb);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float gg = j < 4 ? g0[j & 3] : g1[j & 3], bb = j < 4 ? b0[j & 3] : b1[j & 3];
+    f[j] = (k0 + j < K) ? (v[j] - mean) * rstd * gg + bb : 0.f;
+  }
+}
+
+// split-bf16 operand pair: h + l carries 16 mantissa bits of f
+__device__ __forceinline__ void ff_bf16_split(float f, __bf16& h, __bf16& l) {
+  h = (__bf16)f;
+  l = (__bf16)(f - (float)h);
+}
+
+// ---- small helpers shared by several files ---------------------------------------------------------------------------------
+__device__ __forceinline__ float ff_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// exchanges bits 2 and 3 of a k index (the channel order in which prep.py stores the second GEMM's weights)
+__device__ __forceinline__ int ff_swap23(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
+
+// lo <- the value held by lanes 0..31, hi <- the value held by lanes 32..63, in every lane (lane l and l ^ 32 pair up).
+// v_permlane32_swap exchanges the upper half of its first operand with the lower half of its second; written as inline
+// assembly because this toolchain's builtin returns the first result twice.  The s_nop pairs cover the VALU -> permlane and
+// permlane -> VALU wait states the compiler's hazard recogniser would otherwise insert.
+__device__ __forceinline__ void ff_halves(float v, float& lo, float& hi) {
+  float a = v, b = v;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
+  lo = a; hi = b;
+}
+
+__device__ __forceinline__ int ff_reflect(int i, int n) {   // F.pad(mode='reflect') index map
+  if (i < 0) i = -i;
+  if (i >= n) i = 2 * (n - 1) - i;
+  return i;
+}
+
+__device__ __forceinline__ float ff_clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
 static inline int ff_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

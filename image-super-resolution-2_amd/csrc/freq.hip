@@ -4,12 +4,6 @@
 // band fusion 27-channel concat) address slices in place.  All HBM/LDS-bound, tiny FLOP counts.
 #include "ff_common.h"
 
-__device__ __forceinline__ int reflect_i(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * (n - 1) - i;
-  return i;
-}
-
 // ------------------------------------------------------------------------------------------ DCT
 // One 8x8 block per 64 threads, 4 blocks per workgroup.  coef = D (X D^T); band_b = D^T ((coef.mask_b) D).
 __global__ __launch_bounds__(256) void dct8_bands_kernel(const float* __restrict__ x, int C, int H, int W,
@@ -26,7 +20,7 @@ __global__ __launch_bounds__(256) void dct8_bands_kernel(const float* __restrict
   int c = 0, by = 0, bx = 0;
   if (live) { bx = (int)(blk % nbx); long long t = blk / nbx; by = (int)(t % nby); c = (int)(t / nby); }
   const int yy = by * 8 + i, xx = bx * 8 + j;
-  sX[g][e] = live ? x[((long long)c * H + reflect_i(yy, H)) * W + reflect_i(xx, W)] : 0.f;
+  sX[g][e] = live ? x[((long long)c * H + ff_reflect(yy, H)) * W + ff_reflect(xx, W)] : 0.f;
   __syncthreads();
   float s = 0.f;                                            // T = X D^T : T[i][v] = sum_j X[i][j] D[v][j]
 #pragma unroll
@@ -78,8 +72,8 @@ __global__ __launch_bounds__(256) void dwt_pass_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float v;
-      if (axis == 1) v = in[((long long)c * H + y) * W + reflect_i(2 * x + k - 7, W)];
-      else v = in[((long long)c * H + reflect_i(2 * y + k - 7, H)) * W + x];
+      if (axis == 1) v = in[((long long)c * H + y) * W + ff_reflect(2 * x + k - 7, W)];
+      else v = in[((long long)c * H + ff_reflect(2 * y + k - 7, H)) * W + x];
       a += lo[k] * v;
       b += hi[k] * v;
     }

@@ -8,16 +8,14 @@
 // Images are planar NCHW fp32 [C][H][W] (C = 3 or 1), the layout the plugin's outputs have.
 #include "ff_common.h"
 
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-
 // channel value at (c, y, x) of the evaluated image: clamped, optionally converted to luma (then c == 0)
 __device__ __forceinline__ float metric_px(const float* __restrict__ img, int C, int H, int W, int c, int y, int x, int use_y) {
   const long long P = (long long)H * W, o = (long long)y * W + x;
   if (use_y && C == 3) {
-    const float r = clamp01(img[o]), g = clamp01(img[P + o]), b = clamp01(img[2 * P + o]);
+    const float r = ff_clamp01(img[o]), g = ff_clamp01(img[P + o]), b = ff_clamp01(img[2 * P + o]);
     return (65.481f * r + 128.553f * g + 24.966f * b + 16.0f) / 255.0f;
   }
-  return clamp01(img[(long long)c * P + o]);
+  return ff_clamp01(img[(long long)c * P + o]);
 }
 
 __device__ __forceinline__ double block_sum_256(double v, double* sh) {

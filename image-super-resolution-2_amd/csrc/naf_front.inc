@@ -120,6 +120,8 @@ __global__ __launch_bounds__(512, KS == 4 ? 4 : 2) void naf_front_kernel(NafFron
         for (int e = 0; e < 4; ++e) { v[4 * pass + s4][e] = a[e]; v[4 * pass + s4][4 + e] = b[e]; }
       }
     }
+    // the LayerNorm of ff_common.h (ff_frag_ln_stats / _step / ff_bf16_split), inline on purpose: through the helpers
+    // naf_front_kernel<4, 1> measured 293.2 / 279.3 us against 278.8 / 272.5 us under the bench
     float s = 0.f;
 #pragma unroll
     for (int st = 0; st < KS; ++st)

@@ -8,8 +8,6 @@
 //                          B operand of the second GEMM).  HBM traffic: y in, out out (537 MB at level 0 instead of 2.9 GB).
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // --------------------------------------------------------------------------------------------- dwconv + gate + pool sums
 // A thread owns 4 channels (of each gate half) of a 4-row output strip at one column: a 6 x 3 input window and the 9 tap
 // weights per half live in registers, so an output costs 9 float4 input loads (18 with one pixel per thread) and the
@@ -201,6 +199,10 @@ __global__ __launch_bounds__(512) void naf_ffn_kernel(NafFfnParams p) {
     float v[KS][8];
     float* xs = (KS >= 8) ? reinterpret_cast<float*>(XLs + (size_t)wid * 32 * XLROWB) : XSt + wid * (32 * FF_XS_ROW);
     ff_wave_rows_to_frags<KS / 4>(p.y, p.ldy, tok0, p.M, C, xs, lane, v);
+    // the LayerNorm of ff_common.h (ff_frag_ln_stats / _step / ff_bf16_split), inline on purpose: with the statistics and the split
+    // through the helpers ops.naf_ffn came out different in the last bits from the inline form (sha256 of the output, c = 64 and
+    // 128, split and plain bf16; which instruction rounds differently was not found), and with the step as well
+    // naf_ffn_kernel<8, 1> went from 166 to 170 VGPRs, reported occupancy 3 -> 2
     float s = 0.f;
 #pragma unroll
     for (int st = 0; st < KS; ++st)

@@ -7,12 +7,6 @@
 // All three are HBM-bound: one read of the row / tensor, one write.
 #include "ff_common.h"
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, int ldi, float* __restrict__ out,
                                                         int ldo, int rows, int C, const float* __restrict__ g,
@@ -29,7 +23,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     v[i] = c < C ? x[c] : 0.f;
     s += v[i];
   }
-  const float mean = wave_sum(s) / (float)C;
+  const float mean = ff_wave_sum(s) / (float)C;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -37,7 +31,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const float d = c < C ? v[i] - mean : 0.f;
     q += d * d;
   }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
+  const float rstd = 1.0f / sqrtf(ff_wave_sum(q) / (float)C + eps);
   float* y = out + (long long)row * ldo;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -231,14 +225,14 @@ __global__ __launch_bounds__(256) void vec_mlp_kernel(const float* __restrict__ 
     for (int j = wid; j < Ch; j += 4) {
       float s = 0.f;
       for (int i = lane; i < Cin; i += 64) s += W1[(long long)j * Cin + i] * xin[i];
-      s = wave_sum(s);
+      s = ff_wave_sum(s);
       if (lane == 0) hid[j] = ff_act(s + (b1 ? b1[j] : 0.f), act1);
     }
     __syncthreads();
     for (int o = blockIdx.x * 4 + wid; o < Cout; o += gridDim.x * 4) {
       float s = 0.f;
       for (int i = lane; i < Ch; i += 64) s += W2[(long long)o * Ch + i] * hid[i];
-      s = wave_sum(s);
+      s = ff_wave_sum(s);
       if (lane == 0) out[(long long)b * Cout + o] = ff_act(s + (b2 ? b2[o] : 0.f), act2) * post;
     }
   } else {
@@ -253,7 +247,7 @@ __global__ __launch_bounds__(256) void vec_mlp_kernel(const float* __restrict__ 
       } else {
         for (int i = lane; i < Cin; i += 64) s += W1[(long long)o * Cin + i] * xin[i];
       }
-      s = wave_sum(s);
+      s = ff_wave_sum(s);
       if (lane == 0) out[(long long)b * Ch + o] = ff_act(s + (b1 ? b1[o] : 0.f), act1) * post;
     }
   }
@@ -325,7 +319,7 @@ __global__ __launch_bounds__(1024) void pool_vec_mlp_kernel(const float* __restr
   for (int j = rg; j < Ch; j += 16) {
     float s = 0.f;
     for (int i = lane; i < Cin; i += 64) s += W1[(long long)j * Cin + i] * xin[i];
-    s = wave_sum(s);
+    s = ff_wave_sum(s);
     if (lane == 0) hid[j] = ff_act(s + (b1 ? b1[j] : 0.f), act1);
   }
   __syncthreads();

@@ -16,8 +16,6 @@
 // rotated (prep.pack_rel_overlap) so that  i = 600 - 39 qy - qx + 39 ky + kx  is in [0, 1521).
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define OC_NK 576
 #define OC_RELW 39
 #define OC_RELN 1521
@@ -37,27 +35,8 @@ struct OcabParams {
   const float* qkv; float* out; const float* rel;
   int ldq, ldo, q_off, k_off, v_off, o_off, B, H, W, nwx, nwy, heads, out_bf16;
   float scale;
-#ifdef OC_TIMING
-  unsigned long long* dbg;   // tools/oc_time.cpp: [block][wave][64] wall-clock stamps (debug build only)
-#endif
+  FF_STAMP_MEMBER
 };
-#ifdef OC_TIMING
-static unsigned long long* g_oc_dbg = nullptr;
-#define OC_T(i) do { if (p.dbg && (threadIdx.x & 63) == 0) p.dbg[((long long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 64 + (i)] = wall_clock64(); } while (0)
-#else
-#define OC_T(i) do { } while (0)
-#endif
-
-typedef __attribute__((address_space(3))) const float* oc_lds_cf;
-
-// the value held by lanes 0..31 / 32..63, in every lane (see win_attn_fused_v2.inc: inline assembly because the builtin of this
-// toolchain returns its first result twice)
-__device__ __forceinline__ void oc_halves(float v, float& lo, float& hi) {
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  lo = a; hi = b;
-}
-__device__ __forceinline__ int oc_swap23(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
 
 __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -68,7 +47,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   const int wx = bid % p.nwx; bid /= p.nwx;
   const int wy = bid % p.nwy;
   const int b = bid / p.nwy;
-  OC_T(0);
+  FF_STAMP(64, 0);
 
   // ---- key table in TILE order: key index 32 T + kappa, T = 3 tr + tc, is window position (4 tr + kappa / 8, 8 tc + kappa % 8) ---
   for (int kidx = tid; kidx < OC_NK; kidx += 512) {
@@ -131,7 +110,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
           const unsigned pk = (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, c) << 16);
           *reinterpret_cast<unsigned*>(kb + kl * OC_KROWB + 4 * spr) = pk;
         } else {
-          const int ch = 2 * (spr - 15), pos = oc_swap23(kl);
+          const int ch = 2 * (spr - 15), pos = ff_swap23(kl);
           *reinterpret_cast<__bf16*>(vb + ch * OC_VROWB + 2 * pos) = a;
           *reinterpret_cast<__bf16*>(vb + (ch + 1) * OC_VROWB + 2 * pos) = c;
         }
@@ -173,7 +152,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  OC_T(1);
+  FF_STAMP(64, 1);
   f32x16 o;
   float m_run = -INFINITY;
   const int nsteps = 2 * p.heads;
@@ -184,7 +163,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
       stage_load((n + 1) >> 1, (n + 1) & 1, 0);
       if (st == 1) head_load(h + 1);
     }
-    if (n < 4) OC_T(2 + 4 * n);
+    if (n < 4) FF_STAMP(64, 2 + 4 * n);
     if (st == 0) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -201,7 +180,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
         const int t = 3 * tq + tm;
         unsigned ra = rel0 + 4u * (unsigned)(tq * 4 * OC_RELW + tm * 8);
         asm volatile("" : "+v"(ra));                    // one base register per tile: the gathers below use immediate offsets
-        const oc_lds_cf relp = (oc_lds_cf)(size_t)ra;
+        const ff_lds_cf relp = (ff_lds_cf)(size_t)ra;
         f32x16 sc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sc[r] = relp[(r >> 2) * OC_RELW + (r & 3)];
@@ -218,7 +197,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
         for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
         {
           float lo, hi;
-          oc_halves(mx, lo, hi);
+          ff_halves(mx, lo, hi);
           mx = fmaxf(lo, hi);
         }
         if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0) {
@@ -238,10 +217,10 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
         }
       }
     }
-    if (n < 4) OC_T(3 + 4 * n);
+    if (n < 4) FF_STAMP(64, 3 + 4 * n);
     if (st == 1) {                                       // head finished: channel 30 = register 14 of the upper half-wave holds sum(P)
       float lo, den;
-      oc_halves(o[14], lo, den);
+      ff_halves(o[14], lo, den);
       const float inv = 1.0f / den;
       if (qvalid && p.out_bf16) {                       // bf16 rows (ldo in elements): the consumer rounds to bf16 anyway
         typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -266,12 +245,12 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
       stage_store(buf ^ 1);
       if (st == 1) head_store(h + 1);
     }
-    if (n < 4) OC_T(4 + 4 * n);
+    if (n < 4) FF_STAMP(64, 4 + 4 * n);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                        // the next stage is in LDS; every wave is done with this one
-    if (n < 4) OC_T(5 + 4 * n);
+    if (n < 4) FF_STAMP(64, 5 + 4 * n);
   }
-  OC_T(60);
+  FF_STAMP(64, 60);
 }
 
 extern "C" int ff_ocab_attn(const float* qkv, int ldq, int q_off, int k_off, int v_off, float* out, int ldo, int o_off,
@@ -285,9 +264,7 @@ extern "C" int ff_ocab_attn(const float* qkv, int ldq, int q_off, int k_off, int
   OcabParams p;
   p.qkv = qkv; p.out = out; p.rel = rel_rotated; p.ldq = ldq; p.ldo = ldo; p.q_off = q_off; p.k_off = k_off; p.v_off = v_off; p.o_off = o_off;
   p.B = B; p.H = H; p.W = W; p.nwx = W / 16; p.nwy = H / 16; p.heads = heads; p.scale = scale; p.out_bf16 = out_bf16;
-#ifdef OC_TIMING
-  p.dbg = g_oc_dbg;
-#endif
+  FF_STAMP_ARM(p);
   const long long nblk = (long long)B * p.nwx * p.nwy;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_ocab_attn: grid too large");
   static_assert(OC_LDS <= 160 * 1024, "LDS image too large");

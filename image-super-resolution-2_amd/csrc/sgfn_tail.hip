@@ -16,8 +16,6 @@
 //   * epilogue: + b2 + residual, transposed through LDS into 128-byte row segments.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define SG_TH 8
 #define SG_TW 32
 #define SG_HW (SG_TW + 2)                 // halo width 34
@@ -40,16 +38,8 @@ struct SgfnParams {
   const float* h; const float* stats; const float* gamma; const float* beta; const float* dww; const float* dwb;
   const __bf16* w2; const float* b2; const float* res; float* out;
   int ldh, c2, ldr, ldo, B, H, W, N, HT, ntx, nty;
-#ifdef SG_TIMING
-  unsigned long long* dbg;   // tools/sg_time.cpp: [block][wave][8] wall-clock stamps (debug build only)
-#endif
+  FF_STAMP_MEMBER
 };
-#ifdef SG_TIMING
-static unsigned long long* g_sg_dbg = nullptr;
-#define SG_T(i) do { if (p.dbg && (threadIdx.x & 63) == 0) p.dbg[((long long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define SG_T(i) do { } while (0)
-#endif
 
 __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
   const int ty = bid % p.nty;
   const int b = bid / p.nty;
   const int y0 = ty * SG_TH, x0 = tx * SG_TW;
-  SG_T(0);
+  FF_STAMP(8, 0);
 
   // ---- per-workgroup tables: halo pixel -> token (or -1), its LayerNorm statistics; gamma / beta ------------------------------
   if (tid < SG_HP) {
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
     }
   };
 
-  SG_T(1);
+  FF_STAMP(8, 1);
   stage_load(0);
   x1_load(0, x1c);
   stage_store(0, 0);
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  SG_T(2);
+  FF_STAMP(8, 2);
   for (int c = 0; c < p.HT; ++c) {
     const int buf = c & 1;
     const bool more = c + 1 < p.HT;
@@ -204,7 +194,7 @@ __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
     __builtin_amdgcn_s_barrier();                        // chunk c+1 is staged and its fc2 tile has landed; every wave is done with chunk c
   }
 
-  SG_T(3);
+  FF_STAMP(8, 3);
   // ---- epilogue: + b2 + residual, through the wave's LDS patch (the halo buffers are idle) into 128-byte row segments ---------
   {
     float* patch = reinterpret_cast<float*>(smem) + wid * (32 * 36);
@@ -242,11 +232,8 @@ __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
       }
     }
   }
-  SG_T(4);
-#ifdef SG_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  SG_T(5);
-#endif
+  FF_STAMP(8, 4);
+  FF_STAMP_DRAINED(8, 5);
 }
 
 extern "C" int ff_sgfn_tail(const float* h, int ldh, int c2, const float* stats, const float* gamma, const float* beta,
@@ -264,9 +251,7 @@ extern "C" int ff_sgfn_tail(const float* h, int ldh, int c2, const float* stats,
   p.h = h; p.stats = stats; p.gamma = gamma; p.beta = beta; p.dww = dw_tapmajor; p.dwb = dw_bias; p.w2 = (const __bf16*)fc2_tiles;
   p.b2 = b2; p.res = res; p.out = out; p.ldh = ldh; p.c2 = c2; p.ldr = ldr; p.ldo = ldo; p.B = B; p.H = H; p.W = W; p.N = N; p.HT = hidden_tiles;
   p.ntx = (W + SG_TW - 1) / SG_TW; p.nty = (H + SG_TH - 1) / SG_TH;
-#ifdef SG_TIMING
-  p.dbg = g_sg_dbg;
-#endif
+  FF_STAMP_ARM(p);
   const long long nblk = (long long)B * p.ntx * p.nty;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_sgfn_tail: grid too large");
   static_assert(SG_LDS <= 160 * 1024, "LDS image too large");

@@ -20,7 +20,6 @@ extern "C" int ff_irfft2(const float* spec, int C, int H, int W, const float* tw
 
 #define LS_NB 1024                                  // grid of the grid-stride kernels = number of partials
 
-__device__ __forceinline__ float ls_clamp(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 __device__ __forceinline__ float ls_mask(float x) { return (x >= 0.f && x <= 1.f) ? 1.f : 0.f; }
 __device__ __forceinline__ float ls_sign(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 __device__ __forceinline__ void ls_put(float* __restrict__ dsr, long long i, float g, int acc) { dsr[i] = acc ? dsr[i] + g : g; }
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(256) void pointwise_loss_kernel(int kind, const flo
   __shared__ float red[256];
   float s = 0.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float x = sr[i], d = ls_clamp(x) - hr[i];
+    const float x = sr[i], d = ff_clamp01(x) - hr[i];
     float v, g;
     if (kind == 0) { v = fabsf(d); g = ls_sign(d); }
     else if (kind == 1) { v = sqrtf(d * d + 1e-12f); g = d / v; }
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
     float va = 0.f, vb = 0.f;
     if (y >= 0 && y < H && x >= 0 && x < W) {
       const long long o = (((long long)b * H + y) * W + x) * 3 + c;
-      va = ls_clamp(sr[o]);
+      va = ff_clamp01(sr[o]);
       vb = hr[o];
     }
     pa[ly][lx] = va;
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
       f0 += wk * hq[0][ly + k][lx]; f1 += wk * hq[1][ly + k][lx]; f2 += wk * hq[2][ly + k][lx];
     }
     const long long o = (((long long)b * H + oy) * W + ox) * 3 + c;
-    const float xs = sr[o], xv = ls_clamp(xs), yv = hr[o];
+    const float xs = sr[o], xv = ff_clamp01(xs), yv = hr[o];
     ls_put(dsr, o, -gscale * ls_mask(xs) * (f0 + 2.f * xv * f1 + yv * f2), acc);
   }
 }
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(const float* __restrict__
         const int xx = x + kj - 1;
         if (xx < 0 || xx >= W) continue;
         const long long o = ((b * H + yy) * W + xx) * 3 + c;
-        const float d = ls_clamp(sr[o]) - hr[o];
+        const float d = ff_clamp01(sr[o]) - hr[o];
         gx += ls_kx(ki, kj) * d;
         gy += ls_ky(ki, kj) * d;
       }
@@ -312,7 +311,7 @@ __global__ __launch_bounds__(256) void swt_l0_kernel(const float* __restrict__ s
     const int x = (int)(p % W), y = (int)((p / W) % H);
     const long long b = p / ((long long)W * H);
     float bp[4], bt[4];
-    ls_swt_bands([&](long long o) { return ls_clamp(sr[o]); }, b, y, x, c, H, W, 1, bp);
+    ls_swt_bands([&](long long o) { return ff_clamp01(sr[o]); }, b, y, x, c, H, W, 1, bp);
     ls_swt_bands([&](long long o) { return hr[o]; }, b, y, x, c, H, W, 1, bt);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -393,7 +392,7 @@ __global__ __launch_bounds__(256) void nhwc_to_planes_kernel(const float* __rest
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % 3);
     const long long p = i / 3, b = p / HW, o = (b * 3 + c) * HW + p % HW;
-    P[o] = ls_clamp(sr[i]);
+    P[o] = ff_clamp01(sr[i]);
     T[o] = hr[i];
   }
 }

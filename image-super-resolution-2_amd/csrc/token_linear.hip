@@ -10,8 +10,6 @@
 // Dataflow per n-tile: OUT^T[n][token] = W_tile . X^T   (A = W rows from LDS, B = X fragments), 36 MFMAs (bf16x3).
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // KS = k-steps of 16 (K padded to 16*KS): 12 for the 180-wide transformers, 4 / 8 for NAFNet's 64 / 128 channels.
 // Per W row: 2*KS data slots of 16 bytes + 1 pad slot; a tile (32 rows, hi + lo planes) is 2*32*(2KS+1)/64 DMA pieces
 // (25 / 17 / 9 -- always integral).
@@ -192,6 +190,8 @@ __global__ __launch_bounds__(512) void token_linear_kernel(TokenLinParams p) {
     ff_wave_rows_to_frags<TL_KS / 4>(p.x, p.ldx, tok0, p.M, p.K, xs, lane, v);
     float mean = 0.f, rstd = 1.f;
     if (p.gamma) {
+      // ff_frag_ln_stats, inline on purpose: with the helper token_linear_kernel<1, 8, false, false, 1> goes from 165 to 169 VGPRs
+      // and its reported occupancy from 3 to 2 waves per SIMD (reference and __restrict__ forms alike)
       float s = 0.f;
 #pragma unroll
       for (int st = 0; st < TL_KS; ++st)

@@ -20,8 +20,6 @@
 // Workgroup = 8 waves = 256 tokens: 65 536 tokens -> 256 workgroups = one per CU.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #define TM_KP 192      // padded K (model dim 180)
 #define TM_NP 192      // padded N
 #define TM_KS 12       // k-steps of 16
@@ -100,42 +98,22 @@ __global__ __launch_bounds__(512) void token_mlp_kernel(TokenMlpParams p) {
   unsigned char* xl_row = XLs + (size_t)(wid * 32 + l31) * XLROWB + 16 * hh;     // + 32*st per k-step
   {
     float v[TM_KS][8];
-    float s = 0.f;
     // staging patch = this wave's own x_lo rows (12.8 KB, written only below, after the fragments are in registers)
     ff_wave_rows_to_frags<3>(p.x, p.ldx, (long long)blockIdx.x * 256 + wid * 32, p.M, p.K,
                           reinterpret_cast<float*>(XLs + (size_t)wid * 32 * XLROWB), lane, v);
-#pragma unroll
-    for (int st = 0; st < TM_KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[st][j];
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)p.K;
-    float qv = 0.f;
-#pragma unroll
-    for (int st = 0; st < TM_KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 16 * st + 8 * hh + j;
-        const float d = (k < p.K) ? v[st][j] - mean : 0.f;
-        qv += d * d;
-      }
-    qv += __shfl_xor(qv, 32);
-    const float rstd = 1.0f / sqrtf(qv / (float)p.K + p.eps);
+    float mean, rstd;
+    ff_frag_ln_stats<TM_KS>(v, p.K, hh, p.eps, mean, rstd);
 #pragma unroll
     for (int st = 0; st < TM_KS; ++st) {
-      const int k0 = 16 * st + 8 * hh;
-      const int ka = k0 < p.K ? k0 : 0, kb = k0 + 4 < p.K ? k0 + 4 : 0;     // clamped: values beyond K are unused
-      const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.gamma + ka), b0 = *reinterpret_cast<const f32x4*>(p.beta + ka);
-      const f32x4 g1 = *reinterpret_cast<const f32x4*>(p.gamma + kb), b1v = *reinterpret_cast<const f32x4*>(p.beta + kb);
+      float f[8];
+      ff_frag_ln_step(v[st], p.gamma, p.beta, 16 * st + 8 * hh, p.K, mean, rstd, f);
       bf16x8 lo;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const int k = k0 + j;
-        const float gg = j < 4 ? g0[j & 3] : g1[j & 3], bb = j < 4 ? b0[j & 3] : b1v[j & 3];
-        const float f = (k < p.K) ? (v[st][j] - mean) * rstd * gg + bb : 0.f;
-        const __bf16 h = (__bf16)f;
+        __bf16 h, l;
+        ff_bf16_split(f[j], h, l);
         xh[st][j] = h;
-        lo[j] = (__bf16)(f - (float)h);
+        lo[j] = l;
       }
       *reinterpret_cast<bf16x8*>(xl_row + 32 * st) = lo;
     }
@@ -336,16 +314,8 @@ struct TokenProjMlpParams {
   int lda, ldx, ldc, ldo, K, N, HT;
   float eps;
   int io_bf16;            // plain-bf16 kernel only: bit 0 = att rows are bf16 (lda in elements), bit 1 = c2 rows are bf16 (ldc in elements)
-#ifdef TM_TIMING
-  unsigned long long* dbg;   // tools/pm_time.cpp: [block][wave][64] wall-clock stamps (debug build only)
-#endif
+  FF_STAMP_MEMBER
 };
-#ifdef TM_TIMING
-static unsigned long long* g_tm_dbg = nullptr;
-#define TM_T(i) do { if (p.dbg && lane == 0) p.dbg[((long long)blockIdx.x * 8 + wid) * 64 + (i)] = wall_clock64(); } while (0)
-#else
-#define TM_T(i) do { } while (0)
-#endif
 
 __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -398,7 +368,7 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off1[i]),
                                          (__attribute__((address_space(3))) void*)(dst + (wid + 8 * i) * 1024), 16, 0, 0);
   };
-  TM_T(0);
+  FF_STAMP(64, 0);
   dma_proj(0, 0);
   for (int i = tid; i < p.HT * 32; i += 512) B1s[i] = p.b1[i];
 
@@ -422,7 +392,7 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
     }
   }
 
-  TM_T(1);
+  FF_STAMP(64, 1);
   // ---- proj^T tiles into the output accumulators -------------------------------------------------------------------
   f32x16 oacc[6];
 #pragma unroll
@@ -456,10 +426,10 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  TM_T(2);
+  FF_STAMP(64, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // both image areas are free again: start the MLP's first tiles
-  TM_T(3);
+  FF_STAMP(64, 3);
   dma_w1(0);
   dma_w2(0);
 
@@ -493,9 +463,11 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
       }
     }
   }
-  TM_T(4);
+  FF_STAMP(64, 4);
   // ---- LayerNorm(x1) from the accumulators -> fc1 operand (hi registers, lo rows) -------------------------------------
   {
+    // inline on purpose: through a shared helper (by reference, by value or returning a struct alike) token_projmlp_kernel spills
+    // 28-31 VGPRs (116-128 B of scratch) and token_projmlp_bf16_kernel 6-12 (28-52 B); as written here neither spills
     float s = 0.f;
 #pragma unroll
     for (int n = 0; n < 6; ++n)
@@ -535,10 +507,10 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
         *reinterpret_cast<bf16x8*>(xl_row + 32 * (2 * n + s2)) = lo;
       }
   }
-  TM_T(5);
+  FF_STAMP(64, 5);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  TM_T(6);
+  FF_STAMP(64, 6);
 
   // ---- the MLP over hidden tiles: identical to token_mlp_kernel (W1 columns are permuted to the operand order above) ----
   for (int ht = 0; ht < p.HT; ++ht) {
@@ -569,10 +541,10 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (ht < 3) TM_T(8 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 8 + 4 * ht);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (ht < 3) TM_T(9 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 9 + 4 * ht);
     if (ht + 1 < p.HT) dma_w1(ht + 1);
     bf16x8 gh[2], gl[2];
 #pragma unroll
@@ -607,13 +579,13 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (ht < 3) TM_T(10 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 10 + 4 * ht);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (ht < 3) TM_T(11 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 11 + 4 * ht);
     if (ht + 1 < p.HT) dma_w2(ht + 1);
   }
-  TM_T(40);
+  FF_STAMP(64, 40);
 
   // ---- epilogue: out = accumulators (x1 + fc2 part) + b2, transposed through LDS into 128-byte row segments ------------
   {
@@ -642,11 +614,8 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
       }
     }
   }
-  TM_T(41);
-#ifdef TM_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  TM_T(42);
-#endif
+  FF_STAMP(64, 41);
+  FF_STAMP_DRAINED(64, 42);
 }
 
 // ---- plain-bf16 form of token_projmlp (nterms == 1) ----------------------------------------------------------------------------
@@ -674,7 +643,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok0 = (long long)blockIdx.x * 256 + wid * 32;
   float* patch = reinterpret_cast<float*>(smem + PM_OFF_PATCH + wid * PM_PATCHB);      // the wave's gather / transpose patch
-  TM_T(0);
+  FF_STAMP(64, 0);
 
   // ---- the whole projection (6 tiles x 13 one-KiB pieces, hi plane) by LDS-DMA ----------------------------------------------
 #pragma unroll
@@ -743,7 +712,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
 #pragma unroll
       for (int j = 0; j < 8; ++j) xh[st][j] = (__bf16)v[st][j];
   }
-  TM_T(1);
+  FF_STAMP(64, 1);
 
   // ---- residual slices: coalesced float4 loads (lane = token row lane>>3 (+8i), channel quad), one slice ahead ----------------
   const int tq = lane >> 3, q4 = 4 * (lane & 7);
@@ -764,7 +733,6 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
     for (int i = 0; i < 4; ++i) {
       rx[i] = *reinterpret_cast<const f32x4*>(p.x + (xo[i] + cn));
       if (p.c2 && (p.io_bf16 & 2)) {
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
         const bf16x4 h4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(p.c2) + (co[i] + cn));
         rc[i] = (f32x4){(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
       } else if (p.c2) rc[i] = *reinterpret_cast<const f32x4*>(p.c2 + (co[i] + cn));
@@ -792,10 +760,10 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  TM_T(2);
+  FF_STAMP(64, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // every wave is past the projection image: the MLP's first two tiles may land on it
-  TM_T(3);
+  FF_STAMP(64, 3);
   dma_mlp(0, 0);
   if (p.HT > 1) dma_mlp(1, 1);
 #pragma unroll
@@ -820,10 +788,12 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
       }
     }
   }
-  TM_T(4);
+  FF_STAMP(64, 4);
 
   // ---- LayerNorm(x1) from the accumulators -> fc1 operand --------------------------------------------------------------------
   {
+    // inline on purpose: through a shared helper (by reference, by value or returning a struct alike) token_projmlp_kernel spills
+    // 28-31 VGPRs (116-128 B of scratch) and token_projmlp_bf16_kernel 6-12 (28-52 B); as written here neither spills
     float s = 0.f;
 #pragma unroll
     for (int n = 0; n < 6; ++n)
@@ -859,10 +829,10 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
         asm volatile("" : "+v"(xh[2 * n + s2]) :: "memory");
       }
   }
-  TM_T(5);
+  FF_STAMP(64, 5);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // tiles 0 and 1 of the MLP have landed
-  TM_T(6);
+  FF_STAMP(64, 6);
 
   // ---- the MLP over hidden tiles ---------------------------------------------------------------------------------------------
   for (int ht = 0; ht < p.HT; ++ht) {
@@ -884,7 +854,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (ht < 3) TM_T(8 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 8 + 4 * ht);
     bf16x8 gh[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -894,7 +864,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
         gh[s][j] = (__bf16)g[0];
         gh[s][j + 1] = (__bf16)g[1];
       }
-    if (ht < 3) TM_T(9 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 9 + 4 * ht);
     {
       const unsigned char* ap = smem + PM_OFF_W2 + slot * PM_W2SLOT + l31 * W2ROWB + 16 * hh;
       bf16x8 fa[2];
@@ -910,13 +880,13 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (ht < 3) TM_T(10 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 10 + 4 * ht);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                        // every wave is done with this slot; tile ht+1 has landed everywhere
-    if (ht < 3) TM_T(11 + 4 * ht);
+    if (ht < 3) FF_STAMP(64, 11 + 4 * ht);
     if (ht + 2 < p.HT) dma_mlp(ht + 2, slot);
   }
-  TM_T(40);
+  FF_STAMP(64, 40);
 
   // ---- epilogue: out = accumulators (x1 + fc2 part) + b2, transposed through the wave's patch into 128-byte row segments -----
   {
@@ -943,11 +913,8 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
       }
     }
   }
-  TM_T(41);
-#ifdef TM_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  TM_T(42);
-#endif
+  FF_STAMP(64, 41);
+  FF_STAMP_DRAINED(64, 42);
 }
 
 extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
@@ -969,9 +936,7 @@ extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int l
   p.att = att; p.x = x; p.c2 = c2; p.rs2 = c2_scale; p.out = out; p.gamma = gamma; p.beta = beta;
   p.wp = (const __bf16*)proj_tiles; p.bp = proj_bias_padded; p.w = (const __bf16*)mlp_tiles; p.b1 = b1_padded; p.b2 = b2;
   p.M = M; p.lda = lda; p.ldx = ldx; p.ldc = ldc; p.ldo = ldo; p.K = K; p.N = K; p.HT = hidden_tiles; p.eps = eps; p.io_bf16 = io_bf16;
-#ifdef TM_TIMING
-  p.dbg = g_tm_dbg;
-#endif
+  FF_STAMP_ARM(p);
   const size_t lds = (size_t)(2 * W1PL + 2 * W2PL) * 16 + (size_t)8 * 32 * XLROWB + (size_t)hidden_tiles * 32 * 4;
   FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
   const long long nblk = (M + 255) / 256;

@@ -21,12 +21,6 @@
 //                                    (train.py:338-351, checkpoint_manager.py:400-407) over one flat parameter buffer
 #include "ff_common.h"
 
-__device__ __forceinline__ float tw_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Broadcast operand: kind 0 full [rows][ld], 1 per row (element r*ld), 2 per (group, column) [G][C] with group = r / rpg,
 // 3 one device scalar, 4 absent.
@@ -293,7 +287,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
         else if (y_kind == 2) v *= y[c];
         s += v;
       }
-      s = tw_wave_sum(s) * scale;
+      s = ff_wave_sum(s) * scale;
       if (lane == 0) out[r * ldo] = accumulate ? out[r * ldo] + s : s;
     }
   }
@@ -684,11 +678,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       gv[i] = c < C ? dy[r * ldy + c] : 0.f;
       s += xv[i];
     }
-    const float mean = tw_wave_sum(s) / (float)C;
+    const float mean = ff_wave_sum(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) { const float d = (lane + 64 * i < C) ? xv[i] - mean : 0.f; q += d * d; }
-    const float rstd = 1.0f / sqrtf(tw_wave_sum(q) / (float)C + eps);
+    const float rstd = 1.0f / sqrtf(ff_wave_sum(q) / (float)C + eps);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -702,7 +696,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         xv[i] = xh; gv[i] = gh;
       }
     }
-    const float m1 = tw_wave_sum(s1) / (float)C, m2 = tw_wave_sum(s2) / (float)C;
+    const float m1 = ff_wave_sum(s1) / (float)C, m2 = ff_wave_sum(s2) / (float)C;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = lane + 64 * i;

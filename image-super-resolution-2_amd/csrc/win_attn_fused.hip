@@ -18,8 +18,6 @@
 // HBM traffic per launch: x in, attention out (+ the optional side output): 2-3 x 47 MB instead of 47+141+47 | 141+180+47.
 #include "ff_common.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct WinFusedParams {
   const float* x; float* out;
   const float* gamma; const float* beta;
@@ -32,16 +30,8 @@ struct WinFusedParams {
   int head0, nheads, d, K, zero_pad, rel_rows, rel_stride;
   int out_bf16, xn_bf16;   // plain-bf16 kernel only: out / xn are bf16 rows (ldo / ldxn in elements) -- their consumers round to bf16 anyway
   float eps;
-#ifdef WF_TIMING
-  unsigned long long* dbg;   // tools/wf_time.cpp: [block][wave][64] wall-clock stamps (debug build only)
-#endif
+  FF_STAMP_MEMBER
 };
-#ifdef WF_TIMING
-static unsigned long long* g_wf_dbg = nullptr;
-#define WF_T(i) do { if (p.dbg && lane == 0) p.dbg[((long long)blockIdx.x * 8 + wid) * 64 + (i)] = wall_clock64(); } while (0)
-#else
-#define WF_T(i) do { } while (0)
-#endif
 
 #define WF_KS 12
 #define WF_SLOTS 25                        // 16-byte slots per weight row in LDS (24 data + 1 pad)
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
   const int wx = bid % p.nwx; bid /= p.nwx;
   const int wy = bid % p.nwy;
   const int b = bid / p.nwy;
-  WF_T(0);
+  FF_STAMP(64, 0);
 
   // ---- weight-tile DMA: piece (wid + 8 i) of the 25 one-KiB pieces of a tile image --------------------------------------
   int off[4];
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
   // validity of the wave's 32 tokens as a bit mask (the v tile has tokens in its registers, not in its lanes)
   const unsigned vmask = (unsigned)(__ballot(tvalid) & 0xffffffffu);
   const bool kill_pad = p.zero_pad != 0;               // DAT: q/k/v of the zero-padded tokens are exactly zero
-  WF_T(1);
+  FF_STAMP(64, 1);
 
   // ---- the wave's 32 rows of x -> LayerNorm -> split-bf16 fragments ---------------------------------------------------
   bf16x8 xh[WF_KS], xl[WF_KS];
@@ -180,30 +170,12 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
       }
     }
     float mean = 0.f, rstd = 1.f;
-    if (p.gamma) {
-      float s = 0.f;
-#pragma unroll
-      for (int st = 0; st < WF_KS; ++st)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += v[st][j];
-      s += __shfl_xor(s, 32);
-      mean = s / (float)p.K;
-      float qv = 0.f;
-#pragma unroll
-      for (int st = 0; st < WF_KS; ++st)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float dd = (16 * st + 8 * hh + j < p.K) ? v[st][j] - mean : 0.f;
-          qv += dd * dd;
-        }
-      qv += __shfl_xor(qv, 32);
-      rstd = 1.0f / sqrtf(qv / (float)p.K + p.eps);
-    }
+    if (p.gamma) ff_frag_ln_stats<WF_KS>(v, p.K, hh, p.eps, mean, rstd);
 #pragma unroll
     for (int st = 0; st < WF_KS; ++st) {
       const int k0 = 16 * st + 8 * hh;
       f32x4 g0 = {1.f, 1.f, 1.f, 1.f}, g1 = g0, b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
-      if (p.gamma) {
+      if (p.gamma) {                                   // optional LayerNorm: this site keeps its own form of ff_frag_ln_step
         const int ka = k0 < p.K ? k0 : 0, kb = k0 + 4 < p.K ? k0 + 4 : 0;
         g0 = *reinterpret_cast<const f32x4*>(p.gamma + ka); b0 = *reinterpret_cast<const f32x4*>(p.beta + ka);
         g1 = *reinterpret_cast<const f32x4*>(p.gamma + kb); b1 = *reinterpret_cast<const f32x4*>(p.beta + kb);
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
     }
   }
 
-  WF_T(2);
+  FF_STAMP(64, 2);
   // lane part of the relative-position index: (qy + WH-1) * stride + qx + WW-1 - 4 hh   (window-local coordinates)
   // bias[q][k] = T[(qy - ky + WH-1) * RS + (qx - kx + WW-1)]: lane part minus a compile-time key part; written as
   // REL[rel_base + (CMAX - key part)] so every offset is a non-negative immediate of the ds_read
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
     bf16x8 qh[2], ql[2];
     {
       ring_step();
-      WF_T(3 + 8 * hi);
+      FF_STAMP(64, 3 + 8 * hi);
       f32x16 acc;
       const int nb = it * 32 + 4 * hh;
 #pragma unroll
@@ -304,9 +276,9 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
     }
     // ---- k tile -> K[key][d-permuted] --------------------------------------------------------------------------------
     {
-      WF_T(4 + 8 * hi);
+      FF_STAMP(64, 4 + 8 * hi);
       ring_step();
-      WF_T(5 + 8 * hi);
+      FF_STAMP(64, 5 + 8 * hi);
       f32x16 acc;
       const int nb = it * 32 + 4 * hh;
 #pragma unroll
@@ -330,7 +302,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
     }
     // ---- v tile (operands swapped: lane = channel) -> V^T[d][key-permuted] (+ optional side output) ------------------
     {
-      WF_T(6 + 8 * hi);
+      FF_STAMP(64, 6 + 8 * hi);
       ring_step();
       f32x16 acc;
       const float bv = Bs[it * 32 + l31];
@@ -365,10 +337,10 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
       }
       ++it;
     }
-    WF_T(7 + 8 * hi);
+    FF_STAMP(64, 7 + 8 * hi);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                       // K, V^T and the bias table of this head are complete
-    WF_T(8 + 8 * hi);
+    FF_STAMP(64, 8 + 8 * hi);
 
     // ---- attention: 8 chunks of 32 keys, online softmax (one S^T tile live at a time: the x fragments own 96 registers) --
     f32x16 o;
@@ -445,10 +417,10 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
       m_run = m_new;
     }
     const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
-    WF_T(9 + 8 * hi);
+    FF_STAMP(64, 9 + 8 * hi);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                       // every wave is done with K / V^T / the bias table of this head
-    WF_T(10 + 8 * hi);
+    FF_STAMP(64, 10 + 8 * hi);
 
     // ---- O^T -> rows: transpose through the wave's own K rows (private to it until its next k tile) -----------------
     {
@@ -466,11 +438,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
       }
     }
   }
-  WF_T(60);
-#ifdef WF_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  WF_T(61);
-#endif
+  FF_STAMP(64, 60);
+  FF_STAMP_DRAINED(64, 61);
 }
 
 #include "win_attn_fused_v2.inc"
@@ -502,9 +471,7 @@ extern "C" int ff_win_attn_fused(const float* x, int ldx, float* out, int ldo, i
   p.B = B; p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.sh = shift_h; p.sw = shift_w; p.use_mask = use_mask;
   p.nwx = Wp / ww; p.nwy = Hp / wh; p.head0 = head0; p.nheads = nheads; p.d = d; p.K = K; p.zero_pad = zero_pad_tokens;
   p.rel_rows = rel_rows; p.rel_stride = rel_stride; p.eps = eps; p.out_bf16 = out_bf16; p.xn_bf16 = xn_bf16;
-#ifdef WF_TIMING
-  p.dbg = g_wf_dbg;
-#endif
+  FF_STAMP_ARM(p);
   const long long nblk = (long long)B * p.nwx * p.nwy;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_win_attn_fused: grid too large");
   static_assert(WF_LDS <= 160 * 1024, "LDS image too large");

@@ -31,18 +31,6 @@
 #define W2_OFF_SAME (W2_OFF_REG + 1024)
 #define W2_LDS (W2_OFF_SAME + 9 * 8 * 4)
 
-typedef __attribute__((address_space(3))) const float* w2_lds_cf;
-
-// lo <- the value held by lanes 0..31, hi <- the value held by lanes 32..63, in every lane (lane l and l ^ 32 pair up).
-// v_permlane32_swap exchanges the upper half of its first operand with the lower half of its second; written as inline
-// assembly because this toolchain's builtin returns the first result twice.  The s_nop pairs cover the VALU -> permlane and
-// permlane -> VALU wait states the compiler's hazard recogniser would otherwise insert.
-__device__ __forceinline__ void w2_halves(float v, float& lo, float& hi) {
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-  lo = a; hi = b;
-}
-
 template <int WW, bool ONES>
 __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p) {
   constexpr int WH = 256 / WW;
@@ -61,7 +49,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
   const int wx = bid % p.nwx; bid /= p.nwx;
   const int wy = bid % p.nwy;
   const int b = bid / p.nwy;
-  WF_T(0);
+  FF_STAMP(64, 0);
 
   // ---- LDS-DMA: a head's weight image (38 one-KiB pieces, 5 per wave) and its bias table (<= 10 pieces) ---------------------
   int woff[5];
@@ -130,7 +118,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
   const bool kill_pad = p.zero_pad != 0;
   // shift mask as two extra q/k channels: +-7.0625 (bf16-exact, square 49.88) by the token's row / column region
   const float msy = (qreg_id / 3 == 2) ? -7.0625f : 7.0625f, msx = (qreg_id % 3 == 2) ? -7.0625f : 7.0625f;
-  WF_T(1);
+  FF_STAMP(64, 1);
 
   // ---- the wave's 32 rows of x -> LayerNorm -> bf16 fragments -----------------------------------------------------------------
   bf16x8 xh[WF_KS];
@@ -165,6 +153,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
     // every load of this wave has returned (the x rows were consumed above; the head-0 DMA left long before them): the
     // side-output stores below are then the only traffic in flight and nothing later has to wait for them
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // ff_frag_ln_stats, inline on purpose: with the helper every instantiation goes from 171 / 196 to 246 VGPRs and
+    // win_attn_fused_v2_kernel<32, true> from 46.17 / 45.91 us to 46.36 / 47.23 us under the bench
     float mean = 0.f, rstd = 1.f;
     if (p.gamma) {
       float s = 0.f;
@@ -210,7 +200,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
       }
     }
   }
-  WF_T(2);
+  FF_STAMP(64, 2);
 
   // bias[q][k] = T[(qy - ky + WH-1) RS + (qx - kx + WW-1)].  Register r of a lane holds key 32 t + 31 - c of tile t,
   // c = (r & 3) + 8 (r >> 2) + 4 hh, so the index is (lane part) - (tile part) + (c / WW) RS + (c % WW): ascending in r
@@ -241,7 +231,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
     // past the previous head's attention
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    WF_T(3 + 8 * hi);
+    FF_STAMP(64, 3 + 8 * hi);
     // ---- q tile: stays in registers ----------------------------------------------------------------------------------------
     bf16x8 qh[2];
     {
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
 #pragma unroll
         for (int j = 0; j < 8; ++j) qh[s][j] = (__bf16)acc[8 * s + j];
     }
-    WF_T(4 + 8 * hi);
+    FF_STAMP(64, 4 + 8 * hi);
     // ---- k tile -> K[key][d-permuted] ----------------------------------------------------------------------------------------
     {
       f32x16 acc;
@@ -279,7 +269,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
         *reinterpret_cast<bf16x8*>(kmine + 32 * s) = h8;
       }
     }
-    WF_T(5 + 8 * hi);
+    FF_STAMP(64, 5 + 8 * hi);
     // ---- v tile (operands swapped: lane = channel) -> V^T[d][key-permuted] (+ optional side output) --------------------------
     {
       f32x16 acc;
@@ -308,10 +298,10 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
         }
       }
     }
-    WF_T(6 + 8 * hi);
+    FF_STAMP(64, 6 + 8 * hi);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                       // K and V^T of this head are complete; every wave is done with the weight image
-    WF_T(7 + 8 * hi);
+    FF_STAMP(64, 7 + 8 * hi);
     if (hi + 1 < p.nheads) dma_head(g + 1, buf ^ 1);   // lands while the attention below runs
 
     // ---- attention: 8 tiles of 32 keys, online softmax -------------------------------------------------------------------------
@@ -327,7 +317,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
     for (int t = 0; t < 8; ++t, rel_addr -= 4u * TPR * RS, kp += W2_KWAVE, vq += 64) {
       unsigned ra = rel_addr;
       asm volatile("" : "+v"(ra));                      // one base register per tile: the 16 gathers below use immediates
-      const w2_lds_cf relp = (w2_lds_cf)(size_t)ra;
+      const ff_lds_cf relp = (ff_lds_cf)(size_t)ra;
       f32x16 st;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -353,7 +343,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
       for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
       {
         float lo, hi;
-        w2_halves(mx, lo, hi);
+        ff_halves(mx, lo, hi);
         mx = fmaxf(lo, hi);
       }
       if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0) {          // some query's maximum moves: rescale (wave-uniform branch)
@@ -382,16 +372,16 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
     float den;
     if (ONES) {                                          // channel 30 = register 14 of the upper half-wave holds the row sum of P
       float lo;
-      w2_halves(o[14], lo, den);
+      ff_halves(o[14], lo, den);
     } else {
       den = l_run + __shfl_xor(l_run, 32);
     }
     const float inv = 1.0f / den;
-    WF_T(8 + 8 * hi);
+    FF_STAMP(64, 8 + 8 * hi);
     // the next head's DMA (issued ~an attention ago) and the side-output stores have landed: confirmed here, BEFORE this
     // head's output stores enter the queue, so that no later wait has to drain them
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WF_T(9 + 8 * hi);
+    FF_STAMP(64, 9 + 8 * hi);
 
     // ---- O^T: lane = token, registers = channels, so every lane writes its own row segment directly (eight 8-byte stores
     //      at immediate offsets from one row pointer; the stores drain while the next head is projected) ----------------------
@@ -413,11 +403,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
         if (c + 2 < p.d) *reinterpret_cast<float2*>(orow + 8 * i + 2) = (float2){o[4 * i + 2] * inv, o[4 * i + 3] * inv};
       }
     }
-    WF_T(10 + 8 * hi);
+    FF_STAMP(64, 10 + 8 * hi);
   }
-  WF_T(60);
-#ifdef WF_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  WF_T(61);
-#endif
+  FF_STAMP(64, 60);
+  FF_STAMP_DRAINED(64, 61);
 }

@@ -119,3 +119,37 @@ def test_host_checks_refuse_before_any_launch(dev):
     finally:
         L._lib = real
     assert "ff_d4_rect_nchw" not in calls and "ff_d4_nchw" not in calls
+
+
+def _bit_patterns(shape, seed, dev):
+    """Seeded random 32-bit patterns as int32 (every exponent field: denormals, infinities and NaNs of either kind occur), with
+    -0.0, +-inf, the smallest denormal, a signalling and a payload-carrying quiet NaN planted at the front."""
+    bits = np.random.default_rng(seed).integers(-2**31, 2**31, size=shape, dtype=np.int64).astype(np.int32)
+    special = np.array([0x80000000, 0x7F800000, 0xFF800000, 0x00000001, 0x807FFFFF, 0x7F800001, 0x7FC12345, 0xFFA00000],
+                       dtype=np.uint32).view(np.int32)
+    bits.reshape(-1)[:special.size] = special
+    return torch.from_numpy(bits).to(dev)
+
+
+def test_d4_nchw_is_a_pure_copy_and_d4_rect_agrees(dev):
+    """ops.d4_nchw moves bits: no multiply and no add may touch a value, so denormals, negative zero, infinities and NaN payloads
+    (signalling ones included) arrive unchanged -- compared as int32 against torch's flip / rot90 of the int32 view.  65 x 65 is
+    ragged on both axes and takes the dword rows and the transpose; 7 x 12 takes the float4 rows in a tile narrower than 64.
+    ops.d4_rect with scale 1 is the same permutation through the emit form, t * 1: exact for every value but a signalling NaN,
+    which the multiply quiets (its contract, not the copy's) -- so the same bit patterns with the signalling NaNs made quiet
+    (bit 22 set) must come out of both bit for bit; a flush of denormals, a lost sign of zero or a stray add would show.
+    65 x 65 again, and 130 x 64 (three tiles down, float4 rows)."""
+    from isr2_amd import ops
+    for shape, codes in (((2, 3, 65, 65), range(16)), ((1, 1, 7, 12), [c for c in range(16) if not c & 4])):
+        xi = _bit_patterns(shape, 21, dev)
+        for c in codes:
+            got = ops.d4_nchw(xi.view(torch.float32), [c] * shape[0])
+            assert torch.equal(got.view(torch.int32), torch_d4(xi, c)), (shape, c)
+    for shape, codes in (((2, 3, 65, 65), range(16)), ((1, 2, 130, 64), [c for c in range(16) if not c & 4])):
+        xi = _bit_patterns(shape, 22, dev)
+        snan = ((xi & 0x7F800000) == 0x7F800000) & ((xi & 0x007FFFFF) != 0) & ((xi & 0x00400000) == 0)
+        assert snan.any()
+        x = torch.where(snan, xi | 0x00400000, xi).view(torch.float32)
+        for c in codes:
+            a, b = ops.d4_rect(x, c), ops.d4_nchw(x, [c] * shape[0])
+            assert a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32)), (shape, c)
