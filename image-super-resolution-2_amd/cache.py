@@ -9,6 +9,10 @@
 Plain `torch.save` dicts of CPU float32 tensors: the reference's reader loads them unchanged (its `_normalize_keys` passes
 hat / dat / nafnet through, `:160-175` squeezes the batch dimension).  The frozen experts are the expensive 95 % of the path;
 writing their outputs once is what lets the fusion-only training step (8f rank 1) skip them.
+
+extract() fills a directory from ready-made (stem, lr, hr) tensors, one at a time.  build_from_folders() starts at image folders:
+crop_plan() says which patches, the device cuts them (and makes the LR images of HR-only data sets), host threads decode and write
+beside the GPU (`python -m isr2_amd.build_cache`).
 """
 from __future__ import annotations
 
@@ -69,3 +73,334 @@ def extract(model, samples: Iterable[Tuple[str, T, Optional[T]]], cache_dir: str
         write_sample(cache_dir, stem, lr4, hr, outs, feats)
         n += 1
     return n
+
+
+# ---- from image folders to a cache directory --------------------------------------------------------------------------------------
+IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
+_PLAN_TRIES = 64
+
+
+def crop_plan(lr_h: int, lr_w: int, patch: int, crops: int, seed: int, image_index: int, center: bool = False):
+    """LR (top, left) of the patches cut from image number `image_index` of a data set: a pure function of its arguments.
+    center=True: the single centred position of the reference's non-augmented branch (dataset.py:282-296).  Otherwise `crops`
+    positions, top uniform in [0, lr_h - patch] and left uniform in [0, lr_w - patch] (PairedRandomCrop, augmentations.py:77-83), from a
+    random.Random seeded by (seed, image_index); a repeated position is redrawn (up to 64 tries) while the image has at least `crops`
+    distinct positions.  An image smaller than the patch gives []."""
+    import random
+    lr_h, lr_w, p, crops = int(lr_h), int(lr_w), int(patch), int(crops)
+    if p < 1 or lr_h < p or lr_w < p:
+        return []
+    if center:
+        return [((lr_h - p) // 2, (lr_w - p) // 2)]
+    rng = random.Random(((int(seed) & 0xFFFFFFFF) << 32) | (int(image_index) & 0xFFFFFFFF))
+    n_pos = (lr_h - p + 1) * (lr_w - p + 1)
+    plan = []
+    for _ in range(crops):
+        pos = (rng.randint(0, lr_h - p), rng.randint(0, lr_w - p))
+        tries = 0
+        while n_pos >= crops and pos in plan and tries < _PLAN_TRIES:
+            pos = (rng.randint(0, lr_h - p), rng.randint(0, lr_w - p))
+            tries += 1
+        plan.append(pos)
+    return plan
+
+
+def _image_stems(folder: str) -> Dict[str, str]:
+    out = {}
+    for f in sorted(os.listdir(folder)):
+        stem, ext = os.path.splitext(f)
+        if ext.lower() in IMAGE_EXTS and stem not in out:
+            out[stem] = os.path.join(folder, f)
+    return out
+
+
+class _BuildPipeline:
+    """Host side of build_from_folders, after the plugin's image pipeline: a reader thread decodes the images into pinned uint8
+    slots, writer threads run write_sample (and save the optional LR PNGs) from pinned result slots; the calling thread owns every
+    GPU call.  A slot goes back to its free queue only after the event of the last copy that touched it.  An exception on a worker
+    thread is kept and re-raised on the calling thread."""
+
+    def __init__(self, items, out_dir, tmp_dir, patch, hr_only, write_lr, device, n_writers, n_in_slots=3):
+        import queue
+        import threading
+        self.items, self.out_dir, self.tmp_dir, self.patch, self.hr_only = items, out_dir, tmp_dir, patch, hr_only
+        self.write_lr, self.device = write_lr, device
+        self.err = None
+        self.lock = threading.Lock()
+        self.t = {"decode": 0.0, "write": 0.0}
+        self.skipped = 0
+        self.written = 0
+        self.in_free, self.in_ready = queue.Queue(), queue.Queue()
+        self.out_free, self.out_ready = queue.Queue(), queue.Queue()
+        for _ in range(n_in_slots):
+            self.in_free.put({"lr": None, "hr": None, "ev": None})
+        p = patch
+        shapes = {"lr": (1, 3, p, p), "hr": (3, 4 * p, 4 * p), "o_hat": (1, 3, 4 * p, 4 * p), "o_dat": (1, 3, 4 * p, 4 * p),
+                  "o_nafnet": (1, 3, 4 * p, 4 * p), "f_hat": (1, 180, p, p), "f_dat": (1, 180, p, p), "f_nafnet": (1, 64, p, p)}
+        self.shapes = shapes
+        for _ in range(n_writers + 2):                 # every tensor owns its pinned storage: torch.save writes whole storages
+            self.out_free.put({k: torch.empty(s, dtype=torch.float32).pin_memory() for k, s in shapes.items()})
+        self.reader = threading.Thread(target=self._read_loop, name="ff-cache-reader", daemon=True)
+        self.writers = [threading.Thread(target=self._write_loop, name=f"ff-cache-writer{i}", daemon=True) for i in range(n_writers)]
+        self.reader.start()
+        for t in self.writers:
+            t.start()
+
+    @staticmethod
+    def _pinned(slot, key, nbytes):
+        if slot[key] is None or slot[key].numel() < nbytes:
+            slot[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
+        return slot[key]
+
+    def _read_loop(self):
+        import time
+        import numpy as np
+        from PIL import Image
+        try:
+            for index, (stem, hr_path, lr_path) in enumerate(self.items):
+                t0 = time.perf_counter()
+                hr_img = Image.open(hr_path)
+                W, H = hr_img.size
+                if lr_path is None:
+                    H, W = H - H % 4, W - W % 4                       # HR-only: crop top-left to multiples of 4
+                    h, w = H // 4, W // 4
+                else:
+                    lr_img = Image.open(lr_path)
+                    w, h = lr_img.size
+                    if (H, W) != (4 * h, 4 * w):
+                        raise ValueError(f"{hr_path}: HR is {H}x{W}, not exactly 4x its LR {lr_path} ({h}x{w})")
+                if h < self.patch or w < self.patch:
+                    self.skipped += 1
+                    self.t["decode"] += time.perf_counter() - t0
+                    continue
+                slot = self.in_free.get()
+                if slot is None:
+                    return
+                if slot["ev"] is not None:
+                    slot["ev"].synchronize()                          # the previous uploads out of this slot have finished
+                hr = np.asarray(hr_img.convert("RGB"), dtype=np.uint8)[:H, :W]
+                self._pinned(slot, "hr", hr.size)[:hr.size].view(H, W, 3).numpy()[...] = hr
+                if lr_path is not None:
+                    lr = np.asarray(lr_img.convert("RGB"), dtype=np.uint8)
+                    self._pinned(slot, "lr", lr.size)[:lr.size].view(h, w, 3).numpy()[...] = lr
+                self.t["decode"] += time.perf_counter() - t0
+                self.in_ready.put((slot, index, stem, h, w))
+        except BaseException as e:                                   # noqa: BLE001 -- handed to the calling thread
+            self.err = e
+        finally:
+            self.in_ready.put(None)
+
+    def _write_loop(self):
+        import time
+        try:
+            while True:
+                item = self.out_ready.get()
+                if item is None:
+                    return
+                kind, slot, ev, name = item
+                ev.synchronize()                                     # the device-to-host copies into this slot have finished
+                t0 = time.perf_counter()
+                if kind == "png":
+                    from PIL import Image
+                    h, w = slot["shape"]
+                    Image.fromarray(slot["buf"][:h * w * 3].view(h, w, 3).numpy()).save(os.path.join(self.write_lr, name + ".png"), format="PNG")
+                else:
+                    outs = {k: slot["o_" + k] for k in ("hat", "dat", "nafnet")}
+                    feats = {k: slot["f_" + k] for k in ("hat", "dat", "nafnet")}
+                    p1, p2 = write_sample(self.tmp_dir, name, slot["lr"], slot["hr"], outs, feats)
+                    os.replace(p2, os.path.join(self.out_dir, os.path.basename(p2)))    # the rest part first: a primary part file
+                    os.replace(p1, os.path.join(self.out_dir, os.path.basename(p1)))    # never exists without its partner
+                    self.out_free.put(slot)
+                with self.lock:
+                    self.t["write"] += time.perf_counter() - t0
+                    self.written += kind == "sample"
+        except BaseException as e:                                   # noqa: BLE001
+            self.err = e
+            self.out_free.put(None)                                  # keep the producer from blocking forever
+
+    def check(self):
+        if self.err is not None:
+            raise self.err
+
+    def images(self):
+        """Yields (index, stem, lr_u8 or None, hr_u8) with the uint8 images on the device, in list order."""
+        while True:
+            item = self.in_ready.get()
+            self.check()
+            if item is None:
+                return
+            slot, index, stem, h, w = item
+            hr_u8 = slot["hr"][:48 * h * w].view(4 * h, 4 * w, 3).to(self.device, non_blocking=True)
+            lr_u8 = None if self.hr_only else slot["lr"][:3 * h * w].view(h, w, 3).to(self.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            slot["ev"] = ev
+            self.in_free.put(slot)
+            yield index, stem, lr_u8, hr_u8
+
+    def save_sample(self, stem, lr, hr, outs, feats):
+        """Queue one patch's tensors (device) for write_sample: copied into a pinned slot, written once the copies' event is done."""
+        self.check()
+        slot = self.out_free.get()
+        self.check()
+        slot["lr"].copy_(lr, non_blocking=True)
+        slot["hr"].copy_(hr, non_blocking=True)
+        for k in ("hat", "dat", "nafnet"):
+            slot["o_" + k].copy_(outs[k], non_blocking=True)
+            slot["f_" + k].copy_(feats[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.out_ready.put(("sample", slot, ev, stem))
+
+    def save_png(self, stem, u8):
+        self.check()
+        h, w, _ = u8.shape
+        buf = torch.empty(u8.numel(), dtype=torch.uint8).pin_memory()
+        buf.view(h, w, 3).copy_(u8, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.out_ready.put(("png", {"buf": buf, "shape": (h, w)}, ev, stem))
+
+    def close(self):
+        for _ in self.writers:
+            self.out_ready.put(None)
+        for t in self.writers:
+            t.join()
+        self.in_free.put(None)
+        self.reader.join(timeout=5)
+
+
+class _GraphedExperts:
+    """model.experts_with_features for ONE patch shape, replayed from a HIP graph captured once (the mechanism of FreqFusionHIP.graphed:
+    a warm-up on a side stream, then the capture, with the buffers that outlive a forward keyed to this graph).  The returned tensors
+    are the graph's static output buffers: consume them on the same stream before the next call.  Captured before the pipeline's
+    threads exist, in thread-local capture mode: another thread pinning memory or waiting for an event must not end the capture."""
+
+    def __init__(self, model, patch: int):
+        from . import ops
+        self.graph = None
+        self.key = (id(model), "cache_build", int(patch))
+        dev = model.dev
+        ops.set_capture_key(self.key)
+        try:
+            with torch.cuda.device(dev):
+                self.static_in = torch.zeros((1, 3, patch, patch), device=dev, dtype=torch.float32)
+                cur = torch.cuda.current_stream()
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    model.experts_with_features(self.static_in, streams=True)
+                cur.wait_stream(side)
+                torch.cuda.synchronize(dev)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                    self.outs, self.feats = model.experts_with_features(self.static_in, streams=True)
+        finally:
+            ops.set_capture_key(None)
+
+    def __call__(self, lr: T):
+        self.static_in.copy_(lr, non_blocking=True)
+        self.graph.replay()
+        return self.outs, self.feats
+
+    def close(self):
+        """Destroy the graph NOW: left to the garbage collector, its destructor may run inside a later capture, which HIP refuses."""
+        from . import ops
+        if self.graph is not None:
+            self.graph.reset()
+        self.graph = self.outs = self.feats = self.static_in = None
+        ops.drop_persistent(key=self.key)
+
+
+@torch.no_grad()
+def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] = None, patch: int = 64, crops: int = 5, seed: int = 0,
+                       center: bool = False, writers: int = 4, write_lr: Optional[str] = None, graph: bool = True) -> dict:
+    """Image folders -> the cache directory `python -m isr2_amd.train_cached` reads.  Images are matched by stem, in sorted order; image
+    number i of that order is cut at crop_plan(h, w, patch, crops, seed, i, center) and patch k is written under the stem
+    `{image stem}_p{k}` (the bare image stem with center=True) -- both forms are what list_stems and the reference's reader take.
+
+    With lr_dir every HR image must be exactly 4x its LR partner (anything else is an error naming the file).  Without it the HR
+    image is cropped top-left to multiples of 4 and LR = f32_to_u8_image(resize_aa(u8_to_f32_image(hr))): the antialiased bicubic
+    x1/4 quantised to the uint8 a PNG would hold (write_lr=DIR saves those PNGs), so both modes cut their patches from uint8 images.
+
+    Per image: a reader thread decodes into pinned uint8 slots, the images are uploaded, ops.crop_pairs_u8 cuts every patch pair in one
+    launch, model.experts_with_features runs per patch, the results are copied into pinned slots and `writers` threads call
+    write_sample into a temporary directory and rename the two part files into place.  The expert pass makes the launches extract()
+    makes, so the files hold the same bits: the three experts of a patch run on three streams, as in model.experts(), and since all
+    patches have one shape the pass is captured once into a HIP graph and replayed per patch (graph=False launches it instead: the
+    switch exists for the bit-for-bit comparison of the two).  Images smaller than the patch are skipped and counted.
+    A reader or writer exception ends the run and is re-raised here.
+
+    Returns {graph, images, images_skipped, patches_written, seconds: {total, decode, device, write, wait_reader, wait_writer},
+    patches_per_s}: decode / write are the worker threads' busy time (write summed over the writers), device is GPU time between
+    the upload and the last result copy of each image (events), the waits are the calling thread's stalls on the queues."""
+    import shutil
+    import time
+    from . import ops
+    from .lib import FFError
+    patch, crops, writers = int(patch), int(crops), int(writers)
+    if patch < 1 or crops < 1 or writers < 1:
+        raise FFError(f"build_from_folders: patch, crops and writers must be >= 1, got {patch}, {crops}, {writers}")
+    hr_files = _image_stems(hr_dir)
+    if lr_dir is not None:
+        lr_files = _image_stems(lr_dir)
+        missing = sorted(set(hr_files) ^ set(lr_files))
+        if missing:
+            raise FileNotFoundError(f"build_from_folders: {missing[0]} has no partner in {lr_dir if missing[0] in hr_files else hr_dir}")
+    items = [(stem, hr_files[stem], None if lr_dir is None else lr_files[stem]) for stem in sorted(hr_files)]
+    os.makedirs(out_dir, exist_ok=True)
+    if write_lr is not None:
+        os.makedirs(write_lr, exist_ok=True)
+    tmp_dir = os.path.join(out_dir, f".tmp-{os.getpid()}")
+    os.makedirs(tmp_dir, exist_ok=True)
+    dev = model.dev
+    t_start = time.perf_counter()
+    wait_r = wait_w = 0.0
+    spans = []
+    n_img = 0
+    with torch.cuda.device(dev):
+        experts = _GraphedExperts(model, patch) if graph else (lambda t: model.experts_with_features(t, streams=True))
+        pipe = None
+        try:
+            pipe = _BuildPipeline(items, out_dir, tmp_dir, patch, lr_dir is None, write_lr, dev, writers)
+            it = pipe.images()
+            while True:
+                t0 = time.perf_counter()
+                nxt = next(it, None)
+                wait_r += time.perf_counter() - t0
+                if nxt is None:
+                    break
+                index, stem, lr_u8, hr_u8 = nxt
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                if lr_u8 is None:
+                    h, w = hr_u8.shape[0] // 4, hr_u8.shape[1] // 4
+                    lr_u8 = ops.f32_to_u8_image(ops.resize_aa(ops.u8_to_f32_image(hr_u8), (h, w)))
+                    if write_lr is not None:
+                        pipe.save_png(stem, lr_u8)
+                plan = crop_plan(lr_u8.shape[0], lr_u8.shape[1], patch, crops, seed, index, center)
+                lr, hr = ops.crop_pairs_u8(lr_u8, hr_u8, plan, patch)
+                for k in range(len(plan)):
+                    lr_k = lr[k:k + 1]
+                    if lr_k.data_ptr() % 16:                          # odd patch sizes: the kernels take 16-byte aligned images
+                        lr_k = lr_k.clone()
+                    outs, feats = experts(lr_k)
+                    t0 = time.perf_counter()
+                    pipe.save_sample(stem if center else f"{stem}_p{k}", lr_k, hr[k], outs, feats)
+                    wait_w += time.perf_counter() - t0
+                e1.record()
+                spans.append((e0, e1))
+                n_img += 1
+        finally:
+            if pipe is not None:
+                pipe.close()
+            torch.cuda.synchronize(dev)
+            shutil.rmtree(tmp_dir, ignore_errors=True)
+            if graph:
+                experts.close()
+        pipe.check()
+    total = time.perf_counter() - t_start
+    secs = {"total": total, "decode": pipe.t["decode"], "device": sum(a.elapsed_time(b) for a, b in spans) / 1e3,
+            "write": pipe.t["write"], "wait_reader": wait_r, "wait_writer": wait_w}
+    return {"graph": bool(graph), "images": n_img, "images_skipped": pipe.skipped, "patches_written": pipe.written,
+            "seconds": {k: round(v, 6) for k, v in secs.items()}, "patches_per_s": pipe.written / total if total > 0 else 0.0}

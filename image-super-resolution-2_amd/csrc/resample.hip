@@ -157,3 +157,145 @@ extern "C" int ff_avgpool2(const float* in, int ldi, float* out, int ldo, int B,
   FF_LAUNCH_CHECK("ff_avgpool2");
   return FF_OK;
 }
+
+// ---- cached-expert training sets (isr2_amd.cache.build_from_folders) -------------------------------------------------------------
+// Aligned LR / HR patch pairs cut out of the uploaded uint8 images: lr_u8 [h][w][3], hr_u8 [4h][4w][3] -> lr_out [K][3][p][p],
+// hr_out [K][3][4p][4p], value = u8 / 255 (IEEE division, as u8hwc_to_f32nchw_kernel).  Patch k starts at LR (top, left) =
+// pos[k] and at HR (4 top, 4 left).  One work item = four consecutive pixels of one patch row: twelve byte loads (a pixel is three
+// bytes, so the address is unaligned whenever `left` is odd -- bytes have no alignment) and one 16-byte store into each of the three
+// planes, so a wave writes whole row segments.  VEC = false (p % 4 != 0 on the LR side, or an unaligned output): scalar stores.
+// Items [0, n_lr) cut the LR patches, the rest the HR patches.  The positions are the caller's contract (ops.crop_pairs_u8 checks
+// them on the host before the launch); they are clamped here all the same, so no table can make the kernel leave the images.
+template <bool VEC>
+__device__ __forceinline__ void crop_item(const unsigned char* __restrict__ img, int H, int W, int top, int left, int P, int q, long long item,
+                                          float* __restrict__ out) {
+  const int xg = (int)(item % q); long long t = item / q;
+  const int y = (int)(t % P); const int k = (int)(t / P);
+  const int x = xg * 4;
+  const unsigned char* src = img + ((long long)(top + y) * W + left + x) * 3;
+  float* dst = out + ((long long)k * 3 * P + y) * P + x;
+  const long long plane = (long long)P * P;
+  if (VEC) {
+    f32x4 v[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c][j] = __fdiv_rn((float)src[j * 3 + c], 255.0f);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(dst + c * plane) = v[c];
+  } else {
+    const int n = min(4, P - x);
+    for (int j = 0; j < n; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dst[c * plane + j] = __fdiv_rn((float)src[j * 3 + c], 255.0f);
+  }
+}
+
+template <bool VEC_LR, bool VEC_HR>
+__global__ __launch_bounds__(256) void crop_pairs_u8_kernel(const unsigned char* __restrict__ lr, const unsigned char* __restrict__ hr, int h, int w,
+                                                            const int* __restrict__ pos, int K, int p, float* __restrict__ lr_out,
+                                                            float* __restrict__ hr_out) {
+  const int q_lr = (p + 3) >> 2, q_hr = p;                       // four-pixel groups per patch row
+  const long long n_lr = (long long)K * p * q_lr, total = n_lr + (long long)K * 4 * p * q_hr;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const bool is_hr = i >= n_lr;
+    const long long item = is_hr ? i - n_lr : i;
+    const int k = (int)(item / (is_hr ? (long long)4 * p * q_hr : (long long)p * q_lr));
+    const int top = min(max(pos[2 * k], 0), h - p), left = min(max(pos[2 * k + 1], 0), w - p);
+    if (is_hr) crop_item<VEC_HR>(hr, 4 * h, 4 * w, 4 * top, 4 * left, 4 * p, q_hr, item, hr_out);
+    else crop_item<VEC_LR>(lr, h, w, top, left, p, q_lr, item, lr_out);
+  }
+}
+
+extern "C" int ff_crop_pairs_u8(const unsigned char* lr_u8, const unsigned char* hr_u8, int h, int w, const int* pos, int K, int p,
+                                float* lr_out, float* hr_out, void* stream) {
+  FF_CHECK_ARG(lr_u8 && hr_u8 && pos && lr_out && hr_out, "ff_crop_pairs_u8: null pointer");
+  FF_CHECK_ARG(K >= 1 && p >= 1 && h >= 1 && w >= 1, "ff_crop_pairs_u8: bad sizes (K %d, p %d, image %d x %d)", K, p, h, w);
+  FF_CHECK_ARG(p <= h && p <= w, "ff_crop_pairs_u8: a %d x %d patch does not fit the %d x %d image", p, p, h, w);
+  FF_CHECK_ARG(h <= (1 << 20) && w <= (1 << 20) && p <= 8192 && K <= (1 << 20), "ff_crop_pairs_u8: sizes out of range");
+  const bool vec_hr = (((uintptr_t)hr_out) & 15) == 0, vec_lr = p % 4 == 0 && (((uintptr_t)lr_out) & 15) == 0;
+  const long long total = (long long)K * p * ((p + 3) / 4 + 4 * (long long)p);
+  long long nb = (total + 255) / 256;
+  if (nb > 8192) nb = 8192;
+#define FF_CROP_LAUNCH(A, B) \
+  hipLaunchKernelGGL((crop_pairs_u8_kernel<A, B>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, lr_u8, hr_u8, h, w, pos, K, p, lr_out, hr_out)
+  if (vec_lr && vec_hr) FF_CROP_LAUNCH(true, true);
+  else if (vec_hr) FF_CROP_LAUNCH(false, true);
+  else FF_CROP_LAUNCH(false, false);
+#undef FF_CROP_LAUNCH
+  FF_LAUNCH_CHECK("ff_crop_pairs_u8");
+  return FF_OK;
+}
+
+// Antialiased bicubic x1/4 (the degradation the x4 track is defined on; F.interpolate(mode='bicubic', antialias=True,
+// align_corners=False)), planar fp32 [planes][Hi][Wi] -> [planes][Ho][Wo] with Hi = 4 Ho, Wi = 4 Wo.  Separable, horizontal pass
+// first.  Each axis is driven by a host table (ops.aa_tables): span [O][2] = (first input index, taps <= 16) and wt [O][16] =
+// the normalised fp32 weights, zero padded.  Both passes accumulate acc = fma(w_j, x[first + j], acc) from acc = 0 in ascending j.
+// One workgroup per 16 x 64 output tile: the horizontal pass of the tile's input rows (at most 4*16 + 16) goes to LDS -- a thread
+// keeps one output column and its 16 weights in registers and walks down the rows --, the vertical pass reads LDS columns (lanes on
+// consecutive banks) with wave-uniform weights and stores 64-float row segments.  Table entries are clamped to the image and to
+// the staged rows, so a wrong table gives wrong values, never an access outside the buffers.
+#define AA_TAPS 16
+#define AA_TOY 16
+#define AA_TOX 64
+#define AA_ROWS (4 * AA_TOY + AA_TAPS)
+
+__global__ __launch_bounds__(256) void resize_aa_kernel(const float* __restrict__ in, float* __restrict__ out, int Hi, int Wi, int Ho, int Wo,
+                                                        const int* __restrict__ span_w, const float* __restrict__ wt_w,
+                                                        const int* __restrict__ span_h, const float* __restrict__ wt_h) {
+  __shared__ float rows[AA_ROWS][AA_TOX];
+  const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6;
+  const int ox = blockIdx.x * AA_TOX + lx, oy0 = blockIdx.y * AA_TOY;
+  const int oy1 = min(oy0 + AA_TOY, Ho) - 1;                     // last output row of the tile
+  const float* src = in + (long long)blockIdx.z * Hi * Wi;
+  // input rows [r0, r0 + nr) cover every tap of the tile's output rows
+  const int c0 = min(max(span_h[2 * oy0 + 1], 0), min(AA_TAPS, Hi));
+  const int r0 = min(max(span_h[2 * oy0], 0), Hi - c0);
+  const int c1 = min(max(span_h[2 * oy1 + 1], 0), min(AA_TAPS, Hi));
+  const int nr = min(min(max(span_h[2 * oy1], 0), Hi - c1) + c1 - r0, min(AA_ROWS, Hi - r0));
+  if (ox < Wo) {
+    const int cnt = min(max(span_w[2 * ox + 1], 0), min(AA_TAPS, Wi));
+    const int x0 = min(max(span_w[2 * ox], 0), Wi - cnt);
+    float w[AA_TAPS];
+#pragma unroll
+    for (int j = 0; j < AA_TAPS; j += 4) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(wt_w + (long long)ox * AA_TAPS + j);
+      w[j] = t[0]; w[j + 1] = t[1]; w[j + 2] = t[2]; w[j + 3] = t[3];
+    }
+    for (int r = ly; r < nr; r += 4) {
+      const float* line = src + (long long)(r0 + r) * Wi + x0;
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < AA_TAPS; ++j)
+        if (j < cnt) acc = fmaf(w[j], line[j], acc);
+      rows[r][lx] = acc;
+    }
+  }
+  __syncthreads();
+  if (ox >= Wo) return;
+  for (int oy = oy0 + ly; oy <= oy1; oy += 4) {                  // one wave = one output row: span and weights are wave-uniform
+    const int cnt = min(max(span_h[2 * oy + 1], 0), min(AA_TAPS, Hi));
+    const int y0 = min(max(span_h[2 * oy], 0), Hi - cnt) - r0;
+    const float* wy = wt_h + (long long)oy * AA_TAPS;
+    float acc = 0.f;
+    for (int j = 0; j < cnt; ++j) {
+      const int r = y0 + j;
+      if (r >= 0 && r < nr) acc = fmaf(wy[j], rows[r][lx], acc);
+    }
+    out[((long long)blockIdx.z * Ho + oy) * Wo + ox] = acc;
+  }
+}
+
+extern "C" int ff_resize_aa(const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, const int* span_w, const float* wt_w,
+                            const int* span_h, const float* wt_h, void* stream) {
+  FF_CHECK_ARG(in && out && span_w && wt_w && span_h && wt_h, "ff_resize_aa: null pointer");
+  FF_CHECK_ARG(planes >= 1 && planes <= 65535 && Ho >= 1 && Wo >= 1, "ff_resize_aa: bad sizes (planes %d, out %d x %d)", planes, Ho, Wo);
+  FF_CHECK_ARG(Ho <= (1 << 20) && Wo <= (1 << 20) && Hi == 4 * Ho && Wi == 4 * Wo,
+               "ff_resize_aa: the input must be exactly 4x the output, got %d x %d -> %d x %d", Hi, Wi, Ho, Wo);
+  FF_CHECK_ARG((((uintptr_t)wt_w) & 15) == 0, "ff_resize_aa: wt_w must be 16-byte aligned");
+  const dim3 grid((unsigned)((Wo + AA_TOX - 1) / AA_TOX), (unsigned)((Ho + AA_TOY - 1) / AA_TOY), (unsigned)planes);
+  FF_CHECK_ARG(grid.y <= 65535, "ff_resize_aa: output too tall (%d rows)", Ho);
+  hipLaunchKernelGGL(resize_aa_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, out, Hi, Wi, Ho, Wo, span_w, wt_w, span_h, wt_h);
+  FF_LAUNCH_CHECK("ff_resize_aa");
+  return FF_OK;
+}

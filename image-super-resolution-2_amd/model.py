@@ -80,14 +80,41 @@ class FreqFusionHIP:
         return (ex, pre) if with_pre else ex
 
     @torch.no_grad()
-    def experts_with_features(self, lr: T):
+    def experts_with_features(self, lr: T, streams: bool = False):
         """ExpertEnsemble.forward_all_with_hooks (expert_loader.py:894-951): ({hat,dat,nafnet} SR outputs [1,3,4h,4w],
         {hat [1,180,h,w], dat [1,180,h,w], nafnet [1,64,h,w]} hook features bilinearly resized to the LR resolution, NCHW).
-        The payload of the cached-expert files (isr2_amd/cache.py)."""
+        The payload of the cached-expert files (isr2_amd/cache.py).  streams=True runs the same launches with DAT and NAFNet (and
+        their feature resizes) on the two side streams of experts(), forked from and joined to the caller's stream: the same bits,
+        the small grids of one expert beside those of another (cache.build_from_folders)."""
         if lr.dim() != 4 or lr.shape[0] != 1 or lr.shape[1] != 3:
             raise _lib.FFError(f"expected lr of shape [1,3,h,w], got {tuple(lr.shape)}")
         lr = lr.to(self.dev, torch.float32).contiguous()
         _, _, h, w = lr.shape
+        if streams:
+            from . import ops
+
+            def one(net):
+                raw = {}
+                out = net.forward(lr, feats=raw)
+                return out, {k: ops.nhwc_to_nchw(ops.resize(v, (h, w))) for k, v in raw.items()}
+
+            with torch.cuda.device(self.dev):
+                main = torch.cuda.current_stream()
+                if self._side is None:
+                    self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
+                s1, s2 = self._side
+                s1.wait_stream(main)
+                s2.wait_stream(main)
+                with torch.cuda.stream(s1):
+                    o_dat, f_dat = one(self.dat)
+                with torch.cuda.stream(s2):
+                    o_naf, f_naf = one(self.nafnet)
+                o_hat, f_hat = one(self.hat)
+                main.wait_stream(s1)
+                main.wait_stream(s2)
+                for t in (o_dat, o_naf, *f_dat.values(), *f_naf.values()):
+                    t.record_stream(main)
+            return {"hat": o_hat, "dat": o_dat, "nafnet": o_naf}, {**f_hat, **f_dat, **f_naf}
         raw = {}
         with torch.cuda.device(self.dev):
             outs = {"hat": self.hat.forward(lr, feats=raw), "dat": self.dat.forward(lr, feats=raw),

@@ -1232,6 +1232,111 @@ def d4_rect(x: T, code: int, out: Optional[T] = None, accum: bool = False, scale
     return out
 
 
+# ---- cached-expert data-set builder (cache.build_from_folders): patch pairs and the x1/4 degradation ---------------------------------
+def crop_pairs_u8(lr_u8: T, hr_u8: T, positions, patch: int) -> Tuple[T, T]:
+    """K aligned patch pairs out of one uploaded image pair, one launch: lr_u8 [h,w,3], hr_u8 [4h,4w,3] uint8 HWC on the device,
+    positions = host sequence of LR (top, left) -> (lr [K,3,p,p], hr [K,3,4p,4p]) fp32 = u8 / 255, HR patch k at (4 top, 4 left).
+    Everything, the positions included, is checked here before the launch."""
+    for t, name in ((lr_u8, "lr_u8"), (hr_u8, "hr_u8")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
+                and t.is_contiguous() and t.numel() > 0):
+            raise _lib.FFError(f"crop_pairs_u8: {name} must be a non-empty contiguous CUDA(HIP) uint8 [H,W,3] tensor")
+    if lr_u8.device != hr_u8.device:
+        raise _lib.FFError("crop_pairs_u8: lr_u8 and hr_u8 are on different devices")
+    h, w, _ = lr_u8.shape
+    if tuple(hr_u8.shape) != (4 * h, 4 * w, 3):
+        raise _lib.FFError(f"crop_pairs_u8: hr must be exactly 4x lr ({h}x{w}), got {hr_u8.shape[0]}x{hr_u8.shape[1]}")
+    p = int(patch)
+    if p < 1 or p > h or p > w:
+        raise _lib.FFError(f"crop_pairs_u8: patch {p} does not fit the {h}x{w} LR image")
+    pl = [(int(t_), int(l_)) for t_, l_ in positions]
+    if not pl:
+        raise _lib.FFError("crop_pairs_u8: no positions given")
+    for t_, l_ in pl:
+        if not (0 <= t_ <= h - p and 0 <= l_ <= w - p):
+            raise _lib.FFError(f"crop_pairs_u8: position ({t_}, {l_}) puts a {p}x{p} patch outside the {h}x{w} LR image")
+    K = len(pl)
+    pos = torch.tensor(pl, dtype=torch.int32).to(lr_u8.device)
+    lr = torch.empty((K, 3, p, p), device=lr_u8.device, dtype=torch.float32)
+    hr = torch.empty((K, 3, 4 * p, 4 * p), device=lr_u8.device, dtype=torch.float32)
+    _lib.check(_L().ff_crop_pairs_u8(lr_u8.data_ptr(), hr_u8.data_ptr(), h, w, pos.data_ptr(), K, p, lr.data_ptr(), hr.data_ptr(), _stream()))
+    _note(0.0, 17.0 * K * 3 * p * p * 5.0)
+    return lr, hr
+
+
+AA_TAPS = 16
+
+
+def _cubic_aa(x: float) -> float:
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a
+    return 0.0
+
+
+def aa_tables(n_in: int, n_out: int):
+    """Host tables of one axis of resize_aa (numpy): span int32 [n_out, 2] = (first input index, taps), wt float32 [n_out, 16].
+    ATen's antialiased bicubic restated: s = n_in / n_out, centre s (i + 0.5), support 2 s, taps [int(c - 2s + 0.5), int(c + 2s + 0.5))
+    clipped to the image, raw weight cubic_{a=-0.5}((j + first - c + 0.5) / s) in double, rounded to fp32, then divided by the
+    fp32 sum of the row (summed in ascending j) -- border rows have fewer taps and renormalised weights."""
+    import numpy as np
+    if n_out < 1 or n_in < n_out:
+        raise _lib.FFError(f"aa_tables: expected 1 <= n_out <= n_in, got {n_in} -> {n_out}")
+    s = n_in / n_out
+    span = np.zeros((n_out, 2), dtype=np.int32)
+    wt = np.zeros((n_out, AA_TAPS), dtype=np.float32)
+    for i in range(n_out):
+        c = s * (i + 0.5)
+        lo = max(int(c - 2.0 * s + 0.5), 0)
+        hi = min(int(c + 2.0 * s + 0.5), n_in)
+        if hi - lo > AA_TAPS:
+            raise _lib.FFError(f"aa_tables: {n_in} -> {n_out} needs {hi - lo} taps, the kernel has {AA_TAPS}")
+        raw = [np.float32(_cubic_aa((j + lo - c + 0.5) / s)) for j in range(hi - lo)]
+        tot = np.float32(0.0)
+        for v in raw:
+            tot = np.float32(tot + v)
+        span[i] = (lo, hi - lo)
+        wt[i, :hi - lo] = [np.float32(v / tot) for v in raw]
+    return span, wt
+
+
+_AA_TABLES: Dict[tuple, Tuple[T, T]] = {}
+
+
+def _aa_tables_dev(n_in: int, n_out: int, device) -> Tuple[T, T]:
+    key = (n_in, n_out, str(device))
+    ent = _AA_TABLES.get(key)
+    if ent is None:
+        if len(_AA_TABLES) >= 64:                       # a folder of images brings a handful of sizes; do not grow without bound
+            _AA_TABLES.clear()
+        span, wt = aa_tables(n_in, n_out)
+        ent = _AA_TABLES[key] = (torch.from_numpy(span).to(device), torch.from_numpy(wt).to(device))
+    return ent
+
+
+def resize_aa(x: T, size: Tuple[int, int]) -> T:
+    """Antialiased bicubic x1/4 of a planar image batch: x [B,3,H,W] -> [B,3,H/4,W/4] = F.interpolate(x, size, mode='bicubic',
+    antialias=True, align_corners=False) -- the degradation the x4 track is defined on (ops.resize's bicubic is ATen's plain
+    A = -0.75 kernel without antialiasing: an up-sampler).  `size` must be exactly (H/4, W/4); any other ratio raises."""
+    _chk(x, "resize_aa.x")
+    if x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous() or x.numel() == 0:
+        raise _lib.FFError("resize_aa: expected a non-empty contiguous [B,3,H,W] tensor")
+    B, C, Hi, Wi = x.shape
+    Ho, Wo = (int(v) for v in size)
+    if Ho < 1 or Wo < 1 or Hi != 4 * Ho or Wi != 4 * Wo:
+        raise _lib.FFError(f"resize_aa: only the x1/4 ratio is built: {Hi}x{Wi} -> {Ho}x{Wo} is refused")
+    span_w, wt_w = _aa_tables_dev(Wi, Wo, x.device)
+    span_h, wt_h = _aa_tables_dev(Hi, Ho, x.device)
+    out = torch.empty((B, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    _lib.check(_L().ff_resize_aa(x.data_ptr(), out.data_ptr(), B * C, Hi, Wi, Ho, Wo, span_w.data_ptr(), wt_w.data_ptr(),
+                                 span_h.data_ptr(), wt_h.data_ptr(), _stream()))
+    _note(0.0, 4.0 * B * C * (Hi * Wi + Ho * Wo))
+    return out
+
+
 for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):

@@ -324,6 +324,23 @@ int ff_resize(const float* in, long long isb, long long isc, long long isy, long
               float scale_w, int mode, float mul, void* stream);
 int ff_avgpool2(const float* in, int ldi, float* out, int ldo, int B, int H, int W, int C, void* stream);
 
+/* Device half of the cached-expert data-set builder (isr2_amd.cache.build_from_folders; csrc/resample.hip).  The reference's reader
+ * (src/data/cached_dataset.py:45-50) expects "several crops per image" files that nothing in its tree writes; its pairing rules are
+ * PairedRandomCrop (augmentations.py:77-83) and the centre crop of dataset.py:282-296.
+ * ff_crop_pairs_u8: K aligned patch pairs out of uploaded uint8 images in one launch.  lr_u8 [h][w][3], hr_u8 [4h][4w][3] (HWC), pos =
+ *   DEVICE int32 [K][2] of LR (top, left) with 0 <= top <= h - p, 0 <= left <= w - p (the caller checks them: ops.crop_pairs_u8);
+ *   lr_out [K][3][p][p], hr_out [K][3][4p][4p] fp32 = u8 / 255 (IEEE division, as ff_u8hwc_to_f32nchw); HR patch k starts at
+ *   (4 top, 4 left).
+ * ff_resize_aa: antialiased bicubic x1/4 of planar fp32 [planes][Hi][Wi] -> [planes][Ho][Wo], Hi = 4 Ho, Wi = 4 Wo -- F.interpolate(
+ *   mode='bicubic', antialias=True, align_corners=False), cubic a = -0.5 stretched by the scale.  Separable, horizontal pass first; per
+ *   axis a DEVICE table from ops.aa_tables: span [O][2] int32 = (first input index, number of taps <= 16), wt [O][16] fp32 = normalised
+ *   weights, zero padded (16-byte aligned).  Each pass: acc = fma(w_j, x[first + j], acc) from 0, ascending j.
+ * Both added under ABI version 7 (additive entry points: no existing prototype changed). */
+int ff_crop_pairs_u8(const unsigned char* lr_u8, const unsigned char* hr_u8, int h, int w, const int* pos, int K, int p, float* lr_out,
+                     float* hr_out, void* stream);
+int ff_resize_aa(const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, const int* span_w, const float* wt_w,
+                 const int* span_h, const float* wt_h, void* stream);
+
 /* Frequency bands of the planar LR image x[C][H][W] written into out[H][W][ldo] channel groups.
  * multi_domain_frequency.py:146-196 (DCT), :273-299 (DWT pass), :352-385 (FFT low/high). */
 int ff_dct8_bands(const float* x, int C, int H, int W, const float* dct_mat, const float* masks3,
