@@ -7,8 +7,10 @@
 // All three are HBM-bound: one read of the row / tensor, one write.
 #include "ff_common.h"
 
-template <int NV>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, int ldi, float* __restrict__ out,
+// BF16OUT: bf16 output rows for a consumer that rounds them to bf16 anyway (ff_layernorm_bf16out): the same fp32 value, rounded once
+// here.  (`out` is untyped so that the kernel's name stays one a profiler can demangle.)
+template <int NV, bool BF16OUT>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, int ldi, void* __restrict__ out,
                                                         int ldo, int rows, int C, const float* __restrict__ g,
                                                         const float* __restrict__ bta, float eps) {
   const int lane = threadIdx.x & 63;
@@ -32,23 +34,27 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     q += d * d;
   }
   const float rstd = 1.0f / sqrtf(ff_wave_sum(q) / (float)C + eps);
-  float* y = out + (long long)row * ldo;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = lane + 64 * i;
-    if (c < C) y[c] = (v[i] - mean) * rstd * g[c] + bta[c];
+    if (c < C) {
+      const float yv = (v[i] - mean) * rstd * g[c] + bta[c];
+      if (BF16OUT) reinterpret_cast<__bf16*>(out)[(long long)row * ldo + c] = (__bf16)yv;
+      else reinterpret_cast<float*>(out)[(long long)row * ldo + c] = yv;
+    }
   }
 }
 
-extern "C" int ff_layernorm(const float* in, int ldi, float* out, int ldo, long long rows, int C, const float* gamma,
+template <bool BF16OUT>
+static int layernorm_launch(const char* name, const float* in, int ldi, void* out, int ldo, long long rows, int C, const float* gamma,
                             const float* beta, float eps, void* stream) {
-  FF_CHECK_ARG(in && out && gamma && beta, "ff_layernorm: null pointer");
-  FF_CHECK_ARG(C > 0 && C <= 1024 && ldi >= C && ldo >= C && rows > 0, "ff_layernorm: bad dims C=%d", C);
-  FF_CHECK_ARG(rows < (1LL << 31), "ff_layernorm: too many rows");
+  FF_CHECK_ARG(in && out && gamma && beta, "%s: null pointer", name);
+  FF_CHECK_ARG(C > 0 && C <= 1024 && ldi >= C && ldo >= C && rows > 0, "%s: bad dims C=%d", name, C);
+  FF_CHECK_ARG(rows < (1LL << 31), "%s: too many rows", name);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const int nv = (C + 63) / 64;
-#define LN_CASE(N) hipLaunchKernelGGL(layernorm_kernel<N>, grid, block, 0, st, in, ldi, out, ldo, (int)rows, C, gamma, beta, eps)
+#define LN_CASE(N) hipLaunchKernelGGL((layernorm_kernel<N, BF16OUT>), grid, block, 0, st, in, ldi, out, ldo, (int)rows, C, gamma, beta, eps)
   if (nv <= 1) LN_CASE(1);
   else if (nv <= 2) LN_CASE(2);
   else if (nv <= 3) LN_CASE(3);
@@ -57,8 +63,18 @@ extern "C" int ff_layernorm(const float* in, int ldi, float* out, int ldo, long 
   else if (nv <= 8) LN_CASE(8);
   else LN_CASE(16);
 #undef LN_CASE
-  FF_LAUNCH_CHECK("ff_layernorm");
+  FF_LAUNCH_CHECK(name);
   return FF_OK;
+}
+
+extern "C" int ff_layernorm(const float* in, int ldi, float* out, int ldo, long long rows, int C, const float* gamma,
+                            const float* beta, float eps, void* stream) {
+  return layernorm_launch<false>("ff_layernorm", in, ldi, out, ldo, rows, C, gamma, beta, eps, stream);
+}
+
+extern "C" int ff_layernorm_bf16out(const float* in, int ldi, void* out, int ldo, long long rows, int C, const float* gamma,
+                                    const float* beta, float eps, void* stream) {
+  return layernorm_launch<true>("ff_layernorm_bf16out", in, ldi, out, ldo, rows, C, gamma, beta, eps, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -468,6 +468,10 @@ class NafnetHIP:
     def block(self, x: T, k: dict) -> T:
         c = x.shape[-1]
         flash = ops.fused_modes() and c in (64, 128)                         # HR levels: the bandwidth-bound ones
+        # deep levels in plain bf16: LayerNorm and the SimpleGate epilogue store the bf16 the GEMM would round to, and conv1 / conv4 /
+        # conv5 fetch those rows by LDS-DMA (ops.linear on bf16 rows; bit-equal to the fp32-rows route).  conv3 scales its A operand
+        # in fp32 (kmul), so its rows stay fp32 and pass through registers in the same kernel.
+        rows = not flash and ops.gemm_mode() == "bf16" and ops.rows_gemm() and ops.rows_gemm_ok(c)
         if flash and c == 64:                                                # LayerNorm2d + conv1 + conv2 + SimpleGate + pool sums: one launch (313 vs 381 us at
                                                                              # 1024 x 1024; the 128-channel form fits one workgroup per CU only and ties: 222 vs 217)
             g, pooled = ops.naf_front(x, _tl(k, "c1"), k["n1"][0], k["n1"][1], *k["c2"])
@@ -475,7 +479,7 @@ class NafnetHIP:
             if flash:
                 t = ops.token_linear(x, _tl(k, "c1"), gamma=k["n1"][0], beta=k["n1"][1], eps=1e-6)    # LayerNorm2d + conv1
             else:
-                t = ops.linear(ops.layernorm(x, *k["n1"], eps=1e-6), *k["c1"])
+                t = ops.linear(ops.layernorm(x, *k["n1"], eps=1e-6, out_bf16=rows), *k["c1"])
             g, pooled = ops.dwconv3_gate_pool(t, *k["c2"])                   # conv2 + SimpleGate + SCA pool sums
         sca = ops.vec_mlp(pooled, *k["sca"], None)                           # [1,c]
         if flash and ops.gemm_mode() == "bf16":                              # plain bf16: conv3 + the gated FFN in one launch, y stays on chip
@@ -484,7 +488,7 @@ class NafnetHIP:
             return ops.naf_tail(g, x, k["tail_pk"], sca.reshape(-1), k["beta"], k["n2"][0], k["n2"][1], k["gamma"])
         nf = ops.gemm_mode() != "f32"                                        # the split-bf16 GEMM carries both NAFBlock fusions
         if nf:                                                               # conv3(g * sca): the scale rides on the A operand
-            y = ops.linear(g, *k["c3"], res=x, mul=k["beta"], kmul=sca.reshape(-1))
+            y = ops.linear(g, *k["c3"], res=x, mul=k["beta"], kmul=sca.reshape(-1), rows_gemm=rows)
         else:
             w3 = ops.mix2(k["c3"][0], ca=sca.reshape(-1))                    # conv3(g * sca) == (W3 . diag(sca)) g
             y = ops.linear(g, w3, k["c3"][1], res=x, mul=k["beta"], dynamic_w=True)
@@ -497,7 +501,7 @@ class NafnetHIP:
                 w4, b4 = k["c4"]
                 k["c4i"] = (torch.stack((w4[:c], w4[c:]), dim=1).reshape(2 * c, -1).contiguous(),
                             torch.stack((b4[:c], b4[c:]), dim=1).reshape(-1).contiguous())
-            g = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6), *k["c4i"], gate_pairs=True)
+            g = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6, out_bf16=rows), *k["c4i"], gate_pairs=True, out_bf16=rows)
         else:
             t = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6), *k["c4"])
             g = ops.fma3(None, t[..., :c], t[..., c:])

@@ -112,6 +112,18 @@ def set_halo(on: bool) -> None:
     _HALO = bool(on)
 
 
+_ROWS_GEMM = True   # plain bf16: NAFNet's deep 1x1 GEMMs read bf16 rows through ff_gemm_rows_bf16 (csrc/gemm_rows_bf16.hip); False = fp32 rows through ff_conv2d_bf16s
+
+
+def set_rows_gemm(on: bool) -> None:
+    global _ROWS_GEMM
+    _ROWS_GEMM = bool(on)
+
+
+def rows_gemm() -> bool:
+    return _ROWS_GEMM
+
+
 def empty_rows_bf16(shape, device) -> T:
     """bf16 activation buffer [..., C] for an intermediate whose only consumer rounds it to bf16 anyway (plain-bf16 mode); the row
     pitch is a multiple of 64 elements (128 bytes)."""
@@ -417,9 +429,17 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
 
 def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] = None, mul: Optional[T] = None,
            alpha: float = 1.0, out: Optional[T] = None, dynamic_w: bool = False, kmul: Optional[T] = None,
-           gate_pairs: bool = False) -> T:
+           gate_pairs: bool = False, out_bf16: bool = False, tile_hint: int = 0, rows_gemm: bool = False) -> T:
     """x [..., K] rows view, w [N, K] -> [..., N].  kmul [K]: scale of the input channels (W (kmul * x); split-bf16 modes).
-    gate_pairs: SimpleGate in the epilogue, [..., N / 2] out with out[j] = y[2j] * y[2j+1] (rows of w interleaved by the caller)."""
+    gate_pairs: SimpleGate in the epilogue, [..., N / 2] out with out[j] = y[2j] * y[2j+1] (rows of w interleaved by the caller).
+    bf16 x (plain-bf16 mode, rows_gemm_ok shapes): ff_gemm_rows_bf16, bit-equal to the fp32-rows kernel on x.float(); out_bf16 stores
+    the gated output as bf16 rows for the next such GEMM.  rows_gemm: fp32 x through the same kernel (A staged through registers; the
+    only form that takes kmul), again bit-equal; without it fp32 x stays on ff_conv2d_bf16s."""
+    if x.dtype == torch.bfloat16 or rows_gemm:
+        return _linear_rows_bf16(x, w, bias, act=act, res=res, mul=mul, alpha=alpha, out=out, dynamic_w=dynamic_w, kmul=kmul,
+                                 gate_pairs=gate_pairs, out_bf16=out_bf16, tile_hint=tile_hint)
+    if out_bf16 or tile_hint:
+        raise _lib.FFError("linear: out_bf16 / tile_hint belong to the bf16-rows route (bf16 x, or rows_gemm)")
     xp, ldi, rows, K = rows_view(x, "linear.x")
     N = w.shape[0]
     if w.dim() != 2 or w.shape[1] != K or not w.is_contiguous():
@@ -450,6 +470,45 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
                                         rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
                                         float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], 0, _ptr(kmul), _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K + N * K + rows * No * (2 if res is not None else 1)))
+    return out
+
+
+def rows_gemm_ok(K: int) -> bool:
+    """Shapes ff_gemm_rows_bf16 takes: whole 64-wide K chunks, so that the weight plane of _split_weight is unpadded."""
+    return K % 64 == 0
+
+
+def _linear_rows_bf16(x: T, w: T, bias, *, act, res, mul, alpha, out, dynamic_w, kmul, gate_pairs, out_bf16, tile_hint) -> T:
+    xp, lda, rows, K = rows_view(x, "linear.x|bf16ok")
+    a32 = x.dtype == torch.float32
+    N = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != K or not w.is_contiguous():
+        raise _lib.FFError(f"linear: weight must be [N, {K}], got {tuple(w.shape)}")
+    if _GEMM_MODE != "bf16" or not rows_gemm_ok(K):
+        raise _lib.FFError("linear: the bf16-rows GEMM exists in plain-bf16 mode for K % 64 == 0 only")
+    if kmul is not None and (not a32 or kmul.numel() != K or not kmul.is_contiguous()):
+        raise _lib.FFError(f"linear: kmul scales fp32 input rows only and must be a contiguous [{K}] vector")
+    if act is not None or alpha != 1.0 or (a32 and gate_pairs) or (gate_pairs and (res is not None or mul is not None)) or out_bf16 != gate_pairs:
+        raise _lib.FFError("linear: the bf16-rows GEMM has three epilogues: bias (* mul + res) -> fp32 rows, or the SimpleGate pair "
+                           "product -> bf16 rows")
+    No = N // 2 if gate_pairs else N
+    oshape = tuple(x.shape[:-1]) + (No,)
+    if out is None:
+        out = empty_rows_bf16(oshape, x.device) if out_bf16 else empty_rows(oshape, x.device)
+    elif (out.dtype == torch.bfloat16) != out_bf16:
+        raise _lib.FFError("linear: out dtype does not match out_bf16")
+    op, ldo, orows, oc = rows_view(out, "linear.out|bf16ok" if out_bf16 else "linear.out")
+    if orows != rows or oc != No:
+        raise _lib.FFError("linear: out shape mismatch")
+    rp, ldr = None, 0
+    if res is not None:
+        rp, ldr, rrows, rc = rows_view(res, "linear.res")
+        if rrows != rows or rc != N:
+            raise _lib.FFError("linear: res shape mismatch")
+    hi, _, Kp, _, _ = _split_weight(w, dynamic_w, K)
+    _lib.check(_L().ff_gemm_rows_bf16(xp, 1 if a32 else 0, lda, hi.data_ptr(), Kp, _ptr(kmul), _ptr(bias), _ptr(mul), rp, ldr, op, ldo, rows,
+                                      N, K, 1 if gate_pairs else 0, int(tile_hint), _stream()))
+    _note(2.0 * rows * N * K, (4.0 if a32 else 2.0) * rows * K + 2.0 * N * K + (2.0 if out_bf16 else 4.0) * rows * No + (4.0 * rows * No if res is not None else 0.0))
     return out
 
 
@@ -700,15 +759,19 @@ def naf_tail(g: T, x: T, pk: dict, sca: T, beta: T, ln_g: T, ln_b: T, gamma: T, 
     return out
 
 
-def layernorm(x: T, gamma: T, beta: T, eps: float = 1e-5, out: Optional[T] = None) -> T:
+def layernorm(x: T, gamma: T, beta: T, eps: float = 1e-5, out: Optional[T] = None, out_bf16: bool = False) -> T:
+    """out_bf16: bf16 output rows, (bf16) of the fp32 result, for a consumer that rounds them to bf16 anyway."""
     xp, ldi, rows, C = rows_view(x, "layernorm.x")
     if out is None:
-        out = empty_like_rows(x)
-    op, ldo, orows, oc = rows_view(out, "layernorm.out")
+        out = empty_rows_bf16(tuple(x.shape), x.device) if out_bf16 else empty_like_rows(x)
+    elif (out.dtype == torch.bfloat16) != out_bf16:
+        raise _lib.FFError("layernorm: out dtype does not match out_bf16")
+    op, ldo, orows, oc = rows_view(out, "layernorm.out|bf16ok" if out_bf16 else "layernorm.out")
     if orows != rows or oc != C or gamma.numel() != C or beta.numel() != C:
         raise _lib.FFError("layernorm: shape mismatch")
-    _lib.check(_L().ff_layernorm(xp, ldi, op, ldo, rows, C, gamma.data_ptr(), beta.data_ptr(), float(eps), _stream()))
-    _note(0.0, 8.0 * rows * C)
+    fn = _L().ff_layernorm_bf16out if out_bf16 else _L().ff_layernorm
+    _lib.check(fn(xp, ldi, op, ldo, rows, C, gamma.data_ptr(), beta.data_ptr(), float(eps), _stream()))
+    _note(0.0, (6.0 if out_bf16 else 8.0) * rows * C)
     return out
 
 

@@ -60,6 +60,22 @@ int ff_conv2d_bf16s(const float* in, const void* w_hi, const void* w_lo, int Kp,
                     int nterms, int tile_hint, const float* kmul, void* stream);
 int ff_split_bf16(const float* w, int N, int K, int Kp, int Cin, int Cp, void* hi, void* lo, void* stream);
 
+/* GEMM on bf16 ROWS, plain bf16 (csrc/gemm_rows_bf16.hip): out[M][N] = epilogue(A[M][K] . W[N][K]^T), bit-equal to
+ * ff_conv2d_bf16s(1x1, nterms = 1) on the fp32 upcast of A -- the same MFMA, k order and epilogue arithmetic -- with both operands
+ * fetched by LDS-DMA.  a: bf16 [M][lda]; w_hi: the hi plane of ff_split_bf16 [N][Kp].  Needs K % 64 == 0, Kp == K, lda % 8 == 0
+ * and 16-byte aligned a / w_hi.  bias / mul / res may be NULL.
+ * a_fp32 = 1: a is fp32 [M][lda] (lda % 4 == 0), staged through registers and rounded on the way as ff_conv2d_bf16s does; only then may
+ * kmul [K] be given, the per-input-channel fp32 scale of A (conv3(x * sca)); gate = 0 only.
+ *   gate = 0: out fp32 [M][ldo] = (A w^T + bias) * mul + res   (N % 4 == 0, ldo / ldr % 4 == 0, 16-byte aligned out / res);
+ *   gate = 1: SimpleGate on interleaved columns, out bf16 [M][ldo] with N / 2 channels, out[m][j] = bf16(y[m][2j] * y[m][2j+1])
+ *             (N % 8 == 0, ldo % 4 == 0, no mul / res): what ff_conv2d_bf16s(shuffle = 1) stores, rounded once.
+ * tile_hint 0 = auto; 1 / 2 = the 128x128 / 128x64 tile.
+ * NAFBlock conv1 / conv3 / conv4 / conv5 at 256 / 512 / 1024 channels (nafnet_arch.py:77,95,96).  Added under ABI version 7 (an additive
+ * entry point: no existing prototype changed). */
+int ff_gemm_rows_bf16(const void* a, int a_fp32, int lda, const void* w_hi, int Kp, const float* kmul, const float* bias,
+                      const float* mul, const float* res, int ldr, void* out, int ldo, long long M, int N, int K, int gate,
+                      int tile_hint, void* stream);
+
 /* 3x3 / stride 1 / pad 1 convolution for small channel counts (csrc/conv3x3_small.hip): Cin <= 64, Cout <= 16, exact fp32 on
  * the VALU, out = res + alpha * act(conv(in) + bias).  w_small: fp32 [9][ceil4(Cin)][CT], CT = 1 / 4 / 16 >= Cout, zero padded
  * (prep.pack_conv3x3_small).  Replaces the tail convolutions of the fusion stack at 1024 x 1024: to_rgb (hierarchical_fusion.py:
@@ -224,6 +240,10 @@ int ff_naf_tail(const float* g, int ldg, const float* x, int ldx, float* out, in
  * hat_arch.py:272,307,397,437,964; dat_arch.py:117,734-735,931,1003; nafnet_arch.py:35-41. */
 int ff_layernorm(const float* in, int ldi, float* out, int ldo, long long rows, int C, const float* gamma,
                  const float* beta, float eps, void* stream);
+/* The same LayerNorm with bf16 output rows [rows][ldo]: (bf16) of the value ff_layernorm stores, for a consumer that rounds it to
+ * bf16 anyway (ff_gemm_rows_bf16's A operand).  Added under ABI version 7 (an additive entry point). */
+int ff_layernorm_bf16out(const float* in, int ldi, void* out, int ldo, long long rows, int C, const float* gamma,
+                         const float* beta, float eps, void* stream);
 
 /* Global average pool over the P pixels of each of B images: out[B][C] (AdaptiveAvgPool2d(1):
  * hat_arch.py:50; dat_arch.py:411,603; nafnet_arch.py:86).  work: ff_pool_mean_workspace floats. */
