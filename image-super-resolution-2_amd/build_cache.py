@@ -1,7 +1,7 @@
 """Build a cached-expert training set from image folders (the directory `python -m isr2_amd.train_cached --cache DIR` reads):
 
     python -m isr2_amd.build_cache --hr DIR [--lr DIR] --out DIR [--patch 64] [--crops 5] [--seed 0] [--center] [--write-lr DIR]
-                                   [--weights PATH] [--pretrained DIR] [--gemm bf16x3] [--writers 4] [--device cuda:0]
+                                   [--weights PATH] [--pretrained DIR] [--gemm bf16x3] [--writers 4] [--batch 1] [--device cuda:0]
 
 --hr / --lr: folders of images matched by stem; every HR image must be exactly 4x its LR partner.  Without --lr the LR images are
 made on the device: HR cropped top-left to multiples of 4, antialiased bicubic x1/4, quantised to uint8 (--write-lr DIR keeps them as
@@ -9,7 +9,8 @@ PNGs).  --crops random patches per image (--center: the one centred patch) of --
 isr2_amd.cache.build_from_folders describes the files.  Expert weights come from where the plugin finds them: --pretrained DIR (default
 $FREQFUSION_PRETRAINED, else ./pretrained) with hat/, dat/ and nafnet/ checkpoints; a missing one is replaced by seeded synthetic
 weights with a warning (smoke runs).  --weights: a reference-keyed state dict, bare or under `model_state_dict`, laid over them as
-train_cached lays it.  One JSON line on stdout."""
+train_cached lays it.  --batch N: the patches of an image go through the experts in groups of N (HAT batched in one launch per op); the
+files hold the same bits.  One JSON line on stdout."""
 from __future__ import annotations
 
 import argparse
@@ -73,6 +74,7 @@ def main(argv=None) -> int:
     ap.add_argument("--pretrained", default=os.environ.get("FREQFUSION_PRETRAINED", "pretrained"))
     ap.add_argument("--gemm", default="bf16x3", choices=("f32", "bf16", "bf16x2", "bf16x3"))
     ap.add_argument("--writers", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
 
@@ -81,7 +83,7 @@ def main(argv=None) -> int:
     ops.set_gemm_mode(a.gemm)
     model = FreqFusionHIP(load_state_dict(a.pretrained, a.weights), a.device)
     res = cache.build_from_folders(model, a.hr, a.out, lr_dir=a.lr, patch=a.patch, crops=a.crops, seed=a.seed, center=a.center,
-                                   writers=a.writers, write_lr=a.write_lr)
+                                   writers=a.writers, write_lr=a.write_lr, batch=a.batch)
     print(json.dumps(res), flush=True)
     return 0
 

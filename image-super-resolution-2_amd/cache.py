@@ -271,50 +271,65 @@ class _BuildPipeline:
 
 
 class _GraphedExperts:
-    """model.experts_with_features for ONE patch shape, replayed from a HIP graph captured once (the mechanism of FreqFusionHIP.graphed:
-    a warm-up on a side stream, then the capture, with the buffers that outlive a forward keyed to this graph).  The returned tensors
-    are the graph's static output buffers: consume them on the same stream before the next call.  Captured before the pipeline's
-    threads exist, in thread-local capture mode: another thread pinning memory or waiting for an event must not end the capture."""
+    """model.experts_with_features for ONE patch shape, replayed from a HIP graph captured once per group size (the mechanism of
+    FreqFusionHIP.graphed: a warm-up on a side stream, then the capture, with the buffers that outlive a forward keyed to this graph).
+    A call takes lr [n,3,patch,patch]; every n it meets has a graph of its own (prepare(n) captures it ahead of time).  The returned
+    tensors are the graph's static output buffers: consume them on the same stream before the next call.  Captured before the
+    pipeline's threads exist, in thread-local capture mode: another thread pinning memory or waiting for an event must not end the
+    capture."""
 
-    def __init__(self, model, patch: int):
+    def __init__(self, model, patch: int, sizes=(1,)):
+        self.model, self.patch = model, int(patch)
+        self.ent = {}                                        # n -> (key, graph, static input, outputs, features)
+        for n in sizes:
+            self.prepare(n)
+
+    def prepare(self, n: int):
         from . import ops
-        self.graph = None
-        self.key = (id(model), "cache_build", int(patch))
+        n = int(n)
+        if n in self.ent:
+            return self.ent[n]
+        model, patch = self.model, self.patch
+        key = (id(model), "cache_build", patch) + ((n,) if n > 1 else ())
         dev = model.dev
-        ops.set_capture_key(self.key)
+        graph = None
+        ops.set_capture_key(key)
         try:
             with torch.cuda.device(dev):
-                self.static_in = torch.zeros((1, 3, patch, patch), device=dev, dtype=torch.float32)
+                static_in = torch.zeros((n, 3, patch, patch), device=dev, dtype=torch.float32)
                 cur = torch.cuda.current_stream()
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    model.experts_with_features(self.static_in, streams=True)
+                    model.experts_with_features(static_in, streams=True)
                 cur.wait_stream(side)
                 torch.cuda.synchronize(dev)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    self.outs, self.feats = model.experts_with_features(self.static_in, streams=True)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    outs, feats = model.experts_with_features(static_in, streams=True)
         finally:
             ops.set_capture_key(None)
+        self.ent[n] = (key, graph, static_in, outs, feats)
+        return self.ent[n]
 
     def __call__(self, lr: T):
-        self.static_in.copy_(lr, non_blocking=True)
-        self.graph.replay()
-        return self.outs, self.feats
+        _, graph, static_in, outs, feats = self.prepare(lr.shape[0])
+        static_in.copy_(lr, non_blocking=True)
+        graph.replay()
+        return outs, feats
 
     def close(self):
-        """Destroy the graph NOW: left to the garbage collector, its destructor may run inside a later capture, which HIP refuses."""
+        """Destroy the graphs NOW: left to the garbage collector, a destructor may run inside a later capture, which HIP refuses."""
         from . import ops
-        if self.graph is not None:
-            self.graph.reset()
-        self.graph = self.outs = self.feats = self.static_in = None
-        ops.drop_persistent(key=self.key)
+        for key, graph, *_ in self.ent.values():
+            graph.reset()
+            ops.drop_persistent(key=key)
+        self.ent = {}
 
 
 @torch.no_grad()
 def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] = None, patch: int = 64, crops: int = 5, seed: int = 0,
-                       center: bool = False, writers: int = 4, write_lr: Optional[str] = None, graph: bool = True) -> dict:
+                       center: bool = False, writers: int = 4, write_lr: Optional[str] = None, graph: bool = True, batch: int = 1) -> dict:
     """Image folders -> the cache directory `python -m isr2_amd.train_cached` reads.  Images are matched by stem, in sorted order; image
     number i of that order is cut at crop_plan(h, w, patch, crops, seed, i, center) and patch k is written under the stem
     `{image stem}_p{k}` (the bare image stem with center=True) -- both forms are what list_stems and the reference's reader take.
@@ -329,18 +344,22 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
     makes, so the files hold the same bits: the three experts of a patch run on three streams, as in model.experts(), and since all
     patches have one shape the pass is captured once into a HIP graph and replayed per patch (graph=False launches it instead: the
     switch exists for the bit-for-bit comparison of the two).  Images smaller than the patch are skipped and counted.
+    batch=N: the K patches of an image go through the expert pass in groups of N (model.experts_with_features on [N,3,p,p]: HAT takes
+    the group through one launch per op, DAT and NAFNet run patch by patch beside it); the graph is captured for [N,3,p,p] and a
+    remainder group of K % N patches has a graph of its own.  Every file holds the bits batch=1 writes; batch=1 is that path, launch
+    for launch.
     A reader or writer exception ends the run and is re-raised here.
 
-    Returns {graph, images, images_skipped, patches_written, seconds: {total, decode, device, write, wait_reader, wait_writer},
+    Returns {graph, batch, images, images_skipped, patches_written, seconds: {total, decode, device, write, wait_reader, wait_writer},
     patches_per_s}: decode / write are the worker threads' busy time (write summed over the writers), device is GPU time between
     the upload and the last result copy of each image (events), the waits are the calling thread's stalls on the queues."""
     import shutil
     import time
     from . import ops
     from .lib import FFError
-    patch, crops, writers = int(patch), int(crops), int(writers)
-    if patch < 1 or crops < 1 or writers < 1:
-        raise FFError(f"build_from_folders: patch, crops and writers must be >= 1, got {patch}, {crops}, {writers}")
+    patch, crops, writers, batch = int(patch), int(crops), int(writers), int(batch)
+    if patch < 1 or crops < 1 or writers < 1 or batch < 1:
+        raise FFError(f"build_from_folders: patch, crops, writers and batch must be >= 1, got {patch}, {crops}, {writers}, {batch}")
     hr_files = _image_stems(hr_dir)
     if lr_dir is not None:
         lr_files = _image_stems(lr_dir)
@@ -359,7 +378,9 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
     spans = []
     n_img = 0
     with torch.cuda.device(dev):
-        experts = _GraphedExperts(model, patch) if graph else (lambda t: model.experts_with_features(t, streams=True))
+        n_patch = 1 if center else crops                      # patches per image: whole groups of `batch`, then the remainder
+        sizes = sorted({min(batch, n_patch)} | ({n_patch % batch} if n_patch % batch else set()))
+        experts = _GraphedExperts(model, patch, sizes) if graph else (lambda t: model.experts_with_features(t, streams=True))
         pipe = None
         try:
             pipe = _BuildPipeline(items, out_dir, tmp_dir, patch, lr_dir is None, write_lr, dev, writers)
@@ -380,14 +401,16 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
                         pipe.save_png(stem, lr_u8)
                 plan = crop_plan(lr_u8.shape[0], lr_u8.shape[1], patch, crops, seed, index, center)
                 lr, hr = ops.crop_pairs_u8(lr_u8, hr_u8, plan, patch)
-                for k in range(len(plan)):
-                    lr_k = lr[k:k + 1]
-                    if lr_k.data_ptr() % 16:                          # odd patch sizes: the kernels take 16-byte aligned images
-                        lr_k = lr_k.clone()
-                    outs, feats = experts(lr_k)
-                    t0 = time.perf_counter()
-                    pipe.save_sample(stem if center else f"{stem}_p{k}", lr_k, hr[k], outs, feats)
-                    wait_w += time.perf_counter() - t0
+                for k0 in range(0, len(plan), batch):
+                    lr_g = lr[k0:k0 + batch]
+                    if lr_g.data_ptr() % 16:                          # odd patch sizes: the kernels take 16-byte aligned images
+                        lr_g = lr_g.clone()
+                    outs, feats = experts(lr_g)
+                    for j in range(lr_g.shape[0]):
+                        t0 = time.perf_counter()
+                        pipe.save_sample(stem if center else f"{stem}_p{k0 + j}", lr_g[j:j + 1], hr[k0 + j],
+                                         {k: v[j:j + 1] for k, v in outs.items()}, {k: v[j:j + 1] for k, v in feats.items()})
+                        wait_w += time.perf_counter() - t0
                 e1.record()
                 spans.append((e0, e1))
                 n_img += 1
@@ -402,5 +425,5 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
     total = time.perf_counter() - t_start
     secs = {"total": total, "decode": pipe.t["decode"], "device": sum(a.elapsed_time(b) for a, b in spans) / 1e3,
             "write": pipe.t["write"], "wait_reader": wait_r, "wait_writer": wait_w}
-    return {"graph": bool(graph), "images": n_img, "images_skipped": pipe.skipped, "patches_written": pipe.written,
+    return {"graph": bool(graph), "batch": batch, "images": n_img, "images_skipped": pipe.skipped, "patches_written": pipe.written,
             "seconds": {k: round(v, 6) for k, v in secs.items()}, "patches_per_s": pipe.written / total if total > 0 else 0.0}

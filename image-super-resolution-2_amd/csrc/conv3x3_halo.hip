@@ -18,6 +18,7 @@ struct HaloParams {
   float* pool_part;   // optional [workgroups][Cout padded to nblk*BN]: per-workgroup channel sums of the stored values
   int vec_epi;        // 16-byte epilogue through LDS patches (set by the launcher when the layout allows)
   int io_bf16;        // nterms == 1 only: bit 0 = input rows are bf16 (ldi in elements), bit 1 = output rows are bf16 (ldo in elements)
+  int images;         // ff_conv3x3_halo_images: workgroups are grouped by image and remapped inside their image (see the kernel's tile mapping)
   FF_STAMP_MEMBER
 };
 
@@ -81,13 +82,17 @@ void conv3x3_halo_kernel(HaloParams p) {
   const int l31 = lane & 31, hh = lane >> 5;
   const int wr = wid / WN, wc = wid % WN;
 
-  const int ntile = p.tiles_x * p.tiles_y * p.B;
-  const int L = ff_xcd_remap(blockIdx.x, ntile * p.nblk);
+  // One launch over the whole batch: the XCD remap runs over all B * bpi workgroups, so an image's tiles (and its pool partial rows,
+  // which are indexed by blockIdx.x) interleave with the other images'.  "images" form: workgroups b * bpi .. (b + 1) * bpi - 1 belong to
+  // image b and are remapped among themselves, so image b's partial rows b * bpi + local are the rows, in the order, of its own B == 1 launch.
+  const int bpi = p.tiles_x * p.tiles_y * p.nblk;      // workgroups per image
+  const int bi = p.images ? (int)blockIdx.x / bpi : 0;
+  const int L = p.images ? ff_xcd_remap((int)blockIdx.x - bi * bpi, bpi) : ff_xcd_remap(blockIdx.x, bpi * p.B);
   const int nb = L % p.nblk;
   int t = L / p.nblk;
   const int tx = t % p.tiles_x; t /= p.tiles_x;
   const int ty = t % p.tiles_y;
-  const int b = t / p.tiles_y;
+  const int b = bi + t / p.tiles_y;
   const int y0 = ty * TH, x0 = tx * 16;
   const int n0 = nb * BN;
 
@@ -516,9 +521,11 @@ extern "C" long long ff_conv3x3_halo_pool_rows(int B, int H, int W, int Cout, in
   return (long long)B * ((H + th - 1) / th) * ((W + 15) / 16) * ((Cout + bn - 1) / bn);
 }
 
-extern "C" int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int bn, const float* bias, const float* mul,
+// images != 0 (ff_conv3x3_halo_images): B independent images -- the kernel form is the one a B == 1 launch of one image takes and the
+// workgroups are grouped by image, so every image's output AND pool partial rows are those of its own single-image launch.
+static int conv3x3_halo_launch(const float* in, int ldi, const void* w_img, int bn, const float* bias, const float* mul,
                                const float* res, int ldr, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
-                               int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, void* stream) {
+                               int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, int images, void* stream) {
   FF_CHECK_ARG(nterms == 1 || nterms == 3, "ff_conv3x3_halo: nterms must be 1 or 3");
   FF_CHECK_ARG(io_bf16 == 0 || (nterms == 1 && io_bf16 > 0 && io_bf16 < 4 && shuffle == 0 && !res), "ff_conv3x3_halo: bf16 input / output rows exist for nterms == 1, no shuffle, no residual");
   FF_CHECK_ARG(in && w_img && out, "ff_conv3x3_halo: null pointer");
@@ -533,12 +540,12 @@ extern "C" int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int 
   HaloParams p;
   p.in = in; p.w = (const unsigned char*)w_img; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.ldi = ldi; p.Cout = Cout; p.ldo = ldo; p.ldr = ldr;
-  p.nchunk = (Cin + 63) / 64; p.act = act; p.alpha = alpha; p.shuffle = shuffle; p.pool_part = pool_partials; p.io_bf16 = io_bf16;
+  p.nchunk = (Cin + 63) / 64; p.act = act; p.alpha = alpha; p.shuffle = shuffle; p.pool_part = pool_partials; p.io_bf16 = io_bf16; p.images = images;
   p.vec_epi = shuffle == 0 && Cout % 4 == 0 && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && !(res && pool_partials) &&
               (!res || (ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)) && (!mul || (((uintptr_t)mul) & 15) == 0);
   FF_STAMP_ARM(p);
   hipStream_t st = (hipStream_t)stream;
-  if (halo_small_grid(B, H, W, Cout, bn, nterms)) {
+  if (halo_small_grid(images ? 1 : B, H, W, Cout, bn, nterms)) {
     if (bn == 64) return launch_halo<8, 1, 1, 2, 64, 9, 1>(p, st);     // nine resident tap tiles, three barriers per chunk
     return launch_halo<4, 1, 1, 1, 64, 2, 1>(p, st);                   // 8x16 pixels, 4 waves
   }
@@ -551,4 +558,24 @@ extern "C" int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int 
     case 192: return nterms == 3 ? launch_halo<4, 2, 2, 3, 32, 2, 3>(p, st) : launch_halo<4, 2, 2, 3, 32, 2, 1>(p, st);   // 16x16 pixels x 192, 8 waves (2 per SIMD), 32-channel weight tiles; 88 KB tile + 2 x 27 KB ring
     default: ff_set_error("ff_conv3x3_halo: bn must be 32, 64, 128 or 192"); return FF_ERR_ARG;
   }
+}
+
+extern "C" int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int bn, const float* bias, const float* mul,
+                               const float* res, int ldr, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
+                               int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, void* stream) {
+  return conv3x3_halo_launch(in, ldi, w_img, bn, bias, mul, res, ldr, out, ldo, B, H, W, Cin, Cout, act, alpha, shuffle, pool_partials, nterms,
+                             io_bf16, 0, stream);
+}
+
+// rows of the partial buffer of ff_conv3x3_halo_images: B times the rows of one image's own launch, image b's at b * (rows / B)
+extern "C" long long ff_conv3x3_halo_images_pool_rows(int B, int H, int W, int Cout, int bn, int nterms) {
+  const long long one = ff_conv3x3_halo_pool_rows(1, H, W, Cout, bn, nterms);
+  return (B <= 0 || one < 0) ? -1 : (long long)B * one;
+}
+
+extern "C" int ff_conv3x3_halo_images(const float* in, int ldi, const void* w_img, int bn, const float* bias, const float* mul,
+                                      const float* res, int ldr, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
+                                      int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, void* stream) {
+  return conv3x3_halo_launch(in, ldi, w_img, bn, bias, mul, res, ldr, out, ldo, B, H, W, Cin, Cout, act, alpha, shuffle, pool_partials, nterms,
+                             io_bf16, 1, stream);
 }

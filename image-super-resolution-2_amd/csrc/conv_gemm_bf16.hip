@@ -400,6 +400,23 @@ static int dispatch_bf(const ConvBfParams& p, bool vec4, int cfg, hipStream_t st
   }
 }
 
+// The tile configuration ff_conv2d_bf16s picks for tile_hint <= 0, from M = B * Ho * Wo output rows, Cout, K = KH * KW * Cin and whether the
+// input rows take 16-byte loads.  Exported so that a caller that batches independent images can pass the configuration ONE image would get
+// as its tile_hint (isr2_amd.ops.conv2d(per_image=True)): batched and single-image launches then take the same kernel form.
+extern "C" int ff_conv2d_bf16s_tile(long long M, int Cout, int K, int vec4) {
+  // measured on MI355X (profiles/r01_gemm_shapes_bf16x3_v2.txt): 128x128 tiles win whenever N pads well or K is long
+  const int r192 = Cout % 192, r128 = Cout % 128;
+  // r2 (profiles/r02_gemm_shapes_8wave.txt): the 8-wave forms of the 128-row tiles (two waves per SIMD: one wave's operand
+  // reads and global-load waits hide behind the other's MFMAs) beat the 4-wave forms on every 1x1 shape: cfg 5 replaces 1, 7 replaces 2
+  if (Cout <= 32) return 3;
+  if (Cout <= 64) return 7;
+  if (r128 == 0) return 5;
+  // measured (profiles/r01_gemm_shapes_bf16x3_v3.txt): 256x192 wins for N <= 192 or long K; 128x128 for wide N at K = 180
+  if (vec4 && M >= 256 * 64 && (r192 == 0 || r192 > 128) && (Cout <= 192 || K >= 320)) return 4;
+  if (Cout > 256 || (Cout > 128 && K >= 512)) return 5;
+  return 7;
+}
+
 extern "C" int ff_conv2d_bf16s(const float* in, const void* w_hi, const void* w_lo, int Kp, int Cp, const float* bias,
                                const float* mul, const float* res, float* out, int B, int H, int W, int Cin, int ldi,
                                int Ho, int Wo, int Cout, int ldo, int ldr, int KH, int KW, int sy, int sx, int py, int px,
@@ -435,19 +452,7 @@ extern "C" int ff_conv2d_bf16s(const float* in, const void* w_hi, const void* w_
   FF_CHECK_ARG(!kmul || vec4, "ff_conv2d_bf16s: kmul needs 16-byte aligned input rows");
   hipStream_t st = (hipStream_t)stream;
   int cfg = tile_hint;
-  if (cfg <= 0) {
-    // measured on MI355X (profiles/r01_gemm_shapes_bf16x3_v2.txt): 128x128 tiles win whenever N pads well or K is long
-    const int r192 = Cout % 192, r128 = Cout % 128;
-    // r2 (profiles/r02_gemm_shapes_8wave.txt): the 8-wave forms of the 128-row tiles (two waves per SIMD: one wave's operand
-    // reads and global-load waits hide behind the other's MFMAs) beat the 4-wave forms on every 1x1 shape: cfg 5 replaces 1, 7 replaces 2
-    if (Cout <= 32) cfg = 3;
-    else if (Cout <= 64) cfg = 7;
-    else if (r128 == 0) cfg = 5;
-    // measured (profiles/r01_gemm_shapes_bf16x3_v3.txt): 256x192 wins for N <= 192 or long K; 128x128 for wide N at K = 180
-    else if (vec4 && p.M >= 256 * 64 && (r192 == 0 || r192 > 128) && (Cout <= 192 || p.K >= 320)) cfg = 4;
-    else if (Cout > 256 || (Cout > 128 && p.K >= 512)) cfg = 5;
-    else cfg = 7;
-  }
+  if (cfg <= 0) cfg = ff_conv2d_bf16s_tile(p.M, Cout, p.K, vec4 ? 1 : 0);
   const bool k64 = Kp % 64 == 0 && (Cp == 0 || Cp % 64 == 0) && vec4;
   if (cfg >= 8 && !k64) cfg = cfg == 8 ? 5 : 7;
   switch (nterms) {

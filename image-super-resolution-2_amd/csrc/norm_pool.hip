@@ -298,6 +298,10 @@ __global__ __launch_bounds__(1024) void pool_vec_mlp_kernel(const float* __restr
   float* xin = sm + 16 * CP;             // [Cin]
   float* hid = xin + Cin;                // [Ch]
   const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  // one workgroup per image (ff_pool_vec_mlp_images; blockIdx.x == 0 in the single-image launch): its own rows, its own output row
+  part += (long long)blockIdx.x * rows * ld;
+  out += (long long)blockIdx.x * Cout;
+  if (pooled) pooled += (long long)blockIdx.x * Cin;
   // every 64-channel chunk of the row group's partial sums is accumulated in the same pass (independent loads in flight for all of
   // them), one barrier for the whole reduction
   // a single workgroup is latency bound: the loads of eight rows x four 64-channel chunks are issued before any is consumed
@@ -354,6 +358,19 @@ extern "C" int ff_pool_vec_mlp(const float* part, int rows, int ld, float inv_co
   hipLaunchKernelGGL(pool_vec_mlp_kernel, dim3(1), dim3(1024), (size_t)(16 * ((Cin + 63) & ~63) + Cin + Ch) * 4, (hipStream_t)stream, part, rows, ld,
                      inv_count, Cin, W1, b1, Ch, act1, W2, b2, Cout, act2, post, out, pooled_out);
   FF_LAUNCH_CHECK("ff_pool_vec_mlp");
+  return FF_OK;
+}
+
+// B images in one launch, one workgroup each: image b finishes its own `rows` partial rows at part + b * rows * ld in the summation order of
+// ff_pool_vec_mlp and writes out[b][Cout] (pooled_out[b][Cin]).
+extern "C" int ff_pool_vec_mlp_images(const float* part, int B, int rows, int ld, float inv_count, int Cin, const float* W1, const float* b1,
+                                      int Ch, int act1, const float* W2, const float* b2, int Cout, int act2, float post, float* out,
+                                      float* pooled_out, void* stream) {
+  FF_CHECK_ARG(part && W1 && W2 && out, "ff_pool_vec_mlp_images: null pointer");
+  FF_CHECK_ARG(B > 0 && rows > 0 && Cin > 0 && ld >= Cin && Ch > 0 && Ch <= 64 && Cout > 0 && Cin <= 512, "ff_pool_vec_mlp_images: bad dims (Cin <= 512, hidden width <= 64)");
+  hipLaunchKernelGGL(pool_vec_mlp_kernel, dim3(B), dim3(1024), (size_t)(16 * ((Cin + 63) & ~63) + Cin + Ch) * 4, (hipStream_t)stream, part, rows, ld,
+                     inv_count, Cin, W1, b1, Ch, act1, W2, b2, Cout, act2, post, out, pooled_out);
+  FF_LAUNCH_CHECK("ff_pool_vec_mlp_images");
   return FF_OK;
 }
 

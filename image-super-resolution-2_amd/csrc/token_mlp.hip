@@ -314,6 +314,8 @@ struct TokenProjMlpParams {
   int lda, ldx, ldc, ldo, K, N, HT;
   float eps;
   int io_bf16;            // plain-bf16 kernel only: bit 0 = att rows are bf16 (lda in elements), bit 1 = c2 rows are bf16 (ldc in elements)
+  int wpi, rs2_ld;        // per-image gate (ff_token_projmlp_images): image blockIdx.y reads rs2 + blockIdx.y * rs2_ld; the grid is
+                          // (wpi workgroups per image, images), so the image index costs no division and no vector register
   FF_STAMP_MEMBER
 };
 
@@ -326,7 +328,7 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
   float* B1s = reinterpret_cast<float*>(XLs + 8 * 32 * XLROWB);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  const long long tok0 = (long long)blockIdx.x * 256 + wid * 32;
+  const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;   // blockIdx.y = image (0 in the single-gate launch)
 
   int off1[4], off2[4];
 #pragma unroll
@@ -443,7 +445,7 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
       const int c4 = n * 32 + q4;
       const bool cok = c4 < p.N;
       f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-      if (p.c2 && cok) sc = *reinterpret_cast<const f32x4*>(p.rs2 + c4);
+      if (p.c2 && cok) sc = *reinterpret_cast<const f32x4*>(p.rs2 + (long long)blockIdx.y * p.rs2_ld + c4);
       f32x4 rq[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -641,7 +643,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   float* B1s = Bts + TM_KP;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  const long long tok0 = (long long)blockIdx.x * 256 + wid * 32;
+  const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;   // blockIdx.y = image (0 in the single-gate launch)
   float* patch = reinterpret_cast<float*>(smem + PM_OFF_PATCH + wid * PM_PATCHB);      // the wave's gather / transpose patch
   FF_STAMP(64, 0);
 
@@ -773,7 +775,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
       load_res(n);
       const int c4 = n * 32 + q4;
       f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-      if (p.c2 && c4 < p.N) sc = *reinterpret_cast<const f32x4*>(p.rs2 + c4);
+      if (p.c2 && c4 < p.N) sc = *reinterpret_cast<const f32x4*>(p.rs2 + (long long)blockIdx.y * p.rs2_ld + c4);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         f32x4 r0 = rx[i];
@@ -917,8 +919,10 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   FF_STAMP_DRAINED(64, 42);
 }
 
-extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
-                                float* out, int ldo, long long M, int K, int hidden_tiles, const void* proj_tiles,
+// images == 1: the single-gate launch of ff_token_projmlp, grid (workgroups, 1).  images > 1: grid (workgroups per image, images),
+// image b scales c2 by c2_scale + b * scale_ld.
+static int token_projmlp_launch(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
+                                int scale_ld, int images, float* out, int ldo, long long M, int K, int hidden_tiles, const void* proj_tiles,
                                 const float* proj_bias_padded, const float* gamma, const float* beta, float eps,
                                 const void* mlp_tiles, const float* b1_padded, const float* b2, int nterms, int io_bf16, void* stream) {
   FF_CHECK_ARG(nterms == 1 || nterms == 3, "ff_token_projmlp: nterms must be 1 or 3");
@@ -936,10 +940,12 @@ extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int l
   p.att = att; p.x = x; p.c2 = c2; p.rs2 = c2_scale; p.out = out; p.gamma = gamma; p.beta = beta;
   p.wp = (const __bf16*)proj_tiles; p.bp = proj_bias_padded; p.w = (const __bf16*)mlp_tiles; p.b1 = b1_padded; p.b2 = b2;
   p.M = M; p.lda = lda; p.ldx = ldx; p.ldc = ldc; p.ldo = ldo; p.K = K; p.N = K; p.HT = hidden_tiles; p.eps = eps; p.io_bf16 = io_bf16;
+  p.wpi = (int)(((M + 255) / 256) / images); p.rs2_ld = images > 1 ? scale_ld : 0;
   FF_STAMP_ARM(p);
   const size_t lds = (size_t)(2 * W1PL + 2 * W2PL) * 16 + (size_t)8 * 32 * XLROWB + (size_t)hidden_tiles * 32 * 4;
   FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
   const long long nblk = (M + 255) / 256;
+  const dim3 grid((unsigned)(nblk / images), (unsigned)images);
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_projmlp: grid too large");
   FF_CHECK_ARG(M * (long long)(ldx > ldc ? ldx : ldc) < (1LL << 31), "ff_token_projmlp: too many tokens for 32-bit row offsets");
   static bool attr_set = false;
@@ -957,10 +963,33 @@ extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int l
       if (e != hipSuccess) { ff_set_error("ff_token_projmlp: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
       attr2 = true;
     }
-    hipLaunchKernelGGL(token_projmlp_bf16_kernel, dim3((unsigned)nblk), dim3(512), lds2, (hipStream_t)stream, p);
-  } else hipLaunchKernelGGL(token_projmlp_kernel, dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(token_projmlp_bf16_kernel, grid, dim3(512), lds2, (hipStream_t)stream, p);
+  } else hipLaunchKernelGGL(token_projmlp_kernel, grid, dim3(512), lds, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_token_projmlp");
   return FF_OK;
+}
+
+extern "C" int ff_token_projmlp(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
+                                float* out, int ldo, long long M, int K, int hidden_tiles, const void* proj_tiles,
+                                const float* proj_bias_padded, const float* gamma, const float* beta, float eps,
+                                const void* mlp_tiles, const float* b1_padded, const float* b2, int nterms, int io_bf16, void* stream) {
+  return token_projmlp_launch(att, lda, x, ldx, c2, ldc, c2_scale, 0, 1, out, ldo, M, K, hidden_tiles, proj_tiles, proj_bias_padded, gamma, beta,
+                              eps, mlp_tiles, b1_padded, b2, nterms, io_bf16, stream);
+}
+
+// ff_token_projmlp over B images of rows_per_image tokens each, with one gate vector per image: c2_scale is [B][scale_ld].  A workgroup owns
+// 256 consecutive tokens, so an image must be whole workgroups; B == 1 makes the launch ff_token_projmlp makes.
+extern "C" int ff_token_projmlp_images(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
+                                       int scale_ld, int B, long long rows_per_image, float* out, int ldo, long long M, int K,
+                                       int hidden_tiles, const void* proj_tiles, const float* proj_bias_padded, const float* gamma,
+                                       const float* beta, float eps, const void* mlp_tiles, const float* b1_padded, const float* b2,
+                                       int nterms, int io_bf16, void* stream) {
+  FF_CHECK_ARG(B > 0 && B <= 65535 && rows_per_image > 0 && rows_per_image % 256 == 0, "ff_token_projmlp_images: rows_per_image must be a positive multiple of 256 (1 <= B <= 65535)");
+  FF_CHECK_ARG(M == (long long)B * rows_per_image, "ff_token_projmlp_images: M must be B * rows_per_image");
+  FF_CHECK_ARG(c2 && c2_scale, "ff_token_projmlp_images: the per-image gate needs c2 and c2_scale");
+  FF_CHECK_ARG(scale_ld >= K && scale_ld % 4 == 0, "ff_token_projmlp_images: scale_ld must be >= K and a multiple of 4 (16-byte aligned gate rows)");
+  return token_projmlp_launch(att, lda, x, ldx, c2, ldc, c2_scale, scale_ld, B, out, ldo, M, K, hidden_tiles, proj_tiles, proj_bias_padded, gamma,
+                              beta, eps, mlp_tiles, b1_padded, b2, nterms, io_bf16, stream);
 }
 
 extern "C" int ff_token_mlp(const float* x, int ldx, float* out, int ldo, long long M, int K, int hidden_tiles, int N,

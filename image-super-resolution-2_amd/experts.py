@@ -82,7 +82,19 @@ def _rel_index_oca(ws: int, ows: int) -> T:
 
 
 class HatHIP:
-    """HAT-L (hat_arch.py:710-984): 12 RHAG x (6 HAB + OCAB), dim 180, 6 heads, window 16."""
+    """HAT-L (hat_arch.py:710-984): 12 RHAG x (6 HAB + OCAB), dim 180, 6 heads, window 16.
+
+    forward(lr [B,3,h,w]) runs a batch through ONE launch per op in the fused modes: the window, row and 3x3 kernels take B or plain
+    row counts, and the only per-image quantity -- the channel-attention gate -- is a [B,180] matrix (per-image pool partials from the
+    convolution's epilogue, one finish + MLP workgroup per image, a per-image scale in token_projmlp).  Every choice of kernel route is
+    made from ONE image's dimensions, so each image comes out with the bits of its own B == 1 forward."""
+
+    # Batches are processed in chunks of at most this many padded tokens (B * Hp * Wp): four 256 x 256 tiles, i.e. activation memory
+    # grows to at most four times what one such tile allocates.  An attribute, not an environment switch.  It bounds HAT alone: in
+    # FreqFusionHIP.forward the DAT and NAFNet outputs and the fusion.pre tensors of EVERY image of the batch live until the join, so
+    # that part of the memory grows linearly with B (model._experts_batched).  forward() also keeps a chunk below the 2^31 input
+    # elements up to which ops.conv2d takes the LDS-resident 3x3 kernel, so raising this value cannot move a batch to another route.
+    max_batch_tokens = 262144
 
     def __init__(self, sd: SD, dev, prefix: str = "expert_ensemble.hat.", groups: int = 12, depth: int = 6, ws: int = 16,
                  heads: int = 6, conv_scale: float = 0.01):
@@ -144,7 +156,7 @@ class HatHIP:
         fused = ops.fused_modes()
         # plain bf16: att, the normalised rows and conv1's output are consumed only as MFMA operands (rounded to bf16 there), so they are
         # stored as bf16 -- bit-identical results, half the bytes; conv2's output enters x1 times conv_scale = 0.01 and goes the same way
-        b16 = ops.gemm_mode() == "bf16" and x.shape[0] == 1 and H * W >= 1024 and C % 4 == 0
+        b16 = ops.gemm_mode() == "bf16" and H * W >= 1024 and C % 4 == 0     # (one image's pixels: the route must not depend on B)
         att = ops.empty_rows_bf16(tuple(x.shape), x.device) if b16 else ops.empty_like_rows(x)
         s = blk["shift"]
         if fused:                                                  # norm1 + qkv + (S)W-MSA of all six heads in one launch (csrc/win_attn_fused.hip)
@@ -160,11 +172,12 @@ class HatHIP:
             # LDS bound, not bandwidth bound)
             ops.window_attn(qkv, att, blk["bias"], q_off=0, k_off=C, v_off=2 * C, o_off=0, H=H, W=W, Hp=H, Wp=W, win=(self.ws, self.ws),
                             kwin=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, heads=self.heads, d=d, scale=d ** -0.5)
-        c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16)
+        c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16, per_image=True)
         c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=b16)   # pool partials from the conv epilogue
         gate = ops.vec_mlp(c2mean, *blk["ca1"], "relu", *blk["ca2"], "sigmoid", post=self.conv_scale)
         if fused:                                                  # proj + both residuals + norm2 + MLP: x1 never reaches memory
-            return ops.token_projmlp(att, x, _pm(blk), blk["n2"][0], blk["n2"][1], c2=c2, c2_scale=gate.reshape(-1))
+            # gate [B,180]: one launch for the batch, image b scaled by its own row
+            return ops.token_projmlp(att, x, _pm(blk), blk["n2"][0], blk["n2"][1], c2=c2, c2_scale=gate if x.shape[0] > 1 else gate.reshape(-1))
         t = ops.mix2(x, c2, cb=gate)
         x = ops.linear(att, *blk["proj"], res=t)
         return self._mlp(x, blk)
@@ -198,21 +211,48 @@ class HatHIP:
         for blk in self.blocks[g]:
             y = self.hab(y, blk)
         y = self.ocab_block(y, self.ocab[g])
-        return ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x)
+        return ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x, per_image=True)
 
     def _tail(self, x: T) -> T:
-        x = ops.conv2d(x, *self.before_up, ksize=(3, 3), pad=(1, 1), act="lrelu")
-        x = ops.conv2d(x, *self.up0, ksize=(3, 3), pad=(1, 1), shuffle=2)
-        x = ops.conv2d(x, *self.up2, ksize=(3, 3), pad=(1, 1), shuffle=2)
-        return ops.conv2d(x, *self.last, ksize=(3, 3), pad=(1, 1))
+        x = ops.conv2d(x, *self.before_up, ksize=(3, 3), pad=(1, 1), act="lrelu", per_image=True)
+        x = ops.conv2d(x, *self.up0, ksize=(3, 3), pad=(1, 1), shuffle=2, per_image=True)
+        x = ops.conv2d(x, *self.up2, ksize=(3, 3), pad=(1, 1), shuffle=2, per_image=True)
+        return ops.conv2d(x, *self.last, ksize=(3, 3), pad=(1, 1), per_image=True)
 
-    def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None) -> T:
-        """feats (optional dict): receives feats["hat"] = the conv_after_body output [1,Hp,Wp,180] (NHWC), the tensor the
-        reference's forward hook captures for the cached-expert files (expert_loader.py:838)."""
+    def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
+        """lr [B,3,h,w] -> [B,3,4h,4w] (written into `out` when given).  feats (optional dict): receives feats["hat"] = the conv_after_body output [B,Hp,Wp,180]
+        (NHWC), the tensor the reference's forward hook captures for the cached-expert files (expert_loader.py:838).
+        B > 1: one launch per op for the whole batch in the fused modes (chunks of max_batch_tokens padded tokens), the per-image
+        loop in f32 mode; either way bit-equal to B single forwards.  taps are recorded for B == 1 only."""
+        B, _, h, w = lr.shape
+        Hp, Wp = _ceil_to(h, self.ws), _ceil_to(w, self.ws)
+        if B > 1:
+            if taps is not None:
+                raise ops._lib.FFError("HatHIP.forward: taps are recorded for B == 1 only")
+            nb = 1                                          # images per chunk
+            if ops.fused_modes():
+                # ops.conv2d keeps the LDS-resident 3x3 kernel to inputs of fewer than 2^31 elements (32-bit offsets), counted over the
+                # whole launch.  The largest 3x3 input here is the last convolution's, 16 Hp Wp pixels at a pitch of 64: a chunk stays
+                # under that bound whatever max_batch_tokens says, so a batch never leaves the route its images take alone.
+                nb = max(1, min(int(self.max_batch_tokens) // (Hp * Wp), (2 ** 31 - 1) // (16 * Hp * Wp * 64)))
+            if nb < B:                                      # every chunk writes its slice of the one output (and feature) buffer
+                if out is None:
+                    out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
+                fall = ops.empty_rows((B, Hp, Wp, self.after[0].shape[0]), lr.device) if feats is not None else None
+                for b0 in range(0, B, nb):
+                    self._forward_chunk(lr[b0:b0 + nb], None, {} if feats is not None else None, out[b0:b0 + nb],
+                                        fall[b0:b0 + nb] if feats is not None else None)
+                if feats is not None:
+                    feats["hat"] = fall
+                return out
+        return self._forward_chunk(lr, taps, feats, out, None)
+
+    def _forward_chunk(self, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], feat_out: Optional[T]) -> T:
+        """One launch per op for all of lr [B,3,h,w]; feat_out: where the hooked feature goes (a slice of the batch's buffer)."""
         _, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, self.ws), _ceil_to(w, self.ws)
         xin = ops.nchw_to_nhwc(lr, Hp, Wp, add=self.neg_mean, pad_mode="reflect")
-        feat = ops.conv2d(xin, *self.conv_first, ksize=(3, 3), pad=(1, 1))
+        feat = ops.conv2d(xin, *self.conv_first, ksize=(3, 3), pad=(1, 1), per_image=True)
         x = ops.layernorm(feat, *self.pe_norm)
         for g in range(self.groups):
             if taps is not None and g == 0:
@@ -222,18 +262,18 @@ class HatHIP:
                     taps[f"hat.g0.b{b}"] = y
                 y = self.ocab_block(y, self.ocab[0])
                 taps["hat.g0.ocab"] = y
-                x = ops.conv2d(y, *self.gconv[0], ksize=(3, 3), pad=(1, 1), res=x)
+                x = ops.conv2d(y, *self.gconv[0], ksize=(3, 3), pad=(1, 1), res=x)       # (taps: B == 1)
                 taps["hat.g0.out"] = x
             else:
                 x = self.group(x, g)
         x = ops.layernorm(x, *self.norm)
         if feats is not None:
-            feats["hat"] = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1))
+            feats["hat"] = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), per_image=True, out=feat_out)
             x = ops.mix2(feats["hat"], feat)
         else:
-            x = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), res=feat)
+            x = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), res=feat, per_image=True)
         sr = self._tail(x)
-        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True)
+        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True, out=out)
 
 
 # =============================================================================================== DAT
@@ -399,7 +439,7 @@ class DatHIP:
         z = ops.dwconv2d(gte, *blk["sgc"], mul_in=y[..., :c2])                     # dw3x3(LN(x2)) * x1 in one pass
         return ops.linear(z, *blk["fc2"], res=x)
 
-    def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None) -> T:
+    def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
         _, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, 16), _ceil_to(w, 16)
         xin = ops.nchw_to_nhwc(lr, Hp, Wp, add=self.neg_mean, pad_mode="reflect")
@@ -422,7 +462,7 @@ class DatHIP:
         x = ops.conv2d(x, *self.up0, ksize=(3, 3), pad=(1, 1), shuffle=2)
         x = ops.conv2d(x, *self.up2, ksize=(3, 3), pad=(1, 1), shuffle=2)
         sr = ops.conv2d(x, *self.last, ksize=(3, 3), pad=(1, 1))
-        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True)
+        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True, out=out)
 
 
 # =============================================================================================== NAFNet-SR
@@ -507,7 +547,7 @@ class NafnetHIP:
             g = ops.fma3(None, t[..., :c], t[..., c:])
         return ops.linear(g, *k["c5"], res=y, mul=k["gamma"])
 
-    def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None) -> T:
+    def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
         _, _, h, w = lr.shape
         H, W = 4 * h, 4 * w
         m = 2 ** len(self.enc_n)
@@ -534,4 +574,4 @@ class NafnetHIP:
         if feats is not None:
             feats["nafnet"] = x                                # expert_loader.py:866: the INPUT of the ending conv, [1,Hp,Wp,64]
         x = ops.conv2d(x, *self.ending, ksize=(3, 3), pad=(1, 1), res=inp)
-        return ops.nhwc_to_nchw(x, H, W, clamp01=True)
+        return ops.nhwc_to_nchw(x, H, W, clamp01=True, out=out)

@@ -24,6 +24,13 @@ from .fusion import FusionHIP
 T = torch.Tensor
 
 
+def _image(lr: T, b: int) -> T:
+    """lr[b:b+1] of a contiguous batch, copied when the slice does not start on a 16-byte boundary (odd image sizes): the kernels take
+    16-byte aligned images.  The copy is a torch op, which a recorded plan (plan.py) cannot carry: forward() refuses to record such a batch."""
+    t = lr[b:b + 1]
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class FreqFusionHIP:
     def __init__(self, state_dict: Dict[str, T], device="cuda:0"):
         dev = torch.device(device)
@@ -79,26 +86,81 @@ class FreqFusionHIP:
         ex = {"hat": hat, "dat": dat, "nafnet": naf}
         return (ex, pre) if with_pre else ex
 
+    def _experts_batched(self, lr: T):
+        """The experts of a batch lr [B,3,h,w]: (hat [B,3,4h,4w], [dat_b], [nafnet_b], [pre_b or None]).  One fork / join pair as in
+        experts(): HAT for the whole batch on the caller's stream, DAT for b = 0 .. B-1 on side stream 1, NAFNet and fusion.pre for
+        each b on side stream 2."""
+        B = lr.shape[0]
+        if not self.multi_stream:
+            return (self.hat.forward(lr), [self.dat.forward(_image(lr, b)) for b in range(B)],
+                    [self.nafnet.forward(_image(lr, b)) for b in range(B)], [None] * B)
+        main = torch.cuda.current_stream()
+        if self._side is None:
+            self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
+        s1, s2 = self._side
+        s1.wait_stream(main)
+        s2.wait_stream(main)
+        if self._marker:
+            self._marker("fork")
+        with torch.cuda.stream(s1):
+            dats = [self.dat.forward(_image(lr, b)) for b in range(B)]
+        nafs, pres = [], []
+        with torch.cuda.stream(s2):
+            for b in range(B):
+                nafs.append(self.nafnet.forward(_image(lr, b)))
+                pres.append(self.fusion.pre(_image(lr, b)))
+        hat = self.hat.forward(lr)
+        main.wait_stream(s1)
+        main.wait_stream(s2)
+        if self._marker:
+            self._marker("join")
+        for t in (*dats, *nafs, *(t for pre in pres for t in pre.values())):
+            t.record_stream(main)
+        return hat, dats, nafs, pres
+
     @torch.no_grad()
     def experts_with_features(self, lr: T, streams: bool = False):
-        """ExpertEnsemble.forward_all_with_hooks (expert_loader.py:894-951): ({hat,dat,nafnet} SR outputs [1,3,4h,4w],
-        {hat [1,180,h,w], dat [1,180,h,w], nafnet [1,64,h,w]} hook features bilinearly resized to the LR resolution, NCHW).
+        """ExpertEnsemble.forward_all_with_hooks (expert_loader.py:894-951): ({hat,dat,nafnet} SR outputs [B,3,4h,4w],
+        {hat [B,180,h,w], dat [B,180,h,w], nafnet [B,64,h,w]} hook features bilinearly resized to the LR resolution, NCHW).
         The payload of the cached-expert files (isr2_amd/cache.py).  streams=True runs the same launches with DAT and NAFNet (and
         their feature resizes) on the two side streams of experts(), forked from and joined to the caller's stream: the same bits,
-        the small grids of one expert beside those of another (cache.build_from_folders)."""
-        if lr.dim() != 4 or lr.shape[0] != 1 or lr.shape[1] != 3:
-            raise _lib.FFError(f"expected lr of shape [1,3,h,w], got {tuple(lr.shape)}")
+        the small grids of one expert beside those of another (cache.build_from_folders).
+        B > 1: HAT runs the batch through one launch per op; DAT and NAFNet run image by image into slices of their outputs.  Every
+        image's tensors are those of its own B == 1 call, bit for bit."""
+        if lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3:
+            raise _lib.FFError(f"expected lr of shape [B,3,h,w], got {tuple(lr.shape)}")
         lr = lr.to(self.dev, torch.float32).contiguous()
-        _, _, h, w = lr.shape
-        if streams:
-            from . import ops
+        B, _, h, w = lr.shape
+        from . import ops
 
-            def one(net):
-                raw = {}
-                out = net.forward(lr, feats=raw)
-                return out, {k: ops.nhwc_to_nchw(ops.resize(v, (h, w))) for k, v in raw.items()}
+        def feat_lr(v, out=None):                              # hooked NHWC feature -> [.,C,h,w] at the LR resolution
+            return ops.nhwc_to_nchw(ops.resize(v, (h, w)), out=out)
 
-            with torch.cuda.device(self.dev):
+        def fwd(net, name):                                    # -> (SR output [B,3,4h,4w], [hooked NHWC features])
+            raw = {}
+            if B == 1 or net is self.hat:
+                return net.forward(lr, feats=raw), [raw[name]]
+            o = torch.empty((B, 3, 4 * h, 4 * w), device=self.dev, dtype=torch.float32)
+            raws = []
+            for b in range(B):                                 # per image, into slices of the output
+                net.forward(_image(lr, b), feats=raw, out=o[b:b + 1])
+                raws.append(raw[name])
+            return o, raws
+
+        def finish(raws):
+            if len(raws) == 1:
+                return feat_lr(raws[0])
+            f = torch.empty((B, raws[0].shape[-1], h, w), device=self.dev, dtype=torch.float32)
+            for b, v in enumerate(raws):
+                feat_lr(v, out=f[b:b + 1])
+            return f
+
+        def one(net, name):
+            o, raws = fwd(net, name)
+            return o, finish(raws)
+
+        with torch.cuda.device(self.dev):
+            if streams:
                 main = torch.cuda.current_stream()
                 if self._side is None:
                     self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
@@ -106,22 +168,18 @@ class FreqFusionHIP:
                 s1.wait_stream(main)
                 s2.wait_stream(main)
                 with torch.cuda.stream(s1):
-                    o_dat, f_dat = one(self.dat)
+                    o_dat, f_dat = one(self.dat, "dat")
                 with torch.cuda.stream(s2):
-                    o_naf, f_naf = one(self.nafnet)
-                o_hat, f_hat = one(self.hat)
+                    o_naf, f_naf = one(self.nafnet, "nafnet")
+                o_hat, f_hat = one(self.hat, "hat")
                 main.wait_stream(s1)
                 main.wait_stream(s2)
-                for t in (o_dat, o_naf, *f_dat.values(), *f_naf.values()):
+                for t in (o_dat, o_naf, f_dat, f_naf):
                     t.record_stream(main)
-            return {"hat": o_hat, "dat": o_dat, "nafnet": o_naf}, {**f_hat, **f_dat, **f_naf}
-        raw = {}
-        with torch.cuda.device(self.dev):
-            outs = {"hat": self.hat.forward(lr, feats=raw), "dat": self.dat.forward(lr, feats=raw),
-                    "nafnet": self.nafnet.forward(lr, feats=raw)}
-            from . import ops
-            feats = {k: ops.nhwc_to_nchw(ops.resize(v, (h, w))) for k, v in raw.items()}
-        return outs, feats
+            else:
+                (o_hat, r_hat), (o_dat, r_dat), (o_naf, r_naf) = fwd(self.hat, "hat"), fwd(self.dat, "dat"), fwd(self.nafnet, "nafnet")
+                f_hat, f_dat, f_naf = finish(r_hat), finish(r_dat), finish(r_naf)
+        return {"hat": o_hat, "dat": o_dat, "nafnet": o_naf}, {"hat": f_hat, "dat": f_dat, "nafnet": f_naf}
 
     @torch.no_grad()
     def forward_with_precomputed(self, lr: T, expert_outputs, expert_features=None, taps: Optional[dict] = None) -> T:
@@ -153,14 +211,21 @@ class FreqFusionHIP:
         lr = lr.to(self.dev, torch.float32).contiguous()
         if lr.shape[0] > 1:
             # Every global op of the path is per image (average pools, channel attention statistics, rFFT2, squeeze gates), so a
-            # batch is B independent images: they are sequenced back to back into one output buffer (one launch stream, one
-            # graph when captured through graphed()).  Bit-identical to B single forwards by construction.
+            # batch is B independent images.  HAT takes the whole batch through one launch per op (HatHIP.forward: its only per-image
+            # quantity, the channel-attention gate, is a [B,180] matrix); DAT, NAFNet and the fusion stack are still sequenced per
+            # image.  Bit-identical to B single forwards: every image runs the launches, in the forms, of its own B == 1 forward.
             if taps is not None:
                 raise _lib.FFError("taps are recorded for B == 1 only")
+            if self._marker is not None and (3 * lr.shape[2] * lr.shape[3]) % 4:
+                # plan recording: an image that does not start on a 16-byte boundary is copied by torch (_image), outside the tape
+                raise _lib.FFError(f"a plan of a batch needs images of a multiple of 16 bytes (3 * h * w % 4 == 0), got {tuple(lr.shape)}")
             if out is None:
                 out = torch.empty((lr.shape[0], 3, 4 * lr.shape[2], 4 * lr.shape[3]), device=self.dev, dtype=torch.float32)
-            for b in range(lr.shape[0]):
-                self.forward(lr[b:b + 1], out=out[b:b + 1])
+            with torch.cuda.device(self.dev):
+                hat, dats, nafs, pres = self._experts_batched(lr)
+                for b in range(lr.shape[0]):
+                    self.fusion.forward(_image(lr, b), {"hat": hat[b:b + 1], "dat": dats[b], "nafnet": nafs[b]}, None, pre=pres[b],
+                                        out=out[b:b + 1])
             return out
         with torch.cuda.device(self.dev):
             ex, pre = self.experts(lr, taps, with_pre=True)

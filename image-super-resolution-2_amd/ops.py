@@ -336,25 +336,36 @@ def _nhwc(t: T, name: str):
 
 class PoolPartials:
     """Per-workgroup pool partial sums written by a conv epilogue: mean[c] = inv_count * sum_r part[r][c].  vec_mlp() consumes
-    them directly (ff_pool_vec_mlp: finish + channel-attention MLP in one launch); .mean() finishes them alone."""
+    them directly (ff_pool_vec_mlp: finish + channel-attention MLP in one launch); .mean() finishes them alone.
+    images = B > 1 (conv2d on a batch): part holds B equal groups of rows, image b's -- those of its own single-image launch, in
+    their order -- at rows b * rows_per_image ..; .mean() is [B, C]."""
 
-    def __init__(self, part: T, C: int, inv_count: float):
-        self.part, self.C, self.inv_count = part, C, inv_count
+    def __init__(self, part: T, C: int, inv_count: float, images: int = 1):
+        if images < 1 or part.shape[0] % images:
+            raise _lib.FFError(f"PoolPartials: {part.shape[0]} partial rows do not split into {images} images")
+        self.part, self.C, self.inv_count, self.images = part, C, inv_count, images
+        self.rows_per_image = part.shape[0] // images
 
     def mean(self) -> T:
-        pooled = torch.empty((1, self.C), device=self.part.device, dtype=torch.float32)
-        _lib.check(_L().ff_pool_finish(self.part.data_ptr(), self.part.shape[0], self.part.shape[1], self.C, self.inv_count,
-                                       pooled.data_ptr(), _stream()))
+        pooled = torch.empty((self.images, self.C), device=self.part.device, dtype=torch.float32)
+        for b in range(self.images):                            # per image, the single-image finish (vec_mlp has the one-launch form)
+            _lib.check(_L().ff_pool_finish(self.part[b * self.rows_per_image:].data_ptr(), self.rows_per_image, self.part.shape[1], self.C,
+                                           self.inv_count, pooled[b:].data_ptr(), _stream()))
         return pooled
 
 
 def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1), pad=(0, 0), act=None,
            res: Optional[T] = None, mul: Optional[T] = None, alpha: float = 1.0, shuffle: int = 0,
-           out: Optional[T] = None, tile_hint: int = 0, dynamic_w: bool = False, want_pool: bool = False, out_bf16: bool = False):
+           out: Optional[T] = None, tile_hint: int = 0, dynamic_w: bool = False, want_pool: bool = False, out_bf16: bool = False,
+           per_image: bool = False):
     """x [B,H,W,Cin] (rows view), w packed [Cout, KH*KW*Cin] -> [B,Ho,Wo,Cout] (or pixel-shuffled).
-    want_pool (B == 1): also return the global average pool [1, Cout] of the output -> (out, pooled); the LDS-resident 3x3
+    want_pool: also return the global average pool [B, Cout] of the output -> (out, pooled); the LDS-resident 3x3
     kernel produces it from its epilogue, any other path falls back to ff_pool_mean on the output.  want_pool="partials":
-    the second value is a PoolPartials when the epilogue produced partial sums (else the finished pool)."""
+    the second value is a PoolPartials when the epilogue produced partial sums (else the finished pool).
+    per_image (implied by want_pool; matters for B > 1 only): the batch is B independent images and every image must come out with
+    the bits of its own B == 1 call -- the LDS-resident kernel goes through ff_conv3x3_halo_images (kernel form and pool partial rows
+    of one image's launch), the implicit GEMM gets the tile configuration of one image's row count as its hint."""
+    per_image = bool(per_image or want_pool) and x.dim() == 4 and x.shape[0] > 1
     in_bf16 = x.dtype == torch.bfloat16
     xp, ldi, B, H, W, Cin = _nhwc(x, "conv2d.x|bf16ok" if in_bf16 else "conv2d.x")
     KH, KW = ksize
@@ -374,6 +385,8 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
                and not dynamic_w and Cin >= 32 and Cin % 4 == 0 and ldi % 4 == 0 and xp % 16 == 0
                and (Cout <= 64 or Cin >= 128 or 128 < Cout <= 192)   # measured (profiles/r01_conv3x3_halo_vs_igemm.txt); 64 -> 256 ties
                and H * W >= 1024 and xp != op and B * H * W * ldi < 2 ** 31)
+    # (the last term is the one condition that counts the whole launch: the kernel's 32-bit offsets.  A caller that batches independent
+    # images keeps its batches below it -- HatHIP.forward sizes its chunks so -- and every other term is one image's.)
     if (in_bf16 or out_bf16) and not (halo_ok and _GEMM_MODE == "bf16" and shuffle == 0 and res is None):
         raise _lib.FFError("conv2d: bf16 input / output rows exist for the LDS-resident 3x3 kernel in plain-bf16 mode only")
     rp, ldr = None, 0
@@ -404,19 +417,23 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
             return (_prep.pack_conv3x3_halo(w, Cin, bn, nt_), bn)
         img = PREPARED.get(w, "halo" if nt_ == 3 else "halo1", _mk_halo)
         part = None
-        if want_pool and B == 1 and shuffle == 0 and Cout <= img[1]:
-            prow = int(_L().ff_conv3x3_halo_pool_rows(B, H, W, Cout, img[1], nt_))
+        halo_fn, rows_fn = ((_L().ff_conv3x3_halo_images, _L().ff_conv3x3_halo_images_pool_rows) if per_image else
+                            (_L().ff_conv3x3_halo, _L().ff_conv3x3_halo_pool_rows))
+        if want_pool and (B == 1 or per_image) and shuffle == 0 and Cout <= img[1]:
+            prow = int(rows_fn(B, H, W, Cout, img[1], nt_))
             part = torch.empty((prow, img[1]), device=x.device, dtype=torch.float32)
-        _lib.check(_L().ff_conv3x3_halo(xp, ldi, img[0].data_ptr(), img[1], _ptr(bias), _ptr(mul), rp, ldr, op, ldo, B, H, W,
-                                        Cin, Cout, ACT[act], float(alpha), shuffle, _ptr(part), _nterms(),
-                                        (1 if in_bf16 else 0) | (2 if out_bf16 else 0), _stream()))
+        _lib.check(halo_fn(xp, ldi, img[0].data_ptr(), img[1], _ptr(bias), _ptr(mul), rp, ldr, op, ldo, B, H, W,
+                           Cin, Cout, ACT[act], float(alpha), shuffle, _ptr(part), _nterms(),
+                           (1 if in_bf16 else 0) | (2 if out_bf16 else 0), _stream()))
         if part is not None:
-            pp = PoolPartials(part, Cout, 1.0 / float(H * W))
+            pp = PoolPartials(part, Cout, 1.0 / float(H * W), images=B)
             _note(2.0 * B * Ho * Wo * Cout * KH * KW * Cin, 4.0 * (_numel(x, w, out, res)))
             return out, (pp if want_pool == "partials" else pp.mean())
     else:
         aligned = (ldi % 4 == 0) and (xp % 16 == 0)
         hi, lo, Kp, Cp, _ = _split_weight(w, dynamic_w, Cin if aligned else 0)
+        if per_image and tile_hint <= 0:                    # the tile configuration one image's launch picks for itself
+            tile_hint = int(_L().ff_conv2d_bf16s_tile(Ho * Wo, Cout, KH * KW * Cin, 1 if aligned and Cin % 4 == 0 else 0))
         _lib.check(_L().ff_conv2d_bf16s(xp, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, _ptr(bias), _ptr(mul),
                                         rp, op, B, H, W, Cin, ldi, Ho, Wo, Cout, ldo, ldr, KH, KW, stride[0], stride[1],
                                         pad[0], pad[1], ACT[act], float(alpha), shuffle, GEMM_MODES[_GEMM_MODE], tile_hint,
@@ -625,7 +642,8 @@ def token_mlp(x: T, gamma: T, beta: T, pk: dict, eps: float = 1e-5) -> T:
 def token_projmlp(att: T, x: T, pk: dict, gamma: T, beta: T, *, c2: Optional[T] = None, c2_scale: Optional[T] = None,
                   eps: float = 1e-5) -> T:
     """x1 = x + proj(att) + c2 * c2_scale; return x1 + fc2(GELU(fc1(LayerNorm(x1)))) in one launch (bf16x3); pk from
-    prep.pack_token_projmlp."""
+    prep.pack_token_projmlp.  c2_scale [K] (or [1,K]): one gate for every row.  c2_scale [B,K] with B = x.shape[0] > 1: one gate per image
+    (ff_token_projmlp_images; every image must be a multiple of 256 rows), bit-equal to B calls on the row slices."""
     att_bf16 = att.dtype == torch.bfloat16
     c2_bf16 = c2 is not None and c2.dtype == torch.bfloat16
     if (att_bf16 or c2_bf16) and _GEMM_MODE != "bf16":
@@ -637,14 +655,27 @@ def token_projmlp(att: T, x: T, pk: dict, gamma: T, beta: T, *, c2: Optional[T] 
     cp, ldc = None, 0
     if c2 is not None:
         cp, ldc, cr, ck = rows_view(c2, "token_projmlp.c2|bf16ok" if c2_bf16 else "token_projmlp.c2")
-        if cr != rows or ck != K or c2_scale is None or c2_scale.numel() != K:
+        if cr != rows or ck != K or c2_scale is None:
             raise _lib.FFError("token_projmlp: c2 shape mismatch")
+    nimg = 1
+    if c2 is not None and c2_scale.numel() != K:
+        nimg = int(x.shape[0])
+        if c2_scale.dim() != 2 or tuple(c2_scale.shape) != (nimg, K) or not c2_scale.is_contiguous() or rows % nimg:
+            raise _lib.FFError(f"token_projmlp: c2_scale must be [{K}] or one row per image [{nimg},{K}], got {tuple(c2_scale.shape)}")
+        if (rows // nimg) % 256:
+            raise _lib.FFError(f"token_projmlp: a per-image gate needs images of a multiple of 256 rows, got {rows // nimg}")
     out = empty_like_rows(x)
     op_, ldo_, _, _ = rows_view(out, "token_projmlp.out")
     m = pk["mlp"]
-    _lib.check(_L().ff_token_projmlp(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), op_, ldo_, rows, K, m["ht"], pk["proj"]["w"].data_ptr(),
-                                     pk["proj"]["b"].data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), m["w"].data_ptr(),
-                                     m["b1"].data_ptr(), m["b2"].data_ptr(), _nterms(), (1 if att_bf16 else 0) | (2 if c2_bf16 else 0), _stream()))
+    if nimg > 1:
+        _lib.check(_L().ff_token_projmlp_images(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), K, nimg, rows // nimg, op_, ldo_, rows, K, m["ht"],
+                                                pk["proj"]["w"].data_ptr(), pk["proj"]["b"].data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                float(eps), m["w"].data_ptr(), m["b1"].data_ptr(), m["b2"].data_ptr(), _nterms(),
+                                                (1 if att_bf16 else 0) | (2 if c2_bf16 else 0), _stream()))
+    else:
+        _lib.check(_L().ff_token_projmlp(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), op_, ldo_, rows, K, m["ht"], pk["proj"]["w"].data_ptr(),
+                                         pk["proj"]["b"].data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), m["w"].data_ptr(),
+                                         m["b1"].data_ptr(), m["b2"].data_ptr(), _nterms(), (1 if att_bf16 else 0) | (2 if c2_bf16 else 0), _stream()))
     _note(2.0 * rows * K * K + 4.0 * rows * K * m["ht"] * 32, 4.0 * rows * K * (2 + (0.5 if att_bf16 else 1.0) + (0 if c2 is None else (0.5 if c2_bf16 else 1.0))))
     return out
 
@@ -807,7 +838,12 @@ def vec_mlp(v, W1: T, b1: Optional[T], act1, W2: Optional[T] = None, b2: Optiona
         if W2 is not None and W1.shape[0] <= 64 and v.C <= 512:
             if W1.shape[1] != v.C or W2.shape[1] != W1.shape[0]:
                 raise _lib.FFError("vec_mlp: weight shape mismatch")
-            out = torch.empty((1, W2.shape[0]), device=v.part.device, dtype=torch.float32)
+            out = torch.empty((v.images, W2.shape[0]), device=v.part.device, dtype=torch.float32)
+            if v.images > 1:                                 # one workgroup per image, each in the single-image summation order
+                _lib.check(_L().ff_pool_vec_mlp_images(v.part.data_ptr(), v.images, v.rows_per_image, v.part.shape[1], v.inv_count, v.C,
+                                                       W1.data_ptr(), _ptr(b1), W1.shape[0], ACT[act1], W2.data_ptr(), _ptr(b2), W2.shape[0],
+                                                       ACT[act2], float(post), out.data_ptr(), None, _stream()))
+                return out
             _lib.check(_L().ff_pool_vec_mlp(v.part.data_ptr(), v.part.shape[0], v.part.shape[1], v.inv_count, v.C, W1.data_ptr(), _ptr(b1),
                                             W1.shape[0], ACT[act1], W2.data_ptr(), _ptr(b2), W2.shape[0], ACT[act2], float(post),
                                             out.data_ptr(), None, _stream()))

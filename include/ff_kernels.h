@@ -58,6 +58,10 @@ int ff_conv2d_bf16s(const float* in, const void* w_hi, const void* w_lo, int Kp,
                     const float* res, float* out, int B, int H, int W, int Cin, int ldi, int Ho, int Wo, int Cout,
                     int ldo, int ldr, int KH, int KW, int sy, int sx, int py, int px, int act, float alpha, int shuffle,
                     int nterms, int tile_hint, const float* kmul, void* stream);
+/* The tile configuration ff_conv2d_bf16s picks when tile_hint <= 0, from M = B * Ho * Wo, Cout, K = KH * KW * Cin and vec4 (Cin % 4 == 0,
+ * 16-byte aligned input rows).  A caller that batches independent images passes the value for ONE image's M as tile_hint, so that the
+ * batched launch takes the kernel form the single-image launch takes.  Added under ABI version 7 (an additive entry point). */
+int ff_conv2d_bf16s_tile(long long M, int Cout, int K, int vec4);
 int ff_split_bf16(const float* w, int N, int K, int Kp, int Cin, int Cp, void* hi, void* lo, void* stream);
 
 /* GEMM on bf16 ROWS, plain bf16 (csrc/gemm_rows_bf16.hip): out[M][N] = epilogue(A[M][K] . W[N][K]^T), bit-equal to
@@ -124,6 +128,19 @@ int ff_token_projmlp(const float* att, int lda, const float* x, int ldx, const f
                      float* out, int ldo, long long M, int K, int hidden_tiles, const void* proj_tiles,
                      const float* proj_bias_padded, const float* gamma, const float* beta, float eps,
                      const void* mlp_tiles, const float* b1_padded, const float* b2, int nterms, int io_bf16, void* stream);
+/* ff_token_projmlp over a batch of B images with ONE GATE PER IMAGE (HAT's channel attention is per image): c2_scale is [B][scale_ld]
+ * (scale_ld >= K, scale_ld % 4 == 0) and image b -- tokens b * rows_per_image .. (b + 1) * rows_per_image - 1 -- computes
+ *   x1 = x + proj(att) + c2 * c2_scale[b].
+ * A workgroup owns 256 consecutive tokens, so rows_per_image % 256 == 0 and M == B * rows_per_image are required (anything else is
+ * refused before the launch; HAT pads to multiples of 16 pixels, i.e. of 256 tokens).  The grid is (rows_per_image / 256, B): the image
+ * index is blockIdx.y, uniform per workgroup, no vector register and no division.  Every token's arithmetic is that of ff_token_projmlp,
+ * so the result is bit-equal to B calls on the row slices, and B == 1 makes the launch ff_token_projmlp makes.  c2 and c2_scale are
+ * required.  Added under ABI version 7 (an additive entry point: no existing prototype changed). */
+int ff_token_projmlp_images(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
+                            int scale_ld, int B, long long rows_per_image, float* out, int ldo, long long M, int K,
+                            int hidden_tiles, const void* proj_tiles, const float* proj_bias_padded, const float* gamma,
+                            const float* beta, float eps, const void* mlp_tiles, const float* b1_padded, const float* b2,
+                            int nterms, int io_bf16, void* stream);
 
 /* Window-resident attention block (csrc/win_attn_fused.hip): LayerNorm -> q/k/v projection -> softmax(q k^T + bias (+mask)) v
  * for ALL `nheads` heads of one 256-token window per workgroup; the qkv tensor never exists in memory.
@@ -177,6 +194,18 @@ int ff_pool_finish(const float* part, int rows, int ld, int C, float inv_count, 
 int ff_conv3x3_halo(const float* in, int ldi, const void* w_img, int bn, const float* bias, const float* mul,
                     const float* res, int ldr, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
                     int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, void* stream);
+/* ff_conv3x3_halo over B INDEPENDENT IMAGES, each reproducing the bits of its own B == 1 launch -- output and pool partials.
+ * ff_conv3x3_halo(B > 1) differs from that in two ways: it picks its kernel form (8 or 16 pixel rows per workgroup) from the tile count
+ * of the whole launch, and it indexes the partial rows by workgroup after an XCD remap over ALL tiles, so an image's partial rows
+ * interleave with the others' in an order that depends on B.  Here the form is the one ff_conv3x3_halo(B = 1, H, W, ...) takes, workgroup
+ * w belongs to image w / wpi (wpi = workgroups of one image), the remap runs over the wpi workgroups of that image, and the partial goes
+ * to row w: rows b * wpi .. (b + 1) * wpi - 1 of pool_partials [ff_conv3x3_halo_images_pool_rows(B, ...)][bn] are image b's single-image
+ * rows in their single-image order (finish them with ff_pool_vec_mlp_images, or ff_pool_finish per image).  Same arguments and
+ * restrictions as ff_conv3x3_halo otherwise.  Added under ABI version 7 (additive entry points). */
+long long ff_conv3x3_halo_images_pool_rows(int B, int H, int W, int Cout, int bn, int nterms);
+int ff_conv3x3_halo_images(const float* in, int ldi, const void* w_img, int bn, const float* bias, const float* mul,
+                           const float* res, int ldr, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
+                           int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, void* stream);
 
 /* Token-stationary linear layer for K <= 192 (csrc/token_linear.hip), bf16x3 MFMA:
  *   out = res + res2*res2_scale[n] + act( LayerNorm?(x) . W^T + bias )        (gamma == NULL: no LayerNorm)
@@ -267,6 +296,12 @@ int ff_pool_partials(const float* in, int ld, long long P, int C, float* part, l
 int ff_pool_vec_mlp(const float* part, int rows, int ld, float inv_count, int Cin, const float* W1, const float* b1, int Ch,
                     int act1, const float* W2, const float* b2, int Cout, int act2, float post, float* out, float* pooled_out,
                     void* stream);
+/* ff_pool_vec_mlp for B images in one launch, one workgroup per image: image b finishes the `rows` partial rows at
+ * part + b * rows * ld in the summation order of the single-image launch and writes out[b][Cout] (pooled_out[b][Cin], may be NULL):
+ * bit-equal to B ff_pool_vec_mlp launches.  Added under ABI version 7 (an additive entry point). */
+int ff_pool_vec_mlp_images(const float* part, int B, int rows, int ld, float inv_count, int Cin, const float* W1, const float* b1,
+                           int Ch, int act1, const float* W2, const float* b2, int Cout, int act2, float post, float* out,
+                           float* pooled_out, void* stream);
 
 /* HAT OCAB attention stage (hat_arch.py:392-438), plain bf16 MFMA: softmax(q k^T * scale + bias) v for 16x16 query windows against
  * the 24x24 key windows of nn.Unfold(kernel 24, stride 16, padding 4) -- keys outside the image are zero vectors that still take

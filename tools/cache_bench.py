@@ -1,9 +1,10 @@
 """Throughput of the cached-expert data-set builder on one MI355X.  A synthetic folder of seeded PNG pairs is written to a temporary
 directory; then, alternating in one process, (a) isr2_amd.cache.build_from_folders (with and without the graph replay) and (b) the sequential loop a user would write
 around cache.extract (decode, upload, cut the same patches with torch slicing, extract) fill fresh cache directories; (c) is
-cache.extract alone over patches already cut on the device (no decoding).  Also: the GB/s of ff_crop_pairs_u8 and ff_resize_aa at a
+cache.extract alone over patches already cut on the device (no decoding); (d) with --batch N > 1, build_from_folders(batch=N): the
+patches of an image in groups of N, HAT batched.  Also: the GB/s of ff_crop_pairs_u8 and ff_resize_aa at a
 2040 x 1356 HR image (DIV2K-sized), and the HR-only mode of the builder.
-    python tools/cache_bench.py [--images 12] [--lr-h 128] [--lr-w 160] [--patch 64] [--crops 5] [--rounds 3] [--gemm bf16x3] [--json PATH]"""
+    python tools/cache_bench.py [--images 12] [--lr-h 128] [--lr-w 160] [--patch 64] [--crops 5] [--rounds 3] [--gemm bf16x3] [--batch 1] [--json PATH]"""
 import argparse
 import json
 import os
@@ -64,6 +65,7 @@ def main():
     ap.add_argument("--crops", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--gemm", default="bf16x3")
+    ap.add_argument("--batch", type=int, default=1, help="> 1: also time build_from_folders(batch=N)")
     ap.add_argument("--json")
     a = ap.parse_args()
     from PIL import Image
@@ -116,6 +118,8 @@ def main():
         variants = {"build_from_folders": lambda o: run_builder(o, lr_dir=os.path.join(tmp, "lr")),
                     "build_from_folders_no_graph": lambda o: run_builder(o, lr_dir=os.path.join(tmp, "lr"), graph=False), "extract_loop": run_loop,
                     "extract_only": run_extract_only, "build_from_folders_hr_only": lambda o: run_builder(o)}
+        if a.batch > 1:
+            variants[f"build_from_folders_batch{a.batch}"] = lambda o: run_builder(o, lr_dir=os.path.join(tmp, "lr"), batch=a.batch)
         cache.extract(model, precut[:2], os.path.join(tmp, "warm"))                # code objects, allocator, workspaces
         rates = {k: [] for k in variants}
         last = {}
@@ -135,6 +139,11 @@ def main():
            "no_graph_builder_over_extract_loop": med["build_from_folders_no_graph"] / med["extract_loop"],
            "builder_stage_seconds": secs, "builder_stage_share_of_wall": {k: v / secs["total"] for k, v in secs.items() if k != "total"},
            "kernels": kern}
+    if a.batch > 1:
+        name = f"build_from_folders_batch{a.batch}"
+        bs = last[name]["seconds"]
+        out["batch"] = {"batch": a.batch, "patches_per_s": med[name], "over_batch_1": med[name] / med["build_from_folders"], "stage_seconds": bs,
+                        "stage_share_of_wall": {k: v / bs["total"] for k, v in bs.items() if k != "total"}}
     line = json.dumps(out)
     print(line, flush=True)
     if a.json:
