@@ -42,28 +42,64 @@ class _Weights:
         return self.sd[k].to(self.dev, torch.float32).contiguous() if k in self.sd else None
 
 
-def _tl(blk: dict, key: str) -> dict:
-    """Lazily packed ff_token_linear weights of blk[key] = (W [N,K], b)."""
-    pk = blk.get(key + "_tl")
+def _packed(blk: dict, key: str, build):
+    """blk[key], made by build() on first use: the repacked weights only one contraction mode's kernels read are prepared lazily,
+    once, and kept beside the tensors they were made from (the key is the slot name a recorded plan stores: plan.py)."""
+    pk = blk.get(key)
     if pk is None:
-        pk = blk[key + "_tl"] = pack_token_linear(blk[key][0], blk[key][1])
+        pk = blk[key] = build()
     return pk
+
+
+def _tl(blk: dict, key: str) -> dict:
+    """ff_token_linear weights of blk[key] = (W [N,K], b)."""
+    return _packed(blk, key + "_tl", lambda: pack_token_linear(*blk[key]))
 
 
 def _pm(blk: dict) -> dict:
-    pk = blk.get("projmlp_pk")
-    if pk is None:
-        pk = blk["projmlp_pk"] = pack_token_projmlp(blk["proj"][0], blk["proj"][1], blk["fc1"][0], blk["fc1"][1],
-                                                    blk["fc2"][0], blk["fc2"][1])
-    return pk
+    return _packed(blk, "projmlp_pk", lambda: pack_token_projmlp(*blk["proj"], *blk["fc1"], *blk["fc2"]))
 
 
 def _wf(blk: dict, heads: int, d: int) -> dict:
-    """Lazily packed ff_win_attn_fused weights of blk["qkv"] = (W [3C, C], b)."""
-    pk = blk.get("qkv_wf")
-    if pk is None:
-        pk = blk["qkv_wf"] = pack_win_attn(blk["qkv"][0], blk["qkv"][1], heads, d, d ** -0.5)
-    return pk
+    """ff_win_attn_fused weights of blk["qkv"] = (W [3C, C], b)."""
+    return _packed(blk, "qkv_wf", lambda: pack_win_attn(*blk["qkv"], heads, d, d ** -0.5))
+
+
+class _Trunk:
+    """What HAT and DAT share around their residual groups (hat_arch.py:905-984, dat_arch.py:940-1028): conv_first on the mean-shifted,
+    reflect-padded input, and after the groups the final LayerNorm, conv_after_body with the long residual, the x4 pixel-shuffle
+    tail and conv_last with "+ mean" folded into its bias.  `name` is the key of the hooked feature."""
+
+    def _load_trunk(self, w: _Weights, dev) -> None:
+        self.neg_mean = torch.tensor([-m for m in RGB_MEAN], device=dev)
+        self.conv_first = (w.conv("conv_first"), w("conv_first.bias"))
+        self.norm = (w("norm.weight"), w("norm.bias"))
+        self.after = (w.conv("conv_after_body"), w("conv_after_body.bias"))
+        self.before_up = (w.conv("conv_before_upsample.0"), w("conv_before_upsample.0.bias"))
+        self.up0 = (w.conv("upsample.0"), w("upsample.0.bias"))
+        self.up2 = (w.conv("upsample.2"), w("upsample.2.bias"))
+        self.last = (w.conv("conv_last"), (w("conv_last.bias") - self.neg_mean).contiguous())   # "+ mean" folded into the bias
+
+    def _enter(self, lr: T, Hp: int, Wp: int) -> T:
+        """lr [B,3,h,w] -> conv_first's output [B,Hp,Wp,180].  per_image matters for B > 1 only (ops.conv2d), here and in _exit."""
+        xin = ops.nchw_to_nhwc(lr, Hp, Wp, add=self.neg_mean, pad_mode="reflect")
+        return ops.conv2d(xin, *self.conv_first, ksize=(3, 3), pad=(1, 1), per_image=True)
+
+    def _exit(self, x: T, feat: T, h: int, w: int, feats: Optional[dict], out: Optional[T], feat_out: Optional[T] = None) -> T:
+        """The groups' output x and conv_first's feat -> SR [B,3,4h,4w] (into `out` when given).  feats (optional dict): receives
+        feats[name] = the conv_after_body output [B,Hp,Wp,180] (NHWC, into `feat_out` when given), the tensor the reference's forward
+        hook captures for the cached-expert files (expert_loader.py:838, :850); the residual is then a launch of its own."""
+        x = ops.layernorm(x, *self.norm)
+        if feats is not None:
+            feats[self.name] = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), per_image=True, out=feat_out)
+            x = ops.mix2(feats[self.name], feat)
+        else:
+            x = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), res=feat, per_image=True)
+        x = ops.conv2d(x, *self.before_up, ksize=(3, 3), pad=(1, 1), act="lrelu", per_image=True)
+        x = ops.conv2d(x, *self.up0, ksize=(3, 3), pad=(1, 1), shuffle=2, per_image=True)
+        x = ops.conv2d(x, *self.up2, ksize=(3, 3), pad=(1, 1), shuffle=2, per_image=True)
+        sr = ops.conv2d(x, *self.last, ksize=(3, 3), pad=(1, 1), per_image=True)
+        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True, out=out)
 
 
 # =============================================================================================== HAT
@@ -81,7 +117,7 @@ def _rel_index_oca(ws: int, ows: int) -> T:
     return dy * (ws + ows - 1) + dx
 
 
-class HatHIP:
+class HatHIP(_Trunk):
     """HAT-L (hat_arch.py:710-984): 12 RHAG x (6 HAB + OCAB), dim 180, 6 heads, window 16.
 
     forward(lr [B,3,h,w]) runs a batch through ONE launch per op in the fused modes: the window, row and 3x3 kernels take B or plain
@@ -92,16 +128,17 @@ class HatHIP:
     # Batches are processed in chunks of at most this many padded tokens (B * Hp * Wp): four 256 x 256 tiles, i.e. activation memory
     # grows to at most four times what one such tile allocates.  An attribute, not an environment switch.  It bounds HAT alone: in
     # FreqFusionHIP.forward the DAT and NAFNet outputs and the fusion.pre tensors of EVERY image of the batch live until the join, so
-    # that part of the memory grows linearly with B (model._experts_batched).  forward() also keeps a chunk below the 2^31 input
+    # that part of the memory grows linearly with B (model._run_experts).  forward() also keeps a chunk below the 2^31 input
     # elements up to which ops.conv2d takes the LDS-resident 3x3 kernel, so raising this value cannot move a batch to another route.
     max_batch_tokens = 262144
+    name = "hat"
 
     def __init__(self, sd: SD, dev, prefix: str = "expert_ensemble.hat.", groups: int = 12, depth: int = 6, ws: int = 16,
                  heads: int = 6, conv_scale: float = 0.01):
         w = _Weights(sd, dev, prefix)
         self.dev, self.ws, self.heads, self.groups, self.depth, self.conv_scale = dev, ws, heads, groups, depth, conv_scale
         self.ows = ws + ws // 2
-        self.neg_mean = torch.tensor([-m for m in RGB_MEAN], device=dev)
+        self._load_trunk(w, dev)
         rpi_sa = _rel_index_sa(ws).reshape(-1).to(dev)
         rpi_oca = _rel_index_oca(ws, self.ows).reshape(-1).to(dev)
         n, nk = ws * ws, self.ows * self.ows
@@ -109,7 +146,6 @@ class HatHIP:
         def lin(name):
             return w(name + ".weight"), w(name + ".bias")
 
-        self.conv_first = (w.conv("conv_first"), w("conv_first.bias"))
         self.pe_norm = (w("patch_embed.norm.weight"), w("patch_embed.norm.bias"))
         self.blocks: List[List[dict]] = []
         self.ocab: List[dict] = []
@@ -136,12 +172,6 @@ class HatHIP:
                 bias=tbl[rpi_oca].reshape(n, nk, heads).permute(2, 1, 0).contiguous(), rel=pack_rel_overlap(tbl, ws, self.ows),
                 n2=(w(q + "norm2.weight"), w(q + "norm2.bias")), fc1=lin(q + "mlp.fc1"), fc2=lin(q + "mlp.fc2")))
             self.gconv.append((w.conv(f"layers.{g}.conv"), w(f"layers.{g}.conv.bias")))
-        self.norm = (w("norm.weight"), w("norm.bias"))
-        self.after = (w.conv("conv_after_body"), w("conv_after_body.bias"))
-        self.before_up = (w.conv("conv_before_upsample.0"), w("conv_before_upsample.0.bias"))
-        self.up0 = (w.conv("upsample.0"), w("upsample.0.bias"))
-        self.up2 = (w.conv("upsample.2"), w("upsample.2.bias"))
-        self.last = (w.conv("conv_last"), (w("conv_last.bias") - self.neg_mean).contiguous())   # "+ mean" folded into the bias
 
     # -- blocks -------------------------------------------------------------------------------
     def _mlp(self, x: T, blk: dict) -> T:
@@ -160,9 +190,8 @@ class HatHIP:
         att = ops.empty_rows_bf16(tuple(x.shape), x.device) if b16 else ops.empty_like_rows(x)
         s = blk["shift"]
         if fused:                                                  # norm1 + qkv + (S)W-MSA of all six heads in one launch (csrc/win_attn_fused.hip)
-            if "relp" not in blk:
-                blk["relp"] = pack_win_rel(blk["rel"], self.ws, self.ws)
-            _, xn = ops.win_attn_fused(x, att, _wf(blk, self.heads, d), blk["relp"], gamma=blk["n1"][0], beta=blk["n1"][1], H=H, W=W,
+            relp = _packed(blk, "relp", lambda: pack_win_rel(blk["rel"], self.ws, self.ws))
+            _, xn = ops.win_attn_fused(x, att, _wf(blk, self.heads, d), relp, gamma=blk["n1"][0], beta=blk["n1"][1], H=H, W=W,
                                        Hp=H, Wp=W, win=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, want_xn="bf16" if b16 else True)
         else:
             xn = ops.layernorm(x, *blk["n1"])
@@ -213,15 +242,8 @@ class HatHIP:
         y = self.ocab_block(y, self.ocab[g])
         return ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x, per_image=True)
 
-    def _tail(self, x: T) -> T:
-        x = ops.conv2d(x, *self.before_up, ksize=(3, 3), pad=(1, 1), act="lrelu", per_image=True)
-        x = ops.conv2d(x, *self.up0, ksize=(3, 3), pad=(1, 1), shuffle=2, per_image=True)
-        x = ops.conv2d(x, *self.up2, ksize=(3, 3), pad=(1, 1), shuffle=2, per_image=True)
-        return ops.conv2d(x, *self.last, ksize=(3, 3), pad=(1, 1), per_image=True)
-
     def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
-        """lr [B,3,h,w] -> [B,3,4h,4w] (written into `out` when given).  feats (optional dict): receives feats["hat"] = the conv_after_body output [B,Hp,Wp,180]
-        (NHWC), the tensor the reference's forward hook captures for the cached-expert files (expert_loader.py:838).
+        """lr [B,3,h,w] -> [B,3,4h,4w] (written into `out` when given).  feats (optional dict): receives feats["hat"] (_Trunk._exit).
         B > 1: one launch per op for the whole batch in the fused modes (chunks of max_batch_tokens padded tokens), the per-image
         loop in f32 mode; either way bit-equal to B single forwards.  taps are recorded for B == 1 only."""
         B, _, h, w = lr.shape
@@ -251,8 +273,7 @@ class HatHIP:
         """One launch per op for all of lr [B,3,h,w]; feat_out: where the hooked feature goes (a slice of the batch's buffer)."""
         _, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, self.ws), _ceil_to(w, self.ws)
-        xin = ops.nchw_to_nhwc(lr, Hp, Wp, add=self.neg_mean, pad_mode="reflect")
-        feat = ops.conv2d(xin, *self.conv_first, ksize=(3, 3), pad=(1, 1), per_image=True)
+        feat = self._enter(lr, Hp, Wp)
         x = ops.layernorm(feat, *self.pe_norm)
         for g in range(self.groups):
             if taps is not None and g == 0:
@@ -266,14 +287,7 @@ class HatHIP:
                 taps["hat.g0.out"] = x
             else:
                 x = self.group(x, g)
-        x = ops.layernorm(x, *self.norm)
-        if feats is not None:
-            feats["hat"] = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), per_image=True, out=feat_out)
-            x = ops.mix2(feats["hat"], feat)
-        else:
-            x = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), res=feat, per_image=True)
-        sr = self._tail(x)
-        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True, out=out)
+        return self._exit(x, feat, h, w, feats, out, feat_out)
 
 
 # =============================================================================================== DAT
@@ -298,14 +312,16 @@ def dat_should_shift(g: int, b: int) -> bool:
     return (g % 2 == 0 and b > 0 and (b - 2) % 4 == 0) or (g % 2 != 0 and b % 4 == 0)
 
 
-class DatHIP:
+class DatHIP(_Trunk):
     """DAT (dat_arch.py:864-1028): 6 residual groups x 6 DATB (spatial / channel alternating), dim 180."""
+
+    name = "dat"
 
     def __init__(self, sd: SD, dev, prefix: str = "expert_ensemble.dat.", groups: int = 6, depth: int = 6, split=(8, 32),
                  heads: int = 6):
         w = _Weights(sd, dev, prefix)
         self.dev, self.groups, self.depth, self.split, self.heads = dev, groups, depth, split, heads
-        self.neg_mean = torch.tensor([-m for m in RGB_MEAN], device=dev)
+        self._load_trunk(w, dev)
         C = 180
 
         def lin(name):
@@ -316,7 +332,6 @@ class DatHIP:
             sc, sh = bn_scale_shift({k: v.to(dev) for k, v in sd.items() if k.startswith(prefix + bn)}, prefix + bn)
             return fold_bn_after_conv(wt, w(conv + ".bias"), sc, sh)
 
-        self.conv_first = (w.conv("conv_first"), w("conv_first.bias"))
         self.before = (w("before_RG.1.weight"), w("before_RG.1.bias"))
         self.blocks: List[List[dict]] = []
         self.gconv = []
@@ -348,12 +363,6 @@ class DatHIP:
                 blks.append(blk)
             self.blocks.append(blks)
             self.gconv.append((w.conv(f"layers.{g}.conv"), w(f"layers.{g}.conv.bias")))
-        self.norm = (w("norm.weight"), w("norm.bias"))
-        self.after = (w.conv("conv_after_body"), w("conv_after_body.bias"))
-        self.before_up = (w.conv("conv_before_upsample.0"), w("conv_before_upsample.0.bias"))
-        self.up0 = (w.conv("upsample.0"), w("upsample.0.bias"))
-        self.up2 = (w.conv("upsample.2"), w("upsample.2.bias"))
-        self.last = (w.conv("conv_last"), (w("conv_last.bias") - self.neg_mean).contiguous())
 
     def block(self, x: T, blk: dict) -> T:
         _, H, W, C = x.shape
@@ -369,24 +378,22 @@ class DatHIP:
             att = ops.empty_like_rows(x)
             v = ops.empty_like_rows(x)
             pk = _wf(blk, self.heads, d)
-            if "relp" not in blk:
-                blk["relp"] = []
-                for br in range(2):
-                    wh, ww = (self.split[0], self.split[1]) if br == 0 else (self.split[1], self.split[0])
-                    r6 = torch.zeros(self.heads, blk["rel"][br].shape[1], device=x.device)
-                    r6[hh * br:hh * br + hh] = blk["rel"][br]
-                    blk["relp"].append(pack_win_rel(r6, wh, ww))
+
+            def rel6(br, wh, ww):                                  # the branch's bias table in its three rows of six, the others zero
+                r6 = torch.zeros(self.heads, blk["rel"][br].shape[1], device=x.device)
+                r6[hh * br:hh * br + hh] = blk["rel"][br]
+                return pack_win_rel(r6, wh, ww)
+            relp = _packed(blk, "relp", lambda: [rel6(0, *self.split), rel6(1, *self.split[::-1])])
             for br in range(2):
                 wh, ww = (self.split[0], self.split[1]) if br == 0 else (self.split[1], self.split[0])
                 sh = (wh // 2, ww // 2) if blk["shifted"] else (0, 0)
-                ops.win_attn_fused(x, att, pk, blk["relp"][br], gamma=blk["n1"][0], beta=blk["n1"][1], H=H, W=W, Hp=Hp, Wp=Wp,
+                ops.win_attn_fused(x, att, pk, relp[br], gamma=blk["n1"][0], beta=blk["n1"][1], H=H, W=W, Hp=Hp, Wp=Wp,
                                    win=(wh, ww), shift=sh, use_mask=blk["shifted"], head0=hh * br, nheads=hh, zero_pad=True,
                                    v_out=v, v_off=0)
         elif fused:
             # norm1 + qkv + per-head gram / norms over all tokens in one launch: only v reaches memory (dat_arch.py:617-641)
-            if "cq_pk" not in blk:
-                blk["cq_pk"] = pack_chan_qkv(blk["qkv"][0], blk["qkv"][1], self.heads, C // self.heads)
-            v, wbd = ops.chan_qkv_attn(x, blk["cq_pk"], blk["n1"][0], blk["n1"][1], blk["temp"])
+            cq = _packed(blk, "cq_pk", lambda: pack_chan_qkv(*blk["qkv"], self.heads, C // self.heads))
+            v, wbd = ops.chan_qkv_attn(x, cq, blk["n1"][0], blk["n1"][1], blk["temp"])
         else:
             qkv = ops.linear(ops.layernorm(x, *blk["n1"]), *blk["qkv"])              # [1,H,W,3C] = q | k | v
             v = qkv[..., 2 * C:]
@@ -409,9 +416,8 @@ class DatHIP:
         cm = ops.vec_mlp(ops.pool_partials(ch_in), *blk["ci1"], "gelu", *blk["ci4"], "sigmoid")          # [1,C]; pool finish inside the MLP launch
         if fused:
             # spatial gate (from sp_in, applied to ch_in) + channel gate (applied to sp_in) + projection + residual in one launch
-            if "gp_pk" not in blk:
-                blk["gp_pk"] = pack_token_linear_gated(blk["proj"][0], blk["proj"][1], blk["si0"][0], blk["si0"][1], blk["si3"][0])
-            x = ops.token_linear_gated(sp_in, ch_in, blk["gp_pk"], cm.reshape(-1), blk["si3b"], res=x)
+            gp = _packed(blk, "gp_pk", lambda: pack_token_linear_gated(*blk["proj"], *blk["si0"], blk["si3"][0]))
+            x = ops.token_linear_gated(sp_in, ch_in, gp, cm.reshape(-1), blk["si3b"], res=x)
             return self._sgfn(x, blk)
         sm = ops.linear(ops.linear(sp_in, *blk["si0"], act="gelu"), *blk["si3"], act="sigmoid")          # [1,H,W,1]
         if blk["spatial"]:
@@ -442,8 +448,7 @@ class DatHIP:
     def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
         _, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, 16), _ceil_to(w, 16)
-        xin = ops.nchw_to_nhwc(lr, Hp, Wp, add=self.neg_mean, pad_mode="reflect")
-        feat = ops.conv2d(xin, *self.conv_first, ksize=(3, 3), pad=(1, 1))
+        feat = self._enter(lr, Hp, Wp)
         x = ops.layernorm(feat, *self.before)
         for g in range(self.groups):
             y = x
@@ -452,17 +457,7 @@ class DatHIP:
                 if taps is not None and g < 2:
                     taps[f"dat.g{g}.b{b}"] = y
             x = ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x)
-        x = ops.layernorm(x, *self.norm)
-        if feats is not None:                                  # expert_loader.py:850: hook on conv_after_body
-            feats["dat"] = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1))
-            x = ops.mix2(feats["dat"], feat)
-        else:
-            x = ops.conv2d(x, *self.after, ksize=(3, 3), pad=(1, 1), res=feat)
-        x = ops.conv2d(x, *self.before_up, ksize=(3, 3), pad=(1, 1), act="lrelu")
-        x = ops.conv2d(x, *self.up0, ksize=(3, 3), pad=(1, 1), shuffle=2)
-        x = ops.conv2d(x, *self.up2, ksize=(3, 3), pad=(1, 1), shuffle=2)
-        sr = ops.conv2d(x, *self.last, ksize=(3, 3), pad=(1, 1))
-        return ops.nhwc_to_nchw(sr, 4 * h, 4 * w, clamp01=True, out=out)
+        return self._exit(x, feat, h, w, feats, out)
 
 
 # =============================================================================================== NAFNet-SR
@@ -523,9 +518,8 @@ class NafnetHIP:
             g, pooled = ops.dwconv3_gate_pool(t, *k["c2"])                   # conv2 + SimpleGate + SCA pool sums
         sca = ops.vec_mlp(pooled, *k["sca"], None)                           # [1,c]
         if flash and ops.gemm_mode() == "bf16":                              # plain bf16: conv3 + the gated FFN in one launch, y stays on chip
-            if "tail_pk" not in k:
-                k["tail_pk"] = pack_naf_tail(*k["c3"], *k["c4"], *k["c5"])
-            return ops.naf_tail(g, x, k["tail_pk"], sca.reshape(-1), k["beta"], k["n2"][0], k["n2"][1], k["gamma"])
+            tail = _packed(k, "tail_pk", lambda: pack_naf_tail(*k["c3"], *k["c4"], *k["c5"]))
+            return ops.naf_tail(g, x, tail, sca.reshape(-1), k["beta"], k["n2"][0], k["n2"][1], k["gamma"])
         nf = ops.gemm_mode() != "f32"                                        # the split-bf16 GEMM carries both NAFBlock fusions
         if nf:                                                               # conv3(g * sca): the scale rides on the A operand
             y = ops.linear(g, *k["c3"], res=x, mul=k["beta"], kmul=sca.reshape(-1), rows_gemm=rows)
@@ -533,15 +527,13 @@ class NafnetHIP:
             w3 = ops.mix2(k["c3"][0], ca=sca.reshape(-1))                    # conv3(g * sca) == (W3 . diag(sca)) g
             y = ops.linear(g, w3, k["c3"][1], res=x, mul=k["beta"], dynamic_w=True)
         if flash:
-            if "ffn_pk" not in k:
-                k["ffn_pk"] = pack_naf_ffn(k["c4"][0], k["c4"][1], k["c5"][0], k["c5"][1])
-            return ops.naf_ffn(y, k["ffn_pk"], k["n2"][0], k["n2"][1], k["gamma"])
+            ffn = _packed(k, "ffn_pk", lambda: pack_naf_ffn(*k["c4"], *k["c5"]))
+            return ops.naf_ffn(y, ffn, k["n2"][0], k["n2"][1], k["gamma"])
         if nf:                                                               # conv4 + SimpleGate in one launch: the 2c-wide tensor stays on chip
-            if "c4i" not in k:                                               # rows interleaved: 2j <- j, 2j+1 <- j + c (chunk(2, dim=1) halves)
-                w4, b4 = k["c4"]
-                k["c4i"] = (torch.stack((w4[:c], w4[c:]), dim=1).reshape(2 * c, -1).contiguous(),
-                            torch.stack((b4[:c], b4[c:]), dim=1).reshape(-1).contiguous())
-            g = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6, out_bf16=rows), *k["c4i"], gate_pairs=True, out_bf16=rows)
+            w4, b4 = k["c4"]                                                 # rows interleaved: 2j <- j, 2j+1 <- j + c (chunk(2, dim=1) halves)
+            c4i = _packed(k, "c4i", lambda: (torch.stack((w4[:c], w4[c:]), dim=1).reshape(2 * c, -1).contiguous(),
+                                             torch.stack((b4[:c], b4[c:]), dim=1).reshape(-1).contiguous()))
+            g = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6, out_bf16=rows), *c4i, gate_pairs=True, out_bf16=rows)
         else:
             t = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6), *k["c4"])
             g = ops.fma3(None, t[..., :c], t[..., c:])

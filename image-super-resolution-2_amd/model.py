@@ -11,6 +11,7 @@ constructor raises.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional
 
@@ -24,11 +25,25 @@ from .fusion import FusionHIP
 T = torch.Tensor
 
 
-def _image(lr: T, b: int) -> T:
-    """lr[b:b+1] of a contiguous batch, copied when the slice does not start on a 16-byte boundary (odd image sizes): the kernels take
-    16-byte aligned images.  The copy is a torch op, which a recorded plan (plan.py) cannot carry: forward() refuses to record such a batch."""
-    t = lr[b:b + 1]
-    return t.clone() if t.data_ptr() % 16 else t
+def _per_image(lr: T, fn) -> list:
+    """[fn(b, lr[b:b+1]) for every image b of a contiguous batch]: the one place where what is not batched yet (DAT, NAFNet, the
+    fusion stack) is sequenced image by image; B == 1 is a batch of one.  An image that does not start on a 16-byte boundary (odd
+    image sizes) is copied, since the kernels take 16-byte aligned images.  The copy is a torch op, which a recorded plan (plan.py)
+    cannot carry: forward() refuses to record such a batch."""
+    res = []
+    for b in range(lr.shape[0]):
+        t = lr[b:b + 1]
+        res.append(fn(b, t.clone() if t.data_ptr() % 16 else t))
+    return res
+
+
+def _features_at_lr(raws: list, B: int, h: int, w: int) -> T:
+    """Hooked NHWC features (one tensor for the batch, or one per image) -> [B,C,h,w] bilinearly resized to the LR resolution."""
+    f = torch.empty((B, raws[0].shape[-1], h, w), device=raws[0].device, dtype=torch.float32)
+    n = B // len(raws)
+    for i, v in enumerate(raws):
+        ops.nhwc_to_nchw(ops.resize(v, (h, w)), out=f[i * n:(i + 1) * n])
+    return f
 
 
 class FreqFusionHIP:
@@ -50,136 +65,93 @@ class FreqFusionHIP:
             self.nafnet = NafnetHIP(state_dict, dev)
             self.fusion = FusionHIP(state_dict, dev)
 
-    def experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = False):
-        """ExpertEnsemble.forward_all (expert_loader.py:768-777).  The three experts are independent until the fusion
-        stack, so each runs on its own HIP stream (fork/join on the caller's stream; the whole fan-out is captured
-        into the HIP graph): latency-bound kernels of one expert overlap with bandwidth-bound kernels of another.
-        with_pre: also run the LR-only part of the fusion stack (FusionHIP.pre) behind the shortest expert's stream."""
-        if not self.multi_stream or taps is not None:
-            ex = {"hat": self.hat.forward(lr, taps), "dat": self.dat.forward(lr, taps), "nafnet": self.nafnet.forward(lr, taps)}
-            return (ex, None) if with_pre else ex
+    @contextlib.contextmanager
+    def _fork(self, mark: bool):
+        """The three-stream section: the two side streams (made on first use) wait for the caller's stream on entry and the caller's
+        stream waits for them on exit.  Yields (side 1, side 2, made); the body appends to `made` every tensor it produces on a side
+        stream, and each is handed to the caller's stream (record_stream) after the join.  mark: tell a plan recording where the
+        section starts and ends (self._marker)."""
         main = torch.cuda.current_stream()
         if self._side is None:
             self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
         s1, s2 = self._side
         s1.wait_stream(main)
         s2.wait_stream(main)
-        if self._marker:
+        if mark and self._marker:
             self._marker("fork")
-        pre = None
-        with torch.cuda.stream(s1):
-            dat = self.dat.forward(lr)
-        with torch.cuda.stream(s2):
-            naf = self.nafnet.forward(lr)
-            if with_pre:
-                pre = self.fusion.pre(lr)
-        hat = self.hat.forward(lr)
+        made = []
+        yield s1, s2, made
         main.wait_stream(s1)
         main.wait_stream(s2)
-        if self._marker:
+        if mark and self._marker:
             self._marker("join")
-        dat.record_stream(main)
-        naf.record_stream(main)
-        if pre is not None:
-            for t in pre.values():
-                t.record_stream(main)
+        for t in made:
+            t.record_stream(main)
+
+    def _run_experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = True):
+        """ExpertEnsemble.forward_all (expert_loader.py:768-777) for a batch lr [B,3,h,w]: (hat [B,3,4h,4w], [dat_b], [nafnet_b],
+        [pre_b or None]).  The three experts are independent until the fusion stack, so each runs on its own HIP stream (_fork; the
+        whole fan-out is captured into the HIP graph): latency-bound kernels of one expert overlap with bandwidth-bound kernels of
+        another.  HAT takes the whole batch on the caller's stream, DAT runs for b = 0 .. B-1 on side stream 1, NAFNet and (with_pre)
+        the LR-only part of the fusion stack (FusionHIP.pre) for each b on side stream 2, the shortest expert's.  On one stream, and
+        with taps, the experts run one after the other and pre is left to fusion.forward."""
+        if not self.multi_stream or taps is not None:
+            hat = self.hat.forward(lr, taps)
+            dats = _per_image(lr, lambda b, x: self.dat.forward(x, taps))
+            return hat, dats, _per_image(lr, lambda b, x: self.nafnet.forward(x, taps)), [None] * lr.shape[0]
+        with self._fork(mark=True) as (s1, s2, made):
+            with torch.cuda.stream(s1):
+                dats = _per_image(lr, lambda b, x: self.dat.forward(x))
+            with torch.cuda.stream(s2):
+                naf_pre = _per_image(lr, lambda b, x: (self.nafnet.forward(x), self.fusion.pre(x) if with_pre else None))
+            hat = self.hat.forward(lr)
+            nafs, pres = [n for n, _ in naf_pre], [p for _, p in naf_pre]
+            made += (*dats, *nafs, *(t for pre in pres if pre is not None for t in pre.values()))
+        return hat, dats, nafs, pres
+
+    def experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = False):
+        """The experts of ONE image lr [1,3,h,w]: {hat, dat, nafnet: [1,3,4h,4w]}, or with with_pre ({...}, pre), pre being
+        FusionHIP.pre(lr) on three streams and None otherwise."""
+        hat, (dat,), (naf,), (pre,) = self._run_experts(lr, taps, with_pre)
         ex = {"hat": hat, "dat": dat, "nafnet": naf}
         return (ex, pre) if with_pre else ex
-
-    def _experts_batched(self, lr: T):
-        """The experts of a batch lr [B,3,h,w]: (hat [B,3,4h,4w], [dat_b], [nafnet_b], [pre_b or None]).  One fork / join pair as in
-        experts(): HAT for the whole batch on the caller's stream, DAT for b = 0 .. B-1 on side stream 1, NAFNet and fusion.pre for
-        each b on side stream 2."""
-        B = lr.shape[0]
-        if not self.multi_stream:
-            return (self.hat.forward(lr), [self.dat.forward(_image(lr, b)) for b in range(B)],
-                    [self.nafnet.forward(_image(lr, b)) for b in range(B)], [None] * B)
-        main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
-        s1, s2 = self._side
-        s1.wait_stream(main)
-        s2.wait_stream(main)
-        if self._marker:
-            self._marker("fork")
-        with torch.cuda.stream(s1):
-            dats = [self.dat.forward(_image(lr, b)) for b in range(B)]
-        nafs, pres = [], []
-        with torch.cuda.stream(s2):
-            for b in range(B):
-                nafs.append(self.nafnet.forward(_image(lr, b)))
-                pres.append(self.fusion.pre(_image(lr, b)))
-        hat = self.hat.forward(lr)
-        main.wait_stream(s1)
-        main.wait_stream(s2)
-        if self._marker:
-            self._marker("join")
-        for t in (*dats, *nafs, *(t for pre in pres for t in pre.values())):
-            t.record_stream(main)
-        return hat, dats, nafs, pres
 
     @torch.no_grad()
     def experts_with_features(self, lr: T, streams: bool = False):
         """ExpertEnsemble.forward_all_with_hooks (expert_loader.py:894-951): ({hat,dat,nafnet} SR outputs [B,3,4h,4w],
         {hat [B,180,h,w], dat [B,180,h,w], nafnet [B,64,h,w]} hook features bilinearly resized to the LR resolution, NCHW).
         The payload of the cached-expert files (isr2_amd/cache.py).  streams=True runs the same launches with DAT and NAFNet (and
-        their feature resizes) on the two side streams of experts(), forked from and joined to the caller's stream: the same bits,
+        their feature resizes) on the two side streams of forward(), forked from and joined to the caller's stream: the same bits,
         the small grids of one expert beside those of another (cache.build_from_folders).
-        B > 1: HAT runs the batch through one launch per op; DAT and NAFNet run image by image into slices of their outputs.  Every
+        HAT runs the batch through one launch per op; DAT and NAFNet run image by image into slices of their outputs.  Every
         image's tensors are those of its own B == 1 call, bit for bit."""
         if lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3:
             raise _lib.FFError(f"expected lr of shape [B,3,h,w], got {tuple(lr.shape)}")
         lr = lr.to(self.dev, torch.float32).contiguous()
         B, _, h, w = lr.shape
-        from . import ops
+        nets = {"hat": self.hat, "dat": self.dat, "nafnet": self.nafnet}
 
-        def feat_lr(v, out=None):                              # hooked NHWC feature -> [.,C,h,w] at the LR resolution
-            return ops.nhwc_to_nchw(ops.resize(v, (h, w)), out=out)
-
-        def fwd(net, name):                                    # -> (SR output [B,3,4h,4w], [hooked NHWC features])
+        def fwd(name):                                         # -> (SR output [B,3,4h,4w], [hooked NHWC features])
             raw = {}
-            if B == 1 or net is self.hat:
-                return net.forward(lr, feats=raw), [raw[name]]
+            if name == "hat":
+                return self.hat.forward(lr, feats=raw), [raw[name]]
             o = torch.empty((B, 3, 4 * h, 4 * w), device=self.dev, dtype=torch.float32)
-            raws = []
-            for b in range(B):                                 # per image, into slices of the output
-                net.forward(_image(lr, b), feats=raw, out=o[b:b + 1])
-                raws.append(raw[name])
-            return o, raws
-
-        def finish(raws):
-            if len(raws) == 1:
-                return feat_lr(raws[0])
-            f = torch.empty((B, raws[0].shape[-1], h, w), device=self.dev, dtype=torch.float32)
-            for b, v in enumerate(raws):
-                feat_lr(v, out=f[b:b + 1])
-            return f
-
-        def one(net, name):
-            o, raws = fwd(net, name)
-            return o, finish(raws)
+            return o, _per_image(lr, lambda b, x: (nets[name].forward(x, feats=raw, out=o[b:b + 1]), raw[name])[1])
 
         with torch.cuda.device(self.dev):
             if streams:
-                main = torch.cuda.current_stream()
-                if self._side is None:
-                    self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
-                s1, s2 = self._side
-                s1.wait_stream(main)
-                s2.wait_stream(main)
-                with torch.cuda.stream(s1):
-                    o_dat, f_dat = one(self.dat, "dat")
-                with torch.cuda.stream(s2):
-                    o_naf, f_naf = one(self.nafnet, "nafnet")
-                o_hat, f_hat = one(self.hat, "hat")
-                main.wait_stream(s1)
-                main.wait_stream(s2)
-                for t in (o_dat, o_naf, f_dat, f_naf):
-                    t.record_stream(main)
+                outs, feats = {}, {}
+                with self._fork(mark=False) as (s1, s2, made):
+                    for name, s in (("dat", s1), ("nafnet", s2), ("hat", torch.cuda.current_stream())):
+                        with torch.cuda.stream(s):
+                            outs[name], raws = fwd(name)
+                            feats[name] = _features_at_lr(raws, B, h, w)
+                    made += (outs["dat"], outs["nafnet"], feats["dat"], feats["nafnet"])
             else:
-                (o_hat, r_hat), (o_dat, r_dat), (o_naf, r_naf) = fwd(self.hat, "hat"), fwd(self.dat, "dat"), fwd(self.nafnet, "nafnet")
-                f_hat, f_dat, f_naf = finish(r_hat), finish(r_dat), finish(r_naf)
-        return {"hat": o_hat, "dat": o_dat, "nafnet": o_naf}, {"hat": f_hat, "dat": f_dat, "nafnet": f_naf}
+                done = {name: fwd(name) for name in nets}          # the three forwards, then the three feature resizes
+                outs = {name: o for name, (o, _) in done.items()}
+                feats = {name: _features_at_lr(raws, B, h, w) for name, (_, raws) in done.items()}
+        return {k: outs[k] for k in nets}, {k: feats[k] for k in nets}
 
     @torch.no_grad()
     def forward_with_precomputed(self, lr: T, expert_outputs, expert_features=None, taps: Optional[dict] = None) -> T:
@@ -209,29 +181,25 @@ class FreqFusionHIP:
         if lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3:
             raise _lib.FFError(f"expected lr of shape [B,3,h,w], got {tuple(lr.shape)}")
         lr = lr.to(self.dev, torch.float32).contiguous()
-        if lr.shape[0] > 1:
-            # Every global op of the path is per image (average pools, channel attention statistics, rFFT2, squeeze gates), so a
-            # batch is B independent images.  HAT takes the whole batch through one launch per op (HatHIP.forward: its only per-image
-            # quantity, the channel-attention gate, is a [B,180] matrix); DAT, NAFNet and the fusion stack are still sequenced per
-            # image.  Bit-identical to B single forwards: every image runs the launches, in the forms, of its own B == 1 forward.
-            if taps is not None:
-                raise _lib.FFError("taps are recorded for B == 1 only")
-            if self._marker is not None and (3 * lr.shape[2] * lr.shape[3]) % 4:
-                # plan recording: an image that does not start on a 16-byte boundary is copied by torch (_image), outside the tape
-                raise _lib.FFError(f"a plan of a batch needs images of a multiple of 16 bytes (3 * h * w % 4 == 0), got {tuple(lr.shape)}")
-            if out is None:
-                out = torch.empty((lr.shape[0], 3, 4 * lr.shape[2], 4 * lr.shape[3]), device=self.dev, dtype=torch.float32)
-            with torch.cuda.device(self.dev):
-                hat, dats, nafs, pres = self._experts_batched(lr)
-                for b in range(lr.shape[0]):
-                    self.fusion.forward(_image(lr, b), {"hat": hat[b:b + 1], "dat": dats[b], "nafnet": nafs[b]}, None, pre=pres[b],
-                                        out=out[b:b + 1])
-            return out
+        B, _, h, w = lr.shape
+        # Every global op of the path is per image (average pools, channel attention statistics, rFFT2, squeeze gates), so a batch is
+        # B independent images.  HAT takes the whole batch through one launch per op (HatHIP.forward: its only per-image quantity, the
+        # channel-attention gate, is a [B,180] matrix); DAT, NAFNet and the fusion stack are still sequenced per image (_per_image).
+        # Bit-identical to B single forwards: every image runs the launches, in the forms, of its own B == 1 forward.
+        if B > 1 and taps is not None:
+            raise _lib.FFError("taps are recorded for B == 1 only")
+        if B > 1 and self._marker is not None and (3 * h * w) % 4:
+            # plan recording: an image that does not start on a 16-byte boundary is copied by torch (_per_image), outside the tape
+            raise _lib.FFError(f"a plan of a batch needs images of a multiple of 16 bytes (3 * h * w % 4 == 0), got {tuple(lr.shape)}")
+        if out is None:
+            out = torch.empty((B, 3, 4 * h, 4 * w), device=self.dev, dtype=torch.float32)
         with torch.cuda.device(self.dev):
-            ex, pre = self.experts(lr, taps, with_pre=True)
+            hat, dats, nafs, pres = self._run_experts(lr, taps)
             if taps is not None:
-                taps.update({f"expert.{k}": v for k, v in ex.items()})
-            return self.fusion.forward(lr, ex, taps, pre=pre, out=out)
+                taps.update({"expert.hat": hat, "expert.dat": dats[0], "expert.nafnet": nafs[0]})
+            _per_image(lr, lambda b, x: self.fusion.forward(x, {"hat": hat[b:b + 1], "dat": dats[b], "nafnet": nafs[b]}, taps,
+                                                            pre=pres[b], out=out[b:b + 1]))
+        return out
 
     __call__ = forward
 
@@ -255,9 +223,7 @@ class FreqFusionHIP:
                 torch.cuda.synchronize(self.dev)              # (a replay of the evicted graph may still be in flight on a lane)
                 old = next(iter(self._graphs))
                 self._graphs.pop(old)
-                from . import ops as _ops
-                _ops.drop_persistent(key=(id(self),) + old)   # the concat / padded-input buffers that graph's launches point at
-            from . import ops
+                ops.drop_persistent(key=(id(self),) + old)   # the concat / padded-input buffers that graph's launches point at
             ops.set_lane(lane)
             ops.set_capture_key((id(self),) + key)
             try:
