@@ -29,10 +29,14 @@ struct RowsGemmParams {
   void* out;          // GATE: bf16 [M][ldo] (N / 2 channels); else fp32 [M][ldo]
   int M, N, K;
   int lda, ldo, ldr;
+  int rpi;            // KMI form: rows per image; kmul is [M / rpi][K] and row m is scaled by kmul[m / rpi]
 };
 
-template <int BM, int BN, int WM, int WN, bool GATE, bool A32>
-__global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kernel(RowsGemmParams p) {
+// KMI (A32 only): kmul is looked up per STAGED ROW -- each of a thread's AS rows carries its own image's scale vector, so an m-tile may
+// hold rows of several images and the tiling (and every other line of the kernel) stays the single-image one.  A row's dot product does
+// not depend on which tile holds it, so the rows are bit-equal to the single-image launch on their image alone.
+template <int BM, int BN, int WM, int WN, bool GATE, bool A32, bool KMI>
+__device__ __forceinline__ void gemm_rows_bf16_body(const RowsGemmParams& p) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int MI = TM / 32, NI = TN / 32;
@@ -66,12 +70,15 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kernel(RowsGemmPa
   const float* fsrc[AS + 1];
   int fdst[AS + 1];
   f32x4 ra[AS + 1][2], km[2];
+  const float* ksrc[KMI ? AS + 1 : 1];
+  f32x4 kmi[KMI ? AS + 1 : 1][2];
 #pragma unroll
   for (int i = 0; i < AS; ++i) {
     const int row = (tid >> 3) + 8 * NW * i, q = tid & 7;
     const int m = m0 + row < p.M ? m0 + row : p.M - 1;
     fsrc[i] = reinterpret_cast<const float*>(p.a) + (long long)m * p.lda + 8 * q;
     fdst[i] = row * 128 + (q ^ ((row >> 1) & 7)) * 16;
+    if constexpr (KMI) ksrc[i] = p.kmul + (long long)(m / p.rpi) * p.K + 8 * q;      // (m is clamped into [0, M): a valid image)
   }
   auto load_a = [&](int c) {
 #pragma unroll
@@ -79,7 +86,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kernel(RowsGemmPa
       ra[i][0] = *reinterpret_cast<const f32x4*>(fsrc[i] + 64 * c);
       ra[i][1] = *reinterpret_cast<const f32x4*>(fsrc[i] + 64 * c + 4);
     }
-    if (p.kmul) {
+    if constexpr (KMI) {
+#pragma unroll
+      for (int i = 0; i < AS; ++i) {
+        kmi[i][0] = *reinterpret_cast<const f32x4*>(ksrc[i] + 64 * c);
+        kmi[i][1] = *reinterpret_cast<const f32x4*>(ksrc[i] + 64 * c + 4);
+      }
+    } else if (p.kmul) {
       km[0] = *reinterpret_cast<const f32x4*>(p.kmul + 64 * c + 8 * (tid & 7));
       km[1] = *reinterpret_cast<const f32x4*>(p.kmul + 64 * c + 8 * (tid & 7) + 4);
     }
@@ -88,7 +101,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kernel(RowsGemmPa
 #pragma unroll
     for (int i = 0; i < AS; ++i) {
       f32x4 u = ra[i][0], v = ra[i][1];
-      if (p.kmul) { u *= km[0]; v *= km[1]; }
+      if constexpr (KMI) { u *= kmi[i][0]; v *= kmi[i][1]; }
+      else if (p.kmul) { u *= km[0]; v *= km[1]; }
       const bf16x8 h = {(__bf16)u[0], (__bf16)u[1], (__bf16)u[2], (__bf16)u[3], (__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
       *reinterpret_cast<bf16x8*>(smem + buf * BUFB + fdst[i]) = h;
     }
@@ -222,6 +236,25 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kernel(RowsGemmPa
   }
 }
 
+template <int BM, int BN, int WM, int WN, bool GATE, bool A32>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kernel(RowsGemmParams p) {
+  gemm_rows_bf16_body<BM, BN, WM, WN, GATE, A32, false>(p);
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kmimg_kernel(RowsGemmParams p) {
+  gemm_rows_bf16_body<BM, BN, WM, WN, false, true, true>(p);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int launch_rows_kmimg(const RowsGemmParams& p, hipStream_t st) {
+  constexpr size_t lds = (size_t)2 * (BM + BN) * 128;
+  dim3 grid((unsigned)(ff_cdiv(p.M, BM) * ff_cdiv(p.N, BN))), block(WM * WN * 64);
+  hipLaunchKernelGGL((gemm_rows_bf16_kmimg_kernel<BM, BN, WM, WN>), grid, block, lds, st, p);
+  FF_LAUNCH_CHECK("ff_gemm_rows_bf16_kmul_images");
+  return FF_OK;
+}
+
 template <int BM, int BN, int WM, int WN>
 static int launch_rows(const RowsGemmParams& p, bool gate, bool a32, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * (BM + BN) * 128;
@@ -235,6 +268,12 @@ static int launch_rows(const RowsGemmParams& p, bool gate, bool a32, hipStream_t
     hipLaunchKernelGGL((gemm_rows_bf16_kernel<BM, BN, WM, WN, false, false>), grid, block, lds, st, p);
   FF_LAUNCH_CHECK("ff_gemm_rows_bf16");
   return FF_OK;
+}
+
+// The tile configuration ff_gemm_rows_bf16 picks for tile_hint <= 0 (the table in ff_gemm_rows_bf16).  Exported so that a caller that batches
+// independent images can pass the configuration ONE image's row count would get as its tile_hint.
+extern "C" int ff_gemm_rows_bf16_tile(long long M, int N) {
+  return (long long)ff_cdiv(M, 128) * ff_cdiv(N, 128) <= 256 ? 2 : 1;
 }
 
 extern "C" int ff_gemm_rows_bf16(const void* a, int a_fp32, int lda, const void* w_hi, int Kp, const float* kmul, const float* bias,
@@ -259,7 +298,7 @@ extern "C" int ff_gemm_rows_bf16(const void* a, int a_fp32, int lda, const void*
   }
   RowsGemmParams p;
   p.a = a; p.kmul = kmul; p.w = (const __bf16*)w_hi; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
-  p.M = (int)M; p.N = N; p.K = K; p.lda = lda; p.ldo = ldo; p.ldr = ldr;
+  p.M = (int)M; p.N = N; p.K = K; p.lda = lda; p.ldo = ldo; p.ldr = ldr; p.rpi = 0;
   hipStream_t st = (hipStream_t)stream;
   int cfg = tile_hint;
   // Measured on MI355X, one process, variants alternating, median us per launch (profiles/nafnet_rows_gemm.json; old = ff_conv2d_bf16s
@@ -279,10 +318,38 @@ extern "C" int ff_gemm_rows_bf16(const void* a, int a_fp32, int lda, const void*
   //   65536 x 256 ->  512 gate             48.3    26.0    30.1
   //   65536 x 256 ->  256 residual         37.8    27.0    29.2
   // Every shape is faster than the old route by more than the spread of its repeats, so none stays behind.
-  if (cfg <= 0) cfg = ff_cdiv(M, 128) * ff_cdiv(N, 128) <= 256 ? 2 : 1;
+  if (cfg <= 0) cfg = ff_gemm_rows_bf16_tile(M, N);
   switch (cfg) {
     case 1: return launch_rows<128, 128, 2, 4>(p, gate != 0, a_fp32 != 0, st);      // 64 x 32 per wave
     case 2: return launch_rows<128, 64, 4, 2>(p, gate != 0, a_fp32 != 0, st);       // 32 x 32 per wave
     default: ff_set_error("ff_gemm_rows_bf16: bad tile_hint %d", cfg); return FF_ERR_ARG;
+  }
+}
+
+// conv3 of B independent images in one launch: a is fp32 [M][lda], M == B * rows_per_image, and kmul is [B][K] -- row m is scaled by
+// kmul[m / rows_per_image] before the bf16 rounding.  The fp32-rows epilogue (bias, * mul, + res).  Every row is bit-equal to
+// ff_gemm_rows_bf16(a_fp32 = 1, kmul = kmul[b]) on its image alone; tile_hint <= 0 takes the configuration of ONE image's rows.
+extern "C" int ff_gemm_rows_bf16_kmul_images(const float* a, int lda, const void* w_hi, int Kp, const float* kmul, int B, int rows_per_image,
+                                             const float* bias, const float* mul, const float* res, int ldr, float* out, int ldo,
+                                             long long M, int N, int K, int tile_hint, void* stream) {
+  FF_CHECK_ARG(a && w_hi && kmul && out, "ff_gemm_rows_bf16_kmul_images: null pointer");
+  FF_CHECK_ARG(B >= 1 && rows_per_image >= 1 && M == (long long)B * rows_per_image && M < (1LL << 31),
+               "ff_gemm_rows_bf16_kmul_images: M must be B * rows_per_image and below 2^31 (got M=%lld B=%d rows_per_image=%d)", M, B, rows_per_image);
+  FF_CHECK_ARG(N > 0 && K > 0 && K % 64 == 0 && Kp == K, "ff_gemm_rows_bf16_kmul_images: needs K %% 64 == 0 and an unpadded weight plane (Kp == K), got K=%d Kp=%d", K, Kp);
+  FF_CHECK_ARG(lda >= K && lda % 4 == 0 && (((uintptr_t)a) & 15) == 0 && (((uintptr_t)w_hi) & 15) == 0 && (((uintptr_t)kmul) & 15) == 0,
+               "ff_gemm_rows_bf16_kmul_images: A rows, the weight plane and kmul must be 16-byte aligned (lda %% 4 == 0, lda >= K)");
+  FF_CHECK_ARG(N % 4 == 0 && ldo >= N && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0,
+               "ff_gemm_rows_bf16_kmul_images: needs N %% 4 == 0 and 16-byte aligned output rows");
+  FF_CHECK_ARG(!res || (ldr >= N && ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0), "ff_gemm_rows_bf16_kmul_images: residual rows must be 16-byte aligned");
+  RowsGemmParams p;
+  p.a = a; p.kmul = kmul; p.w = (const __bf16*)w_hi; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
+  p.M = (int)M; p.N = N; p.K = K; p.lda = lda; p.ldo = ldo; p.ldr = ldr; p.rpi = rows_per_image;
+  hipStream_t st = (hipStream_t)stream;
+  int cfg = tile_hint;
+  if (cfg <= 0) cfg = ff_gemm_rows_bf16_tile(rows_per_image, N);
+  switch (cfg) {
+    case 1: return launch_rows_kmimg<128, 128, 2, 4>(p, st);
+    case 2: return launch_rows_kmimg<128, 64, 4, 2>(p, st);
+    default: ff_set_error("ff_gemm_rows_bf16_kmul_images: bad tile_hint %d", cfg); return FF_ERR_ARG;
   }
 }

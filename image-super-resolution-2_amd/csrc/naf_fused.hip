@@ -12,93 +12,20 @@
 // A thread owns 4 channels (of each gate half) of a 4-row output strip at one column: a 6 x 3 input window and the 9 tap
 // weights per half live in registers, so an output costs 9 float4 input loads (18 with one pixel per thread) and the
 // weights are fetched once per strip.  The two halves are evaluated one after the other to reuse the window registers.
-__global__ __launch_bounds__(256) void dwconv3_gate_pool_kernel(const float* __restrict__ in, int ldi, float* __restrict__ out, int ldo,
-                                                                int H, int W, int C, const float* __restrict__ w, const float* __restrict__ bias,
-                                                                float* __restrict__ part) {
-  extern __shared__ float4 red[];                      // [ppb][C/4]
-  const int cv = C >> 2, ppb = 256 / cv;               // float4 channel groups, (column, strip) items per block iteration
-  const int cg = threadIdx.x % cv, ps = threadIdx.x / cv;
-  const int nstrip = (H + 3) >> 2;
-  const long long items = (long long)nstrip * W;
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc_sum = z4;
-  if (ps < ppb) {
-    const int c = 4 * cg;
-    for (long long it = (long long)blockIdx.x * ppb + ps; it < items; it += (long long)gridDim.x * ppb) {
-      const int x = (int)(it % W), y0 = (int)(it / W) * 4;
-      f32x4 ga[4];
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int ch = c + half * C;
-        f32x4 wt[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) wt[k] = *reinterpret_cast<const f32x4*>(w + k * 2 * C + ch);
-        const f32x4 bs = *reinterpret_cast<const f32x4*>(bias + ch);
-        f32x4 win[6][3];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          const int iy = y0 - 1 + r;
-          const bool oky = (unsigned)iy < (unsigned)H;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const int ix = x - 1 + k;
-            const bool ok = oky && (unsigned)ix < (unsigned)W;
-            const f32x4 u = *reinterpret_cast<const f32x4*>(in + (ok ? ((long long)iy * W + ix) * ldi + ch : 0));
-            win[r][k] = ok ? u : z4;
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          f32x4 a = bs;
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) a += win[r + ky][kx] * wt[ky * 3 + kx];
-          ga[r] = half == 0 ? a : ga[r] * a;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (y0 + r < H) {
-          *reinterpret_cast<f32x4*>(out + ((long long)(y0 + r) * W + x) * ldo + c) = ga[r];
-          acc_sum += ga[r];
-        }
-    }
-    red[ps * cv + cg] = (float4){acc_sum[0], acc_sum[1], acc_sum[2], acc_sum[3]};
-  }
-  __syncthreads();
-  if (ps == 0) {
-    float4 s = red[cg];
-    for (int r = 1; r < ppb; ++r) { const float4 t = red[r * cv + cg]; s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w; }
-    *reinterpret_cast<float4*>(part + (long long)blockIdx.x * C + 4 * cg) = s;
-  }
-}
-
-// sum of the per-workgroup partials: 16 channels x 16 partial-lanes per workgroup, 4 independent accumulators per thread
-__global__ __launch_bounds__(256) void pool_reduce_kernel(const float* __restrict__ part, int nch, int C, float invP, float* __restrict__ out) {
-  __shared__ float red[16][17];
-  const int cl = threadIdx.x & 15, r = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (c < C) {
-    int i = r;
-    for (; i + 48 < nch; i += 64) {
-      s0 += part[(long long)i * C + c];
-      s1 += part[(long long)(i + 16) * C + c];
-      s2 += part[(long long)(i + 32) * C + c];
-      s3 += part[(long long)(i + 48) * C + c];
-    }
-    for (; i < nch; i += 16) s0 += part[(long long)i * C + c];
-  }
-  red[r][cl] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (r == 0 && c < C) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) s += red[k][cl];
-    out[c] = s * invP;
-  }
-}
+#define NP_DW_KERNEL dwconv3_gate_pool_kernel
+#define NP_REDUCE_KERNEL pool_reduce_kernel
+#define NP_IMAGES 0
+#include "naf_pool_kernels.inc"
+#undef NP_DW_KERNEL
+#undef NP_REDUCE_KERNEL
+#undef NP_IMAGES
+#define NP_DW_KERNEL dwconv3_gate_pool_images_kernel
+#define NP_REDUCE_KERNEL pool_reduce_images_kernel
+#define NP_IMAGES 1
+#include "naf_pool_kernels.inc"
+#undef NP_DW_KERNEL
+#undef NP_REDUCE_KERNEL
+#undef NP_IMAGES
 
 extern "C" long long ff_dwconv3_gate_pool_workspace(int C) { return (long long)1024 * C; }
 
@@ -117,6 +44,32 @@ extern "C" int ff_dwconv3_gate_pool(const float* in, int ldi, float* out, int ld
                      w_tapmajor, bias, work);
   hipLaunchKernelGGL(pool_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, work, (int)nb, C, 1.0f / (float)P, pooled);
   FF_LAUNCH_CHECK("ff_dwconv3_gate_pool");
+  return FF_OK;
+}
+
+extern "C" long long ff_dwconv3_gate_pool_images_workspace(int B, int C) {
+  if (B < 1 || C < 4) return -1;
+  return (long long)B * ff_dwconv3_gate_pool_workspace(C);
+}
+
+// B independent images [B][H][W] in one launch: image b comes out with the bits of ff_dwconv3_gate_pool on it alone (nb, the item-to-
+// workgroup assignment and the order of every sum are one image's); pooled [B][C], work >= ff_dwconv3_gate_pool_images_workspace(B, C).
+extern "C" int ff_dwconv3_gate_pool_images(const float* in, int ldi, float* out, int ldo, int B, int H, int W, int C, const float* w_tapmajor,
+                                           const float* bias, float* pooled, float* work, long long work_floats, void* stream) {
+  FF_CHECK_ARG(in && out && w_tapmajor && bias && pooled && work, "ff_dwconv3_gate_pool_images: null pointer");
+  FF_CHECK_ARG(B >= 1 && B <= 65535, "ff_dwconv3_gate_pool_images: B must be 1 .. 65535 (got %d)", B);
+  FF_CHECK_ARG(H > 0 && W > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && ldi >= 2 * C && ldi % 4 == 0 && ldo >= C && ldo % 4 == 0, "ff_dwconv3_gate_pool_images: bad dims");
+  FF_CHECK_ARG((((uintptr_t)in) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)w_tapmajor) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)work) & 15) == 0, "ff_dwconv3_gate_pool_images: 16-byte alignment required");
+  const int cv = C / 4, ppb = 256 / cv;
+  const long long P = (long long)H * W;
+  long long nb = ((long long)((H + 3) / 4) * W + ppb - 1) / ppb;      // one image's workgroups, capped as in ff_dwconv3_gate_pool
+  if (nb > 1024) nb = 1024;
+  FF_CHECK_ARG(work_floats >= (long long)B * nb * C, "ff_dwconv3_gate_pool_images: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(dwconv3_gate_pool_images_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), (size_t)ppb * cv * 16, st, in, ldi, out, ldo,
+                     H, W, C, w_tapmajor, bias, work);
+  hipLaunchKernelGGL(pool_reduce_images_kernel, dim3((C + 15) / 16, (unsigned)B), dim3(256), 0, st, work, (int)nb, C, 1.0f / (float)P, pooled);
+  FF_LAUNCH_CHECK("ff_dwconv3_gate_pool_images");
   return FF_OK;
 }
 

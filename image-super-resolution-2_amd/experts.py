@@ -463,7 +463,20 @@ class DatHIP(_Trunk):
 # =============================================================================================== NAFNet-SR
 class NafnetHIP:
     """NAFNetSR (nafnet/__init__.py:117-139 + nafnet_arch.py:137-225): bicubic x4, then the width-64
-    UNet (enc 2/2/4/8, mid 12, dec 2/2/2/2) at HR resolution."""
+    UNet (enc 2/2/4/8, mid 12, dec 2/2/2/2) at HR resolution.
+
+    forward(lr [B,3,h,w]) runs a batch through ONE launch per op in the fused modes.  The block's only per-image quantities are the SCA
+    pool [B,c] and the channel-attention vector it yields (sca / kmul [B,c]); the front, depth-wise and tail kernels and the two conv3
+    GEMMs have per-image forms, everything else works on rows.  Every choice of kernel route or tile is made from ONE image's
+    dimensions, so each image comes out with the bits of its own B == 1 forward."""
+
+    # Batches are processed in chunks of at most this many padded HR pixels (B * Hp * Wp): four 256 x 256 LR tiles' worth, i.e.
+    # activation memory grows to at most four times what one such tile allocates.  An attribute, not an environment switch.
+    # forward() also keeps a chunk below the 32-bit bounds of the kernels it launches, whatever this value says: ops.conv2d takes the
+    # LDS-resident 3x3 kernel (the ending convolution, 64 channels at HR) for inputs of fewer than 2^31 elements counted over the
+    # launch, and ff_naf_tail_images, the two kmul-images GEMMs and the implicit GEMM index rows in 32 bits (B * Hp * Wp < 2^31).
+    # B * Hp * Wp * 64 < 2^31 implies all of them, so a batch never leaves the route its images take alone.
+    max_batch_pixels = 4 * 1024 * 1024
 
     def __init__(self, sd: SD, dev, prefix: str = "expert_ensemble.nafnet.nafnet.", enc=(2, 2, 4, 8), mid: int = 12,
                  dec=(2, 2, 2, 2)):
@@ -487,12 +500,15 @@ class NafnetHIP:
         self.downs = [(w.conv(f"downs.{l}"), w(f"downs.{l}.bias")) for l in range(len(enc))]
         self.ups = [w(f"ups.{l}.0.weight").reshape(w(f"ups.{l}.0.weight").shape[0], -1).contiguous() for l in range(len(dec))]
 
-    def _padded_input(self, B: int, Hp: int, Wp: int, dev) -> T:
+    def _padded_input(self, B: int, Hp: int, Wp: int, dev, cap: Optional[int] = None) -> T:
         """[B,Hp,Wp,3] buffer whose padding (check_image_size, nafnet_arch.py:220-225: zeros right/bottom) was zeroed ONCE when
         the buffer was made; the resampler only ever writes the top-left H x W region, so no fill runs per forward.  Owned by the
         graph entry being captured (its address is in the captured launches) or, for eager forwards, one buffer that is replaced
-        when the size changes (ops.persistent_zeros)."""
-        return ops.persistent_zeros(id(self), "naf_in", (B, Hp, Wp, 3), dev)
+        when the size changes (ops.persistent_zeros).  cap: the images of the largest chunk of this forward -- the buffer is made
+        for cap images and a smaller (remainder) chunk gets its leading slice, so a chunk and its remainder never alternate two
+        sizes (which would replace and re-zero the eager buffer every forward)."""
+        buf = ops.persistent_zeros(id(self), "naf_in", (max(B, cap or B), Hp, Wp, 3), dev)
+        return buf[:B]
 
     def __del__(self):
         try:
@@ -500,8 +516,9 @@ class NafnetHIP:
         except Exception:                                   # interpreter shutdown
             pass
 
-    def block(self, x: T, k: dict) -> T:
-        c = x.shape[-1]
+    def block(self, x: T, k: dict, out: Optional[T] = None) -> T:
+        """One NAFBlock on x [B,H,W,c]; out: where the result goes (a chunk's slice of the batch's feature buffer)."""
+        B, c = x.shape[0], x.shape[-1]
         flash = ops.fused_modes() and c in (64, 128)                         # HR levels: the bandwidth-bound ones
         # deep levels in plain bf16: LayerNorm and the SimpleGate epilogue store the bf16 the GEMM would round to, and conv1 / conv4 /
         # conv5 fetch those rows by LDS-DMA (ops.linear on bf16 rows; bit-equal to the fp32-rows route).  conv3 scales its A operand
@@ -514,39 +531,80 @@ class NafnetHIP:
             if flash:
                 t = ops.token_linear(x, _tl(k, "c1"), gamma=k["n1"][0], beta=k["n1"][1], eps=1e-6)    # LayerNorm2d + conv1
             else:
-                t = ops.linear(ops.layernorm(x, *k["n1"], eps=1e-6, out_bf16=rows), *k["c1"])
+                t = ops.linear(ops.layernorm(x, *k["n1"], eps=1e-6, out_bf16=rows), *k["c1"], tile_hint=self._rows_tile(x, 2 * c, rows))
             g, pooled = ops.dwconv3_gate_pool(t, *k["c2"])                   # conv2 + SimpleGate + SCA pool sums
-        sca = ops.vec_mlp(pooled, *k["sca"], None)                           # [1,c]
+        sca = ops.vec_mlp(pooled, *k["sca"], None)                           # [B,c]: one launch for the batch, image b scaled by its own row
+        sca = sca if B > 1 else sca.reshape(-1)
         if flash and ops.gemm_mode() == "bf16":                              # plain bf16: conv3 + the gated FFN in one launch, y stays on chip
             tail = _packed(k, "tail_pk", lambda: pack_naf_tail(*k["c3"], *k["c4"], *k["c5"]))
-            return ops.naf_tail(g, x, tail, sca.reshape(-1), k["beta"], k["n2"][0], k["n2"][1], k["gamma"])
+            return ops.naf_tail(g, x, tail, sca, k["beta"], k["n2"][0], k["n2"][1], k["gamma"], out=out)
         nf = ops.gemm_mode() != "f32"                                        # the split-bf16 GEMM carries both NAFBlock fusions
         if nf:                                                               # conv3(g * sca): the scale rides on the A operand
-            y = ops.linear(g, *k["c3"], res=x, mul=k["beta"], kmul=sca.reshape(-1), rows_gemm=rows)
+            y = ops.linear(g, *k["c3"], res=x, mul=k["beta"], kmul=sca, rows_gemm=rows)    # (kmul [B,c]: the tile of one image's rows)
         else:
-            w3 = ops.mix2(k["c3"][0], ca=sca.reshape(-1))                    # conv3(g * sca) == (W3 . diag(sca)) g
+            w3 = ops.mix2(k["c3"][0], ca=sca)                                # conv3(g * sca) == (W3 . diag(sca)) g; f32 mode: B == 1
             y = ops.linear(g, w3, k["c3"][1], res=x, mul=k["beta"], dynamic_w=True)
         if flash:
             ffn = _packed(k, "ffn_pk", lambda: pack_naf_ffn(*k["c4"], *k["c5"]))
-            return ops.naf_ffn(y, ffn, k["n2"][0], k["n2"][1], k["gamma"])
+            return ops.naf_ffn(y, ffn, k["n2"][0], k["n2"][1], k["gamma"], out=out)
         if nf:                                                               # conv4 + SimpleGate in one launch: the 2c-wide tensor stays on chip
             w4, b4 = k["c4"]                                                 # rows interleaved: 2j <- j, 2j+1 <- j + c (chunk(2, dim=1) halves)
             c4i = _packed(k, "c4i", lambda: (torch.stack((w4[:c], w4[c:]), dim=1).reshape(2 * c, -1).contiguous(),
                                              torch.stack((b4[:c], b4[c:]), dim=1).reshape(-1).contiguous()))
-            g = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6, out_bf16=rows), *c4i, gate_pairs=True, out_bf16=rows)
+            g = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6, out_bf16=rows), *c4i, gate_pairs=True, out_bf16=rows,
+                           tile_hint=self._rows_tile(y, 2 * c, rows))
         else:
             t = ops.linear(ops.layernorm(y, *k["n2"], eps=1e-6), *k["c4"])
             g = ops.fma3(None, t[..., :c], t[..., c:])
-        return ops.linear(g, *k["c5"], res=y, mul=k["gamma"])
+        return ops.linear(g, *k["c5"], res=y, mul=k["gamma"], tile_hint=self._rows_tile(y, c, rows), out=out)
+
+    @staticmethod
+    def _rows_tile(x: T, N: int, rows: bool) -> int:
+        """tile_hint of a deep-level GEMM on the rows of x [B,H,W,c]: for a batch on the bf16-rows route, the configuration ONE image's
+        rows pick (ff_gemm_rows_bf16's rule counts workgroups, so it depends on the row count); 0 = the kernel's own choice otherwise.
+        (The split-bf16 route's rule, ff_conv2d_bf16s_tile, does not depend on the row count for these widths: N % 128 == 0.)"""
+        if not rows or x.shape[0] == 1:
+            return 0
+        return int(ops._L().ff_gemm_rows_bf16_tile(x.shape[1] * x.shape[2], N))
 
     def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
-        _, _, h, w = lr.shape
+        """lr [B,3,h,w] -> [B,3,4h,4w] (written into `out` when given).  feats (optional dict): receives feats["nafnet"], the input of
+        the ending convolution [B,Hp,Wp,64] (NHWC), the tensor the reference's forward hook captures (expert_loader.py:866).
+        B > 1: one launch per op for the whole batch in the fused modes (chunks of max_batch_pixels padded HR pixels), the per-image
+        loop in f32 mode (its conv3 folds sca into a dynamic weight); either way bit-equal to B single forwards.  taps are recorded
+        for B == 1 only."""
+        B, _, h, w = lr.shape
+        if B > 1:
+            if taps is not None:
+                raise ops._lib.FFError("NafnetHIP.forward: taps are recorded for B == 1 only")
+            m = 2 ** len(self.enc_n)
+            Hp, Wp = _ceil_to(4 * h, m), _ceil_to(4 * w, m)
+            nb = 1                                          # images per chunk
+            if ops.fused_modes():
+                nb = max(1, min(int(self.max_batch_pixels) // (Hp * Wp), (2 ** 31 - 1) // (Hp * Wp * 64)))
+            if nb < B:                                      # every chunk writes its slice of the one output (and feature) buffer
+                if out is None:
+                    out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
+                fall = ops.empty_rows((B, Hp, Wp, self.ending[0].shape[1] // 9), lr.device) if feats is not None else None
+                for b0 in range(0, B, nb):
+                    t = lr[b0:b0 + nb]                      # (the kernels take 16-byte aligned images: odd image sizes are copied)
+                    self._forward_chunk(t.clone() if t.data_ptr() % 16 else t, None, {} if feats is not None else None, out[b0:b0 + nb], nb,
+                                        fall[b0:b0 + nb] if feats is not None else None)
+                if feats is not None:
+                    feats["nafnet"] = fall
+                return out
+        return self._forward_chunk(lr, taps, feats, out, B, None)
+
+    def _forward_chunk(self, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], cap: int, feat_out: Optional[T]) -> T:
+        """One launch per op for all of lr [B,3,h,w] (per_image matters for B > 1 only: ops.conv2d); cap: the largest chunk's images;
+        feat_out: where the hooked feature -- the last block's output -- goes (a slice of the batch's buffer)."""
+        B, _, h, w = lr.shape
         H, W = 4 * h, 4 * w
         m = 2 ** len(self.enc_n)
         Hp, Wp = _ceil_to(H, m), _ceil_to(W, m)
-        inp = self._padded_input(1, Hp, Wp, lr.device)
+        inp = self._padded_input(B, Hp, Wp, lr.device, cap)
         ops.resize(lr, (H, W), mode="bicubic", scale_factor=4.0, layout="nchw", out=inp)
-        x = ops.conv2d(inp, *self.intro, ksize=(3, 3), pad=(1, 1))
+        x = ops.conv2d(inp, *self.intro, ksize=(3, 3), pad=(1, 1), per_image=True)
         skips = []
         for lvl, blks in enumerate(self.encs):
             for b, k in enumerate(blks):
@@ -554,16 +612,16 @@ class NafnetHIP:
                 if taps is not None and lvl == 0:
                     taps[f"naf.enc0.b{b}"] = x
             skips.append(x)
-            x = ops.conv2d(x, *self.downs[lvl], ksize=(2, 2), stride=(2, 2), pad=(0, 0))
+            x = ops.conv2d(x, *self.downs[lvl], ksize=(2, 2), stride=(2, 2), pad=(0, 0), per_image=True)
         for k in self.mids:
             x = self.block(x, k)
         if taps is not None:
             taps["naf.mid"] = x
         for lvl, blks in enumerate(self.decs):
-            x = ops.conv2d(x, self.ups[lvl], None, shuffle=2, res=skips[-1 - lvl])
-            for k in blks:
-                x = self.block(x, k)
+            x = ops.conv2d(x, self.ups[lvl], None, shuffle=2, res=skips[-1 - lvl], per_image=True)
+            for i, k in enumerate(blks):
+                x = self.block(x, k, out=feat_out if lvl == len(self.decs) - 1 and i == len(blks) - 1 else None)
         if feats is not None:
-            feats["nafnet"] = x                                # expert_loader.py:866: the INPUT of the ending conv, [1,Hp,Wp,64]
-        x = ops.conv2d(x, *self.ending, ksize=(3, 3), pad=(1, 1), res=inp)
+            feats["nafnet"] = x                                # expert_loader.py:866: the INPUT of the ending conv, [B,Hp,Wp,64]
+        x = ops.conv2d(x, *self.ending, ksize=(3, 3), pad=(1, 1), res=inp, per_image=True)
         return ops.nhwc_to_nchw(x, H, W, clamp01=True, out=out)

@@ -26,7 +26,7 @@ T = torch.Tensor
 
 
 def _per_image(lr: T, fn) -> list:
-    """[fn(b, lr[b:b+1]) for every image b of a contiguous batch]: the one place where what is not batched yet (DAT, NAFNet, the
+    """[fn(b, lr[b:b+1]) for every image b of a contiguous batch]: the one place where what is not batched yet (DAT, the
     fusion stack) is sequenced image by image; B == 1 is a batch of one.  An image that does not start on a 16-byte boundary (odd
     image sizes) is copied, since the kernels take 16-byte aligned images.  The copy is a torch op, which a recorded plan (plan.py)
     cannot carry: forward() refuses to record such a batch."""
@@ -92,21 +92,24 @@ class FreqFusionHIP:
         """ExpertEnsemble.forward_all (expert_loader.py:768-777) for a batch lr [B,3,h,w]: (hat [B,3,4h,4w], [dat_b], [nafnet_b],
         [pre_b or None]).  The three experts are independent until the fusion stack, so each runs on its own HIP stream (_fork; the
         whole fan-out is captured into the HIP graph): latency-bound kernels of one expert overlap with bandwidth-bound kernels of
-        another.  HAT takes the whole batch on the caller's stream, DAT runs for b = 0 .. B-1 on side stream 1, NAFNet and (with_pre)
-        the LR-only part of the fusion stack (FusionHIP.pre) for each b on side stream 2, the shortest expert's.  On one stream, and
+        another.  HAT takes the whole batch on the caller's stream, DAT runs for b = 0 .. B-1 on side stream 1, NAFNet takes the whole
+        batch (NafnetHIP.forward: one launch per op) and then (with_pre) the LR-only part of the fusion stack (FusionHIP.pre) runs for
+        each b, both on side stream 2, the shortest expert's.  On one stream, and
         with taps, the experts run one after the other and pre is left to fusion.forward."""
         if not self.multi_stream or taps is not None:
             hat = self.hat.forward(lr, taps)
             dats = _per_image(lr, lambda b, x: self.dat.forward(x, taps))
-            return hat, dats, _per_image(lr, lambda b, x: self.nafnet.forward(x, taps)), [None] * lr.shape[0]
+            naf = self.nafnet.forward(lr, taps)
+            return hat, dats, [naf[b:b + 1] for b in range(lr.shape[0])], [None] * lr.shape[0]
         with self._fork(mark=True) as (s1, s2, made):
             with torch.cuda.stream(s1):
                 dats = _per_image(lr, lambda b, x: self.dat.forward(x))
             with torch.cuda.stream(s2):
-                naf_pre = _per_image(lr, lambda b, x: (self.nafnet.forward(x), self.fusion.pre(x) if with_pre else None))
+                naf = self.nafnet.forward(lr)
+                pres = _per_image(lr, lambda b, x: self.fusion.pre(x) if with_pre else None)
             hat = self.hat.forward(lr)
-            nafs, pres = [n for n, _ in naf_pre], [p for _, p in naf_pre]
-            made += (*dats, *nafs, *(t for pre in pres if pre is not None for t in pre.values()))
+            nafs = [naf[b:b + 1] for b in range(lr.shape[0])]
+            made += (*dats, naf, *(t for pre in pres if pre is not None for t in pre.values()))
         return hat, dats, nafs, pres
 
     def experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = False):
@@ -123,7 +126,7 @@ class FreqFusionHIP:
         The payload of the cached-expert files (isr2_amd/cache.py).  streams=True runs the same launches with DAT and NAFNet (and
         their feature resizes) on the two side streams of forward(), forked from and joined to the caller's stream: the same bits,
         the small grids of one expert beside those of another (cache.build_from_folders).
-        HAT runs the batch through one launch per op; DAT and NAFNet run image by image into slices of their outputs.  Every
+        HAT and NAFNet run the batch through one launch per op; DAT runs image by image into slices of its output.  Every
         image's tensors are those of its own B == 1 call, bit for bit."""
         if lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3:
             raise _lib.FFError(f"expected lr of shape [B,3,h,w], got {tuple(lr.shape)}")
@@ -133,8 +136,8 @@ class FreqFusionHIP:
 
         def fwd(name):                                         # -> (SR output [B,3,4h,4w], [hooked NHWC features])
             raw = {}
-            if name == "hat":
-                return self.hat.forward(lr, feats=raw), [raw[name]]
+            if name != "dat":
+                return nets[name].forward(lr, feats=raw), [raw[name]]
             o = torch.empty((B, 3, 4 * h, 4 * w), device=self.dev, dtype=torch.float32)
             return o, _per_image(lr, lambda b, x: (nets[name].forward(x, feats=raw, out=o[b:b + 1]), raw[name])[1])
 
@@ -183,8 +186,9 @@ class FreqFusionHIP:
         lr = lr.to(self.dev, torch.float32).contiguous()
         B, _, h, w = lr.shape
         # Every global op of the path is per image (average pools, channel attention statistics, rFFT2, squeeze gates), so a batch is
-        # B independent images.  HAT takes the whole batch through one launch per op (HatHIP.forward: its only per-image quantity, the
-        # channel-attention gate, is a [B,180] matrix); DAT, NAFNet and the fusion stack are still sequenced per image (_per_image).
+        # B independent images.  HAT and NAFNet take the whole batch through one launch per op (HatHIP.forward, NafnetHIP.forward: their
+        # only per-image quantities, the channel-attention gate [B,180] and the SCA vector [B,c], are matrices); DAT and the fusion stack
+        # are still sequenced per image (_per_image).
         # Bit-identical to B single forwards: every image runs the launches, in the forms, of its own B == 1 forward.
         if B > 1 and taps is not None:
             raise _lib.FFError("taps are recorded for B == 1 only")

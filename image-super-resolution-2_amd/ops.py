@@ -448,6 +448,8 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
            alpha: float = 1.0, out: Optional[T] = None, dynamic_w: bool = False, kmul: Optional[T] = None,
            gate_pairs: bool = False, out_bf16: bool = False, tile_hint: int = 0, rows_gemm: bool = False) -> T:
     """x [..., K] rows view, w [N, K] -> [..., N].  kmul [K]: scale of the input channels (W (kmul * x); split-bf16 modes).
+    kmul [B, K] with B > 1: the rows are B equal groups (rows % B == 0), group b scaled by kmul[b], in one launch -- every group with
+    the bits of its own call with kmul[b] (the tile configuration is taken from one group's row count).
     gate_pairs: SimpleGate in the epilogue, [..., N / 2] out with out[j] = y[2j] * y[2j+1] (rows of w interleaved by the caller).
     bf16 x (plain-bf16 mode, rows_gemm_ok shapes): ff_gemm_rows_bf16, bit-equal to the fp32-rows kernel on x.float(); out_bf16 stores
     the gated output as bf16 rows for the next such GEMM.  rows_gemm: fp32 x through the same kernel (A staged through registers; the
@@ -480,14 +482,33 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
                                   1, 1, 1, 1, 0, 0, ACT[act], float(alpha), 0, 0, _stream()))
     else:
         aligned = (ldi % 4 == 0) and (xp % 16 == 0)
+        images = _kmul_images(kmul, K, rows)                 # (refusals first: nothing is launched, no weight is split, before them)
+        if images > 1 and (act is not None or alpha != 1.0 or gate_pairs or not aligned or K % 4 or N % 4):
+            raise _lib.FFError("linear: kmul [B, K] comes with the (bias, * mul, + res) epilogue on 16-byte aligned rows only")
         hi, lo, Kp, Cp, _ = _split_weight(w, dynamic_w, K if aligned else 0)
-        if kmul is not None and (kmul.numel() != K or not kmul.is_contiguous()):
-            raise _lib.FFError(f"linear: kmul must be a contiguous [{K}] vector")
-        _lib.check(_L().ff_conv2d_bf16s(xp, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, _ptr(bias), _ptr(mul),
-                                        rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
-                                        float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], 0, _ptr(kmul), _stream()))
+        if images > 1:
+            _lib.check(_L().ff_conv2d_bf16s_kmul_images(xp, ldi, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp,
+                                                        kmul.data_ptr(), images, rows // images, _ptr(bias), _ptr(mul), rp, ldr, op, ldo,
+                                                        rows, K, N, GEMM_MODES[_GEMM_MODE], 0, _stream()))
+        else:
+            _lib.check(_L().ff_conv2d_bf16s(xp, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, _ptr(bias), _ptr(mul),
+                                            rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
+                                            float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], 0, _ptr(kmul), _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K + N * K + rows * No * (2 if res is not None else 1)))
     return out
+
+
+def _kmul_images(kmul: Optional[T], K: int, rows: int) -> int:
+    """linear's kmul: [K] (or [1, K]) -> 1; a contiguous [B, K] matrix with B > 1 dividing the row count -> B; anything else raises."""
+    if kmul is None:
+        return 1
+    _chk(kmul, "linear.kmul")
+    if not kmul.is_contiguous() or kmul.numel() % K or (kmul.numel() != K and (kmul.dim() != 2 or kmul.shape[1] != K)):
+        raise _lib.FFError(f"linear: kmul must be a contiguous [{K}] vector or [B, {K}] matrix, got {tuple(kmul.shape)}")
+    images = kmul.numel() // K
+    if images < 1 or rows % images:
+        raise _lib.FFError(f"linear: kmul {tuple(kmul.shape)} needs a row count that B = {images} divides, got {rows} rows")
+    return images
 
 
 def rows_gemm_ok(K: int) -> bool:
@@ -503,8 +524,9 @@ def _linear_rows_bf16(x: T, w: T, bias, *, act, res, mul, alpha, out, dynamic_w,
         raise _lib.FFError(f"linear: weight must be [N, {K}], got {tuple(w.shape)}")
     if _GEMM_MODE != "bf16" or not rows_gemm_ok(K):
         raise _lib.FFError("linear: the bf16-rows GEMM exists in plain-bf16 mode for K % 64 == 0 only")
-    if kmul is not None and (not a32 or kmul.numel() != K or not kmul.is_contiguous()):
-        raise _lib.FFError(f"linear: kmul scales fp32 input rows only and must be a contiguous [{K}] vector")
+    if kmul is not None and not a32:
+        raise _lib.FFError("linear: kmul scales fp32 input rows only")
+    images = _kmul_images(kmul, K, rows)
     if act is not None or alpha != 1.0 or (a32 and gate_pairs) or (gate_pairs and (res is not None or mul is not None)) or out_bf16 != gate_pairs:
         raise _lib.FFError("linear: the bf16-rows GEMM has three epilogues: bias (* mul + res) -> fp32 rows, or the SimpleGate pair "
                            "product -> bf16 rows")
@@ -523,8 +545,12 @@ def _linear_rows_bf16(x: T, w: T, bias, *, act, res, mul, alpha, out, dynamic_w,
         if rrows != rows or rc != N:
             raise _lib.FFError("linear: res shape mismatch")
     hi, _, Kp, _, _ = _split_weight(w, dynamic_w, K)
-    _lib.check(_L().ff_gemm_rows_bf16(xp, 1 if a32 else 0, lda, hi.data_ptr(), Kp, _ptr(kmul), _ptr(bias), _ptr(mul), rp, ldr, op, ldo, rows,
-                                      N, K, 1 if gate_pairs else 0, int(tile_hint), _stream()))
+    if images > 1:
+        _lib.check(_L().ff_gemm_rows_bf16_kmul_images(xp, lda, hi.data_ptr(), Kp, kmul.data_ptr(), images, rows // images, _ptr(bias), _ptr(mul),
+                                                      rp, ldr, op, ldo, rows, N, K, int(tile_hint), _stream()))
+    else:
+        _lib.check(_L().ff_gemm_rows_bf16(xp, 1 if a32 else 0, lda, hi.data_ptr(), Kp, _ptr(kmul), _ptr(bias), _ptr(mul), rp, ldr, op, ldo, rows,
+                                          N, K, 1 if gate_pairs else 0, int(tile_hint), _stream()))
     _note(2.0 * rows * N * K, (4.0 if a32 else 2.0) * rows * K + 2.0 * N * K + (2.0 if out_bf16 else 4.0) * rows * No + (4.0 * rows * No if res is not None else 0.0))
     return out
 
@@ -724,68 +750,104 @@ def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T]
 
 
 def dwconv3_gate_pool(t: T, w_tap: T, bias: T):
-    """t [1,H,W,2C] -> (dw3x3(t)[..., :C] * dw3x3(t)[..., C:], its per-channel mean [1,C]) in one pass."""
+    """t [B,H,W,2C] -> (dw3x3(t)[..., :C] * dw3x3(t)[..., C:], its per-channel mean [B,C]) in one pass.  B > 1: one launch for the
+    batch (ff_dwconv3_gate_pool_images), every image with the bits of its own B == 1 call."""
     tp, ldi, B, H, W, C2 = _nhwc(t, "dwconv3_gate_pool.t")
-    if B != 1 or C2 % 2 or tuple(w_tap.shape) != (9, C2):
-        raise _lib.FFError("dwconv3_gate_pool: expects B == 1, [9, 2C] tap-major weights")
+    if B < 1 or C2 % 2 or tuple(w_tap.shape) != (9, C2):
+        raise _lib.FFError("dwconv3_gate_pool: expects [B,H,W,2C] with B >= 1, [9, 2C] tap-major weights")
     C = C2 // 2
-    out = torch.empty((1, H, W, C), device=t.device, dtype=torch.float32)
-    pooled = torch.empty((1, C), device=t.device, dtype=torch.float32)
-    nwork = int(_L().ff_dwconv3_gate_pool_workspace(C))
-    work = torch.empty(nwork, device=t.device, dtype=torch.float32)
-    _lib.check(_L().ff_dwconv3_gate_pool(tp, ldi, out.data_ptr(), C, H, W, C, w_tap.data_ptr(), bias.data_ptr(), pooled.data_ptr(),
-                                         work.data_ptr(), nwork, _stream()))
-    _note(2.0 * H * W * C2 * 9, 4.0 * H * W * (C2 + C))
+    out = torch.empty((B, H, W, C), device=t.device, dtype=torch.float32)
+    pooled = torch.empty((B, C), device=t.device, dtype=torch.float32)
+    if B == 1:
+        nwork = int(_L().ff_dwconv3_gate_pool_workspace(C))
+        work = torch.empty(nwork, device=t.device, dtype=torch.float32)
+        _lib.check(_L().ff_dwconv3_gate_pool(tp, ldi, out.data_ptr(), C, H, W, C, w_tap.data_ptr(), bias.data_ptr(), pooled.data_ptr(),
+                                             work.data_ptr(), nwork, _stream()))
+    else:
+        nwork = int(_L().ff_dwconv3_gate_pool_images_workspace(B, C))
+        work = torch.empty(nwork, device=t.device, dtype=torch.float32)
+        _lib.check(_L().ff_dwconv3_gate_pool_images(tp, ldi, out.data_ptr(), C, B, H, W, C, w_tap.data_ptr(), bias.data_ptr(),
+                                                    pooled.data_ptr(), work.data_ptr(), nwork, _stream()))
+    _note(2.0 * B * H * W * C2 * 9, 4.0 * B * H * W * (C2 + C))
     return out, pooled
 
 
 def naf_front(x: T, pk: dict, ln_g: T, ln_b: T, w_tap: T, dw_bias: T, eps: float = 1e-6):
-    """x [1,H,W,C] (C = 64 / 128) -> (SimpleGate(dw3x3(conv1(LayerNorm2d(x)))) [1,H,W,C], its per-channel mean [1,C]) in one launch;
-    pk = prep.pack_token_linear(conv1 weight [2C, C], bias), w_tap [9, 2C] tap-major depth-wise weights."""
+    """x [B,H,W,C] (C = 64 / 128) -> (SimpleGate(dw3x3(conv1(LayerNorm2d(x)))) [B,H,W,C], its per-channel mean [B,C]) in one launch;
+    pk = prep.pack_token_linear(conv1 weight [2C, C], bias), w_tap [9, 2C] tap-major depth-wise weights.  B > 1: one launch for
+    the batch (ff_naf_front_images), every image with the bits of its own B == 1 call."""
     xp, ldx, B, H, W, C = _nhwc(x, "naf_front.x")
-    if B != 1 or C not in (64, 128) or pk["N"] != 2 * C or pk["K"] != C or pk["kpad"] != C or tuple(w_tap.shape) != (9, 2 * C):
-        raise _lib.FFError("naf_front: expects B == 1, C in (64, 128), conv1 packed as [2C, C], [9, 2C] tap-major weights")
-    out = torch.empty((1, H, W, C), device=x.device, dtype=torch.float32)
-    pooled = torch.empty((1, C), device=x.device, dtype=torch.float32)
-    nwork = int(_L().ff_naf_front_workspace(H, W, C))
-    work = torch.empty(nwork, device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_naf_front(xp, ldx, H, W, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b"].data_ptr(),
-                                 w_tap.data_ptr(), dw_bias.data_ptr(), out.data_ptr(), C, pooled.data_ptr(), work.data_ptr(), nwork,
-                                 _nterms(), _stream()))
-    _note(2.0 * H * W * 2 * C * (C + 9), 4.0 * H * W * 2 * C)
+    if B < 1 or C not in (64, 128) or pk["N"] != 2 * C or pk["K"] != C or pk["kpad"] != C or tuple(w_tap.shape) != (9, 2 * C):
+        raise _lib.FFError("naf_front: expects [B,H,W,C] with B >= 1, C in (64, 128), conv1 packed as [2C, C], [9, 2C] tap-major weights")
+    out = torch.empty((B, H, W, C), device=x.device, dtype=torch.float32)
+    pooled = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    if B == 1:
+        nwork = int(_L().ff_naf_front_workspace(H, W, C))
+        work = torch.empty(nwork, device=x.device, dtype=torch.float32)
+        _lib.check(_L().ff_naf_front(xp, ldx, H, W, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b"].data_ptr(),
+                                     w_tap.data_ptr(), dw_bias.data_ptr(), out.data_ptr(), C, pooled.data_ptr(), work.data_ptr(), nwork,
+                                     _nterms(), _stream()))
+    else:
+        nwork = int(_L().ff_naf_front_images_workspace(B, H, W, C))
+        work = torch.empty(nwork, device=x.device, dtype=torch.float32)
+        _lib.check(_L().ff_naf_front_images(xp, ldx, B, H, W, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(),
+                                            pk["b"].data_ptr(), w_tap.data_ptr(), dw_bias.data_ptr(), out.data_ptr(), C, pooled.data_ptr(),
+                                            work.data_ptr(), nwork, _nterms(), _stream()))
+    _note(2.0 * B * H * W * 2 * C * (C + 9), 4.0 * B * H * W * 2 * C)
     return out, pooled
 
 
-def naf_ffn(y: T, pk: dict, ln_g: T, ln_b: T, out_scale: T, eps: float = 1e-6) -> T:
+def _dense_out(out: Optional[T], like: T, name: str) -> T:
+    """A fresh dense fp32 tensor of like's shape, or the caller's `out` when it is one (e.g. a leading slice of a batch's buffer)."""
+    if out is None:
+        return torch.empty(tuple(like.shape), device=like.device, dtype=torch.float32)
+    _chk(out, name + ".out")
+    if tuple(out.shape) != tuple(like.shape) or not out.is_contiguous():
+        raise _lib.FFError(f"{name}: out must be a contiguous float32 tensor of shape {tuple(like.shape)}")
+    return out
+
+
+def naf_ffn(y: T, pk: dict, ln_g: T, ln_b: T, out_scale: T, eps: float = 1e-6, out: Optional[T] = None) -> T:
     """y + out_scale * conv5(SimpleGate(conv4(LayerNorm(y)))) in one launch (C = 64 / 128, bf16x3)."""
     yp, ldy, rows, C = rows_view(y, "naf_ffn.y")
     if C != pk["C"]:
         raise _lib.FFError("naf_ffn: channel mismatch")
-    out = torch.empty(tuple(y.shape), device=y.device, dtype=torch.float32)
+    out = _dense_out(out, y, "naf_ffn")
     _lib.check(_L().ff_naf_ffn(yp, ldy, out.data_ptr(), C, rows, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(),
                                pk["b4"].data_ptr(), pk["b5"].data_ptr(), out_scale.data_ptr(), _nterms(), _stream()))
     _note(2.0 * rows * C * 3 * C, 8.0 * rows * C)
     return out
 
 
-def naf_tail(g: T, x: T, pk: dict, sca: T, beta: T, ln_g: T, ln_b: T, gamma: T, eps: float = 1e-6) -> T:
+def naf_tail(g: T, x: T, pk: dict, sca: T, beta: T, ln_g: T, ln_b: T, gamma: T, eps: float = 1e-6, out: Optional[T] = None) -> T:
     """The NAFBlock tail in one launch (C = 64 / 128, plain bf16 only): y = x + beta * conv3(g * sca), then
     y + gamma * conv5(SimpleGate(conv4(LayerNorm(y)))); bit-equal to linear(g, W3, b3, res=x, mul=beta, kmul=sca) followed by
-    naf_ffn.  g, x: rows views; pk from prep.pack_naf_tail."""
+    naf_ffn.  g, x: rows views; pk from prep.pack_naf_tail.  sca [B,C] with g.shape[0] == B > 1: the rows are B equal groups, image b's
+    scaled by sca[b], in one launch (ff_naf_tail_images; every image with the bits of its own call)."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError(f"naf_tail exists for the plain-bf16 contraction mode only, not {_GEMM_MODE!r}")
     gp, ldg, rows, C = rows_view(g, "naf_tail.g")
     xp, ldx, xr, xc = rows_view(x, "naf_tail.x")
     if C != pk["C"] or xr != rows or xc != C or tuple(x.shape) != tuple(g.shape):
         raise _lib.FFError("naf_tail: shape mismatch")
-    for t_, n_ in ((sca, "sca"), (beta, "beta"), (ln_g, "ln_g"), (ln_b, "ln_b"), (gamma, "gamma")):
+    images = sca.shape[0] if isinstance(sca, torch.Tensor) and sca.dim() == 2 and sca.shape[0] > 1 else 1
+    if images > 1:
+        _chk(sca, "naf_tail.sca")
+        if g.dim() < 2 or g.shape[0] != images or tuple(sca.shape) != (images, C) or not sca.is_contiguous():
+            raise _lib.FFError(f"naf_tail: sca {tuple(sca.shape)} must be a contiguous [B, {C}] matrix with B the leading dimension of g {tuple(g.shape)}")
+    for t_, n_ in ((beta, "beta"), (ln_g, "ln_g"), (ln_b, "ln_b"), (gamma, "gamma")) + (() if images > 1 else ((sca, "sca"),)):
         _chk(t_, "naf_tail." + n_)
         if t_.numel() != C or not t_.is_contiguous():
             raise _lib.FFError(f"naf_tail: {n_} must be a contiguous [{C}] vector")
-    out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_naf_tail(gp, ldg, xp, ldx, out.data_ptr(), C, rows, C, sca.data_ptr(), pk["b3"].data_ptr(), beta.data_ptr(),
-                                ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b4"].data_ptr(),
-                                pk["b5"].data_ptr(), gamma.data_ptr(), _stream()))
+    out = _dense_out(out, x, "naf_tail")
+    if images > 1:
+        _lib.check(_L().ff_naf_tail_images(gp, ldg, xp, ldx, out.data_ptr(), C, rows, C, sca.data_ptr(), images, rows // images,
+                                           pk["b3"].data_ptr(), beta.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), float(eps),
+                                           pk["w"].data_ptr(), pk["b4"].data_ptr(), pk["b5"].data_ptr(), gamma.data_ptr(), _stream()))
+    else:
+        _lib.check(_L().ff_naf_tail(gp, ldg, xp, ldx, out.data_ptr(), C, rows, C, sca.data_ptr(), pk["b3"].data_ptr(), beta.data_ptr(),
+                                    ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b4"].data_ptr(),
+                                    pk["b5"].data_ptr(), gamma.data_ptr(), _stream()))
     _note(2.0 * rows * C * 4 * C, 12.0 * rows * C)
     return out
 

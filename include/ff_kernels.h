@@ -62,6 +62,16 @@ int ff_conv2d_bf16s(const float* in, const void* w_hi, const void* w_lo, int Kp,
  * 16-byte aligned input rows).  A caller that batches independent images passes the value for ONE image's M as tile_hint, so that the
  * batched launch takes the kernel form the single-image launch takes.  Added under ABI version 7 (an additive entry point). */
 int ff_conv2d_bf16s_tile(long long M, int Cout, int K, int vec4);
+/* conv3 of B independent images in one launch (1x1; NAFBlock conv3(g * sca) at the deep levels, split-bf16 modes).  in is fp32
+ * [M][ldi] rows with M == B * rows_per_image < 2^31: rows b * rows_per_image .. (b + 1) * rows_per_image - 1 are image b's.  kmul is
+ * [B][Cin], image b's scale vector at kmul + b * Cin, and row m is scaled by kmul[m / rows_per_image] before the split.  Epilogue:
+ * out = (A w^T + bias) * mul + res (Cout % 4 == 0, 16-byte aligned out / res rows).  Every row is bit-equal to ff_conv2d_bf16s(1x1,
+ * kmul = kmul + b * Cin) on its image alone: the kernel is that one with the image of each A row (B = B, H = 1, W = rows_per_image)
+ * indexing kmul, and tile_hint <= 0 takes ff_conv2d_bf16s_tile(rows_per_image, ...), ONE image's configuration (3, 4, 5 or 7).
+ * Added under ABI version 7 (an additive entry point: no existing prototype changed). */
+int ff_conv2d_bf16s_kmul_images(const float* in, int ldi, const void* w_hi, const void* w_lo, int Kp, int Cp, const float* kmul, int B,
+                                int rows_per_image, const float* bias, const float* mul, const float* res, int ldr, float* out, int ldo,
+                                long long M, int Cin, int Cout, int nterms, int tile_hint, void* stream);
 int ff_split_bf16(const float* w, int N, int K, int Kp, int Cin, int Cp, void* hi, void* lo, void* stream);
 
 /* GEMM on bf16 ROWS, plain bf16 (csrc/gemm_rows_bf16.hip): out[M][N] = epilogue(A[M][K] . W[N][K]^T), bit-equal to
@@ -79,6 +89,17 @@ int ff_split_bf16(const float* w, int N, int K, int Kp, int Cin, int Cp, void* h
 int ff_gemm_rows_bf16(const void* a, int a_fp32, int lda, const void* w_hi, int Kp, const float* kmul, const float* bias,
                       const float* mul, const float* res, int ldr, void* out, int ldo, long long M, int N, int K, int gate,
                       int tile_hint, void* stream);
+/* The tile configuration ff_gemm_rows_bf16 picks when tile_hint <= 0, from M and N.  A caller that batches independent images passes the
+ * value for ONE image's M as tile_hint.  Added under ABI version 7 (an additive entry point). */
+int ff_gemm_rows_bf16_tile(long long M, int N);
+/* ff_gemm_rows_bf16(a_fp32 = 1, gate = 0) for B independent images in one launch: a fp32 [M][lda], M == B * rows_per_image < 2^31, rows
+ * b * rows_per_image .. of a / res / out are image b's; kmul is [B][K], image b's vector at kmul + b * K, and row m is scaled by
+ * kmul[m / rows_per_image] before the bf16 rounding (looked up per staged row, so an m-tile may hold rows of several images and the
+ * tiling is the single-image kernel's).  Every row is bit-equal to ff_gemm_rows_bf16(kmul = kmul + b * K) on its image alone.
+ * tile_hint <= 0 takes ff_gemm_rows_bf16_tile(rows_per_image, N).  Added under ABI version 7 (an additive entry point). */
+int ff_gemm_rows_bf16_kmul_images(const float* a, int lda, const void* w_hi, int Kp, const float* kmul, int B, int rows_per_image,
+                                  const float* bias, const float* mul, const float* res, int ldr, float* out, int ldo, long long M,
+                                  int N, int K, int tile_hint, void* stream);
 
 /* 3x3 / stride 1 / pad 1 convolution for small channel counts (csrc/conv3x3_small.hip): Cin <= 64, Cout <= 16, exact fp32 on
  * the VALU, out = res + alpha * act(conv(in) + bias).  w_small: fp32 [9][ceil4(Cin)][CT], CT = 1 / 4 / 16 >= Cout, zero padded
@@ -242,6 +263,14 @@ int ff_token_linear_gated(const float* x, int ldx, const float* x2, int ldx2, co
 long long ff_dwconv3_gate_pool_workspace(int C);
 int ff_dwconv3_gate_pool(const float* in, int ldi, float* out, int ldo, int H, int W, int C, const float* w_tapmajor,
                          const float* bias, float* pooled, float* work, long long work_floats, void* stream);
+/* ff_dwconv3_gate_pool on B independent images in one launch: in [B][H][W][ldi], out [B][H][W][ldo] (image strides H * W * ld),
+ * pooled [B][C].  Grid (nb, B) with nb ONE image's workgroup count (its 1024 cap included): every image keeps its own item-to-workgroup
+ * assignment and summation order, so it comes out with the bits of ff_dwconv3_gate_pool on it alone, whatever B is.  work >=
+ * ff_dwconv3_gate_pool_images_workspace(B, C) = B x the single-image value (-1 for B < 1) floats, laid out [B][nb][C].
+ * Added under ABI version 7 (additive entry points). */
+long long ff_dwconv3_gate_pool_images_workspace(int B, int C);
+int ff_dwconv3_gate_pool_images(const float* in, int ldi, float* out, int ldo, int B, int H, int W, int C, const float* w_tapmajor,
+                                const float* bias, float* pooled, float* work, long long work_floats, void* stream);
 
 /* NAFBlock front half in one launch (csrc/naf_front.inc; nafnet_arch.py:88-98) for C = 64 / 128:
  *   g = SimpleGate(dw3x3(conv1(LayerNorm2d(x)))), pooled = mean over pixels of g (SCA's average pool).
@@ -252,6 +281,15 @@ long long ff_naf_front_workspace(int H, int W, int C);
 int ff_naf_front(const float* x, int ldx, int H, int W, int C, const float* ln_gamma, const float* ln_beta, float eps,
                  const void* w1_tiles, const float* b1, const float* dw_tapmajor, const float* dw_bias, float* out, int ldo,
                  float* pooled, float* work, long long work_floats, int nterms, void* stream);
+/* ff_naf_front on B independent images in one launch: x [B][H*W][ldx], out [B][H*W][ldo] (image strides H * W * ld), pooled [B][C].
+ * Grid (tiles, B): the image is blockIdx.y, the tile index and its XCD remap are those of one image's launch.  work >=
+ * ff_naf_front_images_workspace(B, H, W, C) = B x the single-image value (-1 for B < 1) floats: partial rows [B][tiles][C], each image's
+ * in its single-image order, finished per image in that order.  Image b has the bits of ff_naf_front on it alone.
+ * Added under ABI version 7 (additive entry points). */
+long long ff_naf_front_images_workspace(int B, int H, int W, int C);
+int ff_naf_front_images(const float* x, int ldx, int B, int H, int W, int C, const float* ln_gamma, const float* ln_beta, float eps,
+                        const void* w1_tiles, const float* b1, const float* dw_tapmajor, const float* dw_bias, float* out, int ldo,
+                        float* pooled, float* work, long long work_floats, int nterms, void* stream);
 int ff_naf_ffn(const float* y, int ldy, float* out, int ldo, long long M, int C, const float* gamma_ln, const float* beta_ln,
                float eps, const void* w_tiles, const float* b4, const float* b5, const float* out_scale, int nterms, void* stream);
 
@@ -264,6 +302,14 @@ int ff_naf_ffn(const float* y, int ldy, float* out, int ldo, long long M, int C,
 int ff_naf_tail(const float* g, int ldg, const float* x, int ldx, float* out, int ldo, long long M, int C, const float* sca,
                 const float* b3, const float* beta, const float* gamma_ln, const float* beta_ln, float eps, const void* w_frags,
                 const float* b4, const float* b5, const float* out_scale, void* stream);
+/* ff_naf_tail on the rows of B independent images in one launch: M == B * rows_per_image < 2^31, rows b * rows_per_image .. of g / x /
+ * out are image b's, sca is [B][C] (16-byte aligned; image b's vector at sca + b * C, read from global memory per wave instead of the
+ * LDS constant block).  rows_per_image must be a multiple of 32 -- a wave's 32 rows then belong to one image; anything else is refused
+ * before the launch.  Every row is bit-equal to ff_naf_tail(sca = sca + b * C) on its image alone.
+ * Added under ABI version 7 (an additive entry point: no existing prototype changed). */
+int ff_naf_tail_images(const float* g, int ldg, const float* x, int ldx, float* out, int ldo, long long M, int C, const float* sca,
+                       int B, int rows_per_image, const float* b3, const float* beta, const float* gamma_ln, const float* beta_ln,
+                       float eps, const void* w_frags, const float* b4, const float* b5, const float* out_scale, void* stream);
 
 /* LayerNorm over the last axis of [rows][C] (nn.LayerNorm and NAFNet LayerNorm2d in NHWC):
  * hat_arch.py:272,307,397,437,964; dat_arch.py:117,734-735,931,1003; nafnet_arch.py:35-41. */
