@@ -9,7 +9,7 @@ PNGs).  --crops random patches per image (--center: the one centred patch) of --
 isr2_amd.cache.build_from_folders describes the files.  Expert weights come from where the plugin finds them: --pretrained DIR (default
 $FREQFUSION_PRETRAINED, else ./pretrained) with hat/, dat/ and nafnet/ checkpoints; a missing one is replaced by seeded synthetic
 weights with a warning (smoke runs).  --weights: a reference-keyed state dict, bare or under `model_state_dict`, laid over them as
-train_cached lays it.  --batch N: the patches of an image go through the experts in groups of N (HAT and NAFNet batched: one launch per op); the
+train_cached lays it.  --batch N: the patches of an image go through the experts in groups of N (HAT, DAT and NAFNet batched: one launch per op); the
 files hold the same bits.  One JSON line on stdout."""
 from __future__ import annotations
 

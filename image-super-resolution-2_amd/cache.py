@@ -344,8 +344,8 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
     makes, so the files hold the same bits: the three experts of a patch run on three streams, as in model.experts(), and since all
     patches have one shape the pass is captured once into a HIP graph and replayed per patch (graph=False launches it instead: the
     switch exists for the bit-for-bit comparison of the two).  Images smaller than the patch are skipped and counted.
-    batch=N: the K patches of an image go through the expert pass in groups of N (model.experts_with_features on [N,3,p,p]: HAT and
-    NAFNet take the group through one launch per op, DAT runs patch by patch beside them); the graph is captured for [N,3,p,p] and a
+    batch=N: the K patches of an image go through the expert pass in groups of N (model.experts_with_features on [N,3,p,p]: HAT, DAT
+    and NAFNet each take the group through one launch per op, on three streams); the graph is captured for [N,3,p,p] and a
     remainder group of K % N patches has a graph of its own.  Every file holds the bits batch=1 writes; batch=1 is that path, launch
     for launch.
     A reader or writer exception ends the run and is re-raised here.

@@ -242,6 +242,12 @@ __global__ __launch_bounds__(512) void chan_qkv_kernel(ChanQkvParams p) {
 }
 
 extern "C" long long ff_chan_qkv_workspace(long long M) { return ((M + 255) / 256 + 2) * 5760; }
+// B images of rows_per_image rows through one ff_chan_qkv call + ff_chan_attn_finish_images: B times one image's workspace (which covers the
+// B * nblk partial blocks and the B blocks of G); -1 for a geometry the images entry refuses
+extern "C" long long ff_chan_qkv_images_workspace(int B, long long rows_per_image) {
+  if (B <= 0 || B > 65535 || rows_per_image <= 0 || rows_per_image % 256) return -1;
+  return (long long)B * ff_chan_qkv_workspace(rows_per_image);
+}
 
 extern "C" int ff_chan_qkv(const float* x, int ldx, long long M, int K, const float* gamma, const float* beta, float eps,
                            const void* w_tiles, const float* bias_padded, float* v_out, int ldv, float* work, long long work_floats,

@@ -1,7 +1,9 @@
 // The implicit-GEMM kernel (conv_gemm_bf16.hip includes this file twice).  CIG_KERNEL names the kernel; CIG_KMUL_IMAGES = 0 is the kernel of
 // ff_conv2d_bf16s.  CIG_KMUL_IMAGES = 1 (1x1, VEC4): kmul is [B][Cin] and A row m is scaled by its image's vector, kmul[a_b][ci] -- conv3 of
 // B independent images in one launch (ff_conv2d_bf16s_kmul_images calls it with B = B, H = 1, W = rows per image, so a_b IS the image).
-// Nothing else differs.
+// CIG_W_IMAGES = 1 (1x1, VEC4): the weight planes are [B][Cout][Kp] and an m-tile multiplies by the planes of the image its first row
+// belongs to (ff_conv2d_bf16s_wimages: H = 1, W = rows per image, a multiple of the tile height, so a tile never straddles two images) --
+// DAT's att = v . wbd^T with one block-diagonal matrix per image.  Nothing else differs.
 // BKB = k-values per chunk (one barrier per chunk).  32: the original form.  64 (r2): twice the MFMAs between barriers -- the
 // 8-wave 128-row tiles issue only 12 MFMAs per wave and chunk at 32, and the barrier + staging round trip per chunk, not the
 // MFMA pipe, set their time (SQ counters, tools/gemm_prof.py: MFMA pipe 28 % busy on the 1024 -> 2048 NAFNet GEMM).
@@ -119,7 +121,11 @@ __global__ __launch_bounds__(WM * WN * 64) void CIG_KERNEL(ConvBfParams p) {
       const int r = rem / QB, q = rem % QB;
       uint4 v = {0u, 0u, 0u, 0u};
       if (id < BN * 2 * QB && (NTERMS == 3 || plane == 0) && n0 + r < p.Cout) {
+#if CIG_W_IMAGES
+        const __bf16* src = (plane ? p.w_lo : p.w_hi) + ((long long)(m0 / p.W) * p.Cout + n0 + r) * p.Kp + k0 + 8 * q;
+#else
         const __bf16* src = (plane ? p.w_lo : p.w_hi) + (long long)(n0 + r) * p.Kp + k0 + 8 * q;
+#endif
         v = *reinterpret_cast<const uint4*>(src);
       }
       rb[j] = v;

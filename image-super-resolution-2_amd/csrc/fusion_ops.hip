@@ -65,7 +65,7 @@ __global__ __launch_bounds__(384) void chan_gram_kernel(const float* __restrict_
 
 // stage 2: 180 workgroups of 32 statistics x 8 block slices: a thread sums every 8th partial block of its statistic (four independent
 // accumulators: 8 dependent load rounds at nblk = 256 instead of 64), the slices meet in LDS in a fixed order (deterministic)
-__global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restrict__ part, int nblk, float* __restrict__ G) {
+__device__ __forceinline__ void chan_reduce_body(const float* __restrict__ part, int nblk, float* __restrict__ G) {
   __shared__ float red[8][32];
   const int l = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int e = blockIdx.x * 32 + l;                       // 5760 = 180 x 32
@@ -87,11 +87,17 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restric
     G[e] = t;
   }
 }
+__global__ __launch_bounds__(256) void chan_reduce_kernel(const float* __restrict__ part, int nblk, float* __restrict__ G) {
+  chan_reduce_body(part, nblk, G);
+}
+// grid (180, B): image blockIdx.y reduces its own nblk blocks of part [B][nblk][5760] in the single-image order into G [B][5760]
+__global__ __launch_bounds__(256) void chan_reduce_images_kernel(const float* __restrict__ part, int nblk, float* __restrict__ G) {
+  chan_reduce_body(part + (long long)blockIdx.y * nblk * 5760, nblk, G + (long long)blockIdx.y * 5760);
+}
 
 // stage 3: normalise, softmax rows, emit block-diagonal weight Wbd[co][ci] (one thread per (row, column))
-__global__ __launch_bounds__(256) void chan_attn_weights_kernel(const float* __restrict__ G,
-                                                                const float* __restrict__ temperature,
-                                                                float* __restrict__ wbd) {
+__device__ __forceinline__ void chan_attn_weights_body(const float* __restrict__ G, const float* __restrict__ temperature,
+                                                       float* __restrict__ wbd) {
   const int row = blockIdx.x;                                // head*30 + i
   const int head = row / 30, i = row % 30;
   __shared__ float v[30];
@@ -109,6 +115,17 @@ __global__ __launch_bounds__(256) void chan_attn_weights_kernel(const float* __r
     const int j = c - head * 30;
     wbd[row * 180 + c] = (j >= 0 && j < 30) ? expf(v[j] - mx) / s : 0.f;
   }
+}
+__global__ __launch_bounds__(256) void chan_attn_weights_kernel(const float* __restrict__ G,
+                                                                const float* __restrict__ temperature,
+                                                                float* __restrict__ wbd) {
+  chan_attn_weights_body(G, temperature, wbd);
+}
+// grid (180, B): image blockIdx.y turns G [B][5760] into wbd [B][180][180]
+__global__ __launch_bounds__(256) void chan_attn_weights_images_kernel(const float* __restrict__ G,
+                                                                       const float* __restrict__ temperature,
+                                                                       float* __restrict__ wbd) {
+  chan_attn_weights_body(G + (long long)blockIdx.y * 5760, temperature, wbd + (long long)blockIdx.y * (180 * 180));
 }
 
 extern "C" int ff_chan_attn_weights(const float* qkv, int ld, int q_off, int k_off, long long N, const float* temperature,
@@ -137,6 +154,24 @@ extern "C" int ff_chan_attn_finish(float* work, long long work_floats, int nblk,
   hipLaunchKernelGGL(chan_reduce_kernel, dim3(5760 / 32), dim3(256), 0, st, work, nblk, G);
   hipLaunchKernelGGL(chan_attn_weights_kernel, dim3(180), dim3(64), 0, st, G, temperature, wbd);
   FF_LAUNCH_CHECK("ff_chan_attn_finish");
+  return FF_OK;
+}
+
+// ff_chan_attn_finish for B images in one pair of launches: work holds the partials [B][nblk][5760] that ONE ff_chan_qkv call on all
+// B * rows_per_image rows wrote (a partial is one 256-token workgroup's and rows_per_image % 256 == 0, so no partial mixes two images), then
+// G [B][5760].  Image b reduces its own nblk = rows_per_image / 256 blocks in the single-image order; wbd is [B][180][180].
+extern "C" int ff_chan_attn_finish_images(float* work, long long work_floats, int B, long long rows_per_image, const float* temperature,
+                                          float* wbd, void* stream) {
+  FF_CHECK_ARG(B > 0 && B <= 65535 && rows_per_image > 0 && rows_per_image % 256 == 0 && rows_per_image / 256 < (1LL << 31) / 5760,
+               "ff_chan_attn_finish_images: rows_per_image must be a positive multiple of 256 (1 <= B <= 65535; got B=%d rows_per_image=%lld)", B, rows_per_image);
+  FF_CHECK_ARG(work && temperature && wbd, "ff_chan_attn_finish_images: null pointer");
+  const int nblk = (int)(rows_per_image / 256);
+  FF_CHECK_ARG(work_floats >= (long long)B * (nblk + 1) * 5760, "ff_chan_attn_finish_images: workspace too small (need %lld floats)", (long long)B * (nblk + 1) * 5760);
+  hipStream_t st = (hipStream_t)stream;
+  float* G = work + (long long)B * nblk * 5760;
+  hipLaunchKernelGGL(chan_reduce_images_kernel, dim3(5760 / 32, B), dim3(256), 0, st, work, nblk, G);
+  hipLaunchKernelGGL(chan_attn_weights_images_kernel, dim3(180, B), dim3(64), 0, st, G, temperature, wbd);
+  FF_LAUNCH_CHECK("ff_chan_attn_finish_images");
   return FF_OK;
 }
 

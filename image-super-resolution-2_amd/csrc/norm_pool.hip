@@ -209,6 +209,31 @@ extern "C" int ff_pool_partials(const float* in, int ld, long long P, int C, flo
   return FF_OK;
 }
 
+// first stage of B images of P pixels each in one launch, grid (one image's chunks, B): part [B][ff_pool_partial_rows(P)][C], image b's rows
+// those of its own ff_pool_partials call, in their order (the kernels index the image by blockIdx.y); ff_pool_vec_mlp_images finishes them.
+// P must be a multiple of 256 (the images of a padded batch), so that every image's rows are 16-byte aligned like the first's.
+extern "C" long long ff_pool_partials_images_rows(int B, long long P) {
+  if (B <= 0 || B > 65535 || P <= 0 || P % 256) return -1;
+  return (long long)B * pool_chunks(P, nullptr);
+}
+extern "C" int ff_pool_partials_images(const float* in, int ld, int B, long long P, int C, float* part, long long part_floats, void* stream) {
+  FF_CHECK_ARG(B > 0 && B <= 65535 && P > 0 && P % 256 == 0,
+               "ff_pool_partials_images: the pixels per image must be a positive multiple of 256 (1 <= B <= 65535; got B=%d P=%lld)", B, P);
+  FF_CHECK_ARG(in && part && C > 0 && ld >= C, "ff_pool_partials_images: bad args");
+  int ppc;
+  const int nch = pool_chunks(P, &ppc);
+  FF_CHECK_ARG(part_floats >= (long long)B * nch * C, "ff_pool_partials_images: need %lld floats", (long long)B * nch * C);
+  const bool v4 = (C % 4 == 0) && (ld % 4 == 0) && (C / 4 <= 256) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)part & 15) == 0);
+  if (v4) {
+    const int cv = C / 4, rpi = 256 / cv;
+    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, B), dim3(256), (size_t)rpi * cv * 16, (hipStream_t)stream, in, ld, P, C, ppc, part);
+  } else {
+    hipLaunchKernelGGL(pool_partial_kernel, dim3(nch, B), dim3(256), 0, (hipStream_t)stream, in, ld, P, C, ppc, part);
+  }
+  FF_LAUNCH_CHECK("ff_pool_partials_images");
+  return FF_OK;
+}
+
 // second stage alone: out[c] = inv_count * sum_r part[r][c] over `rows` rows of pitch ld (per-workgroup partials written by a
 // producer kernel's epilogue, e.g. ff_conv3x3_halo pool_partials)
 extern "C" int ff_pool_finish(const float* part, int rows, int ld, int C, float inv_count, float* out, void* stream) {

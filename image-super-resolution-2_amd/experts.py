@@ -313,8 +313,19 @@ def dat_should_shift(g: int, b: int) -> bool:
 
 
 class DatHIP(_Trunk):
-    """DAT (dat_arch.py:864-1028): 6 residual groups x 6 DATB (spatial / channel alternating), dim 180."""
+    """DAT (dat_arch.py:864-1028): 6 residual groups x 6 DATB (spatial / channel alternating), dim 180.
 
+    forward(lr [B,3,h,w]) runs a batch through ONE launch per op in the fused modes.  DAT pads to multiples of 16, so an image is a
+    multiple of 256 token rows and neither a 256-token workgroup nor a GEMM tile straddles two images.  The per-image quantities are the
+    channel blocks' attention matrix wbd [B,180,180] (per-image reduction of the gram partials, per-image weight planes in the att GEMM)
+    and the channel gate cm [B,180] (per-image pool partials, one MLP workgroup per image, a per-image row in token_linear_gated); the
+    window, depth-wise, SGFN and 3x3 kernels index the image themselves.  Every choice of kernel route is made from ONE image's
+    dimensions, so each image comes out with the bits of its own B == 1 forward."""
+
+    # Batches are processed in chunks of at most this many padded tokens (B * Hp * Wp), as HatHIP does: activation memory grows to at most
+    # four times what one 256 x 256 tile allocates.  An attribute, not an environment switch.  forward() also keeps a chunk below the
+    # 32-bit bounds of what it launches, whatever this value says (see there).
+    max_batch_tokens = 262144
     name = "dat"
 
     def __init__(self, sd: SD, dev, prefix: str = "expert_ensemble.dat.", groups: int = 6, depth: int = 6, split=(8, 32),
@@ -365,7 +376,7 @@ class DatHIP(_Trunk):
             self.gconv.append((w.conv(f"layers.{g}.conv"), w(f"layers.{g}.conv.bias")))
 
     def block(self, x: T, blk: dict) -> T:
-        _, H, W, C = x.shape
+        B, H, W, C = x.shape
         half, hh = C // 2, self.heads // 2
         d = half // hh
         fused = ops.fused_modes()
@@ -393,7 +404,7 @@ class DatHIP(_Trunk):
         elif fused:
             # norm1 + qkv + per-head gram / norms over all tokens in one launch: only v reaches memory (dat_arch.py:617-641)
             cq = _packed(blk, "cq_pk", lambda: pack_chan_qkv(*blk["qkv"], self.heads, C // self.heads))
-            v, wbd = ops.chan_qkv_attn(x, cq, blk["n1"][0], blk["n1"][1], blk["temp"])
+            v, wbd = ops.chan_qkv_attn(x, cq, blk["n1"][0], blk["n1"][1], blk["temp"])      # B > 1: wbd [B,180,180], one matrix per image
         else:
             qkv = ops.linear(ops.layernorm(x, *blk["n1"]), *blk["qkv"])              # [1,H,W,3C] = q | k | v
             v = qkv[..., 2 * C:]
@@ -411,13 +422,14 @@ class DatHIP(_Trunk):
         else:
             if not fused:
                 wbd = ops.chan_attn_weights(qkv, 0, C, blk["temp"])
-            att = ops.linear(v, wbd, dynamic_w=True)
+            att = ops.linear(v, wbd, dynamic_w=True)                                 # (B > 1: image b's rows times wbd[b], one launch)
             ch_in, sp_in = att, conv_x
-        cm = ops.vec_mlp(ops.pool_partials(ch_in), *blk["ci1"], "gelu", *blk["ci4"], "sigmoid")          # [1,C]; pool finish inside the MLP launch
+        cm = ops.vec_mlp(ops.pool_partials(ch_in), *blk["ci1"], "gelu", *blk["ci4"], "sigmoid")          # [B,C]; pool finish inside the MLP launch
         if fused:
             # spatial gate (from sp_in, applied to ch_in) + channel gate (applied to sp_in) + projection + residual in one launch
             gp = _packed(blk, "gp_pk", lambda: pack_token_linear_gated(*blk["proj"], *blk["si0"], blk["si3"][0]))
-            x = ops.token_linear_gated(sp_in, ch_in, gp, cm.reshape(-1), blk["si3b"], res=x)
+            # cm [B,180]: one launch for the batch, image b gated by its own row
+            x = ops.token_linear_gated(sp_in, ch_in, gp, cm if B > 1 else cm.reshape(-1), blk["si3b"], res=x)
             return self._sgfn(x, blk)
         sm = ops.linear(ops.linear(sp_in, *blk["si0"], act="gelu"), *blk["si3"], act="sigmoid")          # [1,H,W,1]
         if blk["spatial"]:
@@ -446,6 +458,37 @@ class DatHIP(_Trunk):
         return ops.linear(z, *blk["fc2"], res=x)
 
     def forward(self, lr: T, taps: Optional[dict] = None, feats: Optional[dict] = None, out: Optional[T] = None) -> T:
+        """lr [B,3,h,w] -> [B,3,4h,4w] (written into `out` when given).  feats (optional dict): receives feats["dat"] (_Trunk._exit).
+        B > 1: one launch per op for the whole batch in the fused modes (chunks of max_batch_tokens padded tokens), the per-image
+        loop in f32 mode (its channel attention and dynamic-weight GEMM are single-image); either way bit-equal to B single forwards.
+        taps are recorded for B == 1 only."""
+        B, _, h, w = lr.shape
+        Hp, Wp = _ceil_to(h, 16), _ceil_to(w, 16)
+        if B > 1:
+            if taps is not None:
+                raise ops._lib.FFError("DatHIP.forward: taps are recorded for B == 1 only")
+            nb = 1                                          # images per chunk
+            if ops.fused_modes():
+                # Two launches index the whole chunk in 32 bits: the LDS-resident 3x3 kernel (ops.conv2d keeps it to inputs of fewer
+                # than 2^31 elements; the largest is the last convolution's, 16 Hp Wp pixels at a pitch of 64) and ff_sgfn_tail (B H W
+                # rows of fc1's output at its pitch).  A chunk stays under both whatever max_batch_tokens says, so a batch never
+                # leaves the route its images take alone.
+                ldh = _ceil_to(self.blocks[0][0]["fc1"][0].shape[0], 32)
+                nb = max(1, min(int(self.max_batch_tokens) // (Hp * Wp), (2 ** 31 - 1) // (16 * Hp * Wp * 64), (2 ** 31 - 1) // (Hp * Wp * ldh)))
+            if nb < B:                                      # every chunk writes its slice of the one output (and feature) buffer
+                if out is None:
+                    out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
+                fall = ops.empty_rows((B, Hp, Wp, self.after[0].shape[0]), lr.device) if feats is not None else None
+                for b0 in range(0, B, nb):
+                    self._forward_chunk(lr[b0:b0 + nb], None, {} if feats is not None else None, out[b0:b0 + nb],
+                                        fall[b0:b0 + nb] if feats is not None else None)
+                if feats is not None:
+                    feats["dat"] = fall
+                return out
+        return self._forward_chunk(lr, taps, feats, out, None)
+
+    def _forward_chunk(self, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], feat_out: Optional[T]) -> T:
+        """One launch per op for all of lr [B,3,h,w]; feat_out: where the hooked feature goes (a slice of the batch's buffer)."""
         _, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, 16), _ceil_to(w, 16)
         feat = self._enter(lr, Hp, Wp)
@@ -456,8 +499,8 @@ class DatHIP(_Trunk):
                 y = self.block(y, blk)
                 if taps is not None and g < 2:
                     taps[f"dat.g{g}.b{b}"] = y
-            x = ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x)
-        return self._exit(x, feat, h, w, feats, out)
+            x = ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x, per_image=True)
+        return self._exit(x, feat, h, w, feats, out, feat_out)
 
 
 # =============================================================================================== NAFNet-SR

@@ -26,8 +26,8 @@ T = torch.Tensor
 
 
 def _per_image(lr: T, fn) -> list:
-    """[fn(b, lr[b:b+1]) for every image b of a contiguous batch]: the one place where what is not batched yet (DAT, the
-    fusion stack) is sequenced image by image; B == 1 is a batch of one.  An image that does not start on a 16-byte boundary (odd
+    """[fn(b, lr[b:b+1]) for every image b of a contiguous batch]: the one place where what is not batched yet (the fusion
+    stack) is sequenced image by image; B == 1 is a batch of one.  An image that does not start on a 16-byte boundary (odd
     image sizes) is copied, since the kernels take 16-byte aligned images.  The copy is a torch op, which a recorded plan (plan.py)
     cannot carry: forward() refuses to record such a batch."""
     res = []
@@ -92,24 +92,25 @@ class FreqFusionHIP:
         """ExpertEnsemble.forward_all (expert_loader.py:768-777) for a batch lr [B,3,h,w]: (hat [B,3,4h,4w], [dat_b], [nafnet_b],
         [pre_b or None]).  The three experts are independent until the fusion stack, so each runs on its own HIP stream (_fork; the
         whole fan-out is captured into the HIP graph): latency-bound kernels of one expert overlap with bandwidth-bound kernels of
-        another.  HAT takes the whole batch on the caller's stream, DAT runs for b = 0 .. B-1 on side stream 1, NAFNet takes the whole
-        batch (NafnetHIP.forward: one launch per op) and then (with_pre) the LR-only part of the fusion stack (FusionHIP.pre) runs for
-        each b, both on side stream 2, the shortest expert's.  On one stream, and
+        another.  Every expert takes the whole batch through one launch per op (HatHIP / DatHIP / NafnetHIP.forward): HAT on the
+        caller's stream, DAT on side stream 1, NAFNet and then (with_pre) the LR-only part of the fusion stack (FusionHIP.pre), which
+        runs for each b, on side stream 2, the shortest expert's.  On one stream, and
         with taps, the experts run one after the other and pre is left to fusion.forward."""
         if not self.multi_stream or taps is not None:
             hat = self.hat.forward(lr, taps)
-            dats = _per_image(lr, lambda b, x: self.dat.forward(x, taps))
+            dat = self.dat.forward(lr, taps)
             naf = self.nafnet.forward(lr, taps)
-            return hat, dats, [naf[b:b + 1] for b in range(lr.shape[0])], [None] * lr.shape[0]
+            return hat, [dat[b:b + 1] for b in range(lr.shape[0])], [naf[b:b + 1] for b in range(lr.shape[0])], [None] * lr.shape[0]
         with self._fork(mark=True) as (s1, s2, made):
             with torch.cuda.stream(s1):
-                dats = _per_image(lr, lambda b, x: self.dat.forward(x))
+                dat = self.dat.forward(lr)
             with torch.cuda.stream(s2):
                 naf = self.nafnet.forward(lr)
                 pres = _per_image(lr, lambda b, x: self.fusion.pre(x) if with_pre else None)
             hat = self.hat.forward(lr)
+            dats = [dat[b:b + 1] for b in range(lr.shape[0])]
             nafs = [naf[b:b + 1] for b in range(lr.shape[0])]
-            made += (*dats, naf, *(t for pre in pres if pre is not None for t in pre.values()))
+            made += (dat, naf, *(t for pre in pres if pre is not None for t in pre.values()))
         return hat, dats, nafs, pres
 
     def experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = False):
@@ -126,8 +127,8 @@ class FreqFusionHIP:
         The payload of the cached-expert files (isr2_amd/cache.py).  streams=True runs the same launches with DAT and NAFNet (and
         their feature resizes) on the two side streams of forward(), forked from and joined to the caller's stream: the same bits,
         the small grids of one expert beside those of another (cache.build_from_folders).
-        HAT and NAFNet run the batch through one launch per op; DAT runs image by image into slices of its output.  Every
-        image's tensors are those of its own B == 1 call, bit for bit."""
+        All three experts run the batch through one launch per op.  Every image's tensors are those of its own B == 1 call, bit
+        for bit."""
         if lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3:
             raise _lib.FFError(f"expected lr of shape [B,3,h,w], got {tuple(lr.shape)}")
         lr = lr.to(self.dev, torch.float32).contiguous()
@@ -136,10 +137,7 @@ class FreqFusionHIP:
 
         def fwd(name):                                         # -> (SR output [B,3,4h,4w], [hooked NHWC features])
             raw = {}
-            if name != "dat":
-                return nets[name].forward(lr, feats=raw), [raw[name]]
-            o = torch.empty((B, 3, 4 * h, 4 * w), device=self.dev, dtype=torch.float32)
-            return o, _per_image(lr, lambda b, x: (nets[name].forward(x, feats=raw, out=o[b:b + 1]), raw[name])[1])
+            return nets[name].forward(lr, feats=raw), [raw[name]]
 
         with torch.cuda.device(self.dev):
             if streams:
@@ -186,9 +184,9 @@ class FreqFusionHIP:
         lr = lr.to(self.dev, torch.float32).contiguous()
         B, _, h, w = lr.shape
         # Every global op of the path is per image (average pools, channel attention statistics, rFFT2, squeeze gates), so a batch is
-        # B independent images.  HAT and NAFNet take the whole batch through one launch per op (HatHIP.forward, NafnetHIP.forward: their
-        # only per-image quantities, the channel-attention gate [B,180] and the SCA vector [B,c], are matrices); DAT and the fusion stack
-        # are still sequenced per image (_per_image).
+        # B independent images.  The three experts take the whole batch through one launch per op (HatHIP / DatHIP / NafnetHIP.forward:
+        # their per-image quantities -- HAT's channel-attention gate [B,180], DAT's attention matrix [B,180,180] and channel gate [B,180],
+        # NAFNet's SCA vector [B,c] -- are matrices); the fusion stack is still sequenced per image (_per_image).
         # Bit-identical to B single forwards: every image runs the launches, in the forms, of its own B == 1 forward.
         if B > 1 and taps is not None:
             raise _lib.FFError("taps are recorded for B == 1 only")

@@ -453,7 +453,14 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
     gate_pairs: SimpleGate in the epilogue, [..., N / 2] out with out[j] = y[2j] * y[2j+1] (rows of w interleaved by the caller).
     bf16 x (plain-bf16 mode, rows_gemm_ok shapes): ff_gemm_rows_bf16, bit-equal to the fp32-rows kernel on x.float(); out_bf16 stores
     the gated output as bf16 rows for the next such GEMM.  rows_gemm: fp32 x through the same kernel (A staged through registers; the
-    only form that takes kmul), again bit-equal; without it fp32 x stays on ff_conv2d_bf16s."""
+    only form that takes kmul), again bit-equal; without it fp32 x stays on ff_conv2d_bf16s.
+    w [B, N, K] with B > 1 (dynamic_w=True, split-bf16 modes): the rows are B equal groups of a multiple of 256 rows, group b multiplied by
+    w[b], in one launch (ff_conv2d_bf16s_wimages) -- every group with the bits of its own call with w[b]."""
+    if w.dim() == 3 and w.shape[0] > 1:
+        return _linear_wimages(x, w, bias, act=act, res=res, mul=mul, alpha=alpha, out=out, dynamic_w=dynamic_w, kmul=kmul,
+                               gate_pairs=gate_pairs, out_bf16=out_bf16, tile_hint=tile_hint, rows_gemm=rows_gemm)
+    if w.dim() == 3:                                         # one image: the single-weight entry
+        w = w[0]
     if x.dtype == torch.bfloat16 or rows_gemm:
         return _linear_rows_bf16(x, w, bias, act=act, res=res, mul=mul, alpha=alpha, out=out, dynamic_w=dynamic_w, kmul=kmul,
                                  gate_pairs=gate_pairs, out_bf16=out_bf16, tile_hint=tile_hint)
@@ -495,6 +502,39 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
                                             rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
                                             float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], 0, _ptr(kmul), _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K + N * K + rows * No * (2 if res is not None else 1)))
+    return out
+
+
+def _linear_wimages(x: T, w: T, bias, *, act, res, mul, alpha, out, dynamic_w, kmul, gate_pairs, out_bf16, tile_hint, rows_gemm) -> T:
+    """linear with one weight matrix per image, w [B, N, K].  Every refusal comes before the weight split and the launch."""
+    _chk(w, "linear.w")
+    B, N, K = w.shape
+    if _GEMM_MODE == "f32" or not dynamic_w or not w.is_contiguous():
+        raise _lib.FFError("linear: per-image weights [B, N, K] are contiguous dynamic weights (dynamic_w=True) of the split-bf16 modes")
+    if (x.dtype != torch.float32 or rows_gemm or kmul is not None or gate_pairs or out_bf16 or tile_hint or act is not None
+            or alpha != 1.0):
+        raise _lib.FFError("linear: per-image weights come with fp32 rows and the (bias, * mul, + res) epilogue only")
+    xp, ldi, rows, xk = rows_view(x, "linear.x")
+    if xk != K or rows % B or (rows // B) % 256:
+        raise _lib.FFError(f"linear: per-image weights {tuple(w.shape)} need [rows, {K}] input with B = {B} equal groups of a multiple of "
+                           f"256 rows, got {rows} rows of {xk}")
+    if ldi % 4 or xp % 16 or K % 4 or N % 4:
+        raise _lib.FFError("linear: per-image weights need 16-byte aligned rows, K % 4 == 0 and N % 4 == 0")
+    oshape = tuple(x.shape[:-1]) + (N,)
+    if out is None:
+        out = empty_rows(oshape, x.device)
+    op, ldo, orows, oc = rows_view(out, "linear.out")
+    if orows != rows or oc != N or ldo % 4 or op % 16:
+        raise _lib.FFError("linear: out shape mismatch (per-image weights: 16-byte aligned rows)")
+    rp, ldr = None, 0
+    if res is not None:
+        rp, ldr, rrows, rc = rows_view(res, "linear.res")
+        if rrows != rows or rc != N or ldr % 4 or rp % 16:
+            raise _lib.FFError("linear: res shape mismatch (per-image weights: 16-byte aligned rows)")
+    hi, lo, Kp, Cp, _ = _split_weight(w.reshape(B * N, K), True, K)        # rows are split independently: image b's planes at [b * N, (b + 1) * N)
+    _lib.check(_L().ff_conv2d_bf16s_wimages(xp, ldi, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, B, rows // B,
+                                            _ptr(bias), _ptr(mul), rp, ldr, op, ldo, rows, K, N, GEMM_MODES[_GEMM_MODE], 0, _stream()))
+    _note(2.0 * rows * N * K, 4.0 * (rows * K + B * N * K + rows * N * (2 if res is not None else 1)))
     return out
 
 
@@ -869,11 +909,18 @@ def layernorm(x: T, gamma: T, beta: T, eps: float = 1e-5, out: Optional[T] = Non
 
 
 def pool_partials(x: T):
-    """First stage of the global average pool of one image [1,H,W,C] -> PoolPartials (vec_mlp finishes them in its own launch)."""
+    """First stage of the global average pool of x [B,H,W,C] -> PoolPartials (vec_mlp finishes them in its own launch).  B > 1: one
+    launch for the batch (ff_pool_partials_images; H * W a multiple of 256), PoolPartials(images=B) holding image b's rows as its own
+    B == 1 call writes them."""
     xp, ld, B, H, W, C = _nhwc(x, "pool_partials.x")
-    if B != 1:
-        return pool_mean(x)
     P = H * W
+    if B != 1:
+        if B < 1 or P % 256:
+            raise _lib.FFError(f"pool_partials: a batch needs images of a multiple of 256 pixels, got {tuple(x.shape)}")
+        rows = int(_L().ff_pool_partials_images_rows(B, P))
+        part = torch.empty((rows, C), device=x.device, dtype=torch.float32)
+        _lib.check(_L().ff_pool_partials_images(xp, ld, B, P, C, part.data_ptr(), part.numel(), _stream()))
+        return PoolPartials(part, C, 1.0 / float(P), images=B)
     rows = int(_L().ff_pool_partial_rows(P))
     part = torch.empty((rows, C), device=x.device, dtype=torch.float32)
     _lib.check(_L().ff_pool_partials(xp, ld, P, C, part.data_ptr(), part.numel(), _stream()))
@@ -960,11 +1007,20 @@ def dwconv2d(x: T, w_tap: T, bias: Optional[T] = None, *, ksize=(3, 3), stride=(
 
 def token_linear_gated(x: T, x2: T, pk: dict, cm: T, gb2: float, *, res: Optional[T] = None) -> T:
     """res + W (x * cm[channel] + x2 * sm[token]) + b with sm = sigmoid(gw2 . gelu(GW1 x + gb1) + gb2) in one launch (bf16x3);
-    pk from prep.pack_token_linear_gated."""
+    pk from prep.pack_token_linear_gated.  cm [K] (or [1,K]): one channel gate for every row.  cm [B,K] with B > 1: the rows are B images of
+    a multiple of 256 rows each, image b gated by cm[b], in one launch (ff_token_linear_gated_images) -- bit-equal to B calls."""
     xp, ldx, rows, K = rows_view(x, "token_linear_gated.x")
     x2p, ldx2, r2, k2 = rows_view(x2, "token_linear_gated.x2")
-    if r2 != rows or k2 != K or K != pk["K"] or cm.numel() != K:
+    _chk(cm, "token_linear_gated.cm")
+    if r2 != rows or k2 != K or K != pk["K"]:
         raise _lib.FFError("token_linear_gated: shape mismatch")
+    images = 1
+    if cm.numel() != K:                                      # (refusals first: nothing is launched before them)
+        if cm.dim() != 2 or cm.shape[1] != K or cm.shape[0] < 1 or not cm.is_contiguous():
+            raise _lib.FFError(f"token_linear_gated: cm must be [{K}] or one contiguous row per image [B,{K}], got {tuple(cm.shape)}")
+        images = int(cm.shape[0])
+        if rows % images or (rows // images) % 256:
+            raise _lib.FFError(f"token_linear_gated: a per-image gate needs B = {images} images of a multiple of 256 rows, got {rows} rows")
     N = pk["N"]
     out = empty_rows(tuple(x.shape[:-1]) + (N,), x.device)
     op, ldo, _, _ = rows_view(out, "token_linear_gated.out")
@@ -973,8 +1029,13 @@ def token_linear_gated(x: T, x2: T, pk: dict, cm: T, gb2: float, *, res: Optiona
         rp, ldr, rr, rc = rows_view(res, "token_linear_gated.res")
         if rr != rows or rc != N:
             raise _lib.FFError("token_linear_gated: res shape mismatch")
-    _lib.check(_L().ff_token_linear_gated(xp, ldx, x2p, ldx2, cm.data_ptr(), None, pk["gb1"].data_ptr(), pk["gw2"].data_ptr(), float(gb2),
-                                          op, ldo, rows, K, N, pk["nt"], pk["w"].data_ptr(), pk["b"].data_ptr(), rp, ldr, _nterms(), _stream()))
+    if images > 1:
+        _lib.check(_L().ff_token_linear_gated_images(xp, ldx, x2p, ldx2, cm.data_ptr(), images, rows // images, pk["gb1"].data_ptr(),
+                                                     pk["gw2"].data_ptr(), float(gb2), op, ldo, rows, K, N, pk["nt"], pk["w"].data_ptr(),
+                                                     pk["b"].data_ptr(), rp, ldr, _nterms(), _stream()))
+    else:
+        _lib.check(_L().ff_token_linear_gated(xp, ldx, x2p, ldx2, cm.data_ptr(), None, pk["gb1"].data_ptr(), pk["gw2"].data_ptr(), float(gb2),
+                                              op, ldo, rows, K, N, pk["nt"], pk["w"].data_ptr(), pk["b"].data_ptr(), rp, ldr, _nterms(), _stream()))
     _note(2.0 * rows * N * K + 2.0 * rows * 32 * K, 4.0 * rows * (2 * K + N * (2 if res is not None else 1)))
     return out
 
@@ -1229,10 +1290,28 @@ def chan_attn_weights(qkv: T, q_off: int, k_off: int, temperature: T) -> T:
 
 def chan_qkv_attn(x: T, pk: dict, gamma: T, beta: T, temperature: T, eps: float = 1e-5):
     """DAT channel attention front end in two launches (ff_chan_qkv + ff_chan_attn_finish): x [..., 180] ->
-    (v [..., 180], block-diagonal attention matrix [180, 180]); q and k never reach memory."""
+    (v [..., 180], block-diagonal attention matrix [180, 180]); q and k never reach memory.
+    x [B,H,W,180] with B > 1 (H * W a multiple of 256): still two launches -- ff_chan_qkv's partials are per 256-token workgroup, so one call
+    covers the batch, and ff_chan_attn_finish_images reduces every image's own blocks in the single-image order -> wbd [B,180,180], every
+    image's matrix (and v) with the bits of its own call."""
     xp, ldx, rows, K = rows_view(x, "chan_qkv_attn.x")
     if K != pk["K"]:
         raise _lib.FFError("chan_qkv_attn: K mismatch")
+    images = int(x.shape[0]) if x.dim() == 4 and x.shape[0] > 1 else 1
+    if images > 1:
+        if (rows // images) % 256:
+            raise _lib.FFError(f"chan_qkv_attn: a batch needs images of a multiple of 256 tokens, got {tuple(x.shape)}")
+        v = empty_like_rows(x)
+        vp, ldv, _, _ = rows_view(v, "chan_qkv_attn.v")
+        nwork = int(_L().ff_chan_qkv_images_workspace(images, rows // images))
+        work = torch.empty(nwork, device=x.device, dtype=torch.float32)
+        wbd = torch.empty((images, 180, 180), device=x.device, dtype=torch.float32)
+        _lib.check(_L().ff_chan_qkv(xp, ldx, rows, K, gamma.data_ptr(), beta.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b"].data_ptr(),
+                                    vp, ldv, work.data_ptr(), nwork, _nterms(), _stream()))
+        _lib.check(_L().ff_chan_attn_finish_images(work.data_ptr(), nwork, images, rows // images, temperature.data_ptr(), wbd.data_ptr(),
+                                                   _stream()))
+        _note(2.0 * rows * 576 * K + 2.0 * rows * 6 * 32 * 32, 8.0 * rows * K)
+        return v, wbd
     v = empty_like_rows(x)
     vp, ldv, _, _ = rows_view(v, "chan_qkv_attn.v")
     nwork = int(_L().ff_chan_qkv_workspace(rows))

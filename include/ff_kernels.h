@@ -74,6 +74,14 @@ int ff_conv2d_bf16s_kmul_images(const float* in, int ldi, const void* w_hi, cons
                                 long long M, int Cin, int Cout, int nterms, int tile_hint, void* stream);
 int ff_split_bf16(const float* w, int N, int K, int Kp, int Cin, int Cp, void* hi, void* lo, void* stream);
 
+/* A 1x1 GEMM over B images with one weight matrix PER IMAGE: in [M][ldi], M == B * rows_per_image (rows_per_image % 256 == 0: no m-tile
+ * straddles two images), planes w_hi / w_lo [B][Cout][Kp] (ff_split_bf16 on the [B * Cout][Cin] matrix).  Same K order and epilogue
+ * ((acc + bias) * mul + res, 16-byte rows) as ff_conv2d_bf16s: every row is bit-equal to the single call on its image with its planes;
+ * tile_hint <= 0 takes ff_conv2d_bf16s_tile of ONE image's rows.  DAT's att = v . wbd^T.  Added under ABI version 7 (additive). */
+int ff_conv2d_bf16s_wimages(const float* in, int ldi, const void* w_hi, const void* w_lo, int Kp, int Cp, int B, int rows_per_image,
+                            const float* bias, const float* mul, const float* res, int ldr, float* out, int ldo, long long M, int Cin,
+                            int Cout, int nterms, int tile_hint, void* stream);
+
 /* GEMM on bf16 ROWS, plain bf16 (csrc/gemm_rows_bf16.hip): out[M][N] = epilogue(A[M][K] . W[N][K]^T), bit-equal to
  * ff_conv2d_bf16s(1x1, nterms = 1) on the fp32 upcast of A -- the same MFMA, k order and epilogue arithmetic -- with both operands
  * fetched by LDS-DMA.  a: bf16 [M][lda]; w_hi: the hi plane of ff_split_bf16 [N][Kp].  Needs K % 64 == 0, Kp == K, lda % 8 == 0
@@ -253,6 +261,11 @@ int ff_token_linear(const float* x, int ldx, float* out, int ldo, long long M, i
 int ff_token_linear_gated(const float* x, int ldx, const float* x2, int ldx2, const float* cm, const float* gw1t, const float* gb1,
                           const float* gw2, float gb2, float* out, int ldo, long long M, int K, int N, int n_tiles,
                           const void* w_tiles, const float* bias_padded, const float* res, int ldr, int nterms, void* stream);
+/* ff_token_linear_gated over B images of rows_per_image tokens (a multiple of 256: a workgroup's 256 tokens are one image's) with one
+ * channel gate per image, cm [B][K]; M == B * rows_per_image.  Bit-equal to B single calls.  Added under ABI version 7 (additive). */
+int ff_token_linear_gated_images(const float* x, int ldx, const float* x2, int ldx2, const float* cm, int B, long long rows_per_image,
+                                 const float* gb1, const float* gw2, float gb2, float* out, int ldo, long long M, int K, int N, int n_tiles,
+                                 const void* w_tiles, const float* bias_padded, const float* res, int ldr, int nterms, void* stream);
 
 /* NAFNet block fusions (csrc/naf_fused.hip).
  * ff_dwconv3_gate_pool: out[p][c] = dw3x3(in)[p][c] * dw3x3(in)[p][C + c] (conv2 + SimpleGate, nafnet_arch.py:78-81,51-52)
@@ -335,6 +348,11 @@ int ff_vec_mlp(const float* in, int B, int Cin, const float* W1, const float* b1
  * ff_pool_vec_mlp or ff_pool_finish (inv_count = 1 / P, ld = C). */
 int ff_pool_partial_rows(long long P);
 int ff_pool_partials(const float* in, int ld, long long P, int C, float* part, long long part_floats, void* stream);
+/* The same for B images of P pixels each (P % 256 == 0) in one launch: part [B][ff_pool_partial_rows(P)][C], image b's rows those of its
+ * own ff_pool_partials call in their order; ff_pool_partials_images_rows = B * ff_pool_partial_rows(P) (-1 for a refused geometry).
+ * Finish with ff_pool_vec_mlp_images.  Added under ABI version 7 (additive). */
+long long ff_pool_partials_images_rows(int B, long long P);
+int ff_pool_partials_images(const float* in, int ld, int B, long long P, int C, float* part, long long part_floats, void* stream);
 
 /* ff_pool_finish + the two-layer ff_vec_mlp in one single-workgroup launch (one image, hidden width <= 64):
  *   v[c] = inv_count * sum_r part[r][c] (r < rows, pitch ld);  out = act2(W2 . act1(W1 . v + b1) + b2) * post;
@@ -469,6 +487,13 @@ long long ff_chan_qkv_workspace(long long M);
 int ff_chan_qkv(const float* x, int ldx, long long M, int K, const float* gamma, const float* beta, float eps, const void* w_tiles,
                 const float* bias_padded, float* v_out, int ldv, float* work, long long work_floats, int nterms, void* stream);
 int ff_chan_attn_finish(float* work, long long work_floats, int nblk, const float* temperature, float* wbd, void* stream);
+/* B images: ONE ff_chan_qkv call on all B * rows_per_image rows (rows_per_image % 256 == 0, so every 256-token partial is one image's)
+ * leaves partials [B][nblk][5760] in work; ff_chan_attn_finish_images reduces image b's nblk = rows_per_image / 256 blocks in the
+ * single-image order (G [B][5760] follows the partials) and emits wbd [B][180][180].  work: ff_chan_qkv_images_workspace floats = B times
+ * one image's (-1 for a refused geometry).  Added under ABI version 7 (additive). */
+long long ff_chan_qkv_images_workspace(int B, long long rows_per_image);
+int ff_chan_attn_finish_images(float* work, long long work_floats, int B, long long rows_per_image, const float* temperature, float* wbd,
+                               void* stream);
 
 /* Fusion-stack pointwise kernels (see csrc/fusion_ops.hip for the reference lines). */
 int ff_band_mha_core(const float* qkv, float* out, long long P, int nbands, int heads, void* stream);

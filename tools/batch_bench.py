@@ -1,4 +1,4 @@
-"""Batched HAT and NAFNet against the sequential loop over the same images, on one MI355X, in one process:
+"""Batched HAT, DAT and NAFNet against the sequential loop over the same images, on one MI355X, in one process:
     python tools/batch_bench.py [--cases 64x64x5,64x64x16,256x256x2] [--modes bf16,bf16x3] [--reps 5] [--rounds 5] [--json PATH]
 hat:     HatHIP.forward(lr [B,3,h,w]) (one launch per op for the batch) and the loop `for b: HatHIP.forward(lr[b:b+1])`, each captured
          into one HIP graph and replayed between device events, alternating over --rounds rounds; medians and min..max per form.  The
@@ -6,9 +6,9 @@ hat:     HatHIP.forward(lr [B,3,h,w]) (one launch per op for the batch) and the 
          batch's median is larger than the loop's own min..max spread over the rounds, i.e. whether the gap is more than noise
          (`loss_exceeds_loop_spread`: the same for a batch that is SLOWER than the loop).
 nafnet:  the same two forms of NafnetHIP.forward, the same protocol.
+dat:     the same two forms of DatHIP.forward, the same protocol.
 streams: what each of the three streams of model.experts_with_features carries for one group of --group patches of 64x64 (the cache
-         builder's unit): HAT batched, DAT patch by patch, NAFNet batched (and both patch by patch), each graph-replayed alone -- the
-         longest bounds the group.
+         builder's unit): HAT, DAT and NAFNet batched and patch by patch, each graph-replayed alone -- the longest bounds the group.
 One JSON line per section; --json also writes them to a file."""
 import argparse
 import json
@@ -62,7 +62,7 @@ def _alternate(graphs, reps, rounds):
 
 
 def expert_section(a, hat, ops, name):
-    """`hat` is the expert (HatHIP or NafnetHIP).  NAFNet's zero-padded input belongs to the graphs that are captured here."""
+    """`hat` is the expert (HatHIP, DatHIP or NafnetHIP).  NAFNet's zero-padded input belongs to the graphs that are captured here."""
     res = []
     key = (id(hat), "batch_bench", name)
     ops.set_capture_key(key)
@@ -117,6 +117,7 @@ def streams_section(a, model, ops):
     try:
         graphs = {"hat_batched": _capture(lambda: model.hat.forward(lr, feats={}))[0],
                   "hat_per_patch": _capture(per_patch(model.hat))[0],
+                  "dat_batched": _capture(lambda: model.dat.forward(lr, feats={}))[0],
                   "dat_per_patch": _capture(per_patch(model.dat))[0],
                   "nafnet_batched": _capture(lambda: model.nafnet.forward(lr, feats={}))[0],
                   "nafnet_per_patch": _capture(per_patch(model.nafnet))[0]}
@@ -125,11 +126,12 @@ def streams_section(a, model, ops):
     ms = _alternate(graphs, a.reps, a.rounds)
     st = {k: _stats(v) for k, v in ms.items()}
     now = {k: st[k]["median"] for k in ("hat_batched", "dat_per_patch", "nafnet_batched")}
+    allb = {k: st[k]["median"] for k in ("hat_batched", "dat_batched", "nafnet_batched")}
     after = {k: st[k]["median"] for k in ("hat_batched", "dat_per_patch", "nafnet_per_patch")}
     before = {k: st[k]["median"] for k in ("hat_per_patch", "dat_per_patch", "nafnet_per_patch")}
     out = {"section": "streams", "mode": a.streams_mode, "group": B, "patch": p, "ms_per_group": st,
            "longest_stream_per_patch_hat": max(before, key=before.get), "longest_stream_batched_hat": max(after, key=after.get),
-           "longest_stream_batched_hat_nafnet": max(now, key=now.get)}
+           "longest_stream_batched_hat_nafnet": max(now, key=now.get), "longest_stream_all_batched": max(allb, key=allb.get)}
     graphs.clear()
     torch.cuda.synchronize()
     ops.drop_persistent(key=key)
@@ -144,7 +146,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="alternating rounds; medians and min..max are reported")
     ap.add_argument("--group", type=int, default=5, help="streams section: patches per group")
     ap.add_argument("--streams-mode", default="bf16x3")
-    ap.add_argument("--section", default="all", choices=("all", "hat", "nafnet", "streams"))
+    ap.add_argument("--section", default="all", choices=("all", "hat", "nafnet", "dat", "streams"))
     ap.add_argument("--json")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -160,6 +162,9 @@ def main():
             print(json.dumps(out[-1]), flush=True)
         if a.section in ("all", "nafnet"):
             out.append(expert_section(a, model.nafnet, ops, "nafnet"))
+            print(json.dumps(out[-1]), flush=True)
+        if a.section in ("all", "dat"):
+            out.append(expert_section(a, model.dat, ops, "dat"))
             print(json.dumps(out[-1]), flush=True)
         if a.section in ("all", "streams"):
             out.append(streams_section(a, model, ops))
