@@ -8,17 +8,20 @@
 //   layout    NCHW image <-> NHWC working tensors, mean shift, reflect/zero padding, crop, clamp
 #include "ff_common.h"
 
-__global__ __launch_bounds__(256) void mix2_kernel(float* __restrict__ out, int ldo, const float* __restrict__ a, int lda,
-                                                   const float* __restrict__ b, int ldb, long long rows, int C, float ka,
-                                                   float kb, const float* __restrict__ ca, const float* __restrict__ cb,
-                                                   const float* __restrict__ pa, int ldpa, const float* __restrict__ pb,
-                                                   int ldpb, int clamp01) {
+// IMAGES: the rows are equal groups of rows_per_image rows (one image each) and ca is [B][C], a scale per image and channel.
+template <bool IMAGES>
+__device__ __forceinline__ void mix2_body(float* __restrict__ out, int ldo, const float* __restrict__ a, int lda,
+                                          const float* __restrict__ b, int ldb, long long rows, int C, float ka,
+                                          float kb, const float* __restrict__ ca, const float* __restrict__ cb,
+                                          const float* __restrict__ pa, int ldpa, const float* __restrict__ pb,
+                                          int ldpb, int clamp01, long long rows_per_image) {
   const long long total = rows * C;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long r = i / C;
     const int c = (int)(i - r * C);
     float v = ka * a[r * lda + c];
-    if (ca) v *= ca[c];
+    if (IMAGES) v *= ca[(r / rows_per_image) * C + c];
+    else if (ca) v *= ca[c];
     if (pa) v *= pa[r * ldpa];
     if (b) {
       float u = kb * b[r * ldb + c];
@@ -30,6 +33,20 @@ __global__ __launch_bounds__(256) void mix2_kernel(float* __restrict__ out, int 
     out[r * ldo + c] = v;
   }
 }
+__global__ __launch_bounds__(256) void mix2_kernel(float* __restrict__ out, int ldo, const float* __restrict__ a, int lda,
+                                                   const float* __restrict__ b, int ldb, long long rows, int C, float ka,
+                                                   float kb, const float* __restrict__ ca, const float* __restrict__ cb,
+                                                   const float* __restrict__ pa, int ldpa, const float* __restrict__ pb,
+                                                   int ldpb, int clamp01) {
+  mix2_body<false>(out, ldo, a, lda, b, ldb, rows, C, ka, kb, ca, cb, pa, ldpa, pb, ldpb, clamp01, 0);
+}
+__global__ __launch_bounds__(256) void mix2_images_kernel(float* __restrict__ out, int ldo, const float* __restrict__ a, int lda,
+                                                          const float* __restrict__ b, int ldb, long long rows, int C, float ka,
+                                                          float kb, const float* __restrict__ ca, const float* __restrict__ cb,
+                                                          const float* __restrict__ pa, int ldpa, const float* __restrict__ pb,
+                                                          int ldpb, int clamp01, long long rows_per_image) {
+  mix2_body<true>(out, ldo, a, lda, b, ldb, rows, C, ka, kb, ca, cb, pa, ldpa, pb, ldpb, clamp01, rows_per_image);
+}
 
 extern "C" int ff_mix2(float* out, int ldo, const float* a, int lda, const float* b, int ldb, long long rows, int C,
                        float ka, float kb, const float* ca, const float* cb, const float* pa, int ldpa,
@@ -40,6 +57,22 @@ extern "C" int ff_mix2(float* out, int ldo, const float* a, int lda, const float
   hipLaunchKernelGGL(mix2_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, out, ldo, a, lda, b, ldb, rows, C,
                      ka, kb, ca, cb, pa, ldpa, pb, ldpb, clamp01);
   FF_LAUNCH_CHECK("ff_mix2");
+  return FF_OK;
+}
+
+// ff_mix2 with one channel scale per image: rows = B * rows_per_image, ca [B][C] (required); everything else as ff_mix2.  The value of an
+// element is computed by one thread from its own operands, so every image comes out with the bits of its own ff_mix2 call with ca[b].
+extern "C" int ff_mix2_images(float* out, int ldo, const float* a, int lda, const float* b, int ldb, long long rows, int C,
+                              float ka, float kb, const float* ca, int B, long long rows_per_image, const float* cb, const float* pa,
+                              int ldpa, const float* pb, int ldpb, int clamp01, void* stream) {
+  FF_CHECK_ARG(B > 0 && rows_per_image > 0 && rows == (long long)B * rows_per_image,
+               "ff_mix2_images: rows must be B images of rows_per_image rows (got B=%d rows_per_image=%lld rows=%lld)", B, rows_per_image, rows);
+  FF_CHECK_ARG(out && a && ca && C > 0 && ldo >= C && lda >= C && (!b || ldb >= C), "ff_mix2_images: bad args");
+  long long nb = (rows * C + 255) / 256;
+  if (nb > 8192) nb = 8192;
+  hipLaunchKernelGGL(mix2_images_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, out, ldo, a, lda, b, ldb, rows, C,
+                     ka, kb, ca, cb, pa, ldpa, pb, ldpb, clamp01, rows_per_image);
+  FF_LAUNCH_CHECK("ff_mix2_images");
   return FF_OK;
 }
 

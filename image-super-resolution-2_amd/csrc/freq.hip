@@ -2,14 +2,19 @@
 // :352-385 FFT).  Input is the planar [C][H][W] LR image (B folded into C); the nine bands are written
 // into one NHWC tensor [H][W][27] (band-major channel groups) so the consumers (band_proj 1x1,
 // band fusion 27-channel concat) address slices in place.  All HBM/LDS-bound, tiny FLOP counts.
+// The DCT and FFT writers also exist for a batch (ff_dct8_bands_images / ff_fft_bands_images): x [B][3][H][W] -> out [B][H][W][ldo] in one
+// launch per op, plane p writing channel p % 3 of image p / 3; the DWT pass is planar on both sides and takes the 3 B planes as C.
 #include "ff_common.h"
 
 // ------------------------------------------------------------------------------------------ DCT
 // One 8x8 block per 64 threads, 4 blocks per workgroup.  coef = D (X D^T); band_b = D^T ((coef.mask_b) D).
-__global__ __launch_bounds__(256) void dct8_bands_kernel(const float* __restrict__ x, int C, int H, int W,
-                                                         const float* __restrict__ D, const float* __restrict__ masks,
-                                                         const float* __restrict__ band_scale, float* __restrict__ out,
-                                                         int ldo, int ch_off) {
+// IMAGES: x holds C = 3 B planes [B][3][H][W] and out is [B][H][W][ldo]; plane c is channel c % 3 of image c / 3.  The arithmetic of an
+// 8x8 block does not depend on which workgroup (or which quarter of one) it falls into, so an image's bands are those of its own launch.
+template <bool IMAGES>
+__device__ __forceinline__ void dct8_bands_body(const float* __restrict__ x, int C, int H, int W,
+                                                const float* __restrict__ D, const float* __restrict__ masks,
+                                                const float* __restrict__ band_scale, float* __restrict__ out,
+                                                int ldo, int ch_off) {
   __shared__ float sD[64], sX[4][64], sT[4][64], sC[4][64];
   const int tid = threadIdx.x, g = tid >> 6, e = tid & 63, i = e >> 3, j = e & 7;
   const int nbx = (W + 7) / 8, nby = (H + 7) / 8;
@@ -32,6 +37,7 @@ __global__ __launch_bounds__(256) void dct8_bands_kernel(const float* __restrict
   for (int k = 0; k < 8; ++k) s += sD[i * 8 + k] * sT[g][k * 8 + j];
   sC[g][e] = s;
   __syncthreads();
+  if (IMAGES) { out += (long long)(c / 3) * H * W * ldo; c %= 3; }
   for (int b = 0; b < 3; ++b) {
     // U = (coef.mask) D : U[u][j] = sum_v cm[u][v] D[v][j]
     s = 0.f;
@@ -46,6 +52,18 @@ __global__ __launch_bounds__(256) void dct8_bands_kernel(const float* __restrict
     if (live && yy < H && xx < W) out[((long long)yy * W + xx) * ldo + ch_off + 3 * b + c] = s * band_scale[b];
   }
 }
+__global__ __launch_bounds__(256) void dct8_bands_kernel(const float* __restrict__ x, int C, int H, int W,
+                                                         const float* __restrict__ D, const float* __restrict__ masks,
+                                                         const float* __restrict__ band_scale, float* __restrict__ out,
+                                                         int ldo, int ch_off) {
+  dct8_bands_body<false>(x, C, H, W, D, masks, band_scale, out, ldo, ch_off);
+}
+__global__ __launch_bounds__(256) void dct8_bands_images_kernel(const float* __restrict__ x, int C, int H, int W,
+                                                                const float* __restrict__ D, const float* __restrict__ masks,
+                                                                const float* __restrict__ band_scale, float* __restrict__ out,
+                                                                int ldo, int ch_off) {
+  dct8_bands_body<true>(x, C, H, W, D, masks, band_scale, out, ldo, ch_off);
+}
 
 extern "C" int ff_dct8_bands(const float* x, int C, int H, int W, const float* dct_mat, const float* masks3,
                              const float* band_scale, float* out, int ldo, int ch_off, void* stream) {
@@ -55,6 +73,22 @@ extern "C" int ff_dct8_bands(const float* x, int C, int H, int W, const float* d
   hipLaunchKernelGGL(dct8_bands_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, C, H, W,
                      dct_mat, masks3, band_scale, out, ldo, ch_off);
   FF_LAUNCH_CHECK("ff_dct8_bands");
+  return FF_OK;
+}
+
+// B images in one launch: x [B][3][H][W] -> out [B][H][W][ldo], channels ch_off .. ch_off + 8 of every image.  The 8x8 block index
+// decodes to (b, c, by, bx); 3 B <= 65535 keeps the block count in 32 bits (3 * 65535 * 1024 * 1024 / 4 workgroups at H = W = 8192).
+extern "C" int ff_dct8_bands_images(const float* x, int B, int H, int W, const float* dct_mat, const float* masks3,
+                                    const float* band_scale, float* out, int ldo, int ch_off, void* stream) {
+  FF_CHECK_ARG(B > 0 && 3LL * B <= 65535 && H >= 8 && W >= 8 && H <= 8192 && W <= 8192,
+               "ff_dct8_bands_images: expects 1 <= B <= 21845 images of 8x8 .. 8192x8192 (got B=%d H=%d W=%d)", B, H, W);
+  FF_CHECK_ARG(x && dct_mat && masks3 && band_scale && out, "ff_dct8_bands_images: null pointer");
+  FF_CHECK_ARG(ch_off >= 0 && ldo >= ch_off + 9, "ff_dct8_bands_images: ldo %d is smaller than the channels written (%d + 9)", ldo, ch_off);
+  const long long nblk = 3LL * B * ((H + 7) / 8) * ((W + 7) / 8);
+  FF_CHECK_ARG((nblk + 3) / 4 < (1LL << 31), "ff_dct8_bands_images: too many 8x8 blocks for one grid (%lld)", nblk);
+  hipLaunchKernelGGL(dct8_bands_images_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, 3 * B, H, W,
+                     dct_mat, masks3, band_scale, out, ldo, ch_off);
+  FF_LAUNCH_CHECK("ff_dct8_bands_images");
   return FF_OK;
 }
 
@@ -197,12 +231,16 @@ __global__ __launch_bounds__(256) void cdft_cols_kernel(const float* __restrict_
 }
 
 // c2r along W + band write: low = irfft * s_lo -> out[.., ch_lo + c]; high = (x - irfft) * s_hi -> out[.., ch_hi + c]
-__global__ __launch_bounds__(256) void irdft_rows_bands_kernel(const float* __restrict__ U, const float* __restrict__ x, int C,
-                                                               int H, int W, const float* __restrict__ tc,
-                                                               const float* __restrict__ ts, const float* __restrict__ bscale,
-                                                               float* __restrict__ out, int ldo, int ch_lo, int ch_hi) {
+// IMAGES: C = 3 B planes [B][3][H][W], out [B][H][W][ldo]: plane c writes channel c % 3 of image c / 3.
+template <bool IMAGES>
+__device__ __forceinline__ void irdft_rows_bands_body(const float* __restrict__ U, const float* __restrict__ x, int C,
+                                                      int H, int W, const float* __restrict__ tc,
+                                                      const float* __restrict__ ts, const float* __restrict__ bscale,
+                                                      float* __restrict__ out, int ldo, int ch_lo, int ch_hi) {
   extern __shared__ float sm[];                           // urow[Wf][2] | cos[W] | sin[W]
-  const int r = blockIdx.x, Wf = W / 2 + 1, c = r / H, y = r % H;
+  const int r = blockIdx.x, Wf = W / 2 + 1, y = r % H;
+  int c = r / H;
+  if (IMAGES) { out += (long long)(c / 3) * H * W * ldo; c %= 3; }
   float* urow = sm; float* cs = sm + 2 * Wf; float* sn = cs + W;
   for (int i = threadIdx.x; i < 2 * Wf; i += 256) urow[i] = U[(long long)r * Wf * 2 + i];
   for (int i = threadIdx.x; i < W; i += 256) { cs[i] = tc[i]; sn[i] = ts[i]; }
@@ -232,6 +270,18 @@ __global__ __launch_bounds__(256) void irdft_rows_bands_kernel(const float* __re
     o[ch_lo + c] = s * bscale[0];
     o[ch_hi + c] = (xv - s) * bscale[1];
   }
+}
+__global__ __launch_bounds__(256) void irdft_rows_bands_kernel(const float* __restrict__ U, const float* __restrict__ x, int C,
+                                                               int H, int W, const float* __restrict__ tc,
+                                                               const float* __restrict__ ts, const float* __restrict__ bscale,
+                                                               float* __restrict__ out, int ldo, int ch_lo, int ch_hi) {
+  irdft_rows_bands_body<false>(U, x, C, H, W, tc, ts, bscale, out, ldo, ch_lo, ch_hi);
+}
+__global__ __launch_bounds__(256) void irdft_rows_bands_images_kernel(const float* __restrict__ U, const float* __restrict__ x, int C,
+                                                                      int H, int W, const float* __restrict__ tc,
+                                                                      const float* __restrict__ ts, const float* __restrict__ bscale,
+                                                                      float* __restrict__ out, int ldo, int ch_lo, int ch_hi) {
+  irdft_rows_bands_body<true>(U, x, C, H, W, tc, ts, bscale, out, ldo, ch_lo, ch_hi);
 }
 
 extern "C" int ff_fft_bands(const float* x, int C, int H, int W, const float* twW_cos, const float* twW_sin,
@@ -263,6 +313,50 @@ extern "C" int ff_fft_bands(const float* x, int C, int H, int W, const float* tw
   hipLaunchKernelGGL(irdft_rows_bands_kernel, dim3(C * H), dim3(256), (size_t)Wf * 8 + (size_t)W * 8, st, Y, x, C, H, W, twW_cos, twW_sin,
                      band_scale2, out, ldo, ch_lo, ch_hi);
   FF_LAUNCH_CHECK("ff_fft_bands");
+  return FF_OK;
+}
+
+// B images in one run of the same four kernels over 3 B planes: x [B][3][H][W] -> out [B][H][W][ldo].  The planes index gridDim.y of the
+// column passes and gridDim.x = 3 B H of the row passes, hence 3 B <= 65535.  H is one ff_fft_bands takes: the column tile of a workgroup within 64 KiB of LDS (H <= 481 or 513 <= H <= 1638).
+static bool fft_bands_images_geometry(int B, int H, int W) {
+  return B > 0 && 3LL * B <= 65535 && H > 1 && W > 1 && W <= 8192 && H <= 8192 && (size_t)H * (H <= 512 ? 16 : 4) * 8 + (size_t)H * 8 <= 64 * 1024;
+}
+extern "C" long long ff_fft_bands_images_workspace(int B, int H, int W) {
+  if (!fft_bands_images_geometry(B, H, W)) return -1;
+  return (long long)B * (4LL * 3 * H * (W / 2 + 1));                                  // B x (Y and Z spectra of one image's three planes)
+}
+extern "C" int ff_fft_bands_images(const float* x, int B, int H, int W, const float* twW_cos, const float* twW_sin,
+                                   const float* twH_cos, const float* twH_sin, const float* mask_logits, int msz, float temp,
+                                   const float* band_scale2, float* work, long long work_floats, float* out, int ldo, int ch_lo,
+                                   int ch_hi, void* stream) {
+  FF_CHECK_ARG(fft_bands_images_geometry(B, H, W),
+               "ff_fft_bands_images: expects 1 <= B <= 21845 images with 2 <= W <= 8192 and 2 <= H <= 481 or 513 <= H <= 1638 (got B=%d H=%d W=%d)", B, H, W);
+  FF_CHECK_ARG(x && twW_cos && twW_sin && twH_cos && twH_sin && mask_logits && band_scale2 && work && out, "ff_fft_bands_images: null pointer");
+  const int C = 3 * B, Wf = W / 2 + 1;
+  const long long spec = (long long)C * H * Wf * 2;
+  FF_CHECK_ARG(work_floats >= 2 * spec, "ff_fft_bands_images: workspace too small (need %lld floats)", 2 * spec);
+  FF_CHECK_ARG(msz > 0 && ch_lo >= 0 && ch_hi >= 0 && ldo >= ch_lo + 3 && ldo >= ch_hi + 3,
+               "ff_fft_bands_images: ldo %d is smaller than the channels written (%d + 3, %d + 3)", ldo, ch_lo, ch_hi);
+  float* Y = work;
+  float* Z = work + spec;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), (size_t)W * 12, st, x, C * H, W, twW_cos, twW_sin, Y);
+  // The column decomposition (CB, ksplit, KH) is taken from ONE image's plane count, 3, so image b's workgroups are those of its own launch.
+  // Every output bin is summed by one thread in a fixed order whatever the split, so this is a safeguard, not a fix.
+  const int CB = H <= 512 ? 16 : 4;
+  const size_t clds = (size_t)H * CB * 8 + (size_t)H * 8;
+  const int ncb = (Wf + CB - 1) / CB;
+  int ksplit = 1;
+  while (ncb * 3 * ksplit < 512 && (H + ksplit - 1) / ksplit > 256 / CB) ksplit *= 2;
+  const int KH = (H + ksplit - 1) / ksplit;
+  dim3 gc(ncb, C, (H + KH - 1) / KH);
+  hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Y, H, Wf, CB, KH, -1.f, twH_cos, twH_sin, mask_logits,
+                     msz, temp, Z);
+  hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Z, H, Wf, CB, KH, 1.f, twH_cos, twH_sin,
+                     (const float*)nullptr, 0, 0.f, Y);
+  hipLaunchKernelGGL(irdft_rows_bands_images_kernel, dim3(C * H), dim3(256), (size_t)Wf * 8 + (size_t)W * 8, st, Y, x, C, H, W, twW_cos,
+                     twW_sin, band_scale2, out, ldo, ch_lo, ch_hi);
+  FF_LAUNCH_CHECK("ff_fft_bands_images");
   return FF_OK;
 }
 

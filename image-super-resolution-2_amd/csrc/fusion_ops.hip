@@ -317,34 +317,16 @@ __device__ __forceinline__ void bl_setup(int o, int n_in, int n_out, int& i0, in
   l = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
 }
 
-__global__ __launch_bounds__(256) void fuse_blend_kernel(const float* __restrict__ E, const float* __restrict__ hier,
-                                                         const float* __restrict__ guide, const float* __restrict__ gates,
-                                                         const float* __restrict__ dif, float* __restrict__ out, int Hh, int Wh,
-                                                         int Hl, int Wl) {
-  const long long P = (long long)Hh * Wh;
-  for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long long)gridDim.x * 256) {
-    const int x = (int)(p % Wh), y = (int)(p / Wh);
-    int y0, y1, x0, x1; float ly, lx;
-    bl_setup(y, Hl, Hh, y0, y1, ly);
-    bl_setup(x, Wl, Wh, x0, x1, lx);
-    const long long a = (long long)y0 * Wl + x0, b = (long long)y0 * Wl + x1, c = (long long)y1 * Wl + x0, d = (long long)y1 * Wl + x1;
-#define BL(T, k, s) ((1.f - ly) * ((1.f - lx) * T[a * s + k] + lx * T[b * s + k]) + ly * ((1.f - lx) * T[c * s + k] + lx * T[d * s + k]))
-    float gd[3], gt[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) { gd[e] = BL(guide, e, 3); gt[e] = BL(gates, e, 3); }
-    const float df = BL(dif, 0, 1);
-#undef BL
-    const float gsum = gt[0] + gt[1] + gt[2] + 1e-8f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const float eh = E[p * 9 + ch], ed = E[p * 9 + 3 + ch], en = E[p * 9 + 6 + ch];
-      const float fw = eh * gd[0] + ed * gd[1] + en * gd[2];
-      const float f0 = hier[p * 3 + ch] * 0.7f + fw * 0.3f;
-      const float dyn = (eh * gt[0] + ed * gt[1] + en * gt[2]) / gsum;
-      out[p * 3 + ch] = f0 * (1.f - 0.3f * df) + dyn * (0.3f * df);
-    }
-  }
-}
+#define FB_KERNEL fuse_blend_kernel
+#define FB_IMAGES 0
+#include "fuse_blend_kernel.inc"
+#undef FB_KERNEL
+#undef FB_IMAGES
+#define FB_KERNEL fuse_blend_images_kernel          // B images, one per blockIdx.y (ff_fuse_blend_images)
+#define FB_IMAGES 1
+#include "fuse_blend_kernel.inc"
+#undef FB_KERNEL
+#undef FB_IMAGES
 
 extern "C" int ff_fuse_blend(const float* experts9, const float* hier3, const float* guide3, const float* gates3,
                              const float* dif1, float* out3, int Hh, int Wh, int Hl, int Wl, void* stream) {
@@ -354,5 +336,20 @@ extern "C" int ff_fuse_blend(const float* experts9, const float* hier3, const fl
   hipLaunchKernelGGL(fuse_blend_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, experts9, hier3, guide3, gates3,
                      dif1, out3, Hh, Wh, Hl, Wl);
   FF_LAUNCH_CHECK("ff_fuse_blend");
+  return FF_OK;
+}
+
+// ff_fuse_blend for B images in one launch, grid (one image's blocks, B): every tensor is [B][...] and contiguous, image b's at
+// b * Hh * Wh * {9, 3, 3} (experts9, hier3, out3) and b * Hl * Wl * {3, 3, 1} (guide3, gates3, dif1).
+extern "C" int ff_fuse_blend_images(const float* experts9, const float* hier3, const float* guide3, const float* gates3,
+                                    const float* dif1, float* out3, int B, int Hh, int Wh, int Hl, int Wl, void* stream) {
+  FF_CHECK_ARG(B > 0 && B <= 65535 && Hh > 0 && Wh > 0 && Hl > 0 && Wl > 0,
+               "ff_fuse_blend_images: expects 1 <= B <= 65535 images of positive size (got B=%d HR %dx%d LR %dx%d)", B, Hh, Wh, Hl, Wl);
+  FF_CHECK_ARG(experts9 && hier3 && guide3 && gates3 && dif1 && out3, "ff_fuse_blend_images: null pointer");
+  long long nb = ((long long)Hh * Wh + 255) / 256;
+  if (nb > 8192) nb = 8192;
+  hipLaunchKernelGGL(fuse_blend_images_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), 0, (hipStream_t)stream, experts9, hier3, guide3,
+                     gates3, dif1, out3, Hh, Wh, Hl, Wl);
+  FF_LAUNCH_CHECK("ff_fuse_blend_images");
   return FF_OK;
 }

@@ -295,11 +295,14 @@ def train_epoch(trainer, epoch_data, epoch: int, accumulation_steps: int = 1, lr
 
 @torch.no_grad()
 def validate(trainer, samples: Iterable[dict], use_ema: bool = True, crop_border: int = 4, test_y_channel: bool = True,
-             return_sr: bool = False) -> dict:
+             return_sr: bool = False, batch: int = 1) -> dict:
     """validate_epoch (train.py:413-523) in cached mode -> {'psnr', 'ssim'}: the eval-mode forward_with_precomputed of a FusionHIP
     built from the EMA shadow (use_ema) or the parameters, with the trainer's current BatchNorm buffers, one image per call;
     clamp(0, 1); per-image PSNR / SSIM on the device (isr2_amd.metrics), averaged as MetricCalculator does.  The trainer's own
-    state is only read.  samples: dicts as cache.read_sample returns them (lr [3,h,w], hr, expert_imgs, expert_feats)."""
+    state is only read.  samples: dicts as cache.read_sample returns them (lr [3,h,w], hr, expert_imgs, expert_feats).
+    batch > 1: up to `batch` consecutive samples of equal shapes (and the same feature keys) go through ONE FusionHIP.forward, one launch
+    per op for the group; a sample that differs starts a new group.  PSNR / SSIM stay per image, and `sr` / `per_image` are bit-equal
+    to batch = 1 (the default: one forward per sample, launch for launch what it always was)."""
     from . import metrics, ops
     from . import autograd as ag
     from .fusion import FusionHIP
@@ -313,20 +316,45 @@ def validate(trainer, samples: Iterable[dict], use_ema: bool = True, crop_border
     try:
         with torch.cuda.device(trainer.dev):
             model = FusionHIP(sd, trainer.dev)
-            for s in samples:
-                to4 = lambda t: (t.unsqueeze(0) if t.dim() == 3 else t).to(trainer.dev, torch.float32).contiguous()      # noqa: E731
+            to4 = lambda t: (t.unsqueeze(0) if t.dim() == 3 else t).to(trainer.dev, torch.float32).contiguous()      # noqa: E731
+
+            def load(s):
                 lr, hr = to4(s["lr"]), to4(s["hr"])
                 if lr.shape[0] != 1:
-                    raise _lib.FFError("validate: one image per sample (forward_with_precomputed is B = 1)")
+                    raise _lib.FFError("validate: one image per sample")
                 feats = s.get("expert_feats")
-                sr = model.forward(lr, {k: to4(v) for k, v in s["expert_imgs"].items()},
-                                   feats={k: to4(v) for k, v in feats.items()} if feats else None)
+                return lr, hr, {k: to4(v) for k, v in s["expert_imgs"].items()}, ({k: to4(v) for k, v in feats.items()} if feats else None)
+
+            def shapes(g):
+                return (tuple(g[0].shape), tuple(g[1].shape), tuple(sorted((k, tuple(v.shape)) for k, v in g[2].items())),
+                        tuple(sorted((k, tuple(v.shape)) for k, v in g[3].items())) if g[3] else None)
+
+            def run(group):
+                if len(group) == 1:
+                    lr, hr, ex, feats = group[0]
+                else:                                                 # consecutive samples of one shape: one forward for all of them
+                    cat = lambda ts: torch.cat(list(ts))              # noqa: E731
+                    lr, hr = cat(g[0] for g in group), cat(g[1] for g in group)
+                    ex = {k: cat(g[2][k] for g in group) for k in group[0][2]}
+                    feats = {k: cat(g[3][k] for g in group) for k in group[0][3]} if group[0][3] else None
+                sr = model.forward(lr, ex, feats=feats)
                 sr = ag.k_unary("clamp01", sr)                        # sr.clamp(0, 1), train.py:482
                 hr = ag.k_unary("clamp01", hr)                        # MetricCalculator.update, metrics.py:333-334
-                psnrs.append(metrics.calculate_psnr(sr[0], hr[0], crop_border, test_y_channel))
-                ssims.append(metrics.calculate_ssim(sr[0], hr[0], crop_border, test_y_channel))
-                if return_sr:
-                    srs.append(sr[0].cpu())
+                for b in range(len(group)):
+                    psnrs.append(metrics.calculate_psnr(sr[b], hr[b], crop_border, test_y_channel))
+                    ssims.append(metrics.calculate_ssim(sr[b], hr[b], crop_border, test_y_channel))
+                    if return_sr:
+                        srs.append(sr[b].cpu())
+
+            group = []
+            for s in samples:
+                g = load(s)
+                if group and (len(group) >= max(1, int(batch)) or shapes(g) != shapes(group[0])):
+                    run(group)
+                    group = []
+                group.append(g)
+            if group:
+                run(group)
     finally:
         ops.set_gemm_mode(old_mode)
     res = mean_metrics(psnrs, ssims)

@@ -2,7 +2,10 @@
 
 Mirrors, stage by stage, the reference's eval path src/models/enhanced_fusion.py:418-429 (bands),
 :502-591 (fuse), :593-647 (dynamic selection), :653-688 (refine + edge); the modules it calls are
-cited at each class.  Tensors are NHWC fp32 on the GPU; B = 1 (one image / tile per call).
+cited at each class.  Tensors are NHWC fp32 on the GPU, [B,...]: a batch is B independent images and every op is ONE launch for
+the batch (FusionHIP.forward chunks it), each image with the bits of its own B = 1 call -- the 3x3 convolutions pass per_image, the 1x1
+GEMMs the rows of one image (the tile configuration one image picks), the frequency bands and the blend go through the _images entry
+points; with B = 1 every call is the one a single image always made.
 """
 from __future__ import annotations
 
@@ -33,6 +36,17 @@ def _dct_matrix(n: int = 8) -> T:
     return d
 
 
+def _rpi(t: T, mult: int = 1) -> dict:
+    """ops.linear's hint for the rows of an NHWC batch t [B,H,W,.] (mult rows per pixel): the rows of ONE image.  Nothing for B = 1."""
+    return {"rows_per_image": t.shape[1] * t.shape[2] * mult} if t.shape[0] > 1 else {}
+
+
+def _conv(x: T, w: T, b: Optional[T] = None, **kw) -> T:
+    """The convolutions of the stack: a batch is B independent images (ops.conv2d per_image: the halo kernel's _images form, one image's
+    tile configuration for the implicit GEMM; the routes chosen by H * W are one image's already).  Nothing changes for B = 1."""
+    return ops.conv2d(x, w, b, per_image=True, **kw)
+
+
 def _zigzag_masks(n: int = 8) -> T:
     order = torch.zeros(n, n, dtype=torch.long)
     idx = 0
@@ -47,7 +61,8 @@ def _zigzag_masks(n: int = 8) -> T:
 
 class FreqBands:
     """MultiDomainFrequencyDecomposition.decompose (multi_domain_frequency.py:578-591): LR image
-    [1,3,H,W] -> nine bands as one NHWC tensor [1,H,W,27] (DCT 0-8, DWT 9-20, FFT 21-26)."""
+    [B,3,H,W] -> nine bands as one NHWC tensor [B,H,W,27] (DCT 0-8, DWT 9-20, FFT 21-26).  The DWT passes and the resize take the 3 B
+    planes as they are; the DCT and the FFT write NHWC and go through their _images forms for B > 1."""
 
     def __init__(self, sd: SD, dev):
         m = "multi_domain_freq."
@@ -71,16 +86,18 @@ class FreqBands:
         return self._tw[n]
 
     def __call__(self, lr: T) -> T:
-        _, c, h, w = lr.shape
-        x = lr.reshape(c, h, w).contiguous()
-        out = torch.empty((1, h, w, 27), device=lr.device, dtype=torch.float32)
-        ops.dct8_bands(x, self.dct, self.masks, self.dct_scale, out, 0)
+        B, c, h, w = lr.shape
+        lr = lr.contiguous()
+        x = lr.reshape(B * c, h, w)                              # planes
+        xi = x if B == 1 else lr                                 # the NHWC writers: [3,h,w] for one image, [B,3,h,w] for a batch
+        out = torch.empty((B, h, w, 27), device=lr.device, dtype=torch.float32)
+        ops.dct8_bands(xi, self.dct, self.masks, self.dct_scale, out, 0)
         lo_r, hi_r = ops.dwt_pass(x, 1, self.lo, self.hi)
         ll, lh = ops.dwt_pass(lo_r, 0, self.lo, self.hi)
         hl, hh = ops.dwt_pass(hi_r, 0, self.lo, self.hi)
         for i, sb in enumerate((ll, lh, hl, hh)):
-            ops.resize(sb.unsqueeze(0), (h, w), layout="nchw", out=out[..., 9 + 3 * i:12 + 3 * i], mul=self.sub_scale[i])
-        ops.fft_bands(x, self._twiddle(w), self._twiddle(h), self.mask_logits, self.temp, self.fft_scale, out, 21, 24)
+            ops.resize(sb.reshape(B, c, *sb.shape[1:]), (h, w), layout="nchw", out=out[..., 9 + 3 * i:12 + 3 * i], mul=self.sub_scale[i])
+        ops.fft_bands(xi, self._twiddle(w), self._twiddle(h), self.mask_logits, self.temp, self.fft_scale, out, 21, 24)
         return out
 
 
@@ -133,46 +150,47 @@ class CrossBandLKA:
         self.outp = _lin1x1(sd, p + ".out_proj", dev)
 
     def __call__(self, bands: T) -> T:
-        """bands [1,H,W,27] -> enhanced bands [1,H,W,27]."""
-        _, H, W, _ = bands.shape
+        """bands [B,H,W,27] -> enhanced bands [B,H,W,27]."""
+        B, H, W, _ = bands.shape
         nb, E = self.nb, 64
-        P = H * W
-        tok = torch.empty((1, H, W, nb * E), device=bands.device, dtype=torch.float32)
+        P = B * H * W
+        r1, r9 = _rpi(bands), _rpi(bands, nb)                    # one row per pixel / per (pixel, band) token
+        tok = torch.empty((B, H, W, nb * E), device=bands.device, dtype=torch.float32)
         for i in range(nb):
-            ops.linear(bands[..., 3 * i:3 * i + 3], *self.proj, out=tok[..., E * i:E * (i + 1)])
+            ops.linear(bands[..., 3 * i:3 * i + 3], *self.proj, out=tok[..., E * i:E * (i + 1)], **r1)
         rows = tok.reshape(P * nb, E)                                   # token (pixel, band) rows
         fast = ops.fused_modes()
         if fast:
             qkv = ops.token_linear(rows, self.tl_in, gamma=self.norm[0], beta=self.norm[1])          # LayerNorm + in_proj
         else:
-            qkv = ops.linear(ops.layernorm(rows, *self.norm), *self.in_proj)
+            qkv = ops.linear(ops.layernorm(rows, *self.norm), *self.in_proj, **r9)
         att = ops.band_mha_core(qkv, P, nb, self.heads)
-        x = ops.token_linear(att, self.tl_out, res=rows) if fast else ops.linear(att, *self.out_proj, res=rows)      # [9P, 64]
-        ximg = x.reshape(1, H, W, nb * E)
+        x = ops.token_linear(att, self.tl_out, res=rows) if fast else ops.linear(att, *self.out_proj, res=rows, **r9)      # [9P, 64]
+        ximg = x.reshape(B, H, W, nb * E)
         # LKA block on all bands at once
         t = ops.affine(ximg, *self.bn1)
         a = ops.dwconv2d(t, self.dw5, None, ksize=(5, 5), pad=(2, 2))
         a = ops.dwconv2d(a, self.dwh, None, ksize=(1, 21), pad=(0, 10))
         a = ops.dwconv2d(a, self.dwv, None, ksize=(21, 1), pad=(10, 0))
-        a = ops.linear(a.reshape(P * nb, E), *self.pw, act="sigmoid")
+        a = ops.linear(a.reshape(P * nb, E), *self.pw, act="sigmoid", **r9)
         x = ops.fma3(x, t.reshape(P * nb, E), a, self.scale1)           # x + s1 * (norm1(x) * attn)
         if fast:
             f = ops.token_linear(x, self.tl_ffn0, act="gelu")           # BatchNorm folded in
             x = ops.token_linear(f, self.tl_ffn2, res=x)                # scale2 folded in
         else:
             t2 = ops.affine(x, *self.bn2)
-            f = ops.linear(t2, *self.ffn0, act="gelu")
-            x = ops.linear(f, *self.ffn2, res=x, alpha=self.scale2)
-        ximg = x.reshape(1, H, W, nb * E)
+            f = ops.linear(t2, *self.ffn0, act="gelu", **r9)
+            x = ops.linear(f, *self.ffn2, res=x, alpha=self.scale2, **r9)
+        ximg = x.reshape(B, H, W, nb * E)
         out = torch.empty_like(bands)
         for i in range(nb):
-            ops.linear(ximg[..., E * i:E * (i + 1)], *self.outp, res=bands[..., 3 * i:3 * i + 3], out=out[..., 3 * i:3 * i + 3])
+            ops.linear(ximg[..., E * i:E * (i + 1)], *self.outp, res=bands[..., 3 * i:3 * i + 3], out=out[..., 3 * i:3 * i + 3], **r1)
         return out
 
 
 class Collaborative:
     """EnhancedCollaborativeWithLKA in eval mode (large_kernel_attention.py:250-419), live only in the cached-mode forward
-    (enhanced_fusion.py:756-812): expert features [1,C,h,w] -> one gain per expert and colour channel.  Same building blocks as
+    (enhanced_fusion.py:756-812): expert features [B,C,h,w] -> one gain per image, expert and colour channel.  Same building blocks as
     CrossBandLKA with 3 tokens of 128 channels per pixel; the three experts are batched as 3*128 depth-wise channels / 3P rows."""
 
     def __init__(self, sd: SD, dev, p: str = "collaborative", heads: int = 8):
@@ -204,41 +222,45 @@ class Collaborative:
         self.g_shift = torch.full((3,), 0.9, device=dev)                                   # 1 + 0.2 (m - 0.5) = 0.9 + 0.2 m
 
     def __call__(self, feats: Dict[str, T], hr_hw, taps: Optional[dict] = None):
-        """feats: NCHW {hat [1,180,h,w], dat [1,180,h,w], nafnet [1,64,h,w]} -> three device vectors [3] of per-channel gains."""
+        """feats: NCHW {hat [B,180,h,w], dat [B,180,h,w], nafnet [B,64,h,w]} -> three device matrices [B,3] of per-channel gains."""
         E, ne = 128, 3
         shapes = {tuple(feats[k].shape[2:]) for k in ("hat", "dat", "nafnet")}
         if len(shapes) != 1:
             raise _lib.FFError(f"collaborative: the cached features must share one resolution (cache.py writes them at LR size), got {shapes}")
         h, w = next(iter(shapes))
-        P = h * w
-        tok = torch.empty((1, h, w, ne * E), device=self.dev, dtype=torch.float32)
+        B = feats["hat"].shape[0]
+        if any(feats[k].shape[0] != B for k in ("dat", "nafnet")):
+            raise _lib.FFError("collaborative: the cached features must share one batch size")
+        P = B * h * w
+        tok = torch.empty((B, h, w, ne * E), device=self.dev, dtype=torch.float32)
+        r1, r3 = _rpi(tok), _rpi(tok, ne)                         # one row per pixel / per (pixel, expert) token
         for i, k in enumerate(("hat", "dat", "nafnet")):
-            ops.linear(ops.nchw_to_nhwc(feats[k].to(self.dev, torch.float32)), *self.align[i], out=tok[..., E * i:E * (i + 1)])
+            ops.linear(ops.nchw_to_nhwc(feats[k].to(self.dev, torch.float32)), *self.align[i], out=tok[..., E * i:E * (i + 1)], **r1)
         rows = tok.reshape(P * ne, E)
-        qkv = ops.linear(ops.layernorm(rows, *self.norm1), *self.in_proj)
+        qkv = ops.linear(ops.layernorm(rows, *self.norm1), *self.in_proj, **r3)
         att = ops.band_mha_core(qkv, P, ne, self.heads)
-        x = ops.linear(att, *self.out_proj, res=rows)
-        f = ops.linear(ops.layernorm(x, *self.norm2), *self.ffn0, act="gelu")
-        x = ops.linear(f, *self.ffn2, res=x)
+        x = ops.linear(att, *self.out_proj, res=rows, **r3)
+        f = ops.linear(ops.layernorm(x, *self.norm2), *self.ffn0, act="gelu", **r3)
+        x = ops.linear(f, *self.ffn2, res=x, **r3)
         # LKA block, the three experts at once
-        ximg = x.reshape(1, h, w, ne * E)
+        ximg = x.reshape(B, h, w, ne * E)
         t = ops.affine(ximg, *self.bn1)
         a = ops.dwconv2d(t, self.dw5, None, ksize=(5, 5), pad=(2, 2))
         a = ops.dwconv2d(a, self.dwh, None, ksize=(1, 21), pad=(0, 10))
         a = ops.dwconv2d(a, self.dwv, None, ksize=(21, 1), pad=(10, 0))
-        a = ops.linear(a.reshape(P * ne, E), *self.pw, act="sigmoid")
+        a = ops.linear(a.reshape(P * ne, E), *self.pw, act="sigmoid", **r3)
         x = ops.fma3(x, t.reshape(P * ne, E), a, self.scale1)
-        f = ops.linear(x, *self.lffn0, act="gelu")
-        x = ops.linear(f, *self.lffn2, res=x, alpha=self.scale2)
-        ximg = x.reshape(1, h, w, ne * E)
+        f = ops.linear(x, *self.lffn0, act="gelu", **r3)
+        x = ops.linear(f, *self.lffn2, res=x, alpha=self.scale2, **r3)
+        ximg = x.reshape(B, h, w, ne * E)
         gains = []
         for i in range(ne):
-            up = ops.resize(ximg[..., E * i:E * (i + 1)], hr_hw)                          # [1,H,W,128] bilinear
-            m = ops.pool_mean(ops.linear(up, *self.mod0[i], act="gelu"))                   # [1,32]
-            m = ops.vec_mlp(m, self.mod3[i][0], self.mod3[i][1], "sigmoid")                # [1,3]
+            up = ops.resize(ximg[..., E * i:E * (i + 1)], hr_hw)                          # [B,H,W,128] bilinear
+            m = ops.pool_mean(ops.linear(up, *self.mod0[i], act="gelu", **_rpi(up)))       # [B,32]: ff_pool_mean sums image by image
+            m = ops.vec_mlp(m, self.mod3[i][0], self.mod3[i][1], "sigmoid")                # [B,3]
             if taps is not None:
                 taps[f"collab.mod{i}"] = m
-            gains.append(ops.affine(m, self.g_scale, self.g_shift).reshape(3))
+            gains.append(ops.affine(m, self.g_scale, self.g_shift))                        # [B,3]
         return gains
 
 
@@ -262,12 +284,13 @@ class BandFusion:
         self.res = _lin1x1(sd, p + ".dct_residual", dev)
 
     def __call__(self, xb: T) -> T:
-        """xb [1,H,W,27] -> guidance [1,H,W,9] = (low rgb, mid rgb, high rgb)."""
-        att = ops.conv2d(xb, *self.att, ksize=(3, 3), pad=(1, 1), act="sigmoid")           # [1,H,W,9]
+        """xb [B,H,W,27] -> guidance [B,H,W,9] = (low rgb, mid rgb, high rgb)."""
+        r1 = _rpi(xb)
+        att = _conv(xb, *self.att, ksize=(3, 3), pad=(1, 1), act="sigmoid")           # [B,H,W,9]
         wb = ops.band_weight(xb, att, self.imp)
-        tr = ops.linear(ops.linear(wb, *self.tr0, act="gelu"), *self.tr2)
-        gt = ops.linear(ops.linear(wb, *self.gt0, act="gelu"), *self.gt2, act="sigmoid")
-        r = ops.linear(xb[..., :9], *self.res, alpha=0.3)
+        tr = ops.linear(ops.linear(wb, *self.tr0, act="gelu", **r1), *self.tr2, **r1)
+        gt = ops.linear(ops.linear(wb, *self.gt0, act="gelu", **r1), *self.gt2, act="sigmoid", **r1)
+        r = ops.linear(xb[..., :9], *self.res, alpha=0.3, **r1)
         return ops.fma3(r, tr, gt)
 
 
@@ -292,11 +315,13 @@ class HierFusion:
             w76[:, :, :73] = w.reshape(w.shape[0], 9, 73)
             self.st[name]["c0"] = (w76.reshape(w.shape[0], 9 * 76).contiguous(), b)
 
-    def _cat_buf(self, h: int, w: int, dev, key: str) -> T:
-        """[1,h,w,76] concat buffer whose channels 73..75 are zero (zeroed when the buffer is made; never written again).
+    def _cat_buf(self, B: int, h: int, w: int, dev, key: str, cap: Optional[int] = None) -> T:
+        """[B,h,w,76] concat buffer whose channels 73..75 are zero (zeroed when the buffer is made; never written again).
         Owned by the graph entry being captured, or -- for eager forwards -- one buffer per role that is replaced on a size
-        change (ops.persistent_zeros): HBM stays bounded over a directory of differently sized images."""
-        return ops.persistent_zeros(id(self), key, (1, h, w, 76), dev)
+        change (ops.persistent_zeros): HBM stays bounded over a directory of differently sized images.  cap: the images of the largest
+        chunk of this forward -- the buffer is made for cap images and a smaller (remainder) chunk takes its leading slice, so a chunk
+        and its remainder never alternate two sizes (which would replace and re-zero the eager buffer every forward)."""
+        return ops.persistent_zeros(id(self), key, (max(B, cap or B), h, w, 76), dev)[:B]
 
     def __del__(self):
         try:
@@ -306,8 +331,8 @@ class HierFusion:
 
     def _stage(self, x: T, name: str) -> T:
         k = self.st[name]
-        x = ops.conv2d(x, *k["c0"], ksize=(3, 3), pad=(1, 1), act="gelu")
-        x = ops.conv2d(x, *k["c2"], ksize=(3, 3), pad=(1, 1), act="gelu")
+        x = _conv(x, *k["c0"], ksize=(3, 3), pad=(1, 1), act="gelu")
+        x = _conv(x, *k["c2"], ksize=(3, 3), pad=(1, 1), act="gelu")
         if ops.gemm_mode() != "f32" and k["g0"][0].shape[0] <= 16:
             # SpatialGate (hierarchical_fusion.py:25-43): conv1x1 C -> C/4 -> GELU -> conv1x1 -> 1 -> sigmoid per pixel in ONE pass over x
             # (fp32 VALU, ff_pixel_mlp) instead of two N <= 16 GEMM launches that re-read the 64-channel tensor
@@ -315,28 +340,29 @@ class HierFusion:
                 k["g2b"] = float(k["g2"][1].reshape(-1)[0].cpu())
             gate = ops.pixel_mlp(x, k["g0"][0], k["g0"][1], "gelu", k["g2"][0], k["g2b"], "sigmoid")
         else:
-            gate = ops.linear(ops.linear(x, *k["g0"], act="gelu"), *k["g2"], act="sigmoid")    # [.,1]
+            gate = ops.linear(ops.linear(x, *k["g0"], act="gelu", **_rpi(x)), *k["g2"], act="sigmoid", **_rpi(x))    # [.,1]
         x = ops.mix2(x, pa=gate)
-        r = ops.conv2d(x, *k["r0"], ksize=(3, 3), pad=(1, 1), act="gelu")
-        return ops.conv2d(r, *k["r2"], ksize=(3, 3), pad=(1, 1), res=x, alpha=k["rs"])
+        r = _conv(x, *k["r0"], ksize=(3, 3), pad=(1, 1), act="gelu")
+        return _conv(r, *k["r2"], ksize=(3, 3), pad=(1, 1), res=x, alpha=k["rs"])
 
-    def __call__(self, experts9: T) -> T:
-        _, fh, fw, _ = experts9.shape
+    def __call__(self, experts9: T, cap: Optional[int] = None) -> T:
+        """experts9 [B,4h,4w,9] -> [B,4h,4w,3]; cap: see _cat_buf."""
+        B, fh, fw, _ = experts9.shape
         s1, s2 = (max(fh // 4, 1), max(fw // 4, 1)), (max(fh // 2, 1), max(fw // 2, 1))
         dev = experts9.device
-        f1 = self._stage(ops.resize(experts9, s1), "stage1")                               # [1,h/4,w/4,64]
-        in2 = self._cat_buf(s2[0], s2[1], dev, "in2")
+        f1 = self._stage(ops.resize(experts9, s1), "stage1")                               # [B,h/4,w/4,64]
+        in2 = self._cat_buf(B, s2[0], s2[1], dev, "in2", cap)
         ops.resize(f1, s2, out=in2[..., :64])
         ops.resize(experts9, s2, out=in2[..., 64:73])
         f2 = self._stage(in2, "stage2")
         f2 = ops.mix2(f2, in2[..., :64], kb=self.w12)
-        in3 = self._cat_buf(fh, fw, dev, "in3")
+        in3 = self._cat_buf(B, fh, fw, dev, "in3", cap)
         ops.resize(f2, (fh, fw), out=in3[..., :64])
         ops.mix2(experts9, out=in3[..., 64:73])
-        f3 = self._stage(in3, "stage3")                                                    # [1,fh,fw,32]
+        f3 = self._stage(in3, "stage3")                                                    # [B,fh,fw,32]
         f3 = ops.mix2(f3, in3[..., :32], kb=self.w23)
-        o = ops.conv2d(f3, *self.rgb0, ksize=(3, 3), pad=(1, 1), act="gelu")
-        return ops.conv2d(o, *self.rgb2, ksize=(3, 3), pad=(1, 1), act="sigmoid")
+        o = _conv(f3, *self.rgb0, ksize=(3, 3), pad=(1, 1), act="gelu")
+        return _conv(o, *self.rgb2, ksize=(3, 3), pad=(1, 1), act="sigmoid")
 
 
 class DynamicSelection:
@@ -354,25 +380,25 @@ class DynamicSelection:
 
     def _branch(self, x: T, n: str, out: T):
         w, sc, sh = self.br[n]
-        y = ops.conv2d(x, w, None, ksize=(3, 3), pad=(1, 1), act="relu")
+        y = _conv(x, w, None, ksize=(3, 3), pad=(1, 1), act="relu")
         return ops.affine(y, sc, sh, out=out)
 
     def __call__(self, lr_nhwc: T):
-        _, H, W, _ = lr_nhwc.shape
+        B, H, W, _ = lr_nhwc.shape
         dev = lr_nhwc.device
-        cat = torch.empty((1, H, W, 192), device=dev, dtype=torch.float32)
+        cat = torch.empty((B, H, W, 192), device=dev, dtype=torch.float32)
         self._branch(lr_nhwc, "conv_1x", cat[..., :64])
         for n, sf, sl in (("conv_2x", 0.5, slice(64, 128)), ("conv_4x", 0.25, slice(128, 192))):
             hs, ws = int(math.floor(H * sf)), int(math.floor(W * sf))
             xs = ops.resize(lr_nhwc, (hs, ws), scale_factor=sf)
-            f = self._branch(xs, n, torch.empty((1, hs, ws, 64), device=dev, dtype=torch.float32))
+            f = self._branch(xs, n, torch.empty((B, hs, ws, 64), device=dev, dtype=torch.float32))
             ops.resize(f, (H, W), out=cat[..., sl])
-        feats = ops.linear(cat, *self.fuse)
-        dif = ops.conv2d(lr_nhwc, *self.d0, ksize=(3, 3), pad=(1, 1), act="relu")
-        dif = ops.conv2d(dif, *self.d2, ksize=(3, 3), pad=(1, 1), act="relu")
-        dif = ops.conv2d(dif, *self.d4, ksize=(3, 3), pad=(1, 1), act="sigmoid")           # [1,H,W,1]
-        g = ops.conv2d(feats, *self.g0, ksize=(3, 3), pad=(1, 1), act="relu")
-        g = ops.linear(g, *self.g2, act="sigmoid")                                         # [1,H,W,3]
+        feats = ops.linear(cat, *self.fuse, **_rpi(cat))
+        dif = _conv(lr_nhwc, *self.d0, ksize=(3, 3), pad=(1, 1), act="relu")
+        dif = _conv(dif, *self.d2, ksize=(3, 3), pad=(1, 1), act="relu")
+        dif = _conv(dif, *self.d4, ksize=(3, 3), pad=(1, 1), act="sigmoid")           # [B,H,W,1]
+        g = _conv(feats, *self.g0, ksize=(3, 3), pad=(1, 1), act="relu")
+        g = ops.linear(g, *self.g2, act="sigmoid", **_rpi(g))                              # [B,H,W,3]
         return ops.dynamic_gates(g, dif), dif
 
 
@@ -397,7 +423,7 @@ class EdgeRefine:
         self.e0, self.e2 = _conv_b(sd, p + ".edge_gate.0", dev), _conv_b(sd, p + ".edge_gate.2", dev)
 
     def __call__(self, img: T) -> T:
-        _, H, W, _ = img.shape
+        B, H, W, _ = img.shape
         dev = img.device
         pyr, cur = [], img
         for lv in range(self.levels):
@@ -409,28 +435,28 @@ class EdgeRefine:
                 cur = down
             else:
                 pyr.append(cur)
-        feats = torch.empty((1, H, W, 32 * self.levels), device=dev, dtype=torch.float32)
+        feats = torch.empty((B, H, W, 32 * self.levels), device=dev, dtype=torch.float32)
         for lv, lap in enumerate(pyr):
             k = self.ref[lv]
-            o = ops.conv2d(lap, *k["c1"], ksize=(3, 3), pad=(1, 1), act="gelu")
-            o = ops.conv2d(o, *k["c2"], ksize=(3, 3), pad=(1, 1), act="gelu")
-            idn = ops.linear(lap, *k["pj"])
-            o = ops.conv2d(o, *k["c3"], ksize=(3, 3), pad=(1, 1), res=idn)
-            a = ops.linear(o, *k["a0"], act="gelu")
-            a = ops.conv2d(a, *k["a2"], ksize=(3, 3), pad=(1, 1), act="sigmoid")           # [.,1]
+            o = _conv(lap, *k["c1"], ksize=(3, 3), pad=(1, 1), act="gelu")
+            o = _conv(o, *k["c2"], ksize=(3, 3), pad=(1, 1), act="gelu")
+            idn = ops.linear(lap, *k["pj"], **_rpi(lap))
+            o = _conv(o, *k["c3"], ksize=(3, 3), pad=(1, 1), res=idn)
+            a = ops.linear(o, *k["a0"], act="gelu", **_rpi(o))
+            a = _conv(a, *k["a2"], ksize=(3, 3), pad=(1, 1), act="sigmoid")           # [.,1]
             sl = feats[..., 32 * lv:32 * (lv + 1)]
             if (o.shape[1], o.shape[2]) != (H, W):
                 o = ops.mix2(o, pa=a)
                 ops.resize(o, (H, W), out=sl, mul=self.lw[lv])
             else:
                 ops.mix2(o, pa=a, ka=self.lw[lv], out=sl)
-        e = ops.conv2d(feats, *self.f0, ksize=(3, 3), pad=(1, 1), act="gelu")
-        edge = ops.conv2d(e, *self.f2, ksize=(3, 3), pad=(1, 1))                           # [1,H,W,3]
-        cat = torch.empty((1, H, W, 6), device=dev, dtype=torch.float32)
+        e = _conv(feats, *self.f0, ksize=(3, 3), pad=(1, 1), act="gelu")
+        edge = _conv(e, *self.f2, ksize=(3, 3), pad=(1, 1))                           # [B,H,W,3]
+        cat = torch.empty((B, H, W, 6), device=dev, dtype=torch.float32)
         ops.mix2(img, out=cat[..., :3])
         ops.mix2(edge, out=cat[..., 3:])
-        gate = ops.conv2d(cat, *self.e0, ksize=(3, 3), pad=(1, 1), act="gelu")
-        gate = ops.conv2d(gate, *self.e2, ksize=(3, 3), pad=(1, 1), act="sigmoid")         # [1,H,W,1]
+        gate = _conv(cat, *self.e0, ksize=(3, 3), pad=(1, 1), act="gelu")
+        gate = _conv(gate, *self.e2, ksize=(3, 3), pad=(1, 1), act="sigmoid")         # [B,H,W,1]
         return ops.mix2(img, edge, kb=self.strength, pb=gate, clamp01=True)
 
 
@@ -451,10 +477,42 @@ class FusionHIP:
         # the cached-mode forward's collaborative block, when the checkpoint carries it (synthetic weights: parts += "collab")
         self.collab = Collaborative(sd, dev) if "collaborative.norm1.weight" in sd else None
 
+    # Batches run in chunks of at most this many HR pixels (B * 4h * 4w): NafnetHIP.max_batch_pixels, four 1024 x 1024 outputs' worth of
+    # activations.  An attribute, not an environment switch.  _chunk_images() also keeps a chunk below the 32-bit bounds of its launches.
+    max_batch_pixels = 4 * 1024 * 1024
+
+    def _chunk_images(self, B: int, h: int, w: int) -> int:
+        """Images per chunk of a batch of B LR images h x w.  One in the modes without the fused kernels (f32: the per-image loop the
+        experts keep too).  Otherwise max_batch_pixels, and the 32-bit bounds of the launches: ops.conv2d keeps the LDS-resident 3x3
+        kernel to inputs of fewer than 2^31 elements counted over the launch (the widest here: EdgeRefine's 96-channel features and the
+        76-channel concat buffer at HR), ff_conv2d_bf16s counts the launch's rows in an int, and the widest tensor of all is the
+        collaborative block's [B,4h,4w,128] up-sampling (the 576-channel depth-wise tensors are at LR: 36 floats per HR pixel, and
+        ff_dwconv2d indexes in 64 bits).  B * 16 h w * 128 < 2^31 implies every one of them, and with the DCT's 8 x 8 minimum B <= 16383,
+        inside the grid-dimension bounds of ff_conv3x3_small (B < 65536) and the FFT planes (3 B <= 65535).  So a chunk never moves an
+        image off the route it takes alone."""
+        if B == 1 or not ops.fused_modes():
+            return 1
+        ph = 16 * h * w
+        return max(1, min(B, int(self.max_batch_pixels) // ph, (2 ** 31 - 1) // (ph * 128)))
+
+    @staticmethod
+    def pre_tensors(pre: Optional[dict]):
+        """Every tensor of what pre() returned (model.py hands them from the side stream to the caller's)."""
+        if pre is None:
+            return []
+        if "chunks" in pre:
+            return [t for c in pre["chunks"] for t in c.values()]
+        return list(pre.values())
+
     def pre(self, lr: T) -> dict:
         """Everything that depends on the LR input only (frequency bands, cross-band attention, band fusion -> guidance,
-        dynamic-selection gates, the bilinear LR skip): independent of the experts, so model.py runs it beside them."""
-        _, _, h, w = lr.shape
+        dynamic-selection gates, the bilinear LR skip): independent of the experts, so model.py runs it beside them.
+        lr [B,3,h,w]: a dict of [B,...] tensors when the batch is one chunk, else {"chunks": [that dict for every chunk]} in the chunks
+        forward() takes the same batch in."""
+        B, _, h, w = lr.shape
+        nb = self._chunk_images(B, h, w)
+        if nb < B:
+            return {"chunks": [self.pre(lr[b0:b0 + nb]) for b0 in range(0, B, nb)]}
         raw = self.bands(lr)
         xb = self.xband(raw)
         b3 = self.bfuse(xb)
@@ -465,26 +523,42 @@ class FusionHIP:
         return dict(raw=raw, xb=xb, b3=b3, guide=guide, lr_nhwc=lr_nhwc, gates=gates, dif=dif, up=up)
 
     def forward(self, lr: T, experts: Dict[str, T], taps: Optional[dict] = None, pre: Optional[dict] = None,
-                out: Optional[T] = None, feats: Optional[Dict[str, T]] = None) -> T:
-        """lr NCHW [1,3,h,w]; experts: dict of NCHW [1,3,4h,4w] -> SR NCHW [1,3,4h,4w].  feats (cached-mode forward only,
-        enhanced_fusion.py:794): the hooked expert features; every expert output is then scaled by its collaborative gain."""
-        _, _, h, w = lr.shape
+                out: Optional[T] = None, feats: Optional[Dict[str, T]] = None, _cap: Optional[int] = None) -> T:
+        """lr NCHW [B,3,h,w]; experts: dict of NCHW [B,3,4h,4w] -> SR NCHW [B,3,4h,4w] (written into `out` when given).  feats
+        (cached-mode forward only, enhanced_fusion.py:794): the hooked expert features [B,C,h,w]; every expert output is then scaled by
+        its image's collaborative gain.
+        B > 1: one launch per op for the batch in the fused modes, in chunks of _chunk_images() images that write their slices of the
+        one output buffer; the per-image loop in f32 mode.  Either way every image has the bits of its own B = 1 call.  taps are
+        recorded for B == 1 only."""
+        B, _, h, w = lr.shape
         dev = lr.device
+        if B > 1 and taps is not None:
+            raise _lib.FFError("FusionHIP.forward: taps are recorded for B == 1 only")
+        nb = self._chunk_images(B, h, w)
+        if nb < B:
+            if out is None:
+                out = torch.empty((B, 3, 4 * h, 4 * w), device=dev, dtype=torch.float32)
+            for ci, b0 in enumerate(range(0, B, nb)):
+                sl = slice(b0, b0 + nb)
+                self.forward(lr[sl], {k: experts[k][sl] for k in ("hat", "dat", "nafnet")}, None,
+                             pre["chunks"][ci] if pre is not None else None, out[sl],
+                             {k: v[sl] for k, v in feats.items()} if feats is not None else None, _cap=nb)
+            return out
         if pre is None:
             pre = self.pre(lr)
         raw, xb, b3, guide, gates, dif = pre["raw"], pre["xb"], pre["b3"], pre["guide"], pre["gates"], pre["dif"]
-        e9 = torch.empty((1, 4 * h, 4 * w, 9), device=dev, dtype=torch.float32)
+        e9 = torch.empty((B, 4 * h, 4 * w, 9), device=dev, dtype=torch.float32)
         for i, k in enumerate(("hat", "dat", "nafnet")):
             ops.nchw_to_nhwc(experts[k], out=e9[..., 3 * i:3 * i + 3])
         if feats is not None:
             if self.collab is None:
                 raise _lib.FFError("expert features were passed but the checkpoint holds no collaborative.* weights")
-            gains = self.collab(feats, (4 * h, 4 * w), taps)
+            gains = self.collab(feats, (4 * h, 4 * w), taps)      # [B,3] per expert: ff_mix2_images scales image b by its own row
             for i, k in enumerate(("hat", "dat", "nafnet")):
                 ops.mix2(e9[..., 3 * i:3 * i + 3], ca=gains[i], clamp01=True, out=e9[..., 3 * i:3 * i + 3])       # :415-416
                 if taps is not None:
                     taps[f"collab.out.{k}"] = e9[..., 3 * i:3 * i + 3]
-        hier = self.hier(e9)
+        hier = self.hier(e9, _cap)
         fused = ops.fuse_blend(e9, hier, guide, gates, dif)
         if taps is not None:
             for i in range(9):
@@ -493,10 +567,10 @@ class FusionHIP:
             for i in range(3):
                 taps[f"bands.g{i}"] = b3[..., 3 * i:3 * i + 3]
             taps.update({"fusion.hier": hier, "fusion.gates": gates, "fusion.difficulty": dif, "fusion.fused1": fused})
-        r = ops.conv2d(fused, *self.refine[0], ksize=(3, 3), pad=(1, 1), act="gelu")
-        r = ops.conv2d(r, *self.refine[1], ksize=(3, 3), pad=(1, 1), act="gelu")
-        r = ops.conv2d(r, *self.refine[2], ksize=(3, 3), pad=(1, 1), act="gelu")
-        f = ops.conv2d(r, *self.refine[3], ksize=(3, 3), pad=(1, 1), res=fused, alpha=0.1)
+        r = _conv(fused, *self.refine[0], ksize=(3, 3), pad=(1, 1), act="gelu")
+        r = _conv(r, *self.refine[1], ksize=(3, 3), pad=(1, 1), act="gelu")
+        r = _conv(r, *self.refine[2], ksize=(3, 3), pad=(1, 1), act="gelu")
+        f = _conv(r, *self.refine[3], ksize=(3, 3), pad=(1, 1), res=fused, alpha=0.1)
         f = ops.mix2(f, pre["up"], clamp01=True)
         if taps is not None:
             taps["fusion.pre_edge"] = f

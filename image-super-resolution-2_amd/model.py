@@ -25,18 +25,6 @@ from .fusion import FusionHIP
 T = torch.Tensor
 
 
-def _per_image(lr: T, fn) -> list:
-    """[fn(b, lr[b:b+1]) for every image b of a contiguous batch]: the one place where what is not batched yet (the fusion
-    stack) is sequenced image by image; B == 1 is a batch of one.  An image that does not start on a 16-byte boundary (odd
-    image sizes) is copied, since the kernels take 16-byte aligned images.  The copy is a torch op, which a recorded plan (plan.py)
-    cannot carry: forward() refuses to record such a batch."""
-    res = []
-    for b in range(lr.shape[0]):
-        t = lr[b:b + 1]
-        res.append(fn(b, t.clone() if t.data_ptr() % 16 else t))
-    return res
-
-
 def _features_at_lr(raws: list, B: int, h: int, w: int) -> T:
     """Hooked NHWC features (one tensor for the batch, or one per image) -> [B,C,h,w] bilinearly resized to the LR resolution."""
     f = torch.empty((B, raws[0].shape[-1], h, w), device=raws[0].device, dtype=torch.float32)
@@ -89,34 +77,32 @@ class FreqFusionHIP:
             t.record_stream(main)
 
     def _run_experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = True):
-        """ExpertEnsemble.forward_all (expert_loader.py:768-777) for a batch lr [B,3,h,w]: (hat [B,3,4h,4w], [dat_b], [nafnet_b],
-        [pre_b or None]).  The three experts are independent until the fusion stack, so each runs on its own HIP stream (_fork; the
+        """ExpertEnsemble.forward_all (expert_loader.py:768-777) for a batch lr [B,3,h,w]: (hat, dat, nafnet [B,3,4h,4w] each, pre or
+        None).  The three experts are independent until the fusion stack, so each runs on its own HIP stream (_fork; the
         whole fan-out is captured into the HIP graph): latency-bound kernels of one expert overlap with bandwidth-bound kernels of
         another.  Every expert takes the whole batch through one launch per op (HatHIP / DatHIP / NafnetHIP.forward): HAT on the
-        caller's stream, DAT on side stream 1, NAFNet and then (with_pre) the LR-only part of the fusion stack (FusionHIP.pre), which
-        runs for each b, on side stream 2, the shortest expert's.  On one stream, and
+        caller's stream, DAT on side stream 1, NAFNet and then (with_pre) the LR-only part of the fusion stack (FusionHIP.pre, once
+        for the batch) on side stream 2, the shortest expert's.  On one stream, and
         with taps, the experts run one after the other and pre is left to fusion.forward."""
         if not self.multi_stream or taps is not None:
             hat = self.hat.forward(lr, taps)
             dat = self.dat.forward(lr, taps)
             naf = self.nafnet.forward(lr, taps)
-            return hat, [dat[b:b + 1] for b in range(lr.shape[0])], [naf[b:b + 1] for b in range(lr.shape[0])], [None] * lr.shape[0]
+            return hat, dat, naf, None
         with self._fork(mark=True) as (s1, s2, made):
             with torch.cuda.stream(s1):
                 dat = self.dat.forward(lr)
             with torch.cuda.stream(s2):
                 naf = self.nafnet.forward(lr)
-                pres = _per_image(lr, lambda b, x: self.fusion.pre(x) if with_pre else None)
+                pre = self.fusion.pre(lr) if with_pre else None
             hat = self.hat.forward(lr)
-            dats = [dat[b:b + 1] for b in range(lr.shape[0])]
-            nafs = [naf[b:b + 1] for b in range(lr.shape[0])]
-            made += (dat, naf, *(t for pre in pres if pre is not None for t in pre.values()))
-        return hat, dats, nafs, pres
+            made += (dat, naf, *self.fusion.pre_tensors(pre))
+        return hat, dat, naf, pre
 
     def experts(self, lr: T, taps: Optional[dict] = None, with_pre: bool = False):
         """The experts of ONE image lr [1,3,h,w]: {hat, dat, nafnet: [1,3,4h,4w]}, or with with_pre ({...}, pre), pre being
         FusionHIP.pre(lr) on three streams and None otherwise."""
-        hat, (dat,), (naf,), (pre,) = self._run_experts(lr, taps, with_pre)
+        hat, dat, naf, pre = self._run_experts(lr, taps, with_pre)
         ex = {"hat": hat, "dat": dat, "nafnet": naf}
         return (ex, pre) if with_pre else ex
 
@@ -157,23 +143,29 @@ class FreqFusionHIP:
     @torch.no_grad()
     def forward_with_precomputed(self, lr: T, expert_outputs, expert_features=None, taps: Optional[dict] = None) -> T:
         """CompleteEnhancedFusionSR.forward_with_precomputed (enhanced_fusion.py:756-812): the cached-mode forward.  The expert
-        outputs {hat,dat,nafnet: [1,3,4h,4w]} and, optionally, their hooked features (isr2_amd/cache.py files, or
-        experts_with_features()) come from the caller; only the fusion stack runs, with the collaborative block live when
-        features are given.  The forward half of SURVEY 8f rank 1; no backward is built."""
-        if lr.dim() != 4 or lr.shape[0] != 1 or lr.shape[1] != 3:
-            raise _lib.FFError(f"expected lr of shape [1,3,h,w], got {tuple(lr.shape)}")
+        outputs {hat,dat,nafnet: [B,3,4h,4w]} and, optionally, their hooked features [B,C,h,w] (isr2_amd/cache.py files, or
+        experts_with_features()) come from the caller; only the fusion stack runs (one launch per op for the batch, FusionHIP.forward),
+        with the collaborative block live when features are given.  A [3,..] / [C,..] tensor is one image.  taps: B == 1 only.
+        The forward half of SURVEY 8f rank 1; no backward is built."""
+        if lr.dim() != 4 or lr.shape[0] < 1 or lr.shape[1] != 3:
+            raise _lib.FFError(f"expected lr of shape [B,3,h,w], got {tuple(lr.shape)}")
         lr = lr.to(self.dev, torch.float32).contiguous()
-        _, _, h, w = lr.shape
+        B, _, h, w = lr.shape
+        if B > 1 and taps is not None:
+            raise _lib.FFError("taps are recorded for B == 1 only")
         ex = {}
         for k in ("hat", "dat", "nafnet"):
             t = expert_outputs[k]
             t = t.unsqueeze(0) if t.dim() == 3 else t
-            if tuple(t.shape) != (1, 3, 4 * h, 4 * w):
-                raise _lib.FFError(f"expert output {k}: expected [1,3,{4 * h},{4 * w}], got {tuple(t.shape)}")
+            if tuple(t.shape) != (B, 3, 4 * h, 4 * w):
+                raise _lib.FFError(f"expert output {k}: expected [{B},3,{4 * h},{4 * w}], got {tuple(t.shape)}")
             ex[k] = t.to(self.dev, torch.float32).contiguous()
         feats = None
         if expert_features is not None:
             feats = {k: (v.unsqueeze(0) if v.dim() == 3 else v).to(self.dev, torch.float32).contiguous() for k, v in expert_features.items()}
+            for k, v in feats.items():
+                if v.dim() != 4 or v.shape[0] != B:
+                    raise _lib.FFError(f"expert feature {k}: expected [{B},C,h,w], got {tuple(v.shape)}")
         with torch.cuda.device(self.dev):
             return self.fusion.forward(lr, ex, taps, feats=feats)
 
@@ -186,21 +178,19 @@ class FreqFusionHIP:
         # Every global op of the path is per image (average pools, channel attention statistics, rFFT2, squeeze gates), so a batch is
         # B independent images.  The three experts take the whole batch through one launch per op (HatHIP / DatHIP / NafnetHIP.forward:
         # their per-image quantities -- HAT's channel-attention gate [B,180], DAT's attention matrix [B,180,180] and channel gate [B,180],
-        # NAFNet's SCA vector [B,c] -- are matrices); the fusion stack is still sequenced per image (_per_image).
-        # Bit-identical to B single forwards: every image runs the launches, in the forms, of its own B == 1 forward.
+        # NAFNet's SCA vector [B,c] -- are matrices) and so does the fusion stack (FusionHIP.pre / .forward: the rFFT2 band planes, the
+        # gates and the zero-padded concat buffers are [B,...]; the collaborative gains of the cached mode [B,3]).  No image is copied:
+        # the kernels that read the planar LR batch take an image at any 4-byte offset, so a batch of any size can be recorded as a plan.
+        # Bit-identical to B single forwards: every image is computed in the kernel forms of its own B == 1 forward.
         if B > 1 and taps is not None:
             raise _lib.FFError("taps are recorded for B == 1 only")
-        if B > 1 and self._marker is not None and (3 * h * w) % 4:
-            # plan recording: an image that does not start on a 16-byte boundary is copied by torch (_per_image), outside the tape
-            raise _lib.FFError(f"a plan of a batch needs images of a multiple of 16 bytes (3 * h * w % 4 == 0), got {tuple(lr.shape)}")
         if out is None:
             out = torch.empty((B, 3, 4 * h, 4 * w), device=self.dev, dtype=torch.float32)
         with torch.cuda.device(self.dev):
-            hat, dats, nafs, pres = self._run_experts(lr, taps)
+            hat, dat, naf, pre = self._run_experts(lr, taps)
             if taps is not None:
-                taps.update({"expert.hat": hat, "expert.dat": dats[0], "expert.nafnet": nafs[0]})
-            _per_image(lr, lambda b, x: self.fusion.forward(x, {"hat": hat[b:b + 1], "dat": dats[b], "nafnet": nafs[b]}, taps,
-                                                            pre=pres[b], out=out[b:b + 1]))
+                taps.update({"expert.hat": hat, "expert.dat": dat, "expert.nafnet": naf})
+            self.fusion.forward(lr, {"hat": hat, "dat": dat, "nafnet": naf}, taps, pre=pre, out=out)
         return out
 
     __call__ = forward

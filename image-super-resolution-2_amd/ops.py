@@ -446,8 +446,12 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
 
 def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] = None, mul: Optional[T] = None,
            alpha: float = 1.0, out: Optional[T] = None, dynamic_w: bool = False, kmul: Optional[T] = None,
-           gate_pairs: bool = False, out_bf16: bool = False, tile_hint: int = 0, rows_gemm: bool = False) -> T:
-    """x [..., K] rows view, w [N, K] -> [..., N].  kmul [K]: scale of the input channels (W (kmul * x); split-bf16 modes).
+           gate_pairs: bool = False, out_bf16: bool = False, tile_hint: int = 0, rows_gemm: bool = False,
+           rows_per_image: int = 0) -> T:
+    """x [..., K] rows view, w [N, K] -> [..., N].
+    rows_per_image (fp32-rows route of the split-bf16 modes; 0 = the rows are one image): the rows are equal groups of this many rows, one
+    independent image each, and the implicit GEMM takes the tile configuration ONE group's row count picks for itself
+    (ff_conv2d_bf16s_tile), so every image has the bits of its own call.  A value that equals the row count changes nothing.  kmul [K]: scale of the input channels (W (kmul * x); split-bf16 modes).
     kmul [B, K] with B > 1: the rows are B equal groups (rows % B == 0), group b scaled by kmul[b], in one launch -- every group with
     the bits of its own call with kmul[b] (the tile configuration is taken from one group's row count).
     gate_pairs: SimpleGate in the epilogue, [..., N / 2] out with out[j] = y[2j] * y[2j+1] (rows of w interleaved by the caller).
@@ -461,6 +465,9 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
                                gate_pairs=gate_pairs, out_bf16=out_bf16, tile_hint=tile_hint, rows_gemm=rows_gemm)
     if w.dim() == 3:                                         # one image: the single-weight entry
         w = w[0]
+    rows_per_image = int(rows_per_image)
+    if rows_per_image and (rows_per_image < 0 or x.dtype == torch.bfloat16 or rows_gemm or w.dim() == 3 or (kmul is not None and kmul.numel() != w.shape[-1])):
+        raise _lib.FFError("linear: rows_per_image belongs to the fp32-rows route with one weight matrix and one kmul vector")
     if x.dtype == torch.bfloat16 or rows_gemm:
         return _linear_rows_bf16(x, w, bias, act=act, res=res, mul=mul, alpha=alpha, out=out, dynamic_w=dynamic_w, kmul=kmul,
                                  gate_pairs=gate_pairs, out_bf16=out_bf16, tile_hint=tile_hint)
@@ -484,6 +491,8 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
         rp, ldr, rrows, rc = rows_view(res, "linear.res")
         if rrows != rows or rc != N:
             raise _lib.FFError("linear: res shape mismatch")
+    if rows_per_image and rows % rows_per_image:
+        raise _lib.FFError(f"linear: {rows} rows are not whole images of rows_per_image = {rows_per_image} rows")
     if _GEMM_MODE == "f32":
         _lib.check(_L().ff_conv2d(xp, w.data_ptr(), _ptr(bias), _ptr(mul), rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr,
                                   1, 1, 1, 1, 0, 0, ACT[act], float(alpha), 0, 0, _stream()))
@@ -498,9 +507,12 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
                                                         kmul.data_ptr(), images, rows // images, _ptr(bias), _ptr(mul), rp, ldr, op, ldo,
                                                         rows, K, N, GEMM_MODES[_GEMM_MODE], 0, _stream()))
         else:
+            hint = 0                                         # several images: the tile configuration one image's launch picks for itself
+            if rows_per_image and rows_per_image != rows:
+                hint = int(_L().ff_conv2d_bf16s_tile(rows_per_image, N, K, 1 if aligned and K % 4 == 0 else 0))
             _lib.check(_L().ff_conv2d_bf16s(xp, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, _ptr(bias), _ptr(mul),
                                             rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
-                                            float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], 0, _ptr(kmul), _stream()))
+                                            float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], hint, _ptr(kmul), _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K + N * K + rows * No * (2 if res is not None else 1)))
     return out
 
@@ -1086,6 +1098,8 @@ def sgfn_tail(y: T, c2: int, w_tap: T, dw_bias: Optional[T], stats: T, gamma: T,
 def mix2(a: T, b: Optional[T] = None, *, ka: float = 1.0, kb: float = 1.0, ca: Optional[T] = None,
          cb: Optional[T] = None, pa: Optional[T] = None, pb: Optional[T] = None, clamp01: bool = False,
          out: Optional[T] = None) -> T:
+    """out = ka*a*ca[c]*pa[p] + kb*b*cb[c]*pb[p].  ca [B, C] with B > 1: the rows are B equal groups (one image each) and group b is scaled
+    by ca[b], in one launch (ff_mix2_images) -- every image with the bits of its own call with ca[b]."""
     ap, lda, rows, C = rows_view(a, "mix2.a")
     bp, ldb = None, 0
     if b is not None:
@@ -1108,9 +1122,20 @@ def mix2(a: T, b: Optional[T] = None, *, ka: float = 1.0, kb: float = 1.0, ca: O
 
     pap, ldpa = pvec(pa, "mix2.pa")
     pbp, ldpb = pvec(pb, "mix2.pb")
+    images = 1
+    if ca is not None and ca.dim() == 2 and ca.shape[0] > 1:
+        images = int(ca.shape[0])
+        _chk(ca, "mix2.ca")
+        if ca.shape[1] != C or not ca.is_contiguous() or rows % images:
+            raise _lib.FFError(f"mix2: ca {tuple(ca.shape)} must be a contiguous [B, {C}] matrix with B dividing the {rows} rows")
     for v_, nm in ((ca, "ca"), (cb, "cb")):
-        if v_ is not None and v_.numel() != C:
+        if v_ is not None and v_.numel() != C * (images if nm == "ca" else 1):
             raise _lib.FFError(f"mix2: {nm} must have {C} elements")
+    if images > 1:
+        _lib.check(_L().ff_mix2_images(op, ldo, ap, lda, bp, ldb, rows, C, float(ka), float(kb), ca.data_ptr(), images, rows // images,
+                                       _ptr(cb), pap, ldpa, pbp, ldpb, int(clamp01), _stream()))
+        _note(0.0, 4.0 * rows * C * (3 if b is not None else 2))
+        return out
     _lib.check(_L().ff_mix2(op, ldo, ap, lda, bp, ldb, rows, C, float(ka), float(kb), _ptr(ca), _ptr(cb), pap, ldpa, pbp,
                             ldpb, int(clamp01), _stream()))
     _note(0.0, 4.0 * rows * C * (3 if b is not None else 2))
@@ -1245,10 +1270,26 @@ def avgpool2(x: T) -> T:
     return out
 
 
+def _planar_images(x: T, out: T, name: str):
+    """Planar image(s) [3,H,W] or contiguous [B,3,H,W] and their NHWC output [B,H,W,>=..] -> (B, H, W, out pointer, ldo)."""
+    _chk(x, name + ".x")
+    B = int(x.shape[0]) if x.dim() == 4 else 1
+    C, H, W = x.shape[-3:]
+    op, ldo, ob, oh, ow, _ = _nhwc(out, name + ".out")
+    if B > 1 and (not x.is_contiguous() or C != 3 or (ob, oh, ow) != (B, H, W)):
+        raise _lib.FFError(f"{name}: expected contiguous planar images [B,3,H,W] and out [B,H,W,.], got {tuple(x.shape)} and {tuple(out.shape)}")
+    if B > 1 and out.stride(0) != H * W * ldo:
+        raise _lib.FFError(f"{name}: the images of out must follow each other ([B,H,W,ld] rows)")
+    return B, C, H, W, op, ldo
+
+
 def dct8_bands(x_planar: T, dct_mat: T, masks3: T, band_scale: T, out: T, ch_off: int):
-    _chk(x_planar, "dct8_bands.x")
-    C, H, W = x_planar.shape
-    op, ldo, *_ = _nhwc(out, "dct8_bands.out")
+    """x_planar [3,H,W] (or [1,3,H,W]); [B,3,H,W] with B > 1: the batch in one launch (ff_dct8_bands_images)."""
+    B, C, H, W, op, ldo = _planar_images(x_planar, out, "dct8_bands")
+    if B > 1:
+        _lib.check(_L().ff_dct8_bands_images(x_planar.data_ptr(), B, H, W, dct_mat.data_ptr(), masks3.data_ptr(), band_scale.data_ptr(),
+                                             op, ldo, ch_off, _stream()))
+        return
     _lib.check(_L().ff_dct8_bands(x_planar.data_ptr(), C, H, W, dct_mat.data_ptr(), masks3.data_ptr(), band_scale.data_ptr(),
                                   op, ldo, ch_off, _stream()))
 
@@ -1267,12 +1308,19 @@ def dwt_pass(x_planar: T, axis: int, lo8: T, hi8: T) -> Tuple[T, T]:
 
 def fft_bands(x_planar: T, twW: Tuple[T, T], twH: Tuple[T, T], mask_logits: T, temp: float, band_scale2: T, out: T,
               ch_lo: int, ch_hi: int):
-    _chk(x_planar, "fft_bands.x")
-    C, H, W = x_planar.shape
+    B, C, H, W, op, ldo = _planar_images(x_planar, out, "fft_bands")
+    msz = mask_logits.shape[-1]
+    if B > 1:                                                # the batch through one run of the four kernels (ff_fft_bands_images)
+        nwork = int(_L().ff_fft_bands_images_workspace(B, H, W))
+        if nwork < 0:
+            raise _lib.FFError(f"fft_bands: no batched form for {tuple(x_planar.shape)}")
+        work = torch.empty(nwork, device=x_planar.device, dtype=torch.float32)
+        _lib.check(_L().ff_fft_bands_images(x_planar.data_ptr(), B, H, W, twW[0].data_ptr(), twW[1].data_ptr(), twH[0].data_ptr(),
+                                            twH[1].data_ptr(), mask_logits.data_ptr(), msz, float(temp), band_scale2.data_ptr(),
+                                            work.data_ptr(), nwork, op, ldo, ch_lo, ch_hi, _stream()))
+        return
     nwork = 4 * C * H * (W // 2 + 1)
     work = torch.empty(nwork, device=x_planar.device, dtype=torch.float32)
-    op, ldo, *_ = _nhwc(out, "fft_bands.out")
-    msz = mask_logits.shape[-1]
     _lib.check(_L().ff_fft_bands(x_planar.data_ptr(), C, H, W, twW[0].data_ptr(), twW[1].data_ptr(), twH[0].data_ptr(),
                                  twH[1].data_ptr(), mask_logits.data_ptr(), msz, float(temp), band_scale2.data_ptr(),
                                  work.data_ptr(), nwork, op, ldo, ch_lo, ch_hi, _stream()))
@@ -1354,9 +1402,19 @@ def dynamic_gates(graw: T, dif: T) -> T:
 
 
 def fuse_blend(experts9: T, hier3: T, guide3: T, gates3: T, dif1: T) -> T:
-    _, Hh, Wh, _ = experts9.shape
+    """experts9 [B,Hh,Wh,9], hier3 [B,Hh,Wh,3], guide3 / gates3 [B,Hl,Wl,3], dif1 [B,Hl,Wl,1], all contiguous -> [B,Hh,Wh,3]; B > 1 in one
+    launch (ff_fuse_blend_images)."""
+    B, Hh, Wh, _ = experts9.shape
     _, Hl, Wl, _ = guide3.shape
-    out = torch.empty((1, Hh, Wh, 3), device=experts9.device, dtype=torch.float32)
+    out = torch.empty((B, Hh, Wh, 3), device=experts9.device, dtype=torch.float32)
+    if B > 1:
+        for t, c, hw in ((experts9, 9, (Hh, Wh)), (hier3, 3, (Hh, Wh)), (guide3, 3, (Hl, Wl)), (gates3, 3, (Hl, Wl)), (dif1, 1, (Hl, Wl))):
+            _chk(t, "fuse_blend")
+            if tuple(t.shape) != (B, *hw, c) or not t.is_contiguous():
+                raise _lib.FFError(f"fuse_blend: a batch needs contiguous [{B},{hw[0]},{hw[1]},{c}] tensors, got {tuple(t.shape)}")
+        _lib.check(_L().ff_fuse_blend_images(experts9.data_ptr(), hier3.data_ptr(), guide3.data_ptr(), gates3.data_ptr(), dif1.data_ptr(),
+                                             out.data_ptr(), B, Hh, Wh, Hl, Wl, _stream()))
+        return out
     _lib.check(_L().ff_fuse_blend(experts9.data_ptr(), hier3.data_ptr(), guide3.data_ptr(), gates3.data_ptr(), dif1.data_ptr(),
                                   out.data_ptr(), Hh, Wh, Hl, Wl, _stream()))
     return out

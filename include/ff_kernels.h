@@ -403,6 +403,12 @@ int ff_dwconv3x3_ln(const float* in, int ldi, float* out, int ldo, int B, int H,
 int ff_mix2(float* out, int ldo, const float* a, int lda, const float* b, int ldb, long long rows, int C, float ka,
             float kb, const float* ca, const float* cb, const float* pa, int ldpa, const float* pb, int ldpb,
             int clamp01, void* stream);
+/* ff_mix2 with a channel scale per image: the rows are B equal groups of rows_per_image rows (rows == B * rows_per_image, the first
+ * check) and ca is [B][C] (required): out = ka*a*ca[image][c]*pa[p] + kb*b*cb[c]*pb[p].  Every image has the bits of its own ff_mix2 call
+ * with ca[b] (the cached-mode forward's collaborative gains [B][3] on the batch's expert outputs).  Added under ABI version 7 (additive). */
+int ff_mix2_images(float* out, int ldo, const float* a, int lda, const float* b, int ldb, long long rows, int C, float ka,
+                   float kb, const float* ca, int B, long long rows_per_image, const float* cb, const float* pa, int ldpa,
+                   const float* pb, int ldpb, int clamp01, void* stream);
 /* out = a + alpha*b*c   (a may be NULL) */
 int ff_fma3(float* out, int ldo, const float* a, int lda, const float* b, int ldb, const float* c, int ldc,
             long long rows, int C, float alpha, void* stream);
@@ -470,6 +476,20 @@ int ff_fft_bands(const float* x, int C, int H, int W, const float* twW_cos, cons
                  const float* twH_cos, const float* twH_sin, const float* mask_logits, int msz, float temp,
                  const float* band_scale2, float* work, long long work_floats, float* out, int ldo, int ch_lo,
                  int ch_hi, void* stream);
+/* The DCT and FFT bands of B images in one launch each (one run of the four FFT kernels): x [B][3][H][W] -> out [B][H][W][ldo], the
+ * channel groups of ff_dct8_bands (ch_off .. ch_off + 8) / ff_fft_bands (ch_lo .. + 2, ch_hi .. + 2) in every image, each image with the
+ * bits of its own single-image call.  First check of both: 1 <= B, 3 B <= 65535 (the planes index gridDim.y of the FFT's column passes),
+ * H, W >= 8 (DCT) / H, W > 1, W <= 8192 and an H whose column tile fits 64 KiB of LDS as in ff_fft_bands (H <= 481 or 513 <= H <= 1638) (FFT); then null pointers, the workspace and ldo >= the channels written.
+ * The FFT's column passes take their decomposition (columns per workgroup, output-row split) from ONE image's three planes.
+ * work: ff_fft_bands_images_workspace(B, H, W) floats = B x the 4 * 3 * H * (W / 2 + 1) of one image (-1 for a refused geometry).
+ * Added under ABI version 7 (additive). */
+int ff_dct8_bands_images(const float* x, int B, int H, int W, const float* dct_mat, const float* masks3,
+                         const float* band_scale, float* out, int ldo, int ch_off, void* stream);
+long long ff_fft_bands_images_workspace(int B, int H, int W);
+int ff_fft_bands_images(const float* x, int B, int H, int W, const float* twW_cos, const float* twW_sin,
+                        const float* twH_cos, const float* twH_sin, const float* mask_logits, int msz, float temp,
+                        const float* band_scale2, float* work, long long work_floats, float* out, int ldo, int ch_lo,
+                        int ch_hi, void* stream);
 
 /* DAT channel attention (dat_arch.py:627-647): token-axis L2 norms + per-head 30x30 gram + softmax ->
  * block-diagonal [180][180] matrix (apply with ff_conv2d on v).  work: ff_chan_attn_workspace floats. */
@@ -503,6 +523,11 @@ int ff_freq_guidance(const float* bands3, float* guide, long long P, void* strea
 int ff_dynamic_gates(const float* graw, const float* dif, float* gates, long long P, void* stream);
 int ff_fuse_blend(const float* experts9, const float* hier3, const float* guide3, const float* gates3,
                   const float* dif1, float* out3, int Hh, int Wh, int Hl, int Wl, void* stream);
+/* ff_fuse_blend for B images in one launch (grid: one image's blocks x B): contiguous [B][...] tensors, image b's experts9 / hier3 / out3
+ * at b * Hh * Wh * {9, 3, 3} and guide3 / gates3 / dif1 at b * Hl * Wl * {3, 3, 1}.  First check: 1 <= B <= 65535 and positive sizes.
+ * Added under ABI version 7 (additive). */
+int ff_fuse_blend_images(const float* experts9, const float* hier3, const float* guide3, const float* gates3,
+                         const float* dif1, float* out3, int B, int Hh, int Wh, int Hl, int Wl, void* stream);
 
 /* Device PSNR / SSIM evaluator (csrc/metrics.hip; reference src/utils/metrics.py:30-52 rgb_to_y, :76-126 calculate_psnr,
  * :129-190 calculate_ssim_torch).  a, b: planar fp32 images [C][H][W], C = 1 or 3; values are clamped to [0,1], `crop` border

@@ -1,4 +1,4 @@
-"""Batched HAT, DAT and NAFNet against the sequential loop over the same images, on one MI355X, in one process:
+"""Batched HAT, DAT, NAFNet and fusion stack against the sequential loop over the same images, on one MI355X, in one process:
     python tools/batch_bench.py [--cases 64x64x5,64x64x16,256x256x2] [--modes bf16,bf16x3] [--reps 5] [--rounds 5] [--json PATH]
 hat:     HatHIP.forward(lr [B,3,h,w]) (one launch per op for the batch) and the loop `for b: HatHIP.forward(lr[b:b+1])`, each captured
          into one HIP graph and replayed between device events, alternating over --rounds rounds; medians and min..max per form.  The
@@ -7,6 +7,9 @@ hat:     HatHIP.forward(lr [B,3,h,w]) (one launch per op for the batch) and the 
          (`loss_exceeds_loop_spread`: the same for a batch that is SLOWER than the loop).
 nafnet:  the same two forms of NafnetHIP.forward, the same protocol.
 dat:     the same two forms of DatHIP.forward, the same protocol.
+fusion:  the same two forms of FusionHIP.forward(lr, experts) on given (random) expert outputs [B,3,4h,4w]: no expert runs.
+forward: the whole FreqFusionHIP.forward(lr [B,3,h,w]) against the form it had while the fusion stack was per image: the three experts
+         batched on their three streams, FusionHIP.pre image by image behind NAFNet, then FusionHIP.forward image by image.
 streams: what each of the three streams of model.experts_with_features carries for one group of --group patches of 64x64 (the cache
          builder's unit): HAT, DAT and NAFNet batched and patch by patch, each graph-replayed alone -- the longest bounds the group.
 One JSON line per section; --json also writes them to a file."""
@@ -75,7 +78,8 @@ def expert_section(a, hat, ops, name):
     return {"section": name, "reps": a.reps, "rounds": a.rounds, "cases": res}
 
 
-def _expert_cases(a, hat, ops, res):
+def _expert_cases(a, hat, ops, res, batched=None, loop_of=None):
+    """batched(lr) / loop_of(lr, o_loop)() default to the expert's forward on the batch / image by image into o_loop."""
     for mode in a.modes.split(","):
         ops.set_gemm_mode(mode)
         for case in a.cases.split(","):
@@ -88,8 +92,8 @@ def _expert_cases(a, hat, ops, res):
                     hat.forward(lr[b:b + 1], out=o_loop[b:b + 1])
                 return o_loop
 
-            g_b, o_b = _capture(lambda: hat.forward(lr))
-            g_l, _ = _capture(loop)
+            g_b, o_b = _capture((lambda: batched(lr)) if batched is not None else (lambda: hat.forward(lr)))
+            g_l, _ = _capture(loop_of(lr, o_loop) if loop_of is not None else loop)
             same = bool(torch.equal(o_b, o_loop))
             ms = _alternate({"batched": g_b, "loop": g_l}, a.reps, a.rounds)
             sb, sl = _stats(ms["batched"]), _stats(ms["loop"])
@@ -100,6 +104,69 @@ def _expert_cases(a, hat, ops, res):
                         "gain_exceeds_loop_spread": bool(sl["median"] - sb["median"] > sl["max"] - sl["min"]), "bit_identical": same})
             del g_b, g_l
             torch.cuda.synchronize()
+
+
+def fusion_section(a, model, ops):
+    """FusionHIP.forward on given expert outputs: one call for the batch against one call per image."""
+    fus, res, ex = model.fusion, [], {}
+    key = (id(fus), "batch_bench", "fusion")
+
+    def experts(lr):                                               # made once per case (the first, un-captured warm-up call)
+        B, _, h, w = lr.shape
+        if ex.get("for") is not lr:
+            g = torch.Generator(device="cuda").manual_seed(h + 7 * B)
+            ex.update({k: torch.rand((B, 3, 4 * h, 4 * w), device="cuda", generator=g) for k in ("hat", "dat", "nafnet")})
+            ex["for"] = lr
+        return {k: ex[k] for k in ("hat", "dat", "nafnet")}
+
+    def loop_of(lr, o_loop):
+        def loop():
+            e = experts(lr)
+            for b in range(lr.shape[0]):
+                fus.forward(lr[b:b + 1], {k: v[b:b + 1] for k, v in e.items()}, out=o_loop[b:b + 1])
+            return o_loop
+        return loop
+
+    ops.set_capture_key(key)                                       # the concat buffers belong to the graphs captured here
+    try:
+        _expert_cases(a, fus, ops, res, batched=lambda lr: fus.forward(lr, experts(lr)), loop_of=loop_of)
+    finally:
+        ops.set_capture_key(None)
+        torch.cuda.synchronize()
+        ops.drop_persistent(key=key)
+    return {"section": "fusion", "reps": a.reps, "rounds": a.rounds, "cases": res}
+
+
+def forward_section(a, model, ops):
+    """FreqFusionHIP.forward on a batch against the form with the per-image fusion stack (experts batched on three streams)."""
+    res = []
+    key = (id(model), "batch_bench", "forward")
+    fus = model.fusion
+
+    def loop_of(lr, o_loop):
+        def loop():
+            B = lr.shape[0]
+            with model._fork(mark=False) as (s1, s2, made):
+                with torch.cuda.stream(s1):
+                    dat = model.dat.forward(lr)
+                with torch.cuda.stream(s2):
+                    naf = model.nafnet.forward(lr)
+                    pres = [fus.pre(lr[b:b + 1]) for b in range(B)]
+                hat = model.hat.forward(lr)
+                made += (dat, naf, *(t for p in pres for t in p.values()))
+            for b in range(B):
+                fus.forward(lr[b:b + 1], {"hat": hat[b:b + 1], "dat": dat[b:b + 1], "nafnet": naf[b:b + 1]}, pre=pres[b], out=o_loop[b:b + 1])
+            return o_loop
+        return loop
+
+    ops.set_capture_key(key)
+    try:
+        _expert_cases(a, model, ops, res, batched=lambda lr: model.forward(lr), loop_of=loop_of)
+    finally:
+        ops.set_capture_key(None)
+        torch.cuda.synchronize()
+        ops.drop_persistent(key=key)
+    return {"section": "forward", "reps": a.reps, "rounds": a.rounds, "multi_stream": bool(model.multi_stream), "cases": res}
 
 
 def streams_section(a, model, ops):
@@ -146,7 +213,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="alternating rounds; medians and min..max are reported")
     ap.add_argument("--group", type=int, default=5, help="streams section: patches per group")
     ap.add_argument("--streams-mode", default="bf16x3")
-    ap.add_argument("--section", default="all", choices=("all", "hat", "nafnet", "dat", "streams"))
+    ap.add_argument("--section", default="all", choices=("all", "hat", "nafnet", "dat", "fusion", "forward", "streams"))
     ap.add_argument("--json")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -165,6 +232,12 @@ def main():
             print(json.dumps(out[-1]), flush=True)
         if a.section in ("all", "dat"):
             out.append(expert_section(a, model.dat, ops, "dat"))
+            print(json.dumps(out[-1]), flush=True)
+        if a.section in ("all", "fusion"):
+            out.append(fusion_section(a, model, ops))
+            print(json.dumps(out[-1]), flush=True)
+        if a.section in ("all", "forward"):
+            out.append(forward_section(a, model, ops))
             print(json.dumps(out[-1]), flush=True)
         if a.section in ("all", "streams"):
             out.append(streams_section(a, model, ops))
