@@ -14,6 +14,10 @@
 //     v_permlane32_swap, rescale skipped while no maximum moves, output stored straight from the accumulators.
 // The reference indexes its bias table with NEGATIVE numbers (offset a = ws - ows + 1 = -7) that PyTorch wraps; the table arrives
 // rotated (prep.pack_rel_overlap) so that  i = 600 - 39 qy - qx + 39 ky + kx  is in [0, 1521).
+// ROWS16 (ff_ocab_attn_rows16): q / k / v arrive as bf16 rows with every head slice padded from 30 to 32 channels (64 bytes, 16-byte
+// aligned; channels 30 / 31 exact zeros, q already scaled) -- what ff_token_linear_rows16 writes from prep.pack_ocab_qkv's weights.  The
+// fp32 form rounds the same values to bf16 as they arrive, so both forms feed the MFMAs the same operands; the rows form fetches them
+// with 5 sixteen-byte loads per lane and stage instead of 18 eight-byte ones and converts nothing.
 #include "ff_common.h"
 
 #define OC_NK 576
@@ -30,6 +34,7 @@
 #define OC_OFF_TOK (OC_OFF_REL + 2 * OC_RELB)
 #define OC_LDS (OC_OFF_TOK + OC_NK * 4)
 #define OC_NLOAD 18                       // 288 keys / 16 keys per pass
+#define OC_NLOAD16 5                      // ROWS16: 288 keys x 8 sixteen-byte quarters (4 of k, 4 of v) / 512 lanes, last pass half-masked
 
 struct OcabParams {
   const float* qkv; float* out; const float* rel;
@@ -38,6 +43,7 @@ struct OcabParams {
   FF_STAMP_MEMBER
 };
 
+template <bool ROWS16>
 __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int* ktok = reinterpret_cast<int*>(smem + OC_OFF_TOK);
@@ -79,28 +85,65 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   const int spr = tid & 31, skey = tid >> 5;
   const bool s_on = spr < 30, s_isk = spr < 15;
   const int s_ch = s_isk ? p.k_off + 2 * spr : p.v_off + 2 * (spr - 15);
-  float2 stg[OC_NLOAD];
+  float2 stg[ROWS16 ? 1 : OC_NLOAD];
   float tb[3];
-  float2 qn[8];
+  float2 qn[ROWS16 ? 1 : 8];
+  // ROWS16 staging: item = tid + 512 i of the stage is quarter (item & 7) of key (item >> 3): quarters 0..3 are the key's k slice,
+  // 4..7 its v slice, so eight neighbouring lanes fetch the two 64-byte segments of one key
+  const __bf16* qkv16 = reinterpret_cast<const __bf16*>(p.qkv);
+  const int s_qt = tid & 7;
+  const int s_ch16 = s_qt < 4 ? p.k_off + 8 * s_qt : p.v_off + 8 * (s_qt - 4);
+  bf16x8 stg16[ROWS16 ? OC_NLOAD16 : 1];
+  bf16x8 qn16[2];
   unsigned stg_ok = 0u;                                 // validity of the staged keys (bit i): applied when the stage is STORED -- a select
                                                         // on the loaded value here would make every load wait for its data (measured: 3.5 us
                                                         // per stage just to "issue" the loads, tools/oc_time.cpp)
   // in two halves: a wave stalls at issue once it has more than a dozen or so loads outstanding (tools/oc_time.cpp: "issuing" all 18 took
   // 3.6 us = the latency of the first ones); the second half is issued a third of the way into the stage's tiles
   auto stage_load = [&](int h, int st, int part) {
-    if (part == 0) stg_ok = 0u;
+    if constexpr (ROWS16) {                             // five loads: all of them at the start of the stage
+      if (part == 0) {
+        stg_ok = 0u;
 #pragma unroll
-    for (int i = 0; i < OC_NLOAD; ++i) {
-      if ((i < OC_NLOAD / 2) != (part == 0)) continue;
-      const int tk = s_on ? ktok[st * OC_STK + skey + 16 * i] : -1;
-      stg_ok |= (tk >= 0 ? 1u : 0u) << i;
-      stg[i] = *reinterpret_cast<const float2*>(p.qkv + (tk >= 0 ? (long long)tk * p.ldq + s_ch + h * 30 : 0));
+        for (int i = 0; i < OC_NLOAD16; ++i) {
+          const int kl = (tid + 512 * i) >> 3;
+          const int tk = kl < OC_STK ? ktok[st * OC_STK + kl] : -1;
+          stg_ok |= (tk >= 0 ? 1u : 0u) << i;
+          stg16[i] = *reinterpret_cast<const bf16x8*>(qkv16 + (tk >= 0 ? (long long)tk * p.ldq : 0) + s_ch16 + h * 32);
+        }
+      }
+    } else {
+      if (part == 0) stg_ok = 0u;
+#pragma unroll
+      for (int i = 0; i < OC_NLOAD; ++i) {
+        if ((i < OC_NLOAD / 2) != (part == 0)) continue;
+        const int tk = s_on ? ktok[st * OC_STK + skey + 16 * i] : -1;
+        stg_ok |= (tk >= 0 ? 1u : 0u) << i;
+        stg[i] = *reinterpret_cast<const float2*>(p.qkv + (tk >= 0 ? (long long)tk * p.ldq + s_ch + h * 30 : 0));
+      }
     }
   };
   auto stage_store = [&](int buf) {
     unsigned char* kb = smem + buf * OC_STAGEB;
     unsigned char* vb = kb + OC_KBUF;
-    if (s_on) {
+    if constexpr (ROWS16) {
+#pragma unroll
+      for (int i = 0; i < OC_NLOAD16; ++i) {
+        const int kl = (tid + 512 * i) >> 3;
+        if (kl >= OC_STK) continue;                       // second half of the last pass
+        const bool ok = (stg_ok >> i) & 1u;
+        const bf16x8 z = {};
+        const bf16x8 val = ok ? stg16[i] : z;
+        if (s_qt < 4) {
+          *reinterpret_cast<bf16x8*>(kb + kl * OC_KROWB + 16 * s_qt) = val;
+        } else {
+          const int ch = 8 * (s_qt - 4), pos = ff_swap23(kl);
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (e < 6 || s_qt < 7) *reinterpret_cast<__bf16*>(vb + (ch + e) * OC_VROWB + 2 * pos) = val[e];    // rows 30 / 31 are the kernel's constants
+        }
+      }
+    } else if (s_on) {
 #pragma unroll
       for (int i = 0; i < OC_NLOAD; ++i) {
         const int kl = skey + 16 * i;
@@ -120,13 +163,18 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   auto head_load = [&](int h) {                        // bias table and queries of head h
 #pragma unroll
     for (int i = 0; i < 3; ++i) tb[i] = (tid + 512 * i < OC_RELN) ? p.rel[(long long)h * OC_RELN + tid + 512 * i] : 0.f;
+    if constexpr (ROWS16) {                             // channels 16 s + 8 hh .. + 7 of the head's 32-wide slice: the MFMA operand as stored
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+      for (int s = 0; s < 2; ++s) qn16[s] = *reinterpret_cast<const bf16x8*>(qkv16 + qtok * p.ldq + p.q_off + h * 32 + 16 * s + 8 * hh);
+    } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int dd = 16 * s + 8 * hh + 2 * j;
-        qn[4 * s + j] = dd < 30 ? *reinterpret_cast<const float2*>(p.qkv + qtok * p.ldq + p.q_off + h * 30 + dd) : (float2){0.f, 0.f};
-      }
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int dd = 16 * s + 8 * hh + 2 * j;
+          qn[4 * s + j] = dd < 30 ? *reinterpret_cast<const float2*>(p.qkv + qtok * p.ldq + p.q_off + h * 30 + dd) : (float2){0.f, 0.f};
+        }
+    }
   };
   bf16x8 qh[2];
   auto head_store = [&](int h) {
@@ -134,14 +182,20 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
       if (tid + 512 * i < OC_RELN) tl[tid + 512 * i] = tb[i];
+    if constexpr (ROWS16) {
+      const bf16x8 z = {};
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+      for (int s = 0; s < 2; ++s) qh[s] = qvalid ? qn16[s] : z;
+    } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = qvalid;
-        qh[s][2 * j] = (__bf16)(ok ? qn[4 * s + j].x * p.scale : 0.f);
-        qh[s][2 * j + 1] = (__bf16)(ok ? qn[4 * s + j].y * p.scale : 0.f);
-      }
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool ok = qvalid;
+          qh[s][2 * j] = (__bf16)(ok ? qn[4 * s + j].x * p.scale : 0.f);
+          qh[s][2 * j + 1] = (__bf16)(ok ? qn[4 * s + j].y * p.scale : 0.f);
+        }
+    }
   };
 
   stage_load(0, 0, 0);
@@ -253,6 +307,23 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   FF_STAMP(64, 60);
 }
 
+template <bool ROWS16>
+static int ocab_launch(OcabParams& p, const char* who, void* stream) {
+  FF_STAMP_ARM(p);
+  const long long nblk = (long long)p.B * p.nwx * p.nwy;
+  FF_CHECK_ARG(nblk < (1LL << 31), "%s: grid too large", who);
+  static_assert(OC_LDS <= 160 * 1024, "LDS image too large");
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ocab_attn_kernel<ROWS16>), hipFuncAttributeMaxDynamicSharedMemorySize, OC_LDS);
+    if (e != hipSuccess) { ff_set_error("%s: cannot raise dynamic LDS: %s", who, hipGetErrorString(e)); return FF_ERR_LAUNCH; }
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(ocab_attn_kernel<ROWS16>, dim3((unsigned)nblk), dim3(512), OC_LDS, (hipStream_t)stream, p);
+  FF_LAUNCH_CHECK(who);
+  return FF_OK;
+}
+
 extern "C" int ff_ocab_attn(const float* qkv, int ldq, int q_off, int k_off, int v_off, float* out, int ldo, int o_off,
                             const float* rel_rotated, int B, int H, int W, int heads, int d, int ws, int ows, float scale, int out_bf16, void* stream) {
   FF_CHECK_ARG(qkv && out && rel_rotated, "ff_ocab_attn: null pointer");
@@ -264,17 +335,23 @@ extern "C" int ff_ocab_attn(const float* qkv, int ldq, int q_off, int k_off, int
   OcabParams p;
   p.qkv = qkv; p.out = out; p.rel = rel_rotated; p.ldq = ldq; p.ldo = ldo; p.q_off = q_off; p.k_off = k_off; p.v_off = v_off; p.o_off = o_off;
   p.B = B; p.H = H; p.W = W; p.nwx = W / 16; p.nwy = H / 16; p.heads = heads; p.scale = scale; p.out_bf16 = out_bf16;
-  FF_STAMP_ARM(p);
-  const long long nblk = (long long)B * p.nwx * p.nwy;
-  FF_CHECK_ARG(nblk < (1LL << 31), "ff_ocab_attn: grid too large");
-  static_assert(OC_LDS <= 160 * 1024, "LDS image too large");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ocab_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, OC_LDS);
-    if (e != hipSuccess) { ff_set_error("ff_ocab_attn: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(ocab_attn_kernel, dim3((unsigned)nblk), dim3(512), OC_LDS, (hipStream_t)stream, p);
-  FF_LAUNCH_CHECK("ff_ocab_attn");
-  return FF_OK;
+  return ocab_launch<false>(p, "ff_ocab_attn", stream);
+}
+
+// The rows form: qkv16 holds bf16 rows [B*H*W][ldq] (ldq in elements) with head h of q / k / v at q_off / k_off / v_off + 32 h: 30
+// channels and two exact zeros, q already multiplied by the softmax scale.  Base and pitch are 16-byte aligned, the offsets multiples of 32.
+extern "C" int ff_ocab_attn_rows16(const void* qkv16, int ldq, int q_off, int k_off, int v_off, float* out, int ldo, int o_off,
+                                   const float* rel_rotated, int B, int H, int W, int heads, int d, int ws, int ows, int out_bf16, void* stream) {
+  FF_CHECK_ARG(qkv16 && out && rel_rotated, "ff_ocab_attn_rows16: null pointer");
+  FF_CHECK_ARG(ws == 16 && ows == 24 && d == 30 && heads > 0, "ff_ocab_attn_rows16: built for 16x16 query / 24x24 key windows and head dim 30 (got %d / %d / %d)", ws, ows, d);
+  FF_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "ff_ocab_attn_rows16: H and W must be multiples of the window");
+  FF_CHECK_ARG(ldq > 0 && ldq % 8 == 0 && (((uintptr_t)qkv16) & 15) == 0, "ff_ocab_attn_rows16: qkv rows must be 16-byte aligned (pitch %d in bf16 elements)", ldq);
+  FF_CHECK_ARG(q_off >= 0 && k_off >= 0 && v_off >= 0 && q_off % 32 == 0 && k_off % 32 == 0 && v_off % 32 == 0, "ff_ocab_attn_rows16: q / k / v offsets must be multiples of 32 (got %d / %d / %d)", q_off, k_off, v_off);
+  FF_CHECK_ARG(ldq >= q_off + heads * 32 && ldq >= k_off + heads * 32 && ldq >= v_off + heads * 32, "ff_ocab_attn_rows16: rows too short for %d padded heads", heads);
+  FF_CHECK_ARG(ldo % 2 == 0 && o_off % 2 == 0 && o_off >= 0 && (((uintptr_t)out) & 7) == 0 && ldo >= o_off + heads * d, "ff_ocab_attn_rows16: out rows must be 8-byte aligned and hold every head");
+  FF_CHECK_ARG((long long)B * H * W * (ldq > ldo ? ldq : ldo) < (1LL << 31), "ff_ocab_attn_rows16: tensor too large for 32-bit token offsets");
+  OcabParams p;
+  p.qkv = reinterpret_cast<const float*>(qkv16); p.out = out; p.rel = rel_rotated; p.ldq = ldq; p.ldo = ldo; p.q_off = q_off; p.k_off = k_off; p.v_off = v_off; p.o_off = o_off;
+  p.B = B; p.H = H; p.W = W; p.nwx = W / 16; p.nwy = H / 16; p.heads = heads; p.scale = 1.0f; p.out_bf16 = out_bf16;
+  return ocab_launch<true>(p, "ff_ocab_attn_rows16", stream);
 }

@@ -40,6 +40,7 @@ struct TokenLinParams {
 #endif
 #define TL_KERNEL token_linear_kernel
 #define TL_IMAGES 0
+#define TL_OUT16 0
 #include "token_linear_kernel.inc"
 #undef TL_KERNEL
 #undef TL_IMAGES
@@ -48,6 +49,14 @@ struct TokenLinParams {
 #include "token_linear_kernel.inc"
 #undef TL_KERNEL
 #undef TL_IMAGES
+#undef TL_OUT16
+#define TL_KERNEL token_linear_rows16_kernel       // column-scaled bf16 rows out (ff_token_linear_rows16)
+#define TL_IMAGES 0
+#define TL_OUT16 1
+#include "token_linear_kernel.inc"
+#undef TL_KERNEL
+#undef TL_IMAGES
+#undef TL_OUT16
 
 
 extern "C" int ff_token_linear(const float* x, int ldx, float* out, int ldo, long long M, int K, int kpad, int N, int n_tiles,
@@ -100,6 +109,53 @@ extern "C" int ff_token_linear(const float* x, int ldx, float* out, int ldo, lon
 #undef TL_LAUNCH_NT
 #undef TL_LAUNCH
   FF_LAUNCH_CHECK("ff_token_linear");
+  return FF_OK;
+}
+
+// out16[token][n] = bf16( (LayerNorm?(x)[token] . W[n] + bias[n]) * col_scale[n] ), plain bf16 products: ff_token_linear's nterms == 1,
+// ACT_NONE, VEC4 form with the fp32 result scaled per column and rounded on its way out.  The parameter list is ff_token_linear's (out in
+// bf16 elements, col_scale [n_tiles*32] added); what this form does not have -- split products, an activation, residuals, the xn and
+// statistics side outputs -- is refused in the first check.
+extern "C" int ff_token_linear_rows16(const float* x, int ldx, void* out16, int ldo, long long M, int K, int kpad, int N, int n_tiles,
+                                      const float* gamma, const float* beta, float eps, const void* w_tiles, const float* bias_padded,
+                                      const float* col_scale, int act, const float* res, int ldr, const float* res2, int ldr2,
+                                      const float* res2_scale, float* xn_out, int ldxn, float* stats_out, int stat_lo, int stat_hi,
+                                      float stat_eps, int nterms, void* stream) {
+  FF_CHECK_ARG(nterms == 1 && act == ACT_NONE && !res && !res2 && !res2_scale && !xn_out && !stats_out,
+               "ff_token_linear_rows16: plain bf16 (nterms == 1), no activation, no res / res2 / xn_out / stats_out (got nterms=%d act=%d)", nterms, act);
+  FF_CHECK_ARG(x && out16 && w_tiles && col_scale, "ff_token_linear_rows16: null pointer");
+  FF_CHECK_ARG(M > 0 && K > 0 && K <= 192 && K % 4 == 0 && N > 0 && N % 4 == 0 && n_tiles * 32 >= N, "ff_token_linear_rows16: needs K <= 192, K and N multiples of 4, n_tiles*32 >= N");
+  FF_CHECK_ARG(kpad == 64 || kpad == 128 || kpad == 192, "ff_token_linear_rows16: kpad must be 64, 128 or 192");
+  FF_CHECK_ARG(kpad >= K, "ff_token_linear_rows16: kpad < K");
+  FF_CHECK_ARG(ldx >= K && ldx % 4 == 0 && (((uintptr_t)x) & 15) == 0, "ff_token_linear_rows16: x rows must be 16-byte aligned");
+  FF_CHECK_ARG(ldo >= N && ldo % 4 == 0 && (((uintptr_t)out16) & 7) == 0, "ff_token_linear_rows16: out rows must be 8-byte aligned (pitch in bf16 elements, a multiple of 4)");
+  FF_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "ff_token_linear_rows16: gamma/beta come together");
+  FF_CHECK_ARG(((((uintptr_t)w_tiles) | ((uintptr_t)col_scale)) & 15) == 0 && (!gamma || ((((uintptr_t)gamma) & 15) == 0 && (((uintptr_t)beta) & 15) == 0)), "ff_token_linear_rows16: weights / col_scale / gamma / beta must be 16-byte aligned");
+  TokenLinParams p;
+  p.x = x; p.out = reinterpret_cast<float*>(out16); p.gamma = gamma; p.beta = beta; p.w = (const __bf16*)w_tiles; p.bias = bias_padded;
+  p.res = nullptr; p.res2 = nullptr; p.rs2 = col_scale; p.xn = nullptr; p.ldxn = 0; p.M = M; p.ldx = ldx; p.ldo = ldo; p.ldr = 0; p.ldr2 = 0;
+  p.K = K; p.N = N; p.NT = n_tiles; p.act = ACT_NONE; p.eps = eps;
+  p.stats = nullptr; p.st_lo = 0; p.st_hi = 0; p.st_eps = 0.f;
+  p.x2 = nullptr; p.ldx2 = 0; p.cm = nullptr; p.gw1t = nullptr; p.gb1 = nullptr; p.gw2 = nullptr; p.gb2 = 0.f; p.wpi = 0;
+  const int ks = kpad / 16;
+  const size_t lds = (size_t)2 * 2 * 32 * (2 * ks + 1) * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)2 * n_tiles * 32 * 4;
+  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_linear_rows16: N too large for the LDS image");
+  const long long nblk = (M + 255) / 256;
+  FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_linear_rows16: grid too large");
+#define TL_LAUNCH16(KSV)                                                                                                    \
+  do {                                                                                                                      \
+    static bool attr_set = false;                                                                                           \
+    if (!attr_set) {                                                                                                        \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>), \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
+      if (e != hipSuccess) { ff_set_error("ff_token_linear_rows16: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
+      attr_set = true;                                                                                                      \
+    }                                                                                                                       \
+    hipLaunchKernelGGL((token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p); \
+  } while (0)
+  if (ks == 4) TL_LAUNCH16(4); else if (ks == 8) TL_LAUNCH16(8); else TL_LAUNCH16(12);
+#undef TL_LAUNCH16
+  FF_LAUNCH_CHECK("ff_token_linear_rows16");
   return FF_OK;
 }
 

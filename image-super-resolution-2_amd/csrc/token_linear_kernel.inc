@@ -2,6 +2,9 @@
 // ff_token_linear / ff_token_linear_gated.  TL_IMAGES = 1 (GATED): the rows are B images of wpi 256-token workgroups each, the grid is
 // (wpi, B), and image blockIdx.y takes its channel gate from row blockIdx.y of cm [B][K] -- a wave-uniform offset that costs no division
 // and no vector register.  Nothing else differs.
+// TL_OUT16 = 1 (ff_token_linear_rows16; VEC4, no residuals / side outputs): the epilogue multiplies by a per-column scale (p.rs2, kept in
+// LDS beside Bs) in fp32 and stores bf16 rows -- p.out is then a __bf16 pointer and p.ldo counts bf16 elements.  The accumulator chain is
+// the same text, so a column comes out as bf16(fp32 result * scale).
 template <int ACT, int TL_KS, bool VEC4, bool GATED = false, int NTERMS = 3>
 __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
   constexpr int TL_SLOTS = 2 * TL_KS + 1, TL_ROWB = TL_SLOTS * 16, TL_PL = 32 * TL_SLOTS, TL_PIECES = 2 * TL_PL / 64;
@@ -44,6 +47,10 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
   };
   dma(0, 0);
   for (int i = tid; i < p.NT * 32; i += 512) Bs[i] = p.bias ? p.bias[i] : 0.f;
+#if TL_OUT16
+  float* Ss = Bs + p.NT * 32;                        // [NT*32] column scale
+  for (int i = tid; i < p.NT * 32; i += 512) Ss[i] = p.rs2[i];
+#endif
 
   // ---- x rows (+ LayerNorm) -> split bf16 fragments in registers ------------------------------------------------
   bf16x8 xh[TL_KS], xl[TL_KS];
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
     const bool c4ok = c4 < p.N;
     float rv[16];
     f32x4 rq[4];
-    if (VEC4) {
+    if (VEC4 && !TL_OUT16) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const long long tk = tok0 + tq + 8 * i;
@@ -246,7 +253,7 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
         }
         rq[i] = r0;
       }
-    } else {
+    } else if (!VEC4) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const long long tk = tok0 + 2 * i + hh;
@@ -309,6 +316,28 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
     // this tile's residual loads and the PREVIOUS tile's stores -- so stores always have a full tile to drain
     // (vmcnt counts stores too; waiting right after issuing them would serialise the kernel on HBM write latency).
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#if TL_OUT16
+    {
+      const f32x4 cs = *reinterpret_cast<const f32x4*>(Ss + nt * 32 + 4 * (lane & 7));
+      bf16x4 ov[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 t4 = *reinterpret_cast<const f32x4*>(tr + (tq + 8 * i) * TL_TR + 4 * (lane & 7)) * cs;
+        ov[i] = (bf16x4){(__bf16)t4[0], (__bf16)t4[1], (__bf16)t4[2], (__bf16)t4[3]};
+      }
+      if (c4ok) {
+        __bf16* op = reinterpret_cast<__bf16*>(p.out) + (tok0 + tq) * p.ldo + c4;
+        if (tok0 + 32 <= p.M) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) *reinterpret_cast<bf16x4*>(op + (long long)(8 * i) * p.ldo) = ov[i];
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (tok0 + tq + 8 * i < p.M) *reinterpret_cast<bf16x4*>(op + (long long)(8 * i) * p.ldo) = ov[i];
+        }
+      }
+    }
+#else
     if (VEC4) {
       f32x4 ov[4];
 #pragma unroll
@@ -340,6 +369,7 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
         }
       }
     }
+#endif
   }
   if (p.stats) {
     ssum += __shfl_xor(ssum, 32);

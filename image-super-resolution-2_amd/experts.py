@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .prep import (pack_conv, pack_dw, bn_scale_shift, fold_bn_after_conv, pack_token_linear, pack_naf_ffn, pack_naf_tail,
-                   pack_win_attn, pack_win_rel, pack_token_projmlp, pack_chan_qkv, pack_token_linear_gated, pack_rel_overlap)
+                   pack_win_attn, pack_win_rel, pack_token_projmlp, pack_chan_qkv, pack_token_linear_gated, pack_rel_overlap, pack_ocab_qkv)
 
 T = torch.Tensor
 SD = Dict[str, T]
@@ -215,14 +215,21 @@ class HatHIP(_Trunk):
         _, H, W, C = x.shape
         d = C // self.heads
         fused = ops.fused_modes()
-        if fused:
+        rows16 = ops.gemm_mode() == "bf16" and (self.ws, self.ows, d) == (16, 24, 30) and H % 16 == 0 and W % 16 == 0
+        if rows16:
+            # q / k / v have one consumer, the attention kernel, which rounds them to bf16 (q after the scale): the projection writes
+            # exactly those roundings as head-padded bf16 rows (30 -> 32 channels: 64-byte, 16-byte aligned head slices)
+            pk = _packed(blk, "qkv_r16", lambda: pack_ocab_qkv(*blk["qkv"], self.heads, d))
+            qkv = ops.token_linear_rows16(x, pk, gamma=blk["n1"][0], beta=blk["n1"][1])            # LayerNorm fused
+        elif fused:
             qkv = ops.token_linear(x, _tl(blk, "qkv"), gamma=blk["n1"][0], beta=blk["n1"][1])      # LayerNorm fused
         else:
             qkv = ops.linear(ops.layernorm(x, *blk["n1"]), *blk["qkv"])
-        if ops.gemm_mode() == "bf16" and (self.ws, self.ows, d) == (16, 24, 30) and H % 16 == 0 and W % 16 == 0:
+        if rows16:
             att = ops.empty_rows_bf16(tuple(x.shape), x.device)    # consumed only as an MFMA operand, as in hab
-            ops.ocab_attn(qkv, att, blk["rel"], q_off=0, k_off=C, v_off=2 * C, H=H, W=W, heads=self.heads, d=d, ws=self.ws, ows=self.ows,
-                          scale=d ** -0.5)                 # persistent per-window kernel, compact bias table in LDS (csrc/ocab_attn.hip)
+            hp = self.heads * 32
+            ops.ocab_attn_rows16(qkv, att, blk["rel"], q_off=0, k_off=hp, v_off=2 * hp, H=H, W=W, heads=self.heads, d=d, ws=self.ws,
+                                 ows=self.ows)             # persistent per-window kernel, compact bias table in LDS (csrc/ocab_attn.hip)
         else:
             # 576 keys per window, the bias streams from the expanded table (3.5 MB per head): gathering it in window_attn from the
             # rotated compact table in LDS is bit-identical and 430 MB less traffic per launch, but 314 vs 207 us on MI355X (two

@@ -664,6 +664,28 @@ def ocab_attn(qkv: T, out: T, rel_rotated: T, *, q_off: int, k_off: int, v_off: 
     return out
 
 
+def ocab_attn_rows16(qkv16: T, out: T, rel_rotated: T, *, q_off: int, k_off: int, v_off: int, o_off: int = 0, H: int, W: int, heads: int,
+                     d: int, ws: int, ows: int) -> T:
+    """ocab_attn on the head-padded bf16 rows of token_linear_rows16 (csrc/ocab_attn.hip, ROWS16): head h of q / k / v at
+    q_off / k_off / v_off + 32 h, q already scaled."""
+    if _GEMM_MODE != "bf16":
+        raise _lib.FFError("ocab_attn_rows16 exists for the plain-bf16 contraction mode only")
+    if qkv16.dtype != torch.bfloat16:
+        raise _lib.FFError("ocab_attn_rows16: qkv must be bf16 rows")
+    qp, ldq, B, h_, w_, _ = _nhwc(qkv16, "ocab_attn_rows16.qkv|bf16ok")
+    out_bf16 = out.dtype == torch.bfloat16
+    op, ldo, *_ = _nhwc(out, "ocab_attn_rows16.out|bf16ok" if out_bf16 else "ocab_attn_rows16.out")
+    if (h_, w_) != (H, W) or tuple(out.shape[:3]) != (B, H, W) or tuple(rel_rotated.shape) != (heads, (ws + ows - 1) ** 2) or not rel_rotated.is_contiguous():
+        raise _lib.FFError("ocab_attn_rows16: shape mismatch")
+    if max(q_off, k_off, v_off) + heads * 32 > qkv16.shape[-1]:
+        raise _lib.FFError("ocab_attn_rows16: channel offsets out of range")
+    _lib.check(_L().ff_ocab_attn_rows16(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, rel_rotated.data_ptr(), B, H, W, heads, d, ws, ows,
+                                        int(out_bf16), _stream()))
+    nwin = B * (H // ws) * (W // ws)
+    _note(4.0 * nwin * heads * ws * ws * ows * ows * d, B * H * W * heads * (2.0 * 3 * 32 + (2.0 if out_bf16 else 4.0) * d))
+    return out
+
+
 def win_attn_fused(x: T, out: T, pk: dict, rel_padded: T, *, gamma: Optional[T], beta: Optional[T], eps: float = 1e-5,
                    H: int, W: int, Hp: int, Wp: int, win: Tuple[int, int], shift: Tuple[int, int], use_mask: bool,
                    head0: int = 0, nheads: Optional[int] = None, o_off: int = 0, zero_pad: bool = False,
@@ -799,6 +821,28 @@ def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T]
     if stats is not None:
         return out, stats
     return (out, xn) if want_xn else out
+
+
+def token_linear_rows16(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T] = None, eps: float = 1e-5,
+                        out: Optional[T] = None) -> T:
+    """bf16( (LayerNorm?(x) @ W^T + b) * pk["scale"] ) as bf16 rows in one launch (plain bf16 only; csrc/token_linear.hip); pk from
+    prep.pack_ocab_qkv.  out (optional): a bf16 rows view [..., N] to write into."""
+    if _GEMM_MODE != "bf16":
+        raise _lib.FFError("token_linear_rows16 exists for the plain-bf16 contraction mode only")
+    xp, ldx, rows, K = rows_view(x, "token_linear_rows16.x")
+    if K != pk["K"]:
+        raise _lib.FFError("token_linear_rows16: K mismatch")
+    N = pk["N"]
+    if out is None:
+        out = empty_rows_bf16(tuple(x.shape[:-1]) + (N,), x.device)
+    op, ldo, orows, oc = rows_view(out, "token_linear_rows16.out|bf16ok")
+    if out.dtype != torch.bfloat16 or orows != rows or oc != N:
+        raise _lib.FFError("token_linear_rows16: out must be bf16 rows [rows, N]")
+    _lib.check(_L().ff_token_linear_rows16(xp, ldx, op, ldo, rows, K, pk["kpad"], N, pk["nt"], _ptr(gamma), _ptr(beta), float(eps),
+                                           pk["w"].data_ptr(), _ptr(pk["b"]), pk["scale"].data_ptr(), ACT[None], None, 0, None, 0, None,
+                                           None, 0, None, 0, 0, 0.0, 1, _stream()))
+    _note(2.0 * rows * N * K, 4.0 * rows * K + 2.0 * rows * N)
+    return out
 
 
 def dwconv3_gate_pool(t: T, w_tap: T, bias: T):
@@ -1635,7 +1679,7 @@ def resize_aa(x: T, size: Tuple[int, int]) -> T:
     return out
 
 
-for _n in ("conv2d", "sgfn_tail", "ocab_attn", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
+for _n in ("conv2d", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):
     globals()[_n] = _instrument(globals()[_n])

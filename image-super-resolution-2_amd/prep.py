@@ -146,6 +146,27 @@ def pack_token_linear(w: T, b: Optional[T]) -> dict:
     return dict(nt=nt, K=K, kpad=kpad, N=N, w=torch.stack([hi, lo], dim=1).contiguous(), b=bp)
 
 
+def pack_ocab_qkv(w: T, b: Optional[T], heads: int, d: int) -> dict:
+    """Weights of ff_token_linear_rows16 for HAT OCAB's qkv projection [3*heads*d, K] (d <= 32): the token-linear tile image for
+    N = 3*heads*32 columns in which 32-column tile t is head t % heads of q (t < heads), k (t < 2*heads) or v -- the head's d weight
+    rows and biases, then 32 - d zero rows with zero bias, so the pad columns come out as exact zeros.  "scale" [N]: d ** -0.5 on the
+    q columns (the softmax scale, applied in fp32 before the rounding to bf16), exactly 1 elsewhere."""
+    C = heads * d
+    assert d <= 32 and w.shape[0] == 3 * C
+    K = w.shape[1]
+    N = 3 * heads * 32
+    wp = torch.zeros(3 * heads, 32, K, device=w.device, dtype=w.dtype)
+    wp[:, :d] = w.reshape(3 * heads, d, K)
+    bp = torch.zeros(3 * heads, 32, device=w.device, dtype=w.dtype)
+    if b is not None:
+        bp[:, :d] = b.reshape(3 * heads, d)
+    pk = pack_token_linear(wp.reshape(N, K), bp.reshape(N))
+    scale = torch.ones(N, device=w.device, dtype=torch.float32)
+    scale[:heads * 32] = d ** -0.5
+    pk.update(heads=heads, d=d, scale=scale)
+    return pk
+
+
 def pack_naf_ffn(w4: T, b4: T, w5: T, b5: T) -> dict:
     """Weights of ff_naf_ffn: conv4 [2C, C], conv5 [C, C] -> per gated 32-channel tile g the record
     [W4a_hi, W4a_lo, W4b_hi, W4b_lo (32 x C: rows 32g.. and C+32g..), W5_hi, W5_lo (C x 32, columns 32g.. permuted)]."""

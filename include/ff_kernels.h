@@ -251,6 +251,18 @@ int ff_token_linear(const float* x, int ldx, float* out, int ldo, long long M, i
                     float* xn_out, int ldxn, float* stats_out, int stat_lo,
                     int stat_hi, float stat_eps, int nterms, void* stream);
 
+/* ff_token_linear with a column-scaled bf16 output (csrc/token_linear.hip, plain bf16 products only):
+ *   out16[token][n] = bf16( (LayerNorm?(x) . W^T + bias)[n] * col_scale[n] )
+ * -- the fp32 value ff_token_linear(nterms = 1) would store, times col_scale[n] in fp32, rounded once.  out16: bf16 rows, ldo in
+ * ELEMENTS (a multiple of 4, base 8-byte aligned); col_scale [n_tiles*32], 16-byte aligned.  The parameter list is ff_token_linear's;
+ * nterms != 1, act != none, res, res2, res2_scale, xn_out and stats_out are refused.  With prep.pack_ocab_qkv's weights it writes HAT
+ * OCAB's q (scaled) / k / v as the head-padded rows ff_ocab_attn_rows16 reads. */
+int ff_token_linear_rows16(const float* x, int ldx, void* out16, int ldo, long long M, int K, int kpad, int N, int n_tiles,
+                           const float* gamma, const float* beta, float eps, const void* w_tiles, const float* bias_padded,
+                           const float* col_scale, int act, const float* res, int ldr, const float* res2, int ldr2,
+                           const float* res2_scale, float* xn_out, int ldxn, float* stats_out, int stat_lo,
+                           int stat_hi, float stat_eps, int nterms, void* stream);
+
 /* ff_token_linear with DAT's adaptive-interaction prologue (csrc/token_linear.hip, GATED): the GEMM input is
  *   x * cm[channel] + x2 * sm[token],   sm = sigmoid(gw2 . gelu(GW1 x + gb1) + gb2)
  * i.e. the channel gate on one branch, the spatial gate (conv1x1 180->11 (+BN folded) -> GELU -> conv1x1 11->1 -> sigmoid,
@@ -374,6 +386,13 @@ int ff_pool_vec_mlp_images(const float* part, int B, int rows, int ld, float inv
  * One persistent workgroup per window; built for ws = 16, ows = 24, d = 30 (anything else: ff_window_attn_bf16s). */
 int ff_ocab_attn(const float* qkv, int ldq, int q_off, int k_off, int v_off, float* out, int ldo, int o_off,
                  const float* rel_rotated, int B, int H, int W, int heads, int d, int ws, int ows, float scale, int out_bf16, void* stream);
+
+/* ff_ocab_attn on bf16 rows: qkv16 [B*H*W][ldq] (ldq in ELEMENTS, a multiple of 8; base 16-byte aligned) holds head h of q / k / v
+ * at q_off / k_off / v_off + 32 h (offsets multiples of 32): 30 channels followed by two exact zeros, q already multiplied by the
+ * softmax scale.  The fp32 form rounds q * scale, k and v to bf16 on arrival, so on rows that hold those roundings the two forms agree
+ * bit for bit. */
+int ff_ocab_attn_rows16(const void* qkv16, int ldq, int q_off, int k_off, int v_off, float* out, int ldo, int o_off,
+                        const float* rel_rotated, int B, int H, int W, int heads, int d, int ws, int ows, int out_bf16, void* stream);
 
 /* DAT SGFN tail in one launch (plain bf16 MFMA, fp32 accumulate; dat_arch.py:117-123, 163-170, 736):
  *   out = res + W2 . ( h[:, :c2] * (dw3x3(LayerNorm(h[:, c2:2 c2])) + dw_bias) ) + b2
