@@ -21,9 +21,11 @@ naf_tail (128-row tiles) M = 77 and 300, naf_tail also on row views with ld > C;
 edges), both outputs; sgfn_tail 8x32 and 19x70, with and without the residual; token_projmlp without c2 and with c2 / c2_scale, with
 fp32 and bf16 att / c2 rows (all three non-zero io_bf16 values).
 
-Out of scope: the attention kernels and chan_qkv (win_attn_fused in plain bf16, window_attn_bf16s, ocab_attn) -- their rounded
-intermediates include softmax probabilities and whole-image reductions, they need a flip model of their own and stay on their checks in
-tests/test_ops_gpu.py.
+Covered elsewhere: the attention kernels (win_attn_fused in plain bf16, window_attn_bf16s, ocab_attn), whose rounded intermediate is
+the softmax probability relative to a running maximum, are held to tests/golden/attn_ref.py by tests/test_lowprec_attn_gpu.py
+(win_attn_fused on fixed-point inputs).  What remains on the checks of tests/test_ops_gpu.py: chan_qkv (its reduction spans the whole
+image) and win_attn_fused on generic inputs.  The `_images` and batched forms are pinned bit for bit against the single-image forms by
+tests/test_batched_*_gpu.py.
 
 Measured on MI355X (the line this module prints: per kernel the worst err and err - allow, both as fractions of max(1, max|ref|), and
 the largest allowance shares; figures rounded to three digits here).  err reaches 9e-4 where an intermediate rounded the other way;
