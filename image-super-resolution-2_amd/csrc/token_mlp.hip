@@ -20,19 +20,7 @@
 // Workgroup = 8 waves = 256 tokens: 65 536 tokens -> 256 workgroups = one per CU.
 #include "ff_common.h"
 
-#define TM_KP 192      // padded K (model dim 180)
-#define TM_NP 192      // padded N
-#define TM_KS 12       // k-steps of 16
-#define W1SLOTS 25     // 16-byte slots per W1 row: 24 data (192 bf16) + 1 pad  -> 400 B
-#define W2SLOTS 5      // slots per W2 row: 4 data (32 bf16) + 1 pad            -> 80 B
-#define W1ROWB (W1SLOTS * 16)
-#define W2ROWB (W2SLOTS * 16)
-#define W1PL (32 * W1SLOTS)          // slots per W1 plane  (800)
-#define W2PL (TM_NP * W2SLOTS)       // slots per W2 plane  (960)
-#define W1PIECES (2 * W1PL / 64)      // 25
-#define W2PIECES (2 * W2PL / 64)      // 30
-#define TILE_ELEMS 6144              // bf16 elements per plane per hidden tile (32*192 == 192*32)
-#define XLROWB 400                   // x_lo image row (per token): 192 bf16 + pad
+#include "token_mlp_layout.h"
 
 struct TokenMlpParams {
   const float* x; float* out;
@@ -628,13 +616,6 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
 //   * the residual slice n+1 (x, conv) is in flight while slice n is transposed and tile n+1 is projected;
 //   * gamma / beta come from LDS; GELU is x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3) -- |error| <= 4.8e-4, a sixteenth
 //     of the bf16 rounding the value receives next -- 5 full-rate + 2 transcendental operations instead of 14 + 2.
-#define PM_W1SLOT (13 * 1024)
-#define PM_W2SLOT (15 * 1024)
-#define PM_OFF_W2 (2 * PM_W1SLOT)
-#define PM_PROJB (6 * PM_W1SLOT)
-#define PM_PATCHB (32 * FF_XS_ROW * 4)
-#define PM_OFF_PATCH PM_PROJB
-#define PM_OFF_VEC (PM_OFF_PATCH + 8 * PM_PATCHB)
 
 __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -836,58 +817,9 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   __builtin_amdgcn_s_barrier();                          // tiles 0 and 1 of the MLP have landed
   FF_STAMP(64, 6);
 
-  // ---- the MLP over hidden tiles ---------------------------------------------------------------------------------------------
-  for (int ht = 0; ht < p.HT; ++ht) {
-    const int slot = ht & 1;
-    f32x16 hacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hacc[r] = B1s[ht * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
-    {
-      const unsigned char* ap = smem + slot * PM_W1SLOT + l31 * W1ROWB + 16 * hh;
-      bf16x8 fa[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-#pragma unroll
-      for (int st = 0; st < TM_KS; ++st) {
-        const bf16x8 ah = fa[st & 1];
-        if (st + 2 < TM_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-        __builtin_amdgcn_sched_barrier(0);
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], hacc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (ht < 3) FF_STAMP(64, 8 + 4 * ht);
-    bf16x8 gh[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; j += 2) {
-        const f32x2 g = ff_gelu_sig2((f32x2){hacc[8 * s + j], hacc[8 * s + j + 1]});
-        gh[s][j] = (__bf16)g[0];
-        gh[s][j + 1] = (__bf16)g[1];
-      }
-    if (ht < 3) FF_STAMP(64, 9 + 4 * ht);
-    {
-      const unsigned char* ap = smem + PM_OFF_W2 + slot * PM_W2SLOT + l31 * W2ROWB + 16 * hh;
-      bf16x8 fa[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + (u >> 1) * 32 * W2ROWB + 32 * (u & 1));
-#pragma unroll
-      for (int u = 0; u < 12; ++u) {
-        const int n = u >> 1, s2 = u & 1;
-        const bf16x8 ah = fa[u & 1];
-        if (u + 2 < 12) fa[u & 1] = *reinterpret_cast<const bf16x8*>(ap + ((u + 2) >> 1) * 32 * W2ROWB + 32 * ((u + 2) & 1));
-        __builtin_amdgcn_sched_barrier(0);
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh[s2], oacc[n], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (ht < 3) FF_STAMP(64, 10 + 4 * ht);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                        // every wave is done with this slot; tile ht+1 has landed everywhere
-    if (ht < 3) FF_STAMP(64, 11 + 4 * ht);
-    if (ht + 2 < p.HT) dma_mlp(ht + 2, slot);
-  }
+#define PM_STAMP(i) FF_STAMP(64, i)
+#include "token_projmlp_bf16_mlp.inc"
+#undef PM_STAMP
   FF_STAMP(64, 40);
 
   // ---- epilogue: out = accumulators (x1 + fc2 part) + b2, transposed through the wave's patch into 128-byte row segments -----

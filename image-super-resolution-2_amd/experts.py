@@ -242,10 +242,48 @@ class HatHIP(_Trunk):
         x = ops.linear(att, *blk["proj"], res=x)
         return self._mlp(x, blk)
 
+    def _linked(self, x: T) -> bool:
+        """True where a group's HABs run as attention, (CAB, hab_link) x 5, CAB, token_projmlp: plain bf16 on hab()'s b16 route, at the
+        shape csrc/hab_link.hip is built for.  (The row-offset bound counts the batch; the link is bit-equal to the pair of launches
+        it replaces, so an image still comes out with the bits of its own B == 1 forward.)"""
+        B, H, W, C = x.shape
+        return (ops.gemm_mode() == "bf16" and H * W >= 1024 and (self.ws, self.heads, C) == (16, 6, 180) and H % 16 == 0 and W % 16 == 0
+                and B * H * W * 192 < 2 ** 31)
+
+    def _habs_linked(self, x: T, blks: List[dict]) -> T:
+        """hab() over blks with every block's token_projmlp and the next block's win_attn_fused in one launch (ops.hab_link): the next
+        attention takes x from the MLP's accumulators instead of reading it back.  Same values as the hab() loop, bit for bit."""
+        B, H, W, C = x.shape
+        d, win = C // self.heads, (self.ws, self.ws)
+
+        def relp(blk):
+            return _packed(blk, "relp", lambda: pack_win_rel(blk["rel"], self.ws, self.ws))
+
+        s = blks[0]["shift"]
+        att = ops.empty_rows_bf16(tuple(x.shape), x.device)
+        _, xn = ops.win_attn_fused(x, att, _wf(blks[0], self.heads, d), relp(blks[0]), gamma=blks[0]["n1"][0], beta=blks[0]["n1"][1], H=H, W=W,
+                                   Hp=H, Wp=W, win=win, shift=(s, s), use_mask=s > 0, want_xn="bf16")
+        for i, blk in enumerate(blks):
+            c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=True, per_image=True)
+            c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=True)
+            gate = ops.vec_mlp(c2mean, *blk["ca1"], "relu", *blk["ca2"], "sigmoid", post=self.conv_scale)
+            gate = gate if B > 1 else gate.reshape(-1)
+            if i + 1 < len(blks):
+                nxt = blks[i + 1]
+                s = nxt["shift"]
+                x, xn, att = ops.hab_link(att, x, _pm(blk), blk["n2"][0], blk["n2"][1], c2=c2, c2_scale=gate, wf=_wf(nxt, self.heads, d),
+                                          rel_padded=relp(nxt), gamma1=nxt["n1"][0], beta1=nxt["n1"][1], shift=(s, s), use_mask=s > 0)
+            else:
+                x = ops.token_projmlp(att, x, _pm(blk), blk["n2"][0], blk["n2"][1], c2=c2, c2_scale=gate)
+        return x
+
     def group(self, x: T, g: int) -> T:
-        y = x
-        for blk in self.blocks[g]:
-            y = self.hab(y, blk)
+        if self._linked(x):
+            y = self._habs_linked(x, self.blocks[g])
+        else:
+            y = x
+            for blk in self.blocks[g]:
+                y = self.hab(y, blk)
         y = self.ocab_block(y, self.ocab[g])
         return ops.conv2d(y, *self.gconv[g], ksize=(3, 3), pad=(1, 1), res=x, per_image=True)
 

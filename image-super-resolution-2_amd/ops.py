@@ -780,6 +780,46 @@ def token_projmlp(att: T, x: T, pk: dict, gamma: T, beta: T, *, c2: Optional[T] 
     return out
 
 
+def hab_link(att: T, x: T, pk: dict, gamma2: T, beta2: T, *, c2: T, c2_scale: T, wf: dict, rel_padded: T, gamma1: T, beta1: T,
+             shift: Tuple[int, int], use_mask: bool, eps2: float = 1e-5, eps1: float = 1e-5) -> Tuple[T, T, T]:
+    """One HAB's token_projmlp and the next HAB's win_attn_fused in one launch (csrc/hab_link.hip; plain bf16, 16x16 windows, six
+    heads of 30): x_out = token_projmlp(att, x, pk, gamma2, beta2, c2=c2, c2_scale=c2_scale), then LayerNorm(gamma1, beta1) + qkv (wf,
+    from prep.pack_win_attn) + window attention (rel_padded from prep.pack_win_rel) on x_out, which the attention takes from LDS
+    instead of reading it back.  att / c2 [B,H,W,180] bf16 rows, x [B,H,W,180] fp32; c2_scale [180] (B == 1) or [B,180].
+    -> (x_out fp32, xn bf16, att_out bf16), each bit-equal to the two launches."""
+    if _GEMM_MODE != "bf16":
+        raise _lib.FFError("hab_link exists for the plain-bf16 contraction mode only")
+    if att.dtype != torch.bfloat16 or c2 is None or c2.dtype != torch.bfloat16 or c2_scale is None:
+        raise _lib.FFError("hab_link: att and c2 must be bf16 rows, and the gate is required")
+    ap, lda, B, H, W, K = _nhwc(att, "hab_link.att|bf16ok")
+    xp, ldx, xb, xh_, xw, xk = _nhwc(x, "hab_link.x")
+    cp, ldc, cb, ch, cw, ck = _nhwc(c2, "hab_link.c2|bf16ok")
+    if (xb, xh_, xw, xk) != (B, H, W, K) or (cb, ch, cw, ck) != (B, H, W, K) or K != pk["mlp"]["K"] or K != wf["K"]:
+        raise _lib.FFError("hab_link: shape mismatch")
+    if tuple(c2_scale.shape) not in (((K,), (1, K)) if B == 1 else ((B, K),)) or not c2_scale.is_contiguous():
+        raise _lib.FFError(f"hab_link: c2_scale must be [{K}] for one image or one row per image [{B},{K}], got {tuple(c2_scale.shape)}")
+    if tuple(rel_padded.shape[:2]) != (wf["heads"], 31) or not rel_padded.is_contiguous():
+        raise _lib.FFError("hab_link: rel_padded must be [heads][31][stride]")
+    out = empty_like_rows(x)
+    op_, ldo_, *_ = _nhwc(out, "hab_link.out")
+    xn = empty_rows_bf16(tuple(x.shape), x.device)
+    xnp, ldxn, *_ = _nhwc(xn, "hab_link.xn|bf16ok")
+    ao = empty_rows_bf16(tuple(x.shape), x.device)
+    aop, ldao, *_ = _nhwc(ao, "hab_link.att_out|bf16ok")
+    m = pk["mlp"]
+    _lib.check(_L().ff_hab_link(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), K, B, H * W, op_, ldo_, B * H * W, K, m["ht"],
+                                pk["proj"]["w"].data_ptr(), pk["proj"]["b"].data_ptr(), gamma2.data_ptr(), beta2.data_ptr(), float(eps2),
+                                m["w"].data_ptr(), m["b1"].data_ptr(), m["b2"].data_ptr(), 1, 3,
+                                aop, ldao, 0, gamma1.data_ptr(), beta1.data_ptr(), float(eps1), wf["w"].data_ptr(), wf["b"].data_ptr(),
+                                rel_padded.data_ptr(), rel_padded.shape[1], rel_padded.shape[2], H, W, 16, 16, shift[0], shift[1],
+                                int(use_mask), wf["heads"], wf["d"], xnp, ldxn, 1, 1, _stream()))
+    rows, nwin, nh, d = B * H * W, B * (H // 16) * (W // 16), wf["heads"], wf["d"]
+    # the parents' sums (token_projmlp with bf16 att / c2, win_attn_fused with bf16 xn / out) minus the attention's read of x
+    _note(2.0 * rows * K * K + 4.0 * rows * K * m["ht"] * 32 + 2.0 * nwin * 256 * K * 3 * nh * d + 4.0 * nwin * nh * 256 * 256 * d,
+          4.0 * rows * K * 3.0 + 4.0 * rows * (K * 0.5 + nh * d * 0.5))
+    return out, xn, ao
+
+
 def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T] = None, eps: float = 1e-5, act=None,
                  res: Optional[T] = None, res2: Optional[T] = None, res2_scale: Optional[T] = None, want_xn: bool = False,
                  stats_range: Optional[Tuple[int, int]] = None, stats_eps: float = 1e-5):
@@ -1679,7 +1719,7 @@ def resize_aa(x: T, size: Tuple[int, int]) -> T:
     return out
 
 
-for _n in ("conv2d", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
+for _n in ("conv2d", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "hab_link", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):
     globals()[_n] = _instrument(globals()[_n])

@@ -195,6 +195,28 @@ int ff_win_attn_fused(const float* x, int ldx, float* out, int ldo, int o_off, c
                       int use_mask, int head0, int nheads, int d, int K, int zero_pad_tokens, float* xn_out, int ldxn,
                       float* v_out, int ldv, int v_off, int nterms, int out_bf16, int xn_bf16, void* stream);
 
+/* HAB link, plain bf16 (csrc/hab_link.hip): block i's ff_token_projmlp_images and block i+1's ff_win_attn_fused in ONE launch.
+ *   x_out = x1 + fc2(GELU(fc1(LayerNorm2(x1)))),  x1 = x + proj(att) + c2 * c2_scale[image]        (the first 25 arguments: those of
+ *                                                                                                   ff_token_projmlp_images)
+ *   xn_out = LayerNorm1(x_out),  att_out = (S)W-MSA of all six heads on xn_out                      (the rest: those of ff_win_attn_fused
+ *                                                                                                   with head0 = 0, Hp = H, Wp = W, no v_out)
+ * A workgroup is one (shifted) 16 x 16 window of block i+1; the final x of its 256 tokens passes from the MLP's accumulators to the
+ * attention's LayerNorm through LDS, so the attention never reads x_out back.  x_out is still written (block i+1's residual).  Every
+ * statement of the arithmetic is the parents', in their order: all three outputs are BIT EQUAL to the two launches.
+ * Refused before any launch (FF_ERR_ARG): nterms != 1; a window other than 16 x 16; d != 30 or nheads != 6; K != 180; H or W not a
+ * multiple of 16; io_bf16 != 3, out_bf16 != 1 or xn_bf16 != 1 (att, c2, xn_out and att_out are bf16 rows, pitches in elements; att and
+ * xn rows padded to 192); c2 or c2_scale NULL; rows_per_image != H * W or M != B * rows_per_image; more than 12 hidden tiles; rows or
+ * weights that miss the alignment of the parents; B * H * W * ld >= 2^31 for any pitch.
+ * Added under ABI version 7 (an additive entry point: no existing prototype changed). */
+int ff_hab_link(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
+                int scale_ld, int B, long long rows_per_image, float* x_out, int ldxo, long long M, int K, int hidden_tiles,
+                const void* proj_tiles, const float* proj_bias_padded, const float* gamma2, const float* beta2, float eps2,
+                const void* mlp_tiles, const float* b1_padded, const float* b2, int nterms, int io_bf16,
+                float* att_out, int ldo, int o_off, const float* gamma1, const float* beta1, float eps1,
+                const void* qkv_tiles, const float* qkv_bias_padded, const float* rel_padded, int rel_rows, int rel_stride,
+                int H, int W, int wh, int ww, int shift_h, int shift_w, int use_mask, int nheads, int d,
+                float* xn_out, int ldxn, int out_bf16, int xn_bf16, void* stream);
+
 /* Fused transformer feed-forward on tokens (csrc/token_mlp.hip): out = x + fc2(GELU(fc1(LayerNorm(x)))), bf16x3 MFMA.
  * Replaces hat_arch.py:307 (norm2 + Mlp.forward :88-94 + residual) in one launch; the hidden activation stays on chip.
  * K, N <= 192.  w_tiles: bf16 [hidden_tiles][4][6144] = per 32-wide hidden tile the planes W1_hi, W1_lo ([32][192], zero
