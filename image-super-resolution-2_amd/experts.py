@@ -201,8 +201,11 @@ class HatHIP(_Trunk):
             # LDS bound, not bandwidth bound)
             ops.window_attn(qkv, att, blk["bias"], q_off=0, k_off=C, v_off=2 * C, o_off=0, H=H, W=W, Hp=H, Wp=W, win=(self.ws, self.ws),
                             kwin=(self.ws, self.ws), shift=(s, s), use_mask=s > 0, heads=self.heads, d=d, scale=d ** -0.5)
-        c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16, per_image=True)
-        c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=b16)   # pool partials from the conv epilogue
+        if b16 and self._cab_fused(xn):                            # both convolutions in one launch, c1 in LDS (csrc/cab_fused.hip): same bits
+            c2, c2mean = ops.cab_fused(xn, blk["cab0"], blk["cab2"])
+        else:
+            c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=b16, per_image=True)
+            c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=b16)   # pool partials from the conv epilogue
         gate = ops.vec_mlp(c2mean, *blk["ca1"], "relu", *blk["ca2"], "sigmoid", post=self.conv_scale)
         if fused:                                                  # proj + both residuals + norm2 + MLP: x1 never reaches memory
             # gate [B,180]: one launch for the batch, image b scaled by its own row
@@ -242,6 +245,11 @@ class HatHIP(_Trunk):
         x = ops.linear(att, *blk["proj"], res=x)
         return self._mlp(x, blk)
 
+    def _cab_fused(self, xn: T) -> bool:
+        """True where CAB's two convolutions run as one launch (ops.cab_fused): plain bf16 on hab()'s b16 route, 180 channels, H and W
+        multiples of 16.  Bit-equal to the two launches, so the route may differ between shapes without moving a result."""
+        return ops.cab_fused_ok(xn)
+
     def _linked(self, x: T) -> bool:
         """True where a group's HABs run as attention, (CAB, hab_link) x 5, CAB, token_projmlp: plain bf16 on hab()'s b16 route, at the
         shape csrc/hab_link.hip is built for.  (The row-offset bound counts the batch; the link is bit-equal to the pair of launches
@@ -264,8 +272,11 @@ class HatHIP(_Trunk):
         _, xn = ops.win_attn_fused(x, att, _wf(blks[0], self.heads, d), relp(blks[0]), gamma=blks[0]["n1"][0], beta=blks[0]["n1"][1], H=H, W=W,
                                    Hp=H, Wp=W, win=win, shift=(s, s), use_mask=s > 0, want_xn="bf16")
         for i, blk in enumerate(blks):
-            c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=True, per_image=True)
-            c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=True)
+            if self._cab_fused(xn):
+                c2, c2mean = ops.cab_fused(xn, blk["cab0"], blk["cab2"])
+            else:
+                c1 = ops.conv2d(xn, *blk["cab0"], ksize=(3, 3), pad=(1, 1), act="gelu", out_bf16=True, per_image=True)
+                c2, c2mean = ops.conv2d(c1, *blk["cab2"], ksize=(3, 3), pad=(1, 1), want_pool="partials", out_bf16=True)
             gate = ops.vec_mlp(c2mean, *blk["ca1"], "relu", *blk["ca2"], "sigmoid", post=self.conv_scale)
             gate = gate if B > 1 else gate.reshape(-1)
             if i + 1 < len(blks):

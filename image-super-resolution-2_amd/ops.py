@@ -820,6 +820,57 @@ def hab_link(att: T, x: T, pk: dict, gamma2: T, beta2: T, *, c2: T, c2_scale: T,
     return out, xn, ao
 
 
+def cab_fused_ok(x: T) -> bool:
+    """True where ops.cab_fused replaces conv2d(gelu) + conv2d(pool partials) of HAT's CAB: plain bf16, bf16 rows the kernel's 16-byte
+    loads can take (a constant pitch that is a multiple of 8 elements, a 16-byte aligned base), one image of at least 1024 pixels, 180
+    channels, H and W multiples of 16, and the launch within the kernel's 32-bit row offsets.  Anything else keeps the two launches."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_cuda:
+        return False
+    B, H, W, C = x.shape
+    if not (_HALO and _GEMM_MODE == "bf16" and C == 180 and H * W >= 1024 and H % 16 == 0 and W % 16 == 0):
+        return False
+    ld = x.stride(2)
+    rows_ok = x.stride(3) == 1 and x.stride(1) == W * ld and (B == 1 or x.stride(0) == H * W * ld)
+    return rows_ok and ld % 8 == 0 and ld >= C and x.data_ptr() % 16 == 0 and B * H * W * max(ld, 192) < 2 ** 31
+
+
+def cab_fused(xn: T, cab0: Tuple[T, T], cab2: Tuple[T, T], out: Optional[T] = None):
+    """HAT's CAB without its gate in one launch (csrc/cab_fused.hip; plain bf16): c2 = conv3x3(gelu(conv3x3(xn) + b0)) + b2 with c1 kept in
+    LDS.  xn [B,H,W,180] bf16 rows; cab0 = (packed weight [60, 9*180], bias), cab2 = (packed weight [180, 9*60], bias), the pairs conv2d
+    takes.  -> (c2 bf16 rows, PoolPartials), bit for bit what conv2d(xn, *cab0, act="gelu", out_bf16=True, per_image=True) followed by
+    conv2d(c1, *cab2, want_pool="partials", out_bf16=True) return: the same weight images (prep.pack_conv3x3_halo, kinds "halo1"), the
+    same MFMA order, and image b's partial rows are those of its own B == 1 call."""
+    if _GEMM_MODE != "bf16":
+        raise _lib.FFError("cab_fused exists for the plain-bf16 contraction mode only")
+    if xn.dtype != torch.bfloat16:
+        raise _lib.FFError("cab_fused: xn must be bf16 rows")
+    from . import prep as _prep
+    xp, ldi, B, H, W, Cin = _nhwc(xn, "cab_fused.xn|bf16ok")
+    (w0, b0), (w2, b2) = cab0, cab2
+    Cmid, Cout = w0.shape[0], w2.shape[0]
+    if w0.dim() != 2 or w0.shape[1] != 9 * Cin or w2.dim() != 2 or w2.shape[1] != 9 * Cmid or b0 is None or b2 is None:
+        raise _lib.FFError(f"cab_fused: packed weights must be [Cmid, {9 * Cin}] and [Cout, 9 * Cmid], both with a bias")
+    img0 = PREPARED.get(w0, "halo1", lambda: (_prep.pack_conv3x3_halo(w0, Cin, _prep.halo_bn(Cmid), 1), _prep.halo_bn(Cmid)))
+    img2 = PREPARED.get(w2, "halo1", lambda: (_prep.pack_conv3x3_halo(w2, Cmid, _prep.halo_bn(Cout), 1), _prep.halo_bn(Cout)))
+    if (img0[1], img2[1]) != (64, 192):
+        raise _lib.FFError(f"cab_fused: weight images of tile widths {img0[1]} / {img2[1]}, built for 64 / 192")
+    oshape = (B, H, W, Cout)
+    if out is None:
+        out = empty_rows_bf16(oshape, xn.device)
+    elif tuple(out.shape) != oshape or out.dtype != torch.bfloat16:
+        raise _lib.FFError(f"cab_fused: out must be bf16 rows {oshape}")
+    op, ldo, *_ = _nhwc(out, "cab_fused.out|bf16ok")
+    prow = int(_L().ff_conv3x3_halo_images_pool_rows(B, H, W, Cout, 192, 1))
+    if prow < 0:
+        raise _lib.FFError("cab_fused: bad shape")
+    part = torch.empty((prow, 192), device=xn.device, dtype=torch.float32)
+    _lib.check(_L().ff_cab_fused(xp, ldi, img0[0].data_ptr(), img0[0].numel() * img0[0].element_size(), _ptr(b0),
+                                 img2[0].data_ptr(), img2[0].numel() * img2[0].element_size(), _ptr(b2), op, ldo, part.data_ptr(),
+                                 B, H, W, Cin, Cmid, Cout, 1, 3, _stream()))
+    _note(2.0 * B * H * W * 9 * (Cin * Cmid + Cmid * Cout), 2.0 * _numel(xn, out) + 2.0 * _numel(w0, w2))
+    return out, PoolPartials(part, Cout, 1.0 / float(H * W), images=B)
+
+
 def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T] = None, eps: float = 1e-5, act=None,
                  res: Optional[T] = None, res2: Optional[T] = None, res2_scale: Optional[T] = None, want_xn: bool = False,
                  stats_range: Optional[Tuple[int, int]] = None, stats_eps: float = 1e-5):
@@ -1719,7 +1770,7 @@ def resize_aa(x: T, size: Tuple[int, int]) -> T:
     return out
 
 
-for _n in ("conv2d", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "hab_link", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
+for _n in ("conv2d", "cab_fused", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "hab_link", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):
     globals()[_n] = _instrument(globals()[_n])

@@ -258,6 +258,19 @@ int ff_conv3x3_halo_images(const float* in, int ldi, const void* w_img, int bn, 
                            const float* res, int ldr, float* out, int ldo, int B, int H, int W, int Cin, int Cout,
                            int act, float alpha, int shuffle, float* pool_partials, int nterms, int io_bf16, void* stream);
 
+/* HAT's CAB in one launch (csrc/cab_fused.hip), plain bf16 only: c2 = conv3x3(gelu(conv3x3(xn) + bias1)) + bias2 on bf16 rows, c1 kept
+ * in LDS.  xn [B][H][W][ldi] and c2 [B][H][W][ldo] are bf16 rows (io_bf16 must be 3, pitches in elements, ldi % 8 == 0, ldo % 4 == 0),
+ * w1_img / w2_img are the nterms = 1 images of prep.pack_conv3x3_halo for (Cmid, Cin, bn 64) and (Cout, Cmid, bn 192) and w1_bytes /
+ * w2_bytes their sizes, which must be ff_conv3x3_halo_weight_bytes of those shapes.  pool_partials
+ * [ff_conv3x3_halo_images_pool_rows(B, H, W, Cout, 192, 1)][192]: image b's rows at b * (rows / B).  c2 and the partial rows are bit for
+ * bit those of ff_conv3x3_halo_images(xn -> c1, gelu, bf16 rows) followed by ff_conv3x3_halo_images(c1 -> c2, pool partials).
+ * Refused: nterms != 1, rows that are not bf16, channels other than 180 -> 60 -> 180, H or W not a multiple of 16, H * W < 1024, pitches or
+ * addresses the 16-byte paths cannot take, weight images of another size, B * H * W * pitch >= 2^31, c2 aliasing xn.
+ * Added under ABI version 7 (additive entry point). */
+int ff_cab_fused(const void* xn, int ldi, const void* w1_img, long long w1_bytes, const float* bias1,
+                 const void* w2_img, long long w2_bytes, const float* bias2, void* c2, int ldo, float* pool_partials,
+                 int B, int H, int W, int Cin, int Cmid, int Cout, int nterms, int io_bf16, void* stream);
+
 /* Token-stationary linear layer for K <= 192 (csrc/token_linear.hip), bf16x3 MFMA:
  *   out = res + res2*res2_scale[n] + act( LayerNorm?(x) . W^T + bias )        (gamma == NULL: no LayerNorm)
  * x is read once and kept in registers, W streams through LDS by DMA.  Replaces nn.LayerNorm + nn.Linear (+GELU,
