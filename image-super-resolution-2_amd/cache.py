@@ -278,8 +278,8 @@ class _GraphedExperts:
     pipeline's threads exist, in thread-local capture mode: another thread pinning memory or waiting for an event must not end the
     capture."""
 
-    def __init__(self, model, patch: int, sizes=(1,)):
-        self.model, self.patch = model, int(patch)
+    def __init__(self, model, patch: int, sizes=(1,), tag="cache_build"):
+        self.model, self.patch, self.tag = model, int(patch), tag      # tag: tells the graphs of two owners of one model apart
         self.ent = {}                                        # n -> (key, graph, static input, outputs, features)
         for n in sizes:
             self.prepare(n)
@@ -290,7 +290,7 @@ class _GraphedExperts:
         if n in self.ent:
             return self.ent[n]
         model, patch = self.model, self.patch
-        key = (id(model), "cache_build", patch) + ((n,) if n > 1 else ())
+        key = (id(model), self.tag, patch) + ((n,) if n > 1 else ())
         dev = model.dev
         graph = None
         ops.set_capture_key(key)

@@ -1,4 +1,4 @@
-"""Whole training epochs from a cached-expert directory (isr2_amd/cache.py files), the way the reference runs them:
+"""Whole training epochs, the way the reference runs them -- from a cached-expert directory (isr2_amd/cache.py files):
 
     train.py:1056-1160   for epoch: warm-up / schedule -> train_epoch_cached -> validate_epoch (EMA weights) -> save latest / best
     train.py:306-383     train_epoch_cached with accumulation_steps = A           -> train_epoch()
@@ -13,6 +13,16 @@ tensors with ops.d4_nchw (csrc/augment.hip) -- one launch per tensor per batch.
 Two things cannot be bit-compared with the reference, both "parity unpinned (RNG stream)": the attention-dropout masks (train.py
 of this package) and the shuffle / augmentation draws, which here come from numpy's counter-based Philox keyed by (seed, epoch) so
 that an epoch is reproducible and a resumed run repeats the uninterrupted one.
+
+-- or from image folders with the three frozen experts run on every micro-batch (train.py:130-250 train_epoch, what the shipped
+configuration selects: dataset.train.cache_data false, repeat_factor 6):
+
+    src/data/dataset.py:236-296, :562-565; augmentations.py:77-79, :128-135, :169-171   -> live_plan(), ImagePool, LiveEpoch
+    train.py:413-523 on centre patches                                                     -> live_val_samples()
+
+The images are decoded once into one device buffer; a micro-batch is one sampler launch (csrc/sample_batch.hip: crop, u8 -> fp32
+and the paired D4 symmetry) and one replay of the captured expert graph, with nothing read from disk.  Its crop and augmentation
+draws are a third "parity unpinned (RNG stream)".
 """
 from __future__ import annotations
 
@@ -395,3 +405,333 @@ def fit(trainer, train_data, val_samples, out_dir: str, epochs: int, start_epoch
         log(json.dumps(row))
         last = row
     return dict(last, best_psnr=best_psnr)
+
+
+# ======================================================================================================================
+# live experts: micro-batches cut from image folders, the three frozen experts run on every batch (the reference's train_epoch,
+# train.py:130-250, which configs/train_config.yaml selects with dataset.train.cache_data: false and repeat_factor: 6)
+def pool_members(sizes: Sequence[Tuple[int, int]], patch: int) -> Tuple[List[int], int]:
+    """-> (positions in `sizes` of the LR images (h, w) that hold a patch x patch crop, number of images left out).  The reference
+    resizes smaller images with OpenCV (dataset.py:262-280); that is not reproduced, they are skipped and counted as in crop_plan."""
+    p = int(patch)
+    if p < 1:
+        raise _lib.FFError(f"pool_members: patch {p} must be >= 1")
+    keep = [i for i, (h, w) in enumerate(sizes) if int(h) >= p and int(w) >= p]
+    return keep, len(sizes) - len(keep)
+
+
+def pool_layout(sizes: Sequence[Tuple[int, int]]) -> Tuple[np.ndarray, int]:
+    """The packed layout of an ImagePool: sizes = LR (h, w) per image -> (offsets int64 [n, 2] = byte offsets of the LR image
+    [h][w][3] and of its HR partner [4h][4w][3], total bytes).  uint8 HWC, back to back in list order, LR before HR, no padding."""
+    offs, n = np.zeros((len(sizes), 2), dtype=np.int64), 0
+    for i, (h, w) in enumerate(sizes):
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise _lib.FFError(f"pool_layout: image {i} has size {h}x{w}")
+        offs[i] = (n, n + 3 * h * w)
+        n += 51 * h * w                                               # 3 h w + 3 (4h) (4w)
+    return offs, n
+
+
+def live_plan(sizes: Sequence[Tuple[int, int]], repeat_factor: int, batch_size: int, patch: int, seed: int, epoch: int, augment: bool = True,
+              shuffle: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """-> (idx, top, left, codes), each [nb, batch_size]: dataset indices in 0 .. n_images * repeat_factor (entry i reads image
+    i % n_images, dataset.py:236-249), the LR patch origin and the D4 code of every sample of the epoch.  Shuffled order, incomplete
+    last batch dropped (dataset.py:562-565).  sizes = LR (h, w) per image, all >= patch.  The draws restate the reference's
+    augmentation: top uniform in [0, h - p], left uniform in [0, w - p] (augmentations.py:77-79), hflip and vflip with p = 0.5 each
+    (:128-135), and a rotation with p = 0.5 whose k is uniform in {1, 2, 3} (:169-171) -- k = 0 half of the time, NOT the uniform k of
+    the cached mode.  augment=False: code 0 at the centre position ((h - p) // 2, (w - p) // 2) (dataset.py:282-296).
+    Everything is a function of (seed, epoch) through numpy's counter-based Philox -- a draw belongs to a position in the epoch --
+    so a resumed run repeats the uninterrupted one; the reference's own streams: parity unpinned (RNG stream)."""
+    n_img, p = len(sizes), int(patch)
+    if n_img < 1 or repeat_factor < 1 or batch_size < 1 or p < 1:
+        raise _lib.FFError(f"live_plan: need images, repeat_factor, batch_size and patch >= 1, got {n_img}, {repeat_factor}, {batch_size}, {p}")
+    hw = np.asarray(sizes, dtype=np.int64).reshape(n_img, 2)
+    if (hw < p).any():
+        raise _lib.FFError(f"live_plan: image {int(np.argmax((hw < p).any(axis=1)))} is smaller than the {p}x{p} patch")
+    n = n_img * int(repeat_factor)
+    nb = n // int(batch_size)
+    m = nb * int(batch_size)
+    key = [int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFFFFFFFFFF]
+    gen = lambda c: np.random.Generator(np.random.Philox(key=key, counter=[0, 0, 0, c]))     # noqa: E731 -- one stream per quantity
+    order = (gen(0).permutation(n) if shuffle else np.arange(n))[:m].astype(np.int64)
+    room = hw[order % n_img] - p                                      # [m, 2]: the largest top / left of each sample's image
+    if augment:
+        top = gen(1).integers(0, room[:, 0] + 1, dtype=np.int64)
+        left = gen(2).integers(0, room[:, 1] + 1, dtype=np.int64)
+        flips = gen(3).integers(0, 4, size=m, dtype=np.int64)         # bit 0 hflip, bit 1 vflip: two independent fair draws
+        turn = gen(4).integers(0, 2, size=m, dtype=np.int64)          # rotate at all?
+        k = np.where(turn == 1, gen(5).integers(1, 4, size=m, dtype=np.int64), 0)
+        codes = (flips | (k << 2)).astype(np.int32)
+    else:
+        top, left, codes = room[:, 0] // 2, room[:, 1] // 2, np.zeros(m, dtype=np.int32)
+    shp = (nb, int(batch_size))
+    return order.reshape(shp), top.reshape(shp), left.reshape(shp), codes.reshape(shp)
+
+
+class ImagePool:
+    """Every image pair of a folder (or two), decoded once and resident on the device as ONE packed uint8 buffer.
+
+        pool = ImagePool(hr_dir, lr_dir=None, patch=64, device="cuda:0", readers=8, max_bytes=64 << 30)
+        pool.buf [total_bytes] uint8, pool.sizes [(h, w)] LR sizes, pool.offsets int64 [n, 2], pool.stems, pool.skipped
+
+    Pairing and order follow cache.build_from_folders: matched by stem, sorted, image index = position in that order (among the
+    images kept).  Pass 1 reads the sizes from the headers, leaves out (and counts) images smaller than the patch, lays the pool out
+    (pool_layout) and allocates it; more than max_bytes is an error -- there is no second route.  Pass 2: `readers` host threads
+    (at most 16) decode into pinned uint8 slots and make no GPU call; the calling thread uploads each image into its place.
+    With lr_dir an HR image that is not exactly 4x its LR partner is an error naming the file.  Without it HR is cropped top-left to
+    multiples of 4 and LR = f32_to_u8_image(resize_aa(u8_to_f32_image(hr))) on the device, as build_from_folders makes it.
+    A reader's exception ends construction and is re-raised."""
+
+    def __init__(self, hr_dir: str, lr_dir: Optional[str] = None, patch: int = 64, device="cuda:0", readers: int = 8, max_bytes: int = 64 << 30):
+        from PIL import Image
+        self.patch, self.dev = int(patch), torch.device(device)
+        if self.patch < 1 or int(readers) < 1:
+            raise _lib.FFError(f"ImagePool: patch and readers must be >= 1, got {patch}, {readers}")
+        if self.dev.type != "cuda" or not torch.cuda.is_available():
+            raise _lib.FFError("ImagePool needs an MI355X (torch device 'cuda'): the images live on the device")
+        hr_files = cache._image_stems(hr_dir)
+        lr_files = None
+        if lr_dir is not None:
+            lr_files = cache._image_stems(lr_dir)
+            missing = sorted(set(hr_files) ^ set(lr_files))
+            if missing:
+                raise FileNotFoundError(f"ImagePool: {missing[0]} has no partner in {lr_dir if missing[0] in hr_files else hr_dir}")
+        items, sizes = [], []
+        for stem in sorted(hr_files):                                 # pass 1: headers only
+            W, H = Image.open(hr_files[stem]).size
+            if lr_files is None:
+                h, w = H // 4, W // 4
+            else:
+                w, h = Image.open(lr_files[stem]).size
+                if (H, W) != (4 * h, 4 * w):
+                    raise _lib.FFError(f"{hr_files[stem]}: HR is {H}x{W}, not exactly 4x its LR {lr_files[stem]} ({h}x{w})")
+            items.append((stem, hr_files[stem], None if lr_files is None else lr_files[stem]))
+            sizes.append((h, w))
+        keep, self.skipped = pool_members(sizes, self.patch)
+        if not keep:
+            raise _lib.FFError(f"{hr_dir}: no image holds a {self.patch}x{self.patch} LR patch ({self.skipped} skipped)")
+        self.stems = [items[i][0] for i in keep]
+        self.sizes = [sizes[i] for i in keep]
+        self.offsets, self.total_bytes = pool_layout(self.sizes)
+        if self.total_bytes > int(max_bytes):
+            raise _lib.FFError(f"ImagePool: {len(keep)} images need {self.total_bytes} bytes on the device, max_bytes allows {int(max_bytes)}")
+        with torch.cuda.device(self.dev):
+            self.buf = torch.empty(self.total_bytes, dtype=torch.uint8, device=self.dev)
+            self._fill([items[i] for i in keep], lr_files is None, max(1, min(16, int(readers))))
+
+    def _fill(self, items, hr_only: bool, n_readers: int):
+        from . import ops
+        from PIL import Image
+        slot_bytes = max(51 * h * w for h, w in self.sizes)
+        free, ready, stop, nxt, lock = queue.Queue(), queue.Queue(), threading.Event(), [0], threading.Lock()
+        for _ in range(n_readers + 2):                                # pinned here: the readers make no GPU call
+            free.put(torch.empty(slot_bytes, dtype=torch.uint8, pin_memory=True))
+
+        def reader():
+            try:
+                while not stop.is_set():
+                    with lock:
+                        i = nxt[0]
+                        nxt[0] += 1
+                    if i >= len(items):
+                        break
+                    slot = free.get()
+                    if slot is None:
+                        return
+                    (h, w), (_, hr_path, lr_path) = self.sizes[i], items[i]
+                    hr = np.asarray(Image.open(hr_path).convert("RGB"), dtype=np.uint8)[:4 * h, :4 * w]
+                    if hr.shape != (4 * h, 4 * w, 3):
+                        raise _lib.FFError(f"{hr_path}: decoded to {hr.shape[0]}x{hr.shape[1]}, its header said {4 * h}x{4 * w} or more")
+                    slot[3 * h * w:51 * h * w].view(4 * h, 4 * w, 3).numpy()[...] = hr
+                    if lr_path is not None:
+                        lr = np.asarray(Image.open(lr_path).convert("RGB"), dtype=np.uint8)
+                        if lr.shape != (h, w, 3):
+                            raise _lib.FFError(f"{lr_path}: decoded to {lr.shape[0]}x{lr.shape[1]}, its header said {h}x{w}")
+                        slot[:3 * h * w].view(h, w, 3).numpy()[...] = lr
+                    ready.put((i, slot))
+                ready.put(None)
+            except BaseException as e:                                # noqa: BLE001 -- re-raised on the calling thread
+                ready.put(e)
+
+        threads = [threading.Thread(target=reader, name=f"ff-pool-reader{i}", daemon=True) for i in range(n_readers)]
+        for t in threads:
+            t.start()
+        pending, done = [], 0                                         # (event of the last copy out of a slot, slot)
+        try:
+            while done < n_readers:
+                for ent in [e for e in pending if e[0].query()]:
+                    pending.remove(ent)
+                    free.put(ent[1])
+                try:
+                    item = ready.get(timeout=0.05 if pending else None)
+                except queue.Empty:                                   # the readers may be out of slots: hand the oldest one back
+                    ev, slot = pending.pop(0)
+                    ev.synchronize()
+                    free.put(slot)
+                    continue
+                if isinstance(item, BaseException):
+                    raise item
+                if item is None:
+                    done += 1
+                    continue
+                i, slot = item
+                (h, w), (lo, ho) = self.sizes[i], (int(v) for v in self.offsets[i])
+                if hr_only:                                           # the LR image is made here, from the uploaded HR image
+                    hr_u8 = slot[3 * h * w:51 * h * w].view(4 * h, 4 * w, 3).to(self.dev, non_blocking=True)
+                    self.buf[ho:ho + 48 * h * w].copy_(hr_u8.view(-1))
+                    lr_u8 = ops.f32_to_u8_image(ops.resize_aa(ops.u8_to_f32_image(hr_u8), (h, w)))
+                    self.buf[lo:lo + 3 * h * w].copy_(lr_u8.view(-1))
+                else:                                                 # LR and HR are adjacent in the slot as they are in the pool
+                    self.buf[lo:lo + 51 * h * w].copy_(slot[:51 * h * w], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append((ev, slot))
+        finally:
+            stop.set()
+            for _ in threads:
+                free.put(None)
+            for t in threads:
+                t.join(timeout=60)
+            torch.cuda.synchronize(self.dev)
+
+    def __len__(self) -> int:
+        return len(self.sizes)
+
+    def image(self, i: int) -> Tuple[T, T]:
+        """(lr_u8 [h,w,3], hr_u8 [4h,4w,3]): views of image i inside the pool."""
+        (h, w), (lo, ho) = self.sizes[i], (int(v) for v in self.offsets[i])
+        return self.buf[lo:lo + 3 * h * w].view(h, w, 3), self.buf[ho:ho + 48 * h * w].view(4 * h, 4 * w, 3)
+
+
+class LiveEpoch:
+    """Micro-batches cut from an ImagePool with the experts run on each, epoch by epoch; interchangeable with CachedEpoch in
+    train_epoch and fit.
+
+        data = LiveEpoch(model, pool, batch_size=14, repeat_factor=6, augment=True, seed=0, overlap=True)
+        for lr, hr, outs, feats in data.batches(epoch): ...           # device tensors, len(data) of them
+        data.close()
+
+    An epoch uploads its descriptor table (live_plan -> int64 [nb, B, 8]) once; a micro-batch is then ONE ops.sample_pairs_u8 launch
+    that writes the augmented patches straight into the expert graph's input, and one replay of that graph
+    (model.experts_with_features(lr, streams=True) for [B,3,p,p], captured here, before any thread of the caller's exists, in the
+    process's contraction mode ops.gemm_mode()).  The four yielded objects are static buffers of a lane: they hold a micro-batch until
+    the next but `lanes - 1` is asked for, and the consumer reads them on the stream that asked (train_epoch does).
+    overlap=True: two lanes, each with its own captured graph and buffers; the sampler launch and the replay of micro-batch n + 1 are
+    queued on a side stream before micro-batch n is handed out, so they run beside the step the host is still launching.  Events
+    order every reuse: the asking stream waits for a lane's replay, the side stream waits until the consumer of a lane's previous
+    micro-batch has queued its work (known when it asks for the next one).  The tensors hold the bits of overlap=False.
+    Nothing is read from disk during an epoch, so `wait_s` stays 0.  close() destroys the graphs explicitly."""
+
+    def __init__(self, model, pool: ImagePool, batch_size: int, repeat_factor: int = 6, augment: bool = True, seed: int = 0, overlap: bool = True,
+                 shuffle: bool = True):
+        self.model, self.pool, self.B, self.repeat = model, pool, int(batch_size), int(repeat_factor)
+        self.augment, self.seed, self.shuffle, self.overlap = bool(augment), int(seed), shuffle, bool(overlap)
+        if self.B < 1 or self.repeat < 1:
+            raise _lib.FFError(f"LiveEpoch: batch_size and repeat_factor must be >= 1, got {batch_size}, {repeat_factor}")
+        if len(pool) * self.repeat < self.B:
+            raise _lib.FFError(f"LiveEpoch: {len(pool)} images x repeat {self.repeat} do not fill one batch of {self.B} (drop_last)")
+        if torch.device(model.dev) != pool.dev:
+            raise _lib.FFError(f"LiveEpoch: the model is on {model.dev}, the pool on {pool.dev}")
+        self.dev = pool.dev
+        self.wait_s = 0.0
+        self._lanes = []
+        p = pool.patch
+        with torch.cuda.device(self.dev):
+            try:
+                for k in range(2 if self.overlap else 1):
+                    ge = cache._GraphedExperts(model, p, (), tag=("live", id(self), k))
+                    self._lanes.append({"experts": ge})
+                    _, graph, lr, outs, feats = ge.prepare(self.B)
+                    self._lanes[-1].update(graph=graph, lr=lr, outs=outs, feats=feats, ready=torch.cuda.Event(), consumed=None,
+                                           hr=torch.empty((self.B, 3, 4 * p, 4 * p), device=self.dev, dtype=torch.float32))
+            except BaseException:
+                self.close()
+                raise
+            self._side = torch.cuda.Stream(device=self.dev) if self.overlap else None
+
+    def __len__(self) -> int:
+        return len(self.pool) * self.repeat // self.B
+
+    def plan(self, epoch: int):
+        return live_plan(self.pool.sizes, self.repeat, self.B, self.pool.patch, self.seed, epoch, self.augment, self.shuffle)
+
+    def descriptors(self, epoch: int) -> np.ndarray:
+        """The epoch's sampler table, int64 [nb, B, 8] = {lr_off, hr_off, h, w, top, left, code, 0} (ops.sample_pairs_u8)."""
+        idx, top, left, codes = self.plan(epoch)
+        img = idx % len(self.pool)
+        d = np.zeros(idx.shape + (8,), dtype=np.int64)
+        d[..., 0:2] = self.pool.offsets[img]
+        d[..., 2:4] = np.asarray(self.pool.sizes, dtype=np.int64)[img]
+        d[..., 4], d[..., 5], d[..., 6] = top, left, codes
+        return d
+
+    def batches(self, epoch: int):
+        from . import ops
+        if not self._lanes:
+            raise _lib.FFError("LiveEpoch: closed")
+        desc = self.descriptors(epoch)
+        nb, p, lanes = desc.shape[0], self.pool.patch, self._lanes
+        with torch.cuda.device(self.dev):
+            main = torch.cuda.current_stream()
+            desc_dev = torch.from_numpy(desc).to(self.dev)            # ONE upload per epoch
+            side = self._side if self.overlap else main
+            if self.overlap:
+                side.wait_stream(main)                                # the table, and whatever the caller queued before the epoch
+                desc_dev.record_stream(side)
+
+            def launch(b):                                            # sampler + expert replay of micro-batch b, on `side`
+                L = lanes[b % len(lanes)]
+                if self.overlap and L["consumed"] is not None:
+                    side.wait_event(L["consumed"])                    # the lane's previous micro-batch has been read
+                with torch.cuda.stream(side):
+                    ops.sample_pairs_u8(self.pool.buf, desc[b], p, desc_dev=desc_dev[b], out=(L["lr"], L["hr"]))
+                    L["graph"].replay()
+                    if self.overlap:
+                        L["ready"].record(side)
+
+            try:
+                if self.overlap and nb:
+                    launch(0)
+                for b in range(nb):
+                    if not self.overlap:
+                        launch(b)
+                    elif b + 1 < nb:
+                        launch(b + 1)                                 # queued before step b is: it runs beside that step
+                    L = lanes[b % len(lanes)]
+                    if self.overlap:
+                        main.wait_event(L["ready"])
+                    yield L["lr"], L["hr"], L["outs"], L["feats"]
+                    if self.overlap:                                  # the consumer is back: its reads of this lane are queued on `main`
+                        L["consumed"] = torch.cuda.Event()
+                        L["consumed"].record(main)
+            finally:
+                if self.overlap:
+                    main.wait_stream(side)                            # an abandoned epoch leaves nothing running beside the caller
+                    for L in lanes:
+                        L["consumed"] = None
+
+    def close(self):
+        lanes, self._lanes = self._lanes, []
+        if lanes:
+            torch.cuda.synchronize(self.dev)
+        for L in lanes:
+            L["experts"].close()
+
+
+@torch.no_grad()
+def live_val_samples(model, hr_dir: str, lr_dir: Optional[str] = None, patch: int = 64) -> List[dict]:
+    """The validation set of a live run, computed once (the experts are frozen): per image the centre patch and the three expert
+    images, dicts in cache.read_sample's shape {lr [3,p,p], hr [3,4p,4p], expert_imgs, filename} on the host.  No features: the
+    eval path skips the collaborative block (enhanced_fusion.py:331, 359-362).  validate() takes the list as it is."""
+    from . import ops
+    with torch.cuda.device(model.dev):
+        pool = ImagePool(hr_dir, lr_dir, patch=patch, device=model.dev, readers=4)
+        out = []
+        for i, stem in enumerate(pool.stems):
+            h, w = pool.sizes[i]
+            lr_u8, hr_u8 = pool.image(i)
+            lr, hr = ops.crop_pairs_u8(lr_u8.clone(), hr_u8.clone(), cache.crop_plan(h, w, patch, 1, 0, i, center=True), patch)
+            outs, _ = model.experts_with_features(lr, streams=True)
+            out.append({"lr": lr[0].cpu(), "hr": hr[0].cpu(), "expert_imgs": {k: outs[k][0].cpu() for k in EXPERTS}, "filename": stem})
+    return out

@@ -1697,6 +1697,49 @@ def crop_pairs_u8(lr_u8: T, hr_u8: T, positions, patch: int) -> Tuple[T, T]:
     return lr, hr
 
 
+# ---- live-expert training (epoch.ImagePool / LiveEpoch): one micro-batch out of the resident image pool -----------------------------
+def sample_pairs_u8(pool: T, desc_host, patch: int, desc_dev: Optional[T] = None, out: Optional[Tuple[T, T]] = None) -> Tuple[T, T]:
+    """B augmented patch pairs out of one packed pool of uint8 HWC images, one launch (csrc/sample_batch.hip).  pool: 1-D uint8 device
+    tensor; desc_host: host int64 [B][8] rows {lr_off, hr_off, h, w, top, left, code, 0} (byte offsets, LR image [h,w,3], HR partner
+    [4h,4w,3], LR patch origin, d4 code) -> (lr [B,3,p,p], hr [B,3,4p,4p]) fp32 = u8 / 255, the bits of
+    d4_nchw(crop_pairs_u8(...), codes).  Every row is checked here before the launch.  desc_dev: the same table already on the device
+    (int64 [B,8]); out: (lr, hr) tensors to fill."""
+    import numpy as np
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
+            and pool.numel() > 0):
+        raise _lib.FFError("sample_pairs_u8: pool must be a non-empty contiguous 1-D CUDA(HIP) uint8 tensor")
+    p = int(patch)
+    d = np.ascontiguousarray(np.asarray(desc_host, dtype=np.int64))
+    if d.ndim != 2 or d.shape[1] != 8 or d.shape[0] < 1 or p < 1:
+        raise _lib.FFError(f"sample_pairs_u8: need B >= 1 rows of 8 fields and patch >= 1, got a table of shape {d.shape} and patch {p}")
+    B, n = d.shape[0], pool.numel()
+    for b in range(B):
+        lo, ho, h, w, top, left, code, _ = (int(v) for v in d[b])
+        if h < 1 or w < 1 or lo < 0 or ho < 0 or lo + 3 * h * w > n or ho + 48 * h * w > n:
+            raise _lib.FFError(f"sample_pairs_u8: sample {b}: image {h}x{w} at byte offsets {lo} / {ho} leaves the pool of {n} bytes")
+        if not (0 <= top <= h - p and 0 <= left <= w - p):
+            raise _lib.FFError(f"sample_pairs_u8: sample {b}: position ({top}, {left}) puts a {p}x{p} patch outside the {h}x{w} LR image")
+        if not 0 <= code < D4_CODES:
+            raise _lib.FFError(f"sample_pairs_u8: sample {b}: d4 code {code}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(d).to(pool.device)
+    elif not (desc_dev.is_cuda and desc_dev.dtype == torch.int64 and desc_dev.is_contiguous() and tuple(desc_dev.shape) == (B, 8)
+              and desc_dev.device == pool.device):
+        raise _lib.FFError(f"sample_pairs_u8: desc_dev must be a contiguous int64 [{B}, 8] tensor on the pool's device")
+    shapes = ((B, 3, p, p), (B, 3, 4 * p, 4 * p))
+    if out is None:
+        lr, hr = (torch.empty(s, device=pool.device, dtype=torch.float32) for s in shapes)
+    else:
+        lr, hr = out
+        for t, s in zip((lr, hr), shapes):
+            _chk(t, "sample_pairs_u8.out")
+            if tuple(t.shape) != s or not t.is_contiguous() or t.device != pool.device:
+                raise _lib.FFError(f"sample_pairs_u8: out must be contiguous {list(shapes[0])} and {list(shapes[1])} tensors on the pool's device")
+    _lib.check(_L().ff_sample_pairs_u8(pool.data_ptr(), desc_dev.data_ptr(), B, p, lr.data_ptr(), hr.data_ptr(), _stream()))
+    _note(0.0, 17.0 * B * 3 * p * p * 5.0)
+    return lr, hr
+
+
 AA_TAPS = 16
 
 

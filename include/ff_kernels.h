@@ -520,6 +520,15 @@ int ff_crop_pairs_u8(const unsigned char* lr_u8, const unsigned char* hr_u8, int
 int ff_resize_aa(const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, const int* span_w, const float* wt_w,
                  const int* span_h, const float* wt_h, void* stream);
 
+/* One training micro-batch out of a resident image pool (isr2_amd.epoch.ImagePool / LiveEpoch; csrc/sample_batch.hip): crop, u8 -> fp32
+ * and the paired D4 augmentation of B samples, LR and HR, in one launch.  pool: one device byte buffer, every image uint8 HWC packed
+ * back to back (nothing aligned).  desc: DEVICE int64 [B][8] = {lr_off, hr_off, h, w, top, left, code, 0} -- byte offsets into pool, LR
+ * image [h][w][3], HR partner [4h][4w][3], LR patch origin with 0 <= top <= h - p, 0 <= left <= w - p, code as ff_d4_nchw (bit 0
+ * flip(-1), bit 1 flip(-2), bits 2-3 rot90 k); the caller checks them (ops.sample_pairs_u8), the kernel clamps top / left all the same.
+ * lr_out [B][3][p][p], hr_out [B][3][4p][4p] fp32 = u8 / 255 (IEEE division): the bits of ff_d4_nchw(ff_crop_pairs_u8(...)).
+ * First check: null pointers, B < 1, p < 1.  Added under ABI version 7 (additive). */
+int ff_sample_pairs_u8(const unsigned char* pool, const long long* desc, int B, int p, float* lr_out, float* hr_out, void* stream);
+
 /* Frequency bands of the planar LR image x[C][H][W] written into out[H][W][ldo] channel groups.
  * multi_domain_frequency.py:146-196 (DCT), :273-299 (DWT pass), :352-385 (FFT low/high). */
 int ff_dct8_bands(const float* x, int C, int H, int W, const float* dct_mat, const float* masks3,
