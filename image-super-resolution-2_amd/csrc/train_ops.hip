@@ -76,7 +76,7 @@ __device__ __forceinline__ float ew_unary_apply(int op, float x, float g, float 
   switch (op) {
     case U_GELU: return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
     case U_RELU: return x > 0.f ? x : 0.f;
-    case U_SIGMOID: return 1.0f / (1.0f + expf(-x));
+    case U_SIGMOID: return x < -87.f ? expf(x) : 1.0f / (1.0f + expf(-x));         // below -87 exp(-x) nears FLT_MAX; sigmoid(x) = exp(x) to 1e-38 there
     case U_SOFTPLUS: return x > 20.f ? x : log1pf(expf(x));                      // F.softplus(beta 1, threshold 20)
     case U_ABS: return fabsf(x);
     case U_CLAMP01: return fminf(fmaxf(x, 0.f), 1.f);
@@ -91,7 +91,7 @@ __device__ __forceinline__ float ew_unary_apply(int op, float x, float g, float 
     }
     case U_RELU_BWD: return x > 0.f ? g : 0.f;
     case U_SIGMOID_BWD_Y: return g * x * (1.0f - x);                              // x = sigmoid output
-    case U_SOFTPLUS_BWD: return x > 20.f ? g : g / (1.0f + expf(-x));
+    case U_SOFTPLUS_BWD: return x > 20.f ? g : (x < -87.f ? g * expf(x) : g / (1.0f + expf(-x)));   // same tail as U_SIGMOID
     case U_ABS_BWD: return x > 0.f ? g : (x < 0.f ? -g : 0.f);                    // torch: sgn(0) = 0
     case U_CLAMP01_BWD: return (x >= 0.f && x <= 1.f) ? g : 0.f;                  // torch.clamp: bounds inclusive
     case U_RECIP_BWD: return -g * x * x;                                          // x = the reciprocal y = 1/(u+eps): dy/du = -y^2
