@@ -22,7 +22,9 @@ configuration selects: dataset.train.cache_data false, repeat_factor 6):
 
 The images are decoded once into one device buffer; a micro-batch is one sampler launch (csrc/sample_batch.hip: crop, u8 -> fp32
 and the paired D4 symmetry) and one replay of the captured expert graph, with nothing read from disk.  Its crop and augmentation
-draws are a third "parity unpinned (RNG stream)".
+draws are a third "parity unpinned (RNG stream)".  LiveEpoch(color_jitter=...) adds the reference's paired colour jitter
+(augmentations.py:207-264 -> live_jitter_plan(), csrc/color_jitter.hip) between the two: its draws are one more unpinned RNG stream,
+and its 8-bit HSV step restates OpenCV's published definition without an OpenCV binary to compare with: "parity unpinned (OpenCV absent)".
 """
 from __future__ import annotations
 
@@ -469,6 +471,32 @@ def live_plan(sizes: Sequence[Tuple[int, int]], repeat_factor: int, batch_size: 
     return order.reshape(shp), top.reshape(shp), left.reshape(shp), codes.reshape(shp)
 
 
+JITTER_DEFAULTS = dict(prob=0.5, brightness=0.2, contrast=0.2, saturation=0.2)   # ColorJitter's and SRTrainAugmentation's class defaults
+
+
+def live_jitter_plan(nb: int, batch_size: int, seed: int, epoch: int, prob: float = 0.5, brightness: float = 0.2, contrast: float = 0.2,
+                     saturation: float = 0.2) -> np.ndarray:
+    """-> fp32 [nb, batch_size, 4] = {apply, bf, cf, sf}: the colour-jitter table of an epoch (ops.color_jitter_pairs), one row per sample
+    of live_plan's epoch.  The reference (augmentations.py:222-228): apply = random() < prob; each factor = 1 + uniform(-r, r), shared by
+    the LR and the HR patch.  The training set is built without jitter arguments (dataset.py:111-119), so the class defaults hold --
+    prob 0.5 and 0.2 for the three ranges -- not the YAML's values, which are never read.  Drawn in fp64 and rounded to fp32; a row keeps
+    its drawn factors when apply is 0.  live_plan's Philox key with counters 6..9 (apply, brightness, contrast, saturation): live_plan's
+    own streams 0..5 are untouched, and the table is a function of (seed, epoch) only, so a resumed run repeats the uninterrupted one.
+    The reference's `random` stream: parity unpinned (RNG stream)."""
+    nb, B = int(nb), int(batch_size)
+    rng = (float(brightness), float(contrast), float(saturation))
+    if nb < 0 or B < 1 or not 0.0 <= float(prob) <= 1.0 or not all(0.0 <= r < 1.0 for r in rng):
+        raise _lib.FFError(f"live_jitter_plan: need nb >= 0, batch_size >= 1, prob in [0, 1] and ranges in [0, 1), got {nb}, {B}, {prob}, {rng}")
+    m = nb * B
+    key = [int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFFFFFFFFFF]
+    gen = lambda c: np.random.Generator(np.random.Philox(key=key, counter=[0, 0, 0, c]))     # noqa: E731 -- one stream per quantity
+    t = np.empty((m, 4), dtype=np.float32)
+    t[:, 0] = gen(6).random(m) < float(prob)
+    for j, r in enumerate(rng):
+        t[:, 1 + j] = (1.0 + gen(7 + j).uniform(-r, r, size=m)).astype(np.float32)
+    return t.reshape(nb, B, 4)
+
+
 class ImagePool:
     """Every image pair of a folder (or two), decoded once and resident on the device as ONE packed uint8 buffer.
 
@@ -621,12 +649,24 @@ class LiveEpoch:
     queued on a side stream before micro-batch n is handed out, so they run beside the step the host is still launching.  Events
     order every reuse: the asking stream waits for a lane's replay, the side stream waits until the consumer of a lane's previous
     micro-batch has queued its work (known when it asks for the next one).  The tensors hold the bits of overlap=False.
+    color_jitter: None (nothing changes), True (the reference's defaults, JITTER_DEFAULTS) or a dict with any of {prob, brightness,
+    contrast, saturation}: the epoch's jitter table (live_jitter_plan -> fp32 [nb, B, 4]) is uploaded once as well, and
+    ops.color_jitter_pairs runs in place on the lane's lr / hr between the sampler launch and the replay, on the same stream -- the
+    experts and the fusion stack both see the jittered LR, as in the reference.  Independent of `augment`.
     Nothing is read from disk during an epoch, so `wait_s` stays 0.  close() destroys the graphs explicitly."""
 
     def __init__(self, model, pool: ImagePool, batch_size: int, repeat_factor: int = 6, augment: bool = True, seed: int = 0, overlap: bool = True,
-                 shuffle: bool = True):
+                 shuffle: bool = True, color_jitter=None):
         self.model, self.pool, self.B, self.repeat = model, pool, int(batch_size), int(repeat_factor)
         self.augment, self.seed, self.shuffle, self.overlap = bool(augment), int(seed), shuffle, bool(overlap)
+        if color_jitter is None or color_jitter is False:
+            self.jitter = None
+        else:
+            extra = {} if color_jitter is True else dict(color_jitter)
+            if set(extra) - set(JITTER_DEFAULTS):
+                raise _lib.FFError(f"LiveEpoch: color_jitter takes {sorted(JITTER_DEFAULTS)}, got {sorted(extra)}")
+            self.jitter = dict(JITTER_DEFAULTS, **extra)
+            live_jitter_plan(0, 1, 0, 0, **self.jitter)               # the ranges are checked here, not in the first epoch
         if self.B < 1 or self.repeat < 1:
             raise _lib.FFError(f"LiveEpoch: batch_size and repeat_factor must be >= 1, got {batch_size}, {repeat_factor}")
         if len(pool) * self.repeat < self.B:
@@ -666,19 +706,27 @@ class LiveEpoch:
         d[..., 4], d[..., 5], d[..., 6] = top, left, codes
         return d
 
+    def jitter_table(self, epoch: int) -> Optional[np.ndarray]:
+        """The epoch's colour-jitter table, fp32 [nb, B, 4] = {apply, bf, cf, sf} (ops.color_jitter_pairs); None without color_jitter."""
+        return None if self.jitter is None else live_jitter_plan(len(self), self.B, self.seed, epoch, **self.jitter)
+
     def batches(self, epoch: int):
         from . import ops
         if not self._lanes:
             raise _lib.FFError("LiveEpoch: closed")
         desc = self.descriptors(epoch)
+        jit = self.jitter_table(epoch)
         nb, p, lanes = desc.shape[0], self.pool.patch, self._lanes
         with torch.cuda.device(self.dev):
             main = torch.cuda.current_stream()
             desc_dev = torch.from_numpy(desc).to(self.dev)            # ONE upload per epoch
+            jit_dev = None if jit is None else torch.from_numpy(jit).to(self.dev)
             side = self._side if self.overlap else main
             if self.overlap:
-                side.wait_stream(main)                                # the table, and whatever the caller queued before the epoch
+                side.wait_stream(main)                                # the tables, and whatever the caller queued before the epoch
                 desc_dev.record_stream(side)
+                if jit_dev is not None:
+                    jit_dev.record_stream(side)
 
             def launch(b):                                            # sampler + expert replay of micro-batch b, on `side`
                 L = lanes[b % len(lanes)]
@@ -686,6 +734,8 @@ class LiveEpoch:
                     side.wait_event(L["consumed"])                    # the lane's previous micro-batch has been read
                 with torch.cuda.stream(side):
                     ops.sample_pairs_u8(self.pool.buf, desc[b], p, desc_dev=desc_dev[b], out=(L["lr"], L["hr"]))
+                    if jit is not None:
+                        ops.color_jitter_pairs(L["lr"], L["hr"], jit[b], table_dev=jit_dev[b])
                     L["graph"].replay()
                     if self.overlap:
                         L["ready"].record(side)

@@ -1740,6 +1740,41 @@ def sample_pairs_u8(pool: T, desc_host, patch: int, desc_dev: Optional[T] = None
     return lr, hr
 
 
+def color_jitter_pairs(lr: T, hr: T, table_host, table_dev: Optional[T] = None) -> Tuple[T, T]:
+    """The reference's paired colour jitter on a sampled micro-batch, IN PLACE, two launches (csrc/color_jitter.hip): lr [B,3,p,p] and
+    hr [B,3,4p,4p] contiguous fp32 device tensors holding u8 / 255 (what sample_pairs_u8 writes); table_host: host fp32 [B][4] rows
+    {apply, bf, cf, sf} -- apply 0 leaves the sample's two patches untouched, else brightness bf, contrast cf around each patch's own
+    mean, saturation sf through the 8-bit HSV conversion (none when sf == 1).  Every row is checked here before the launch: apply in
+    {0, 1}, factors finite and in (0, 2).  table_dev: the same table already on the device (fp32 [B,4]).  -> (lr, hr)."""
+    import numpy as np
+    for t, name in ((lr, "lr"), (hr, "hr")):
+        _chk(t, "color_jitter_pairs." + name)
+        if t.dim() != 4 or not t.is_contiguous():
+            raise _lib.FFError(f"color_jitter_pairs: {name} must be a contiguous 4-D tensor, got {list(t.shape)}")
+    B, p = int(lr.shape[0]), int(lr.shape[2])
+    if B < 1 or p < 1 or tuple(lr.shape) != (B, 3, p, p) or tuple(hr.shape) != (B, 3, 4 * p, 4 * p) or hr.device != lr.device:
+        raise _lib.FFError(f"color_jitter_pairs: need lr [B,3,p,p] and hr [B,3,4p,4p] on one device, got {list(lr.shape)} and {list(hr.shape)}")
+    tb = np.ascontiguousarray(np.asarray(table_host, dtype=np.float32))
+    if tb.shape != (B, 4):
+        raise _lib.FFError(f"color_jitter_pairs: the table must be [{B}, 4] = {{apply, bf, cf, sf}}, got {tb.shape}")
+    for b in range(B):
+        ap, bf, cf, sf = (float(v) for v in tb[b])
+        if ap not in (0.0, 1.0):
+            raise _lib.FFError(f"color_jitter_pairs: sample {b}: apply is {ap}, expected 0 or 1")
+        if not all(np.isfinite(v) and 0.0 < v < 2.0 for v in (bf, cf, sf)):
+            raise _lib.FFError(f"color_jitter_pairs: sample {b}: factors ({bf}, {cf}, {sf}) must be finite and inside (0, 2)")
+    if table_dev is None:
+        table_dev = torch.from_numpy(tb).to(lr.device)
+    elif not (isinstance(table_dev, torch.Tensor) and table_dev.is_cuda and table_dev.dtype == torch.float32 and table_dev.is_contiguous()
+              and tuple(table_dev.shape) == (B, 4) and table_dev.device == lr.device):
+        raise _lib.FFError(f"color_jitter_pairs: table_dev must be a contiguous float32 [{B}, 4] tensor on lr's device")
+    nbytes = int(_L().ff_color_jitter_workspace(B))
+    work = torch.empty(nbytes // 8, device=lr.device, dtype=torch.int64)
+    _lib.check(_L().ff_color_jitter_pairs(lr.data_ptr(), hr.data_ptr(), table_dev.data_ptr(), B, p, work.data_ptr(), nbytes, _stream()))
+    _note(0.0, 17.0 * float(tb[:, 0].sum()) * 3 * p * p * 4.0 * 3.0)  # applied samples: read for the sums, read and written by the pixel pass
+    return lr, hr
+
+
 AA_TAPS = 16
 
 

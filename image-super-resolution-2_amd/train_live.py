@@ -5,7 +5,7 @@ warm-up 5 epochs + cosine restarts, batch 14, accumulation_steps 2, EMA 0.9995, 
     python -m isr2_amd.train_live --hr DIR [--lr DIR] --val-hr DIR [--val-lr DIR] --out DIR --epochs N [--resume] [--weights PATH]
                                   [--expert-weights DIR] [--batch 14] [--accum 2] [--repeat 6] [--patch 64] [--validate-every 1]
                                   [--seed 0] [--no-augment] [--dropout 0.1] [--gemm f32] [--expert-gemm bf16x3] [--readers 8]
-                                  [--pool-gb 64] [--device cuda:0]
+                                  [--pool-gb 64] [--device cuda:0] [--color-jitter] [--jitter-prob 0.5] [--jitter-range 0.2 0.2 0.2]
 
 --hr / --lr: folders of images matched by stem, every HR image exactly 4x its LR partner; without --lr the LR images are made on the
 device (antialiased bicubic x1/4 of the HR image cropped to multiples of 4, quantised to uint8).  The training images are decoded once
@@ -17,7 +17,12 @@ the plugin finds them; a missing one is replaced by seeded synthetic weights wit
 reference-keyed fusion (+ collaborative) state dict, bare or under `model_state_dict`; without it the seeded synthetic weights.
 --expert-gemm is the experts' contraction mode, --gemm the trainer's.  One JSON line per epoch on stdout; DIR/latest.pth after every
 epoch, DIR/best.pth on a new best validation PSNR (EMA weights).  --resume continues at the epoch after DIR/latest.pth's.
-Not applied: the reference's colour jitter, its OpenCV resize of images smaller than the patch, SyncBatchNorm / several GPUs."""
+--color-jitter: the reference's paired colour jitter on the device (augmentations.py:207-264; epoch.live_jitter_plan, two launches per
+micro-batch between the sampler and the experts, csrc/color_jitter.hip): with probability --jitter-prob a sample's LR and HR patch get
+brightness, contrast and saturation factors 1 + uniform(-r, r), r = --jitter-range B C S.  The defaults are the values the reference
+trains with (its class defaults; the YAML's are never read).  Off unless asked for; validation samples are never jittered.  Its
+draws are parity unpinned (RNG stream), its 8-bit HSV step parity unpinned (OpenCV absent).
+Not applied: the reference's OpenCV resize of images smaller than the patch, SyncBatchNorm / several GPUs."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +56,9 @@ def main(argv=None) -> int:
     ap.add_argument("--readers", type=int, default=8)
     ap.add_argument("--pool-gb", type=float, default=64.0)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--color-jitter", action="store_true")
+    ap.add_argument("--jitter-prob", type=float, default=0.5)
+    ap.add_argument("--jitter-range", type=float, nargs=3, default=[0.2, 0.2, 0.2], metavar=("B", "C", "S"))
     a = ap.parse_args(argv)
 
     from . import epoch as E
@@ -75,7 +83,8 @@ def main(argv=None) -> int:
         best = float(ck.get("metrics", {}).get("best_psnr", best))
     val = E.live_val_samples(model, a.val_hr, a.val_lr, patch=a.patch)
     pool = E.ImagePool(a.hr, a.lr, patch=a.patch, device=a.device, readers=a.readers, max_bytes=int(a.pool_gb * (1 << 30)))
-    data = E.LiveEpoch(model, pool, a.batch, a.repeat, augment=not a.no_augment, seed=a.seed)
+    jitter = dict(prob=a.jitter_prob, brightness=a.jitter_range[0], contrast=a.jitter_range[1], saturation=a.jitter_range[2]) if a.color_jitter else None
+    data = E.LiveEpoch(model, pool, a.batch, a.repeat, augment=not a.no_augment, seed=a.seed, color_jitter=jitter)
     try:
         E.fit(tr, data, val, a.out, a.epochs, start, a.accum, a.validate_every, best, log=lambda line: print(line, flush=True))
     finally:

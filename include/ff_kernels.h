@@ -529,6 +529,19 @@ int ff_resize_aa(const float* in, float* out, int planes, int Hi, int Wi, int Ho
  * First check: null pointers, B < 1, p < 1.  Added under ABI version 7 (additive). */
 int ff_sample_pairs_u8(const unsigned char* pool, const long long* desc, int B, int p, float* lr_out, float* hr_out, void* stream);
 
+/* The reference's paired colour jitter (augmentations.py:207-264) on a sampled micro-batch, in place (csrc/color_jitter.hip;
+ * ops.color_jitter_pairs, epoch.LiveEpoch(color_jitter=...)).  lr [B][3][p][p], hr [B][3][4p][4p] fp32 = u / 255 as ff_sample_pairs_u8 writes
+ * them; table: DEVICE fp32 [B][4] = {apply, bf, cf, sf} -- apply == 0 leaves both patches of that sample untouched bit for bit.  Per patch
+ * (each with its OWN mean): mean = float(double(bf) * (double(S) / (255.0 * 3 P P))) with S the exact integer sum of the patch's bytes
+ * rint(255 x); x2 = (x * bf - mean) * cf + mean, every fp32 step rounded on its own (no fused multiply-add); sf == 1: out = clip(x2, 0, 1);
+ * otherwise q = (u8) trunc(255 clip(x2)), 8-bit RGB -> HSV (12-bit fixed point, H in 0..179), S' = (u8) trunc(clip(S * sf, 0, 255)), HSV ->
+ * RGB (fp32 sector table, bytes by rint), out = byte / 255.  Two launches: the integer sums (64-bit partials in the workspace, no atomics),
+ * then the per-pixel pass.  workspace: ff_color_jitter_workspace(B) BYTES (-1 for B < 1), 8-byte aligned, need not be zeroed.
+ * First check: null pointers, B < 1, p < 1; then p <= 8192, B <= 2^20, the workspace size, the grid bound.  Added under ABI version 7
+ * (additive). */
+long long ff_color_jitter_workspace(int B);
+int ff_color_jitter_pairs(float* lr, float* hr, const float* table, int B, int p, void* workspace, long long workspace_bytes, void* stream);
+
 /* Frequency bands of the planar LR image x[C][H][W] written into out[H][W][ldo] channel groups.
  * multi_domain_frequency.py:146-196 (DCT), :273-299 (DWT pass), :352-385 (FFT low/high). */
 int ff_dct8_bands(const float* x, int C, int H, int W, const float* dct_mat, const float* masks3,

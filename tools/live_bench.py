@@ -1,7 +1,7 @@
 """Time live-expert training epochs on one MI355X, next to the cached epoch of tools/epoch_bench.py measured in the same session.
 
     python tools/live_bench.py [--images 48] [--lr-size 128] [--batch 14] [--repeat 7] [--accum 2] [--rounds 3] [--mode f32]
-                               [--expert-mode bf16x3] [--cached-samples 112] [--out FILE]
+                               [--expert-mode bf16x3] [--cached-samples 112] [--color-jitter] [--out FILE]
 
 A seeded synthetic folder of PNG pairs is written to a temporary directory and decoded into an isr2_amd.epoch.ImagePool.  Then:
   * parts of one micro-batch, device events over repeated calls after a warm-up: the sampler launch (ops.sample_pairs_u8 -- with the
@@ -12,6 +12,11 @@ A seeded synthetic folder of PNG pairs is written to a temporary directory and d
     spread (max - min); the overlap's margin over the single lane is compared with five times the single lane's own spread;
   * the cached epoch: tools/epoch_bench.py as a child process after the live runs (the cached loader is the code path of the parent
     commit), --cached-samples synthetic samples.
+  * --color-jitter: both live forms are LiveEpoch(color_jitter=True) -- the reference's defaults, about half of the samples applied --,
+    and the two launches of ops.color_jitter_pairs (csrc/color_jitter.hip) on a sampled micro-batch are reported per micro-batch beside
+    sampler, experts and step: once with the epoch's table as drawn and once with every sample applied.  To compare with the plain
+    loop, run the tool with and without the flag in one job, alternating the two (one process each: a process keeps the two forms and
+    the streams it always had).
 One JSON document on stdout (and in --out)."""
 import argparse
 import json
@@ -71,6 +76,7 @@ def main():
     ap.add_argument("--mode", default="f32")
     ap.add_argument("--expert-mode", default="bf16x3")
     ap.add_argument("--cached-samples", type=int, default=112)
+    ap.add_argument("--color-jitter", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -91,8 +97,10 @@ def main():
         pool = E.ImagePool(hr_dir, lr_dir, patch=p, readers=8)
         t_pool = time.perf_counter() - t0
         res["pool"] = {"images": len(pool), "bytes": pool.total_bytes, "build_s": t_pool, "images_per_s": len(pool) / t_pool}
-        forms = {False: E.LiveEpoch(model, pool, B, a.repeat, augment=True, seed=0, overlap=False),
-                 True: E.LiveEpoch(model, pool, B, a.repeat, augment=True, seed=0, overlap=True)}
+        names = {False: "overlap_off", True: "overlap_on"}
+        jitter = True if a.color_jitter else None
+        forms = {False: E.LiveEpoch(model, pool, B, a.repeat, augment=True, seed=0, overlap=False, color_jitter=jitter),
+                 True: E.LiveEpoch(model, pool, B, a.repeat, augment=True, seed=0, overlap=True, color_jitter=jitter)}
         try:
             single = forms[False]
             L = single._lanes[0]
@@ -116,13 +124,33 @@ def main():
             ms_sample = event_ms(sample, 50)
             res["parts_ms_per_micro_batch"] = {"sampler_launch": ms_sample, "sampler_bytes": moved, "sampler_GBps": moved / ms_sample / 1e6,
                                                "expert_replay": event_ms(L["graph"].replay, 10), "step": event_ms(step, 10)}
-            # whole epochs, the two forms alternating
-            rows = {False: [], True: []}
-            for form in (False, True):                                # one unmeasured epoch each: allocator, second lane's first replay
+            if a.color_jitter:
+                jit = single.jitter_table(0)
+                every = jit.copy()
+                every[..., 0] = 1.0
+
+                def jitter_ms(table):
+                    dev = torch.from_numpy(table).cuda()
+
+                    def run():                                        # a fresh sample first: the jitter always sees u8 / 255
+                        b = k[0] % desc.shape[0]
+                        sample()
+                        ops.color_jitter_pairs(L["lr"], L["hr"], table[b], table_dev=dev[b])
+                    return event_ms(run, 50) - ms_sample
+
+                full = 3 * B * p * p * 17 * 4 * 3                     # fp32 read for the sums, read and written by the pixel pass
+                ms_drawn, ms_every = jitter_ms(jit), jitter_ms(every)
+                res["parts_ms_per_micro_batch"].update({"jitter_two_launches_as_drawn": ms_drawn, "jitter_applied_share": float(jit[..., 0].mean()),
+                                                        "jitter_two_launches_every_sample": ms_every, "jitter_bytes_every_sample": full,
+                                                        "jitter_GBps_every_sample": full / ms_every / 1e6,
+                                                        "jitter_note": "sampler + jitter timed together, the sampler's own time subtracted"})
+            # whole epochs, the forms alternating
+            rows = {form: [] for form in forms}
+            for form in forms:                                        # one unmeasured epoch each: allocator, second lane's first replay
                 E.train_epoch(tr, forms[form], 0, a.accum)
             torch.cuda.synchronize()
             for r in range(a.rounds):
-                for form in (False, True):
+                for form in forms:
                     t0 = time.perf_counter()
                     out = E.train_epoch(tr, forms[form], 1 + r, a.accum)
                     torch.cuda.synchronize()
@@ -132,9 +160,10 @@ def main():
                                        "ms_per_micro_batch": 1e3 * wall / out["micro_batches"], "data_wait_share": forms[form].wait_s / wall,
                                        "loss": out["loss"]})
             summ = {}
-            for form, name in ((False, "overlap_off"), (True, "overlap_on")):
+            for form, name in names.items():
                 v = [x["samples_per_s"] for x in rows[form]]
-                summ[name] = {"samples_per_s_median": statistics.median(v), "samples_per_s_spread": max(v) - min(v), "rounds": rows[form]}
+                summ[name] = {"samples_per_s_median": statistics.median(v), "samples_per_s_min": min(v), "samples_per_s_max": max(v),
+                              "samples_per_s_spread": max(v) - min(v), "rounds": rows[form]}
             margin = summ["overlap_on"]["samples_per_s_median"] - summ["overlap_off"]["samples_per_s_median"]
             need = 5 * summ["overlap_off"]["samples_per_s_spread"]
             summ["overlap_margin_samples_per_s"] = margin
