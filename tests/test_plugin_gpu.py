@@ -328,17 +328,26 @@ def test_config4_image_through_the_plugin(tmp_path, dev, hip_model, monkeypatch,
     whole = np.array(Image.open(tmp_path / "whole" / "big_2k.png").convert("RGB"))
     assert whole.shape == (4 * 1356, 4 * 2040, 3)
     lr_t = torch.from_numpy(lr.astype(np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0).to(dev)
-    a = hip_model(lr_t)[0, :, 2000:2512, 3000:3512].clone()
-    assert torch.isfinite(a).all() and a.min().item() >= 0.0 and a.max().item() <= 1.0
+    # the second and third crop lie where element offsets pass 2^31: a 64- or 128-pitch HR tensor wraps at HR row 4112, the pitch-76
+    # and pitch-96 buffers at rows 3462 and 2741 -- one crop straddles row 4112, one is past every wrap row
+    crops = [(2000, 3000), (3900, 7600), (4900, 7600)]
+    full = hip_model(lr_t)
+    got = [full[0, :, y:y + 512, x:x + 512].clone() for y, x in crops]
+    del full
+    for g in got:
+        assert torch.isfinite(g).all() and g.min().item() >= 0.0 and g.max().item() <= 1.0
     ops.set_gemm_mode("f32")
     try:
-        exact = FreqFusionHIP(synth_sd, dev)(lr_t)[0, :, 2000:2512, 3000:3512].clone()
+        full = FreqFusionHIP(synth_sd, dev)(lr_t)
+        exact = [full[0, :, y:y + 512, x:x + 512].clone() for y, x in crops]
+        del full
     finally:
         ops.set_gemm_mode("bf16x3")
-    psnr = O.psnr(a.cpu(), exact.cpu())
-    print("config 4 image, whole: PSNR(bf16x3, f32) on a 512x512 crop =", psnr)
-    assert psnr >= 100.0
-    del exact
+    for (y, x), g, e in zip(crops, got, exact):
+        psnr = O.psnr(g.cpu(), e.cpu())
+        print(f"config 4 image, whole: PSNR(bf16x3, f32) on the 512x512 crop at HR ({y}, {x}) =", psnr)
+        assert psnr >= 100.0
+    del exact, got
     torch.cuda.empty_cache()
 
     # (b) the tile path
