@@ -309,12 +309,8 @@ extern "C" int ff_cab_fused(const void* xn, int ldi, const void* w1_img, long lo
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.ldi = ldi; p.Cmid = Cmid; p.Cout = Cout; p.ldo = ldo; p.ldr = 0;
   p.tiles_x = W / 16; p.tiles_y = H / 16; p.io_bf16 = io_bf16; p.alpha = 1.0f;
   FF_STAMP_ARM(p);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cab_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CAB_LDS);
-    if (e != hipSuccess) { ff_set_error("ff_cab_fused: cannot raise dynamic LDS to %d: %s", (int)CAB_LDS, hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once;
+  if (!ff_raise_lds(once, "ff_cab_fused", CAB_LDS, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &cab_fused_kernel)) return FF_ERR_LAUNCH;
   const long long nblocks = (long long)B * p.tiles_x * p.tiles_y;     // (< 2^31 / (256 * 184) by the offset check)
   hipLaunchKernelGGL(cab_fused_kernel, dim3((unsigned)nblocks), dim3(512), CAB_LDS, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_cab_fused");

@@ -263,13 +263,8 @@ extern "C" int ff_chan_qkv(const float* x, int ldx, long long M, int K, const fl
   p.M = M; p.ldx = ldx; p.ldv = ldv; p.K = K; p.C = 180; p.eps = eps;
   static_assert(CQ_LDS <= 160 * 1024, "LDS image too large");
   static_assert(8 * 32 * FF_XS_ROW * 4 <= 8 * CQ_RED * 4 + 8 * 32 * CQ_TR * 4, "gather patch must fit in the reduction + transpose area");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chan_qkv_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, CQ_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chan_qkv_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, CQ_LDS);
-    if (e != hipSuccess) { ff_set_error("ff_chan_qkv: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once;
+  if (!ff_raise_lds(once, "ff_chan_qkv", CQ_LDS, FF_LDS_SAY_ERR, &chan_qkv_kernel<3>, &chan_qkv_kernel<1>)) return FF_ERR_LAUNCH;
   if (nterms == 3) hipLaunchKernelGGL(chan_qkv_kernel<3>, dim3((unsigned)nblk), dim3(512), CQ_LDS, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(chan_qkv_kernel<1>, dim3((unsigned)nblk), dim3(512), CQ_LDS, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_chan_qkv");

@@ -395,13 +395,9 @@ static int launch_halo(HaloParams& p, hipStream_t st) {
   bool attr_failed = false;
   auto go = [&](auto A) {                      // the activation is a template parameter: one epilogue per kernel
     constexpr int ACT = decltype(A)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<WM, WN, MI, NI, WK, ACT, NSLOT, NTERMS>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { ff_set_error("ff_conv3x3_halo: cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e)); attr_failed = true; return; }
-      attr_set = true;
-    }
+    static ff_device_once once;
+    attr_failed = !ff_raise_lds(once, "ff_conv3x3_halo", lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &conv3x3_halo_kernel<WM, WN, MI, NI, WK, ACT, NSLOT, NTERMS>);
+    if (attr_failed) return;
     hipLaunchKernelGGL((conv3x3_halo_kernel<WM, WN, MI, NI, WK, ACT, NSLOT, NTERMS>), dim3((unsigned)nblocks), dim3(WM * WN * 64), lds, st, p);
   };
   FF_DISPATCH_ACT(p.act, go);

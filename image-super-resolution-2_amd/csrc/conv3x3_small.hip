@@ -81,13 +81,8 @@ extern "C" int ff_conv3x3_small(const float* in, int ldi, const float* w_small, 
   const size_t lds = (size_t)324 * (p.CinP + 4) * 4;
 #define SC_LAUNCH(CTV)                                                                                                      \
   do {                                                                                                                      \
-    static bool attr_set = false;                                                                                           \
-    if (!attr_set) {                                                                                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_small_kernel<CTV>),                         \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 324 * 68 * 4);                         \
-      if (e != hipSuccess) { ff_set_error("ff_conv3x3_small: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
-      attr_set = true;                                                                                                      \
-    }                                                                                                                       \
+    static ff_device_once once;                                                                                             \
+    if (!ff_raise_lds(once, "ff_conv3x3_small", 324 * 68 * 4, FF_LDS_SAY_ERR, &conv3x3_small_kernel<CTV>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL(conv3x3_small_kernel<CTV>, grid, dim3(256), lds, (hipStream_t)stream, p);                            \
   } while (0)
   if (ct == 1) SC_LAUNCH(1); else if (ct == 4) SC_LAUNCH(4); else SC_LAUNCH(16);

@@ -62,66 +62,37 @@ struct ConvBfParams {
 #undef CIG_KMUL_IMAGES
 #undef CIG_W_IMAGES
 
-template <int BM, int BN, int WM, int WN, int NT>
-static int launch_bf_wimg(const ConvBfParams& p, hipStream_t st) {
+// The two per-image forms of the 1x1 GEMM share one launcher and one dispatcher.  WIMG picks the kernel and the entry point's name:
+// per-image weight planes (ff_conv2d_bf16s_wimages) or per-image kmul rows (ff_conv2d_bf16s_kmul_images).
+template <bool WIMG>
+static const char* bf_images_who() { return WIMG ? "ff_conv2d_bf16s_wimages" : "ff_conv2d_bf16s_kmul_images"; }
+
+template <bool WIMG, int BM, int BN, int WM, int WN, int NT>
+static int launch_bf_images(const ConvBfParams& p, hipStream_t st) {
+  const char* const who = bf_images_who<WIMG>();
   const int mt = ff_cdiv(p.M, BM), nt = ff_cdiv(p.Cout, BN);
   constexpr size_t lds = (size_t)2 * (BM + BN) * (32 * 4 + 16);
   static_assert(lds <= 160 * 1024 && lds >= (size_t)WM * WN * 32 * 36 * 4, "LDS budget");
-  static_assert(256 % BM == 0, "an m-tile must not straddle two images of a multiple of 256 rows");
-  if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_bf16_wimg_kernel<BM, BN, WM, WN, true, NT, 32>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { ff_set_error("ff_conv2d_bf16s_wimages: cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-      attr_set = true;
-    }
-  }
-  hipLaunchKernelGGL((conv_igemm_bf16_wimg_kernel<BM, BN, WM, WN, true, NT, 32>), dim3((unsigned)(mt * nt)), dim3(WM * WN * 64), lds, st, p);
-  FF_LAUNCH_CHECK("ff_conv2d_bf16s_wimages");
+  static_assert(!WIMG || 256 % BM == 0, "an m-tile must not straddle two images of a multiple of 256 rows");
+  void (*kernel)(ConvBfParams);
+  if constexpr (WIMG) kernel = &conv_igemm_bf16_wimg_kernel<BM, BN, WM, WN, true, NT, 32>;
+  else kernel = &conv_igemm_bf16_kmimg_kernel<BM, BN, WM, WN, true, NT, 32>;
+  static ff_device_once once;
+  if (lds > 64 * 1024 && !ff_raise_lds(once, who, lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, kernel)) return FF_ERR_LAUNCH;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(mt * nt)), dim3(WM * WN * 64), lds, st, p);
+  FF_LAUNCH_CHECK(who);
   return FF_OK;
 }
 
 // the configurations ff_conv2d_bf16s_tile can name for a 1x1 with 16-byte rows
-template <int NT>
-static int dispatch_bf_wimg(const ConvBfParams& p, int cfg, hipStream_t st) {
+template <bool WIMG, int NT>
+static int dispatch_bf_images(const ConvBfParams& p, int cfg, hipStream_t st) {
   switch (cfg) {
-    case 3: return launch_bf_wimg<256, 32, 4, 1, NT>(p, st);
-    case 4: return launch_bf_wimg<256, 192, 4, 2, NT>(p, st);
-    case 5: return launch_bf_wimg<128, 128, 2, 4, NT>(p, st);
-    case 7: return launch_bf_wimg<128, 64, 4, 2, NT>(p, st);
-    default: ff_set_error("ff_conv2d_bf16s_wimages: tile_hint %d is not one of 3, 4, 5, 7", cfg); return FF_ERR_ARG;
-  }
-}
-
-template <int BM, int BN, int WM, int WN, int NT>
-static int launch_bf_kmimg(const ConvBfParams& p, hipStream_t st) {
-  const int mt = ff_cdiv(p.M, BM), nt = ff_cdiv(p.Cout, BN);
-  constexpr size_t lds = (size_t)2 * (BM + BN) * (32 * 4 + 16);
-  static_assert(lds <= 160 * 1024 && lds >= (size_t)WM * WN * 32 * 36 * 4, "LDS budget");
-  if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_bf16_kmimg_kernel<BM, BN, WM, WN, true, NT, 32>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { ff_set_error("ff_conv2d_bf16s_kmul_images: cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-      attr_set = true;
-    }
-  }
-  hipLaunchKernelGGL((conv_igemm_bf16_kmimg_kernel<BM, BN, WM, WN, true, NT, 32>), dim3((unsigned)(mt * nt)), dim3(WM * WN * 64), lds, st, p);
-  FF_LAUNCH_CHECK("ff_conv2d_bf16s_kmul_images");
-  return FF_OK;
-}
-
-// the configurations ff_conv2d_bf16s_tile can name for a 1x1 with 16-byte rows
-template <int NT>
-static int dispatch_bf_kmimg(const ConvBfParams& p, int cfg, hipStream_t st) {
-  switch (cfg) {
-    case 3: return launch_bf_kmimg<256, 32, 4, 1, NT>(p, st);
-    case 4: return launch_bf_kmimg<256, 192, 4, 2, NT>(p, st);
-    case 5: return launch_bf_kmimg<128, 128, 2, 4, NT>(p, st);
-    case 7: return launch_bf_kmimg<128, 64, 4, 2, NT>(p, st);
-    default: ff_set_error("ff_conv2d_bf16s_kmul_images: tile_hint %d is not one of 3, 4, 5, 7", cfg); return FF_ERR_ARG;
+    case 3: return launch_bf_images<WIMG, 256, 32, 4, 1, NT>(p, st);
+    case 4: return launch_bf_images<WIMG, 256, 192, 4, 2, NT>(p, st);
+    case 5: return launch_bf_images<WIMG, 128, 128, 2, 4, NT>(p, st);
+    case 7: return launch_bf_images<WIMG, 128, 64, 4, 2, NT>(p, st);
+    default: ff_set_error("%s: tile_hint %d is not one of 3, 4, 5, 7", bf_images_who<WIMG>(), cfg); return FF_ERR_ARG;
   }
 }
 
@@ -131,17 +102,10 @@ static int launch_bf(const ConvBfParams& p, bool vec4, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * (BM + BN) * (BKB * 4 + 16);
   static_assert(lds <= 160 * 1024 && lds >= (size_t)WM * WN * 32 * 36 * 4, "LDS budget (staging ring; the epilogue patch reuses it)");
   dim3 grid((unsigned)(mt * nt)), block(WM * WN * 64);
-  if (lds > 64 * 1024) {
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[vec4 ? 1 : 0]) {
-      hipError_t e = vec4 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_bf16_kernel<BM, BN, WM, WN, true, NT, BKB>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                          : hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_bf16_kernel<BM, BN, WM, WN, false, NT, BKB>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { ff_set_error("ff_conv2d_bf16s: cannot raise dynamic LDS to %zu: %s", lds, hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-      attr_set[vec4 ? 1 : 0] = true;
-    }
-  }
+  static ff_device_once once[2];       // [vec4]
+  if (lds > 64 * 1024 && !(vec4 ? ff_raise_lds(once[1], "ff_conv2d_bf16s", lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &conv_igemm_bf16_kernel<BM, BN, WM, WN, true, NT, BKB>)
+                                : ff_raise_lds(once[0], "ff_conv2d_bf16s", lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &conv_igemm_bf16_kernel<BM, BN, WM, WN, false, NT, BKB>)))
+    return FF_ERR_LAUNCH;
   if (vec4)
     hipLaunchKernelGGL((conv_igemm_bf16_kernel<BM, BN, WM, WN, true, NT, BKB>), grid, block, lds, st, p);
   else
@@ -229,38 +193,50 @@ extern "C" int ff_conv2d_bf16s(const float* in, const void* w_hi, const void* w_
   }
 }
 
+// The body of the two per-image 1x1 entry points below, after their own checks of B, rows_per_image and M: the checks they share (the two
+// whose wording differs pick it by form), the params fill and the dispatch.  kmul is [B][Cin] (WIMG: nullptr), w_hi / w_lo [B][Cout][Kp] if WIMG.
+template <bool WIMG>
+static int conv2d_bf16s_images_launch(const float* in, int ldi, const void* w_hi, const void* w_lo, int Kp, int Cp, const float* kmul, int B,
+                                      int rows_per_image, const float* bias, const float* mul, const float* res, int ldr, float* out, int ldo,
+                                      long long M, int Cin, int Cout, int nterms, int tile_hint, void* stream) {
+  const char* const who = bf_images_who<WIMG>();
+  FF_CHECK_ARG(in && w_hi && out && (WIMG || kmul), "%s: null pointer", who);
+  FF_CHECK_ARG(nterms >= 1 && nterms <= 3 && (nterms < 3 || w_lo), "%s: nterms must be 1..3 (3 needs w_lo)", who);
+  FF_CHECK_ARG(Cin > 0 && Cout > 0 && Cin % 4 == 0 && ldi >= Cin && ldi % 4 == 0 && (((uintptr_t)in) & 15) == 0 && (((uintptr_t)kmul) & 15) == 0,
+               WIMG ? "%s: needs Cin %% 4 == 0 and 16-byte aligned input rows (ldi %% 4 == 0)"
+                    : "%s: needs Cin %% 4 == 0, 16-byte aligned input rows (ldi %% 4 == 0) and kmul", who);
+  FF_CHECK_ARG(Kp % 32 == 0 && Kp >= Cin && (Cp == 0 || (Cp % 32 == 0 && Cp >= Cin && Kp == Cp)), "%s: Kp must be Cin rounded up to 32 (TAP layout: Kp == Cp)", who);
+  FF_CHECK_ARG((((uintptr_t)w_hi) & 15) == 0 && (!w_lo || (((uintptr_t)w_lo) & 15) == 0) && (!WIMG || ((long long)Cout * Kp) % 8 == 0),
+               WIMG ? "%s: every image's weight planes must be 16-byte aligned" : "%s: weight planes must be 16-byte aligned", who);
+  FF_CHECK_ARG(Cout % 4 == 0 && ldo >= Cout && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!res || (ldr >= Cout && ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)),
+               "%s: needs Cout %% 4 == 0 and 16-byte aligned output / residual rows", who);
+  ConvBfParams p{};
+  p.in = in; p.w_hi = (const __bf16*)w_hi; p.w_lo = (const __bf16*)w_lo; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
+  p.kmul = kmul;
+  p.B = B; p.H = 1; p.W = rows_per_image; p.Cin = Cin; p.ldi = ldi;
+  p.Ho = 1; p.Wo = rows_per_image; p.Cout = Cout; p.ldo = ldo; p.ldr = ldr;
+  p.KH = 1; p.KW = 1; p.sy = 1; p.sx = 1;
+  p.K = Cin; p.Kp = Kp; p.Cp = Cp; p.M = (int)M;
+  p.alpha = 1.f; p.vec_out = 1;
+  hipStream_t st = (hipStream_t)stream;
+  int cfg = tile_hint;
+  if (cfg <= 0) cfg = ff_conv2d_bf16s_tile(rows_per_image, Cout, Cin, 1);
+  switch (nterms) {
+    case 1: return dispatch_bf_images<WIMG, 1>(p, cfg, st);
+    case 2: return dispatch_bf_images<WIMG, 2>(p, cfg, st);
+    default: return dispatch_bf_images<WIMG, 3>(p, cfg, st);
+  }
+}
+
 // conv3 of B independent images in one launch (1x1): in is fp32 [M][ldi] rows, M == B * rows_per_image, kmul is [B][Cin] and row m is
 // scaled by kmul[m / rows_per_image] before the split.  Epilogue: (acc + bias) * mul + res, the 16-byte form.  Every row is bit-equal to
 // ff_conv2d_bf16s(1x1, kmul = kmul[b]) on its image alone; tile_hint <= 0 takes ff_conv2d_bf16s_tile of ONE image's rows.
 extern "C" int ff_conv2d_bf16s_kmul_images(const float* in, int ldi, const void* w_hi, const void* w_lo, int Kp, int Cp, const float* kmul,
                                            int B, int rows_per_image, const float* bias, const float* mul, const float* res, int ldr,
                                            float* out, int ldo, long long M, int Cin, int Cout, int nterms, int tile_hint, void* stream) {
-  FF_CHECK_ARG(in && w_hi && kmul && out, "ff_conv2d_bf16s_kmul_images: null pointer");
   FF_CHECK_ARG(B >= 1 && rows_per_image >= 1 && M == (long long)B * rows_per_image && M < (1LL << 31),
                "ff_conv2d_bf16s_kmul_images: M must be B * rows_per_image and below 2^31 (got M=%lld B=%d rows_per_image=%d)", M, B, rows_per_image);
-  FF_CHECK_ARG(nterms >= 1 && nterms <= 3 && (nterms < 3 || w_lo), "ff_conv2d_bf16s_kmul_images: nterms must be 1..3 (3 needs w_lo)");
-  FF_CHECK_ARG(Cin > 0 && Cout > 0 && Cin % 4 == 0 && ldi >= Cin && ldi % 4 == 0 && (((uintptr_t)in) & 15) == 0 && (((uintptr_t)kmul) & 15) == 0,
-               "ff_conv2d_bf16s_kmul_images: needs Cin %% 4 == 0, 16-byte aligned input rows (ldi %% 4 == 0) and kmul");
-  FF_CHECK_ARG(Kp % 32 == 0 && Kp >= Cin && (Cp == 0 || (Cp % 32 == 0 && Cp >= Cin && Kp == Cp)), "ff_conv2d_bf16s_kmul_images: Kp must be Cin rounded up to 32 (TAP layout: Kp == Cp)");
-  FF_CHECK_ARG((((uintptr_t)w_hi) & 15) == 0 && (!w_lo || (((uintptr_t)w_lo) & 15) == 0), "ff_conv2d_bf16s_kmul_images: weight planes must be 16-byte aligned");
-  FF_CHECK_ARG(Cout % 4 == 0 && ldo >= Cout && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!res || (ldr >= Cout && ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)),
-               "ff_conv2d_bf16s_kmul_images: needs Cout %% 4 == 0 and 16-byte aligned output / residual rows");
-  ConvBfParams p;
-  p.in = in; p.w_hi = (const __bf16*)w_hi; p.w_lo = (const __bf16*)w_lo; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
-  p.kmul = kmul; p.gate = 0;
-  p.B = B; p.H = 1; p.W = rows_per_image; p.Cin = Cin; p.ldi = ldi;
-  p.Ho = 1; p.Wo = rows_per_image; p.Cout = Cout; p.ldo = ldo; p.ldr = ldr;
-  p.KH = 1; p.KW = 1; p.sy = 1; p.sx = 1; p.py = 0; p.px = 0;
-  p.K = Cin; p.Kp = Kp; p.Cp = Cp; p.M = (int)M;
-  p.act = 0; p.alpha = 1.f; p.shuffle = 0; p.vec_out = 1;
-  hipStream_t st = (hipStream_t)stream;
-  int cfg = tile_hint;
-  if (cfg <= 0) cfg = ff_conv2d_bf16s_tile(rows_per_image, Cout, Cin, 1);
-  switch (nterms) {
-    case 1: return dispatch_bf_kmimg<1>(p, cfg, st);
-    case 2: return dispatch_bf_kmimg<2>(p, cfg, st);
-    default: return dispatch_bf_kmimg<3>(p, cfg, st);
-  }
+  return conv2d_bf16s_images_launch<false>(in, ldi, w_hi, w_lo, Kp, Cp, kmul, B, rows_per_image, bias, mul, res, ldr, out, ldo, M, Cin, Cout, nterms, tile_hint, stream);
 }
 
 // A 1x1 GEMM whose rows are B equal groups, each multiplied by its OWN weight planes: in is fp32 [M][ldi] rows, M == B * rows_per_image,
@@ -274,31 +250,7 @@ extern "C" int ff_conv2d_bf16s_wimages(const float* in, int ldi, const void* w_h
   FF_CHECK_ARG(B >= 1 && rows_per_image >= 1 && rows_per_image % 256 == 0 && M == (long long)B * rows_per_image && M < (1LL << 31),
                "ff_conv2d_bf16s_wimages: rows_per_image must be a positive multiple of 256, M == B * rows_per_image and below 2^31 (got M=%lld B=%d rows_per_image=%d)",
                M, B, rows_per_image);
-  FF_CHECK_ARG(in && w_hi && out, "ff_conv2d_bf16s_wimages: null pointer");
-  FF_CHECK_ARG(nterms >= 1 && nterms <= 3 && (nterms < 3 || w_lo), "ff_conv2d_bf16s_wimages: nterms must be 1..3 (3 needs w_lo)");
-  FF_CHECK_ARG(Cin > 0 && Cout > 0 && Cin % 4 == 0 && ldi >= Cin && ldi % 4 == 0 && (((uintptr_t)in) & 15) == 0,
-               "ff_conv2d_bf16s_wimages: needs Cin %% 4 == 0 and 16-byte aligned input rows (ldi %% 4 == 0)");
-  FF_CHECK_ARG(Kp % 32 == 0 && Kp >= Cin && (Cp == 0 || (Cp % 32 == 0 && Cp >= Cin && Kp == Cp)), "ff_conv2d_bf16s_wimages: Kp must be Cin rounded up to 32 (TAP layout: Kp == Cp)");
-  FF_CHECK_ARG((((uintptr_t)w_hi) & 15) == 0 && (!w_lo || (((uintptr_t)w_lo) & 15) == 0) && ((long long)Cout * Kp) % 8 == 0,
-               "ff_conv2d_bf16s_wimages: every image's weight planes must be 16-byte aligned");
-  FF_CHECK_ARG(Cout % 4 == 0 && ldo >= Cout && ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!res || (ldr >= Cout && ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)),
-               "ff_conv2d_bf16s_wimages: needs Cout %% 4 == 0 and 16-byte aligned output / residual rows");
-  ConvBfParams p;
-  p.in = in; p.w_hi = (const __bf16*)w_hi; p.w_lo = (const __bf16*)w_lo; p.bias = bias; p.mul = mul; p.res = res; p.out = out;
-  p.kmul = nullptr; p.gate = 0;
-  p.B = B; p.H = 1; p.W = rows_per_image; p.Cin = Cin; p.ldi = ldi;
-  p.Ho = 1; p.Wo = rows_per_image; p.Cout = Cout; p.ldo = ldo; p.ldr = ldr;
-  p.KH = 1; p.KW = 1; p.sy = 1; p.sx = 1; p.py = 0; p.px = 0;
-  p.K = Cin; p.Kp = Kp; p.Cp = Cp; p.M = (int)M;
-  p.act = 0; p.alpha = 1.f; p.shuffle = 0; p.vec_out = 1;
-  hipStream_t st = (hipStream_t)stream;
-  int cfg = tile_hint;
-  if (cfg <= 0) cfg = ff_conv2d_bf16s_tile(rows_per_image, Cout, Cin, 1);
-  switch (nterms) {
-    case 1: return dispatch_bf_wimg<1>(p, cfg, st);
-    case 2: return dispatch_bf_wimg<2>(p, cfg, st);
-    default: return dispatch_bf_wimg<3>(p, cfg, st);
-  }
+  return conv2d_bf16s_images_launch<true>(in, ldi, w_hi, w_lo, Kp, Cp, nullptr, B, rows_per_image, bias, mul, res, ldr, out, ldo, M, Cin, Cout, nterms, tile_hint, stream);
 }
 
 // fp32 [N][K] -> bf16 planes hi/lo [N][Kp], zero filled; lo may be NULL.

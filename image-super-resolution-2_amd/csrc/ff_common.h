@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include "ff_device_once.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -34,6 +35,28 @@ void ff_set_error(const char* fmt, ...);
       return FF_ERR_LAUNCH;                                                \
     }                                                                      \
   } while (0)
+
+// ---- dynamic LDS above the 64 KB default ----------------------------------------------------------------------------------------
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to a (kernel, device) pair.  A launch site keeps one `static ff_device_once` -- one
+// per instantiation where the site is a template or a launch macro -- and raises its kernel(s) through it before the launch: once per
+// device, from any thread (two first callers may both set the attribute, which is harmless).  On failure the error text is
+// "<who>: cannot raise dynamic LDS[ to <bytes>][: <hip error>]", `say` picking the parts (every entry point keeps the wording it always
+// had), and the site returns FF_ERR_LAUNCH.
+enum { FF_LDS_SAY_ERR = 1, FF_LDS_SAY_SIZE = 2 };
+template <class... Kernel>
+static inline bool ff_raise_lds(ff_device_once& once, const char* who, size_t bytes, int say, Kernel*... kernels) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) { ff_set_error("%s: cannot identify the device: %s", who, hipGetErrorString(e)); return false; }
+  return once.run(dev, [&] {
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)), ...);
+    if (e == hipSuccess) return true;
+    char to[32] = "";
+    if (say & FF_LDS_SAY_SIZE) snprintf(to, sizeof to, " to %zu", bytes);
+    ff_set_error("%s: cannot raise dynamic LDS%s%s%s", who, to, (say & FF_LDS_SAY_ERR) ? ": " : "", (say & FF_LDS_SAY_ERR) ? hipGetErrorString(e) : "");
+    return false;
+  });
+}
 
 // ---- phase stamps: a debug aid of tools/*_time.cpp, compiled in with -DFF_TIMING only -------------------------------------------
 // A kernel's params struct carries FF_STAMP_MEMBER, its entry point says FF_STAMP_ARM(p), and lane 0 of every wave writes

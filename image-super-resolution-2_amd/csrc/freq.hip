@@ -284,36 +284,49 @@ __global__ __launch_bounds__(256) void irdft_rows_bands_images_kernel(const floa
   irdft_rows_bands_body<true>(U, x, C, H, W, tc, ts, bscale, out, ldo, ch_lo, ch_hi);
 }
 
-extern "C" int ff_fft_bands(const float* x, int C, int H, int W, const float* twW_cos, const float* twW_sin,
-                            const float* twH_cos, const float* twH_sin, const float* mask_logits, int msz, float temp,
-                            const float* band_scale2, float* work, long long work_floats, float* out, int ldo, int ch_lo,
-                            int ch_hi, void* stream) {
-  FF_CHECK_ARG(x && twW_cos && twW_sin && twH_cos && twH_sin && mask_logits && band_scale2 && work && out, "ff_fft_bands: null pointer");
-  FF_CHECK_ARG(C > 0 && H > 1 && W > 1 && W <= 8192 && H <= 8192, "ff_fft_bands: bad dims");
+// The four launches of both entry points over C planes: ff_fft_bands (one image) and, with images set, ff_fft_bands_images (C = 3 B).
+// The column decomposition (CB, ksplit, KH) is sized for split_planes planes: C, or ONE image's 3, so that image b's workgroups are those
+// of its own launch.  Every output bin is summed by one thread in a fixed order whatever the split, so this is a safeguard, not a fix.
+static int fft_bands_launch(const char* who, const float* x, int C, int split_planes, bool images, int H, int W, const float* twW_cos,
+                            const float* twW_sin, const float* twH_cos, const float* twH_sin, const float* mask_logits, int msz, float temp,
+                            const float* band_scale2, float* work, long long work_floats, float* out, int ldo, int ch_lo, int ch_hi, void* stream) {
+  FF_CHECK_ARG(x && twW_cos && twW_sin && twH_cos && twH_sin && mask_logits && band_scale2 && work && out, "%s: null pointer", who);
+  FF_CHECK_ARG(C > 0 && H > 1 && W > 1 && W <= 8192 && H <= 8192, "%s: bad dims", who);
   const int Wf = W / 2 + 1;
   const long long spec = (long long)C * H * Wf * 2;
-  FF_CHECK_ARG(work_floats >= 2 * spec, "ff_fft_bands: workspace too small (need %lld floats)", 2 * spec);
+  FF_CHECK_ARG(work_floats >= 2 * spec, "%s: workspace too small (need %lld floats)", who, 2 * spec);
+  const int CB = H <= 512 ? 16 : 4;
+  const size_t clds = (size_t)H * CB * 8 + (size_t)H * 8;
+  FF_CHECK_ARG(clds <= 64 * 1024, "%s: H too large for the column tile", who);
   float* Y = work;
   float* Z = work + spec;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), (size_t)W * 12, st, x, C * H, W, twW_cos, twW_sin, Y);
-  const int CB = H <= 512 ? 16 : 4;
-  const size_t clds = (size_t)H * CB * 8 + (size_t)H * 8;
-  FF_CHECK_ARG(clds <= 64 * 1024, "ff_fft_bands: H too large for the column tile");
   // split the output rows of a column block over workgroups until the grid has a few per CU
   const int ncb = (Wf + CB - 1) / CB;
   int ksplit = 1;
-  while (ncb * C * ksplit < 512 && (H + ksplit - 1) / ksplit > 256 / CB) ksplit *= 2;
+  while (ncb * split_planes * ksplit < 512 && (H + ksplit - 1) / ksplit > 256 / CB) ksplit *= 2;
   const int KH = (H + ksplit - 1) / ksplit;
   dim3 gc(ncb, C, (H + KH - 1) / KH);
   hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Y, H, Wf, CB, KH, -1.f, twH_cos, twH_sin, mask_logits,
                      msz, temp, Z);
   hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Z, H, Wf, CB, KH, 1.f, twH_cos, twH_sin,
                      (const float*)nullptr, 0, 0.f, Y);
-  hipLaunchKernelGGL(irdft_rows_bands_kernel, dim3(C * H), dim3(256), (size_t)Wf * 8 + (size_t)W * 8, st, Y, x, C, H, W, twW_cos, twW_sin,
-                     band_scale2, out, ldo, ch_lo, ch_hi);
-  FF_LAUNCH_CHECK("ff_fft_bands");
+  const size_t rlds = (size_t)Wf * 8 + (size_t)W * 8;
+  if (images)
+    hipLaunchKernelGGL(irdft_rows_bands_images_kernel, dim3(C * H), dim3(256), rlds, st, Y, x, C, H, W, twW_cos, twW_sin, band_scale2, out, ldo, ch_lo, ch_hi);
+  else
+    hipLaunchKernelGGL(irdft_rows_bands_kernel, dim3(C * H), dim3(256), rlds, st, Y, x, C, H, W, twW_cos, twW_sin, band_scale2, out, ldo, ch_lo, ch_hi);
+  FF_LAUNCH_CHECK(who);
   return FF_OK;
+}
+
+extern "C" int ff_fft_bands(const float* x, int C, int H, int W, const float* twW_cos, const float* twW_sin,
+                            const float* twH_cos, const float* twH_sin, const float* mask_logits, int msz, float temp,
+                            const float* band_scale2, float* work, long long work_floats, float* out, int ldo, int ch_lo,
+                            int ch_hi, void* stream) {
+  return fft_bands_launch("ff_fft_bands", x, C, C, false, H, W, twW_cos, twW_sin, twH_cos, twH_sin, mask_logits, msz, temp, band_scale2, work,
+                          work_floats, out, ldo, ch_lo, ch_hi, stream);
 }
 
 // B images in one run of the same four kernels over 3 B planes: x [B][3][H][W] -> out [B][H][W][ldo].  The planes index gridDim.y of the
@@ -331,33 +344,10 @@ extern "C" int ff_fft_bands_images(const float* x, int B, int H, int W, const fl
                                    int ch_hi, void* stream) {
   FF_CHECK_ARG(fft_bands_images_geometry(B, H, W),
                "ff_fft_bands_images: expects 1 <= B <= 21845 images with 2 <= W <= 8192 and 2 <= H <= 481 or 513 <= H <= 1638 (got B=%d H=%d W=%d)", B, H, W);
-  FF_CHECK_ARG(x && twW_cos && twW_sin && twH_cos && twH_sin && mask_logits && band_scale2 && work && out, "ff_fft_bands_images: null pointer");
-  const int C = 3 * B, Wf = W / 2 + 1;
-  const long long spec = (long long)C * H * Wf * 2;
-  FF_CHECK_ARG(work_floats >= 2 * spec, "ff_fft_bands_images: workspace too small (need %lld floats)", 2 * spec);
   FF_CHECK_ARG(msz > 0 && ch_lo >= 0 && ch_hi >= 0 && ldo >= ch_lo + 3 && ldo >= ch_hi + 3,
                "ff_fft_bands_images: ldo %d is smaller than the channels written (%d + 3, %d + 3)", ldo, ch_lo, ch_hi);
-  float* Y = work;
-  float* Z = work + spec;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), (size_t)W * 12, st, x, C * H, W, twW_cos, twW_sin, Y);
-  // The column decomposition (CB, ksplit, KH) is taken from ONE image's plane count, 3, so image b's workgroups are those of its own launch.
-  // Every output bin is summed by one thread in a fixed order whatever the split, so this is a safeguard, not a fix.
-  const int CB = H <= 512 ? 16 : 4;
-  const size_t clds = (size_t)H * CB * 8 + (size_t)H * 8;
-  const int ncb = (Wf + CB - 1) / CB;
-  int ksplit = 1;
-  while (ncb * 3 * ksplit < 512 && (H + ksplit - 1) / ksplit > 256 / CB) ksplit *= 2;
-  const int KH = (H + ksplit - 1) / ksplit;
-  dim3 gc(ncb, C, (H + KH - 1) / KH);
-  hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Y, H, Wf, CB, KH, -1.f, twH_cos, twH_sin, mask_logits,
-                     msz, temp, Z);
-  hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Z, H, Wf, CB, KH, 1.f, twH_cos, twH_sin,
-                     (const float*)nullptr, 0, 0.f, Y);
-  hipLaunchKernelGGL(irdft_rows_bands_images_kernel, dim3(C * H), dim3(256), (size_t)Wf * 8 + (size_t)W * 8, st, Y, x, C, H, W, twW_cos,
-                     twW_sin, band_scale2, out, ldo, ch_lo, ch_hi);
-  FF_LAUNCH_CHECK("ff_fft_bands_images");
-  return FF_OK;
+  return fft_bands_launch("ff_fft_bands_images", x, 3 * B, 3, true, H, W, twW_cos, twW_sin, twH_cos, twH_sin, mask_logits, msz, temp, band_scale2, work,
+                          work_floats, out, ldo, ch_lo, ch_hi, stream);
 }
 
 // ------------------------------------------------------------------------------------------ plain rfft2 / irfft2 ('ortho')

@@ -364,9 +364,6 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   FF_STAMP_DRAINED(128, 64 + 61);
 }
 
-// One device's "dynamic LDS raised" flags: hipFuncSetAttribute is per device, so the guard is too.
-static bool g_hl_attr[64];
-
 extern "C" int ff_hab_link(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
                            int scale_ld, int B, long long rows_per_image, float* x_out, int ldxo, long long M, int K, int hidden_tiles,
                            const void* proj_tiles, const float* proj_bias_padded, const float* gamma2, const float* beta2, float eps2,
@@ -419,14 +416,8 @@ extern "C" int ff_hab_link(const float* att, int lda, const float* x, int ldx, c
   FF_STAMP_ARM(p);
   const long long nblk = (long long)B * p.nwx * p.nwy;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_hab_link: grid too large");
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess || dev < 0 || dev >= 64) { ff_set_error("ff_hab_link: cannot identify the device: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-  if (!g_hl_attr[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hab_link_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, HL_LDS);
-    if (e != hipSuccess) { ff_set_error("ff_hab_link: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    g_hl_attr[dev] = true;
-  }
+  static ff_device_once once;
+  if (!ff_raise_lds(once, "ff_hab_link", HL_LDS, FF_LDS_SAY_ERR, &hab_link_kernel)) return FF_ERR_LAUNCH;
   hipLaunchKernelGGL(hab_link_kernel, dim3((unsigned)nblk), dim3(512), HL_LDS, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_hab_link");
   return FF_OK;

@@ -47,47 +47,61 @@ extern "C" long long ff_naf_front_workspace(int H, int W, int C) {
   return (long long)((H + NF_TY - 1) / NF_TY) * ((W + NF_TX - 1) / NF_TX) * C;
 }
 
-extern "C" int ff_naf_front(const float* x, int ldx, int H, int W, int C, const float* ln_gamma, const float* ln_beta, float eps,
+extern "C" long long ff_naf_front_images_workspace(int B, int H, int W, int C) {
+  const long long one = ff_naf_front_workspace(H, W, C);
+  if (B < 1 || one < 0) return -1;
+  return (long long)B * one;
+}
+
+// The body of both entry points: B == 0 is ff_naf_front (one image, a grid of tiles), B >= 1 ff_naf_front_images (grid (tiles, B)).
+static int naf_front_launch(const char* who, const float* x, int ldx, int B, int H, int W, int C, const float* ln_gamma, const float* ln_beta, float eps,
                             const void* w1_tiles, const float* b1, const float* dw_tapmajor, const float* dw_bias, float* out, int ldo,
                             float* pooled, float* work, long long work_floats, int nterms, void* stream) {
-  FF_CHECK_ARG(nterms == 1 || nterms == 3, "ff_naf_front: nterms must be 1 or 3");
-  FF_CHECK_ARG(x && ln_gamma && ln_beta && w1_tiles && b1 && dw_tapmajor && dw_bias && out && pooled && work, "ff_naf_front: null pointer");
-  FF_CHECK_ARG(C == 64 || C == 128, "ff_naf_front: built for 64 / 128 channels (got %d)", C);
-  FF_CHECK_ARG(H > 0 && W > 0 && ldx >= C && ldx % 4 == 0 && ldo >= C && ldo % 4 == 0, "ff_naf_front: bad dims");
+  FF_CHECK_ARG(nterms == 1 || nterms == 3, "%s: nterms must be 1 or 3", who);
+  FF_CHECK_ARG(x && ln_gamma && ln_beta && w1_tiles && b1 && dw_tapmajor && dw_bias && out && pooled && work, "%s: null pointer", who);
+  FF_CHECK_ARG(C == 64 || C == 128, "%s: built for 64 / 128 channels (got %d)", who, C);
+  FF_CHECK_ARG(H > 0 && W > 0 && ldx >= C && ldx % 4 == 0 && ldo >= C && ldo % 4 == 0, "%s: bad dims", who);
   FF_CHECK_ARG((((uintptr_t)x) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)w1_tiles) & 15) == 0 && (((uintptr_t)b1) & 15) == 0 &&
                (((uintptr_t)dw_tapmajor) & 15) == 0 && (((uintptr_t)dw_bias) & 15) == 0 && (((uintptr_t)ln_gamma) & 15) == 0 && (((uintptr_t)ln_beta) & 15) == 0,
-               "ff_naf_front: 16-byte alignment required");
-  FF_CHECK_ARG((long long)(NF_TY + 2) * W * ldx < (1LL << 31), "ff_naf_front: row too long for the 32-bit offsets inside a tile");
+               "%s: 16-byte alignment required", who);
+  FF_CHECK_ARG((long long)(NF_TY + 2) * W * ldx < (1LL << 31), "%s: row too long for the 32-bit offsets inside a tile", who);
   NafFrontParams p;
   p.x = x; p.ldx = ldx; p.gamma = ln_gamma; p.beta = ln_beta; p.eps = eps; p.w1 = (const __bf16*)w1_tiles; p.b1 = b1;
   p.wdw = dw_tapmajor; p.bdw = dw_bias; p.out = out; p.ldo = ldo; p.part = work; p.H = H; p.W = W; p.C = C;
   p.tiles_x = (W + NF_TX - 1) / NF_TX; p.tiles_y = (H + NF_TY - 1) / NF_TY;
   const long long nb = (long long)p.tiles_x * p.tiles_y;
-  FF_CHECK_ARG(nb < (1LL << 31) && work_floats >= nb * C, "ff_naf_front: workspace too small (ff_naf_front_workspace)");
+  FF_CHECK_ARG(nb < (1LL << 31) && work_floats >= (B ? B : 1) * nb * C, "%s: workspace too small (%s_workspace)", who, who);
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)NF_MT * 32 * NF_TS * 4 + (size_t)2 * 32 * (4 * C + 16) + 8 * 8 * 4 * 4 + (size_t)11 * 2 * C * 4;
-#define NF_LAUNCH(KSV, NTM)                                                                                                  \
+  const float inv_hw = 1.0f / ((float)H * (float)W);
+#define NF_LAUNCH(KERNEL, GRID, KSV, NTM)                                                                                    \
   do {                                                                                                                       \
-    static bool attr_set = false;                                                                                            \
-    if (!attr_set) {                                                                                                         \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&naf_front_kernel<KSV, NTM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        ff_set_error("ff_naf_front: cannot raise dynamic LDS to %zu", lds); return FF_ERR_LAUNCH; }                          \
-      attr_set = true;                                                                                                       \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((naf_front_kernel<KSV, NTM>), dim3((unsigned)nb), dim3(512), lds, st, p);                             \
+    static ff_device_once once;                                                                                              \
+    if (!ff_raise_lds(once, who, lds, FF_LDS_SAY_SIZE, &KERNEL<KSV, NTM>)) return FF_ERR_LAUNCH;                             \
+    hipLaunchKernelGGL((KERNEL<KSV, NTM>), GRID, dim3(512), lds, st, p);                                                     \
   } while (0)
-  if (C == 64) { if (nterms == 3) NF_LAUNCH(4, 3); else NF_LAUNCH(4, 1); }
-  else { if (nterms == 3) NF_LAUNCH(8, 3); else NF_LAUNCH(8, 1); }
+#define NF_LAUNCH_C(KERNEL, GRID)                                                                                            \
+  do {                                                                                                                       \
+    if (C == 64) { if (nterms == 3) NF_LAUNCH(KERNEL, GRID, 4, 3); else NF_LAUNCH(KERNEL, GRID, 4, 1); }                     \
+    else { if (nterms == 3) NF_LAUNCH(KERNEL, GRID, 8, 3); else NF_LAUNCH(KERNEL, GRID, 8, 1); }                             \
+  } while (0)
+  if (!B) {
+    NF_LAUNCH_C(naf_front_kernel, dim3((unsigned)nb));
+    hipLaunchKernelGGL(pool_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, work, (int)nb, C, inv_hw, pooled);
+  } else {
+    NF_LAUNCH_C(naf_front_images_kernel, dim3((unsigned)nb, (unsigned)B));
+    hipLaunchKernelGGL(pool_reduce_images_kernel, dim3((C + 15) / 16, (unsigned)B), dim3(256), 0, st, work, (int)nb, C, inv_hw, pooled);
+  }
+#undef NF_LAUNCH_C
 #undef NF_LAUNCH
-  hipLaunchKernelGGL(pool_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, work, (int)nb, C, 1.0f / ((float)H * (float)W), pooled);
-  FF_LAUNCH_CHECK("ff_naf_front");
+  FF_LAUNCH_CHECK(who);
   return FF_OK;
 }
 
-extern "C" long long ff_naf_front_images_workspace(int B, int H, int W, int C) {
-  const long long one = ff_naf_front_workspace(H, W, C);
-  if (B < 1 || one < 0) return -1;
-  return (long long)B * one;
+extern "C" int ff_naf_front(const float* x, int ldx, int H, int W, int C, const float* ln_gamma, const float* ln_beta, float eps,
+                            const void* w1_tiles, const float* b1, const float* dw_tapmajor, const float* dw_bias, float* out, int ldo,
+                            float* pooled, float* work, long long work_floats, int nterms, void* stream) {
+  return naf_front_launch("ff_naf_front", x, ldx, 0, H, W, C, ln_gamma, ln_beta, eps, w1_tiles, b1, dw_tapmajor, dw_bias, out, ldo, pooled, work, work_floats, nterms, stream);
 }
 
 // B independent images x [B][H][W] (image stride H * W * ldx) in one launch: image b comes out with the bits of ff_naf_front on it alone.
@@ -95,37 +109,7 @@ extern "C" long long ff_naf_front_images_workspace(int B, int H, int W, int C) {
 extern "C" int ff_naf_front_images(const float* x, int ldx, int B, int H, int W, int C, const float* ln_gamma, const float* ln_beta, float eps,
                                    const void* w1_tiles, const float* b1, const float* dw_tapmajor, const float* dw_bias, float* out, int ldo,
                                    float* pooled, float* work, long long work_floats, int nterms, void* stream) {
-  FF_CHECK_ARG(x && ln_gamma && ln_beta && w1_tiles && b1 && dw_tapmajor && dw_bias && out && pooled && work, "ff_naf_front_images: null pointer");
-  FF_CHECK_ARG(nterms == 1 || nterms == 3, "ff_naf_front_images: nterms must be 1 or 3");
   FF_CHECK_ARG(B >= 1 && B <= 65535, "ff_naf_front_images: B must be 1 .. 65535 (got %d)", B);
-  FF_CHECK_ARG(C == 64 || C == 128, "ff_naf_front_images: built for 64 / 128 channels (got %d)", C);
-  FF_CHECK_ARG(H > 0 && W > 0 && ldx >= C && ldx % 4 == 0 && ldo >= C && ldo % 4 == 0, "ff_naf_front_images: bad dims");
-  FF_CHECK_ARG((((uintptr_t)x) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)w1_tiles) & 15) == 0 && (((uintptr_t)b1) & 15) == 0 &&
-               (((uintptr_t)dw_tapmajor) & 15) == 0 && (((uintptr_t)dw_bias) & 15) == 0 && (((uintptr_t)ln_gamma) & 15) == 0 && (((uintptr_t)ln_beta) & 15) == 0,
-               "ff_naf_front_images: 16-byte alignment required");
-  FF_CHECK_ARG((long long)(NF_TY + 2) * W * ldx < (1LL << 31), "ff_naf_front_images: row too long for the 32-bit offsets inside a tile");
-  NafFrontParams p;
-  p.x = x; p.ldx = ldx; p.gamma = ln_gamma; p.beta = ln_beta; p.eps = eps; p.w1 = (const __bf16*)w1_tiles; p.b1 = b1;
-  p.wdw = dw_tapmajor; p.bdw = dw_bias; p.out = out; p.ldo = ldo; p.part = work; p.H = H; p.W = W; p.C = C;
-  p.tiles_x = (W + NF_TX - 1) / NF_TX; p.tiles_y = (H + NF_TY - 1) / NF_TY;
-  const long long nb = (long long)p.tiles_x * p.tiles_y;
-  FF_CHECK_ARG(nb < (1LL << 31) && work_floats >= (long long)B * nb * C, "ff_naf_front_images: workspace too small (ff_naf_front_images_workspace)");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)NF_MT * 32 * NF_TS * 4 + (size_t)2 * 32 * (4 * C + 16) + 8 * 8 * 4 * 4 + (size_t)11 * 2 * C * 4;
-#define NF_LAUNCH(KSV, NTM)                                                                                                  \
-  do {                                                                                                                       \
-    static bool attr_set = false;                                                                                            \
-    if (!attr_set) {                                                                                                         \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&naf_front_images_kernel<KSV, NTM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-        ff_set_error("ff_naf_front_images: cannot raise dynamic LDS to %zu", lds); return FF_ERR_LAUNCH; }                   \
-      attr_set = true;                                                                                                       \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((naf_front_images_kernel<KSV, NTM>), dim3((unsigned)nb, (unsigned)B), dim3(512), lds, st, p);         \
-  } while (0)
-  if (C == 64) { if (nterms == 3) NF_LAUNCH(4, 3); else NF_LAUNCH(4, 1); }
-  else { if (nterms == 3) NF_LAUNCH(8, 3); else NF_LAUNCH(8, 1); }
-#undef NF_LAUNCH
-  hipLaunchKernelGGL(pool_reduce_images_kernel, dim3((C + 15) / 16, (unsigned)B), dim3(256), 0, st, work, (int)nb, C, 1.0f / ((float)H * (float)W), pooled);
-  FF_LAUNCH_CHECK("ff_naf_front_images");
-  return FF_OK;
+  return naf_front_launch("ff_naf_front_images", x, ldx, B, H, W, C, ln_gamma, ln_beta, eps, w1_tiles, b1, dw_tapmajor, dw_bias, out, ldo, pooled, work, work_floats, nterms, stream);
 }
+

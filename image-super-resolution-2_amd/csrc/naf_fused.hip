@@ -29,48 +29,47 @@
 
 extern "C" long long ff_dwconv3_gate_pool_workspace(int C) { return (long long)1024 * C; }
 
-extern "C" int ff_dwconv3_gate_pool(const float* in, int ldi, float* out, int ldo, int H, int W, int C, const float* w_tapmajor,
-                                    const float* bias, float* pooled, float* work, long long work_floats, void* stream) {
-  FF_CHECK_ARG(in && out && w_tapmajor && bias && pooled && work, "ff_dwconv3_gate_pool: null pointer");
-  FF_CHECK_ARG(H > 0 && W > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && ldi >= 2 * C && ldi % 4 == 0 && ldo >= C && ldo % 4 == 0, "ff_dwconv3_gate_pool: bad dims");
-  FF_CHECK_ARG((((uintptr_t)in) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)w_tapmajor) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)work) & 15) == 0, "ff_dwconv3_gate_pool: 16-byte alignment required");
-  const int cv = C / 4, ppb = 256 / cv;
-  const long long P = (long long)H * W;
-  long long nb = ((long long)((H + 3) / 4) * W + ppb - 1) / ppb;      // (column, 4-row strip) items
-  if (nb > 1024) nb = 1024;      // 4 workgroups per CU: enough to stream at HBM rate, few enough partials to reduce
-  FF_CHECK_ARG(work_floats >= nb * C, "ff_dwconv3_gate_pool: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(dwconv3_gate_pool_kernel, dim3((unsigned)nb), dim3(256), (size_t)ppb * cv * 16, st, in, ldi, out, ldo, H, W, C,
-                     w_tapmajor, bias, work);
-  hipLaunchKernelGGL(pool_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, work, (int)nb, C, 1.0f / (float)P, pooled);
-  FF_LAUNCH_CHECK("ff_dwconv3_gate_pool");
-  return FF_OK;
-}
-
 extern "C" long long ff_dwconv3_gate_pool_images_workspace(int B, int C) {
   if (B < 1 || C < 4) return -1;
   return (long long)B * ff_dwconv3_gate_pool_workspace(C);
 }
 
-// B independent images [B][H][W] in one launch: image b comes out with the bits of ff_dwconv3_gate_pool on it alone (nb, the item-to-
-// workgroup assignment and the order of every sum are one image's); pooled [B][C], work >= ff_dwconv3_gate_pool_images_workspace(B, C).
+// The body of both entry points: B == 0 is ff_dwconv3_gate_pool (one image), B >= 1 ff_dwconv3_gate_pool_images (grid (nb, B): nb, the
+// item-to-workgroup assignment and the order of every sum are one image's).
+static int dwconv3_gate_pool_launch(const char* who, const float* in, int ldi, float* out, int ldo, int B, int H, int W, int C, const float* w_tapmajor,
+                                    const float* bias, float* pooled, float* work, long long work_floats, void* stream) {
+  FF_CHECK_ARG(in && out && w_tapmajor && bias && pooled && work, "%s: null pointer", who);
+  FF_CHECK_ARG(H > 0 && W > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && ldi >= 2 * C && ldi % 4 == 0 && ldo >= C && ldo % 4 == 0, "%s: bad dims", who);
+  FF_CHECK_ARG((((uintptr_t)in) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)w_tapmajor) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)work) & 15) == 0, "%s: 16-byte alignment required", who);
+  const int cv = C / 4, ppb = 256 / cv;
+  const float inv_p = 1.0f / (float)((long long)H * W);
+  long long nb = ((long long)((H + 3) / 4) * W + ppb - 1) / ppb;      // (column, 4-row strip) items of one image
+  if (nb > 1024) nb = 1024;      // 4 workgroups per CU: enough to stream at HBM rate, few enough partials to reduce
+  FF_CHECK_ARG(work_floats >= (B ? B : 1) * nb * C, "%s: workspace too small", who);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)ppb * cv * 16;
+  if (!B) {
+    hipLaunchKernelGGL(dwconv3_gate_pool_kernel, dim3((unsigned)nb), dim3(256), lds, st, in, ldi, out, ldo, H, W, C, w_tapmajor, bias, work);
+    hipLaunchKernelGGL(pool_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, work, (int)nb, C, inv_p, pooled);
+  } else {
+    hipLaunchKernelGGL(dwconv3_gate_pool_images_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), lds, st, in, ldi, out, ldo, H, W, C, w_tapmajor, bias, work);
+    hipLaunchKernelGGL(pool_reduce_images_kernel, dim3((C + 15) / 16, (unsigned)B), dim3(256), 0, st, work, (int)nb, C, inv_p, pooled);
+  }
+  FF_LAUNCH_CHECK(who);
+  return FF_OK;
+}
+
+extern "C" int ff_dwconv3_gate_pool(const float* in, int ldi, float* out, int ldo, int H, int W, int C, const float* w_tapmajor,
+                                    const float* bias, float* pooled, float* work, long long work_floats, void* stream) {
+  return dwconv3_gate_pool_launch("ff_dwconv3_gate_pool", in, ldi, out, ldo, 0, H, W, C, w_tapmajor, bias, pooled, work, work_floats, stream);
+}
+
+// B independent images [B][H][W] in one launch: image b comes out with the bits of ff_dwconv3_gate_pool on it alone;
+// pooled [B][C], work >= ff_dwconv3_gate_pool_images_workspace(B, C).
 extern "C" int ff_dwconv3_gate_pool_images(const float* in, int ldi, float* out, int ldo, int B, int H, int W, int C, const float* w_tapmajor,
                                            const float* bias, float* pooled, float* work, long long work_floats, void* stream) {
-  FF_CHECK_ARG(in && out && w_tapmajor && bias && pooled && work, "ff_dwconv3_gate_pool_images: null pointer");
   FF_CHECK_ARG(B >= 1 && B <= 65535, "ff_dwconv3_gate_pool_images: B must be 1 .. 65535 (got %d)", B);
-  FF_CHECK_ARG(H > 0 && W > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && ldi >= 2 * C && ldi % 4 == 0 && ldo >= C && ldo % 4 == 0, "ff_dwconv3_gate_pool_images: bad dims");
-  FF_CHECK_ARG((((uintptr_t)in) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)w_tapmajor) & 15) == 0 && (((uintptr_t)bias) & 15) == 0 && (((uintptr_t)work) & 15) == 0, "ff_dwconv3_gate_pool_images: 16-byte alignment required");
-  const int cv = C / 4, ppb = 256 / cv;
-  const long long P = (long long)H * W;
-  long long nb = ((long long)((H + 3) / 4) * W + ppb - 1) / ppb;      // one image's workgroups, capped as in ff_dwconv3_gate_pool
-  if (nb > 1024) nb = 1024;
-  FF_CHECK_ARG(work_floats >= (long long)B * nb * C, "ff_dwconv3_gate_pool_images: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(dwconv3_gate_pool_images_kernel, dim3((unsigned)nb, (unsigned)B), dim3(256), (size_t)ppb * cv * 16, st, in, ldi, out, ldo,
-                     H, W, C, w_tapmajor, bias, work);
-  hipLaunchKernelGGL(pool_reduce_images_kernel, dim3((C + 15) / 16, (unsigned)B), dim3(256), 0, st, work, (int)nb, C, 1.0f / (float)P, pooled);
-  FF_LAUNCH_CHECK("ff_dwconv3_gate_pool_images");
-  return FF_OK;
+  return dwconv3_gate_pool_launch("ff_dwconv3_gate_pool_images", in, ldi, out, ldo, B, H, W, C, w_tapmajor, bias, pooled, work, work_floats, stream);
 }
 
 // --------------------------------------------------------------------------------------------- flash gated FFN
@@ -294,12 +293,8 @@ static int launch_naf_ffn(const NafFfnParams& p, hipStream_t st) {
   constexpr int C = 16 * KS;
   const size_t lds = (size_t)4 * 32 * (2 * KS + 1) * 16 + (size_t)2 * C * 5 * 16 + (size_t)8 * 32 * (KS * 32 + 16) + (size_t)2 * C * 4 +
                      (KS >= 8 ? 0 : (size_t)8 * 32 * FF_XS_ROW * 4);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&naf_ffn_kernel<KS, NTERMS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { ff_set_error("ff_naf_ffn: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once;
+  if (!ff_raise_lds(once, "ff_naf_ffn", 160 * 1024, FF_LDS_SAY_ERR, &naf_ffn_kernel<KS, NTERMS>)) return FF_ERR_LAUNCH;
   const long long nblk = (p.M + 255) / 256;
   if (nblk >= (1LL << 31)) { ff_set_error("ff_naf_ffn: grid too large"); return FF_ERR_ARG; }
   hipLaunchKernelGGL((naf_ffn_kernel<KS, NTERMS>), dim3((unsigned)nblk), dim3(512), lds, st, p);

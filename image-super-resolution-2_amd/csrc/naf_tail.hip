@@ -68,13 +68,9 @@ static int launch_naf_tail(NafTailParams& p, hipStream_t st) {
   constexpr int C = 16 * KS;
   constexpr size_t lds = (size_t)8 * C * C + (size_t)9 * C * 4 + (size_t)NW * 32 * ((KS == 4 ? 64 : 32) + 4) * 4 + (IMG ? (size_t)NW * C * 4 : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = IMG ? hipFuncSetAttribute(reinterpret_cast<const void*>(&naf_tail_images_kernel<KS, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                       : hipFuncSetAttribute(reinterpret_cast<const void*>(&naf_tail_kernel<KS, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { ff_set_error("ff_naf_tail: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once;
+  if (!(IMG ? ff_raise_lds(once, "ff_naf_tail", lds, FF_LDS_SAY_ERR, &naf_tail_images_kernel<KS, NW>)
+            : ff_raise_lds(once, "ff_naf_tail", lds, FF_LDS_SAY_ERR, &naf_tail_kernel<KS, NW>))) return FF_ERR_LAUNCH;
   const long long ntiles = (p.M + NW * 32 - 1) / (NW * 32);
   if (ntiles >= (1LL << 31)) { ff_set_error("ff_naf_tail: too many rows"); return FF_ERR_ARG; }
   p.ntiles = (int)ntiles;
@@ -87,19 +83,30 @@ static int launch_naf_tail(NafTailParams& p, hipStream_t st) {
   return FF_OK;
 }
 
+// The body of both entry points: B == 0 is ff_naf_tail (one sca vector for all rows), B >= 1 ff_naf_tail_images (sca [B][C]).
+static int naf_tail_launch(const char* who, const float* g, int ldg, const float* x, int ldx, float* out, int ldo, long long M, int C,
+                           const float* sca, int B, int rows_per_image, const float* b3, const float* beta, const float* gamma_ln,
+                           const float* beta_ln, float eps, const void* w_frags, const float* b4, const float* b5, const float* out_scale,
+                           void* stream) {
+  FF_CHECK_ARG(g && x && out && sca && b3 && beta && gamma_ln && beta_ln && w_frags && b4 && b5 && out_scale, "%s: null pointer", who);
+  FF_CHECK_ARG(M > 0 && (C == 64 || C == 128), "%s: C must be 64 or 128", who);
+  FF_CHECK_ARG(ldg >= C && ldg % 4 == 0 && ldx >= C && ldx % 4 == 0 && ldo >= C, "%s: row strides must be >= C (g, x: multiples of 4)", who);
+  FF_CHECK_ARG((((uintptr_t)g) & 15) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)w_frags) & 15) == 0 && (!B || (((uintptr_t)sca) & 15) == 0),
+               "%s: 16-byte alignment required", who);
+  FF_CHECK_ARG(out != g && out != x, "%s: out must not alias g or x", who);
+  NafTailParams p{};
+  p.g = g; p.x = x; p.out = out; p.w = (const __bf16*)w_frags; p.sca = sca; p.b3 = b3; p.beta = beta; p.gamma_ln = gamma_ln;
+  p.beta_ln = beta_ln; p.b4 = b4; p.b5 = b5; p.oscale = out_scale; p.M = M; p.ldg = ldg; p.ldx = ldx; p.ldo = ldo; p.eps = eps;
+  p.rpi = rows_per_image; p.nimg = B ? B : 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (!B) return C == 64 ? launch_naf_tail<4, 4, 2>(p, st) : launch_naf_tail<8, 4, 1>(p, st);
+  return C == 64 ? launch_naf_tail<4, 4, 2, true>(p, st) : launch_naf_tail<8, 4, 1, true>(p, st);
+}
+
 extern "C" int ff_naf_tail(const float* g, int ldg, const float* x, int ldx, float* out, int ldo, long long M, int C,
                            const float* sca, const float* b3, const float* beta, const float* gamma_ln, const float* beta_ln,
                            float eps, const void* w_frags, const float* b4, const float* b5, const float* out_scale, void* stream) {
-  FF_CHECK_ARG(g && x && out && sca && b3 && beta && gamma_ln && beta_ln && w_frags && b4 && b5 && out_scale, "ff_naf_tail: null pointer");
-  FF_CHECK_ARG(M > 0 && (C == 64 || C == 128), "ff_naf_tail: C must be 64 or 128");
-  FF_CHECK_ARG(ldg >= C && ldg % 4 == 0 && ldx >= C && ldx % 4 == 0 && ldo >= C, "ff_naf_tail: row strides must be >= C (g, x: multiples of 4)");
-  FF_CHECK_ARG((((uintptr_t)g) & 15) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)w_frags) & 15) == 0, "ff_naf_tail: 16-byte alignment required");
-  FF_CHECK_ARG(out != g && out != x, "ff_naf_tail: out must not alias g or x");
-  NafTailParams p;
-  p.g = g; p.x = x; p.out = out; p.w = (const __bf16*)w_frags; p.sca = sca; p.b3 = b3; p.beta = beta; p.gamma_ln = gamma_ln;
-  p.beta_ln = beta_ln; p.b4 = b4; p.b5 = b5; p.oscale = out_scale; p.M = M; p.ldg = ldg; p.ldx = ldx; p.ldo = ldo; p.eps = eps;
-  p.ntiles = 0; p.rpi = 0; p.nimg = 1;
-  return C == 64 ? launch_naf_tail<4, 4, 2>(p, (hipStream_t)stream) : launch_naf_tail<8, 4, 1>(p, (hipStream_t)stream);
+  return naf_tail_launch("ff_naf_tail", g, ldg, x, ldx, out, ldo, M, C, sca, 0, 0, b3, beta, gamma_ln, beta_ln, eps, w_frags, b4, b5, out_scale, stream);
 }
 
 // B independent images' rows in one launch: sca [B][C], rows b * rows_per_image .. of g / x / out are image b's.  Every row comes out
@@ -109,18 +116,8 @@ extern "C" int ff_naf_tail_images(const float* g, int ldg, const float* x, int l
                                   const float* sca, int B, int rows_per_image, const float* b3, const float* beta, const float* gamma_ln,
                                   const float* beta_ln, float eps, const void* w_frags, const float* b4, const float* b5,
                                   const float* out_scale, void* stream) {
-  FF_CHECK_ARG(g && x && out && sca && b3 && beta && gamma_ln && beta_ln && w_frags && b4 && b5 && out_scale, "ff_naf_tail_images: null pointer");
   FF_CHECK_ARG(B >= 1 && rows_per_image > 0 && rows_per_image % 32 == 0,
                "ff_naf_tail_images: rows_per_image must be a positive multiple of 32 (got B=%d rows_per_image=%d)", B, rows_per_image);
   FF_CHECK_ARG(M == (long long)B * rows_per_image && M < (1LL << 31), "ff_naf_tail_images: M must be B * rows_per_image and below 2^31 (got M=%lld)", M);
-  FF_CHECK_ARG(C == 64 || C == 128, "ff_naf_tail_images: C must be 64 or 128");
-  FF_CHECK_ARG(ldg >= C && ldg % 4 == 0 && ldx >= C && ldx % 4 == 0 && ldo >= C, "ff_naf_tail_images: row strides must be >= C (g, x: multiples of 4)");
-  FF_CHECK_ARG((((uintptr_t)g) & 15) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)w_frags) & 15) == 0 && (((uintptr_t)sca) & 15) == 0,
-               "ff_naf_tail_images: 16-byte alignment required");
-  FF_CHECK_ARG(out != g && out != x, "ff_naf_tail_images: out must not alias g or x");
-  NafTailParams p;
-  p.g = g; p.x = x; p.out = out; p.w = (const __bf16*)w_frags; p.sca = sca; p.b3 = b3; p.beta = beta; p.gamma_ln = gamma_ln;
-  p.beta_ln = beta_ln; p.b4 = b4; p.b5 = b5; p.oscale = out_scale; p.M = M; p.ldg = ldg; p.ldx = ldx; p.ldo = ldo; p.eps = eps;
-  p.ntiles = 0; p.rpi = rows_per_image; p.nimg = B;
-  return C == 64 ? launch_naf_tail<4, 4, 2, true>(p, (hipStream_t)stream) : launch_naf_tail<8, 4, 1, true>(p, (hipStream_t)stream);
+  return naf_tail_launch("ff_naf_tail_images", g, ldg, x, ldx, out, ldo, M, C, sca, B, rows_per_image, b3, beta, gamma_ln, beta_ln, eps, w_frags, b4, b5, out_scale, stream);
 }

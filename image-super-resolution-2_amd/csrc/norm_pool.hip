@@ -193,20 +193,26 @@ static int pool_chunks(long long P, int* ppc_out) {
   return (int)((P + ppc - 1) / ppc);
 }
 extern "C" int ff_pool_partial_rows(long long P) { return P > 0 ? pool_chunks(P, nullptr) : 0; }
-extern "C" int ff_pool_partials(const float* in, int ld, long long P, int C, float* part, long long part_floats, void* stream) {
-  FF_CHECK_ARG(in && part && P > 0 && C > 0 && ld >= C, "ff_pool_partials: bad args");
+
+// The body of ff_pool_partials (images == 1) and ff_pool_partials_images: grid (one image's chunks, images).
+static int pool_partials_launch(const char* who, const float* in, int ld, int images, long long P, int C, float* part, long long part_floats, void* stream) {
+  FF_CHECK_ARG(in && part && P > 0 && C > 0 && ld >= C, "%s: bad args", who);
   int ppc;
   const int nch = pool_chunks(P, &ppc);
-  FF_CHECK_ARG(part_floats >= (long long)nch * C, "ff_pool_partials: need %lld floats", (long long)nch * C);
+  FF_CHECK_ARG(part_floats >= (long long)images * nch * C, "%s: need %lld floats", who, (long long)images * nch * C);
   const bool v4 = (C % 4 == 0) && (ld % 4 == 0) && (C / 4 <= 256) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)part & 15) == 0);
   if (v4) {
     const int cv = C / 4, rpi = 256 / cv;
-    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, 1), dim3(256), (size_t)rpi * cv * 16, (hipStream_t)stream, in, ld, P, C, ppc, part);
+    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, images), dim3(256), (size_t)rpi * cv * 16, (hipStream_t)stream, in, ld, P, C, ppc, part);
   } else {
-    hipLaunchKernelGGL(pool_partial_kernel, dim3(nch, 1), dim3(256), 0, (hipStream_t)stream, in, ld, P, C, ppc, part);
+    hipLaunchKernelGGL(pool_partial_kernel, dim3(nch, images), dim3(256), 0, (hipStream_t)stream, in, ld, P, C, ppc, part);
   }
-  FF_LAUNCH_CHECK("ff_pool_partials");
+  FF_LAUNCH_CHECK(who);
   return FF_OK;
+}
+
+extern "C" int ff_pool_partials(const float* in, int ld, long long P, int C, float* part, long long part_floats, void* stream) {
+  return pool_partials_launch("ff_pool_partials", in, ld, 1, P, C, part, part_floats, stream);
 }
 
 // first stage of B images of P pixels each in one launch, grid (one image's chunks, B): part [B][ff_pool_partial_rows(P)][C], image b's rows
@@ -219,19 +225,7 @@ extern "C" long long ff_pool_partials_images_rows(int B, long long P) {
 extern "C" int ff_pool_partials_images(const float* in, int ld, int B, long long P, int C, float* part, long long part_floats, void* stream) {
   FF_CHECK_ARG(B > 0 && B <= 65535 && P > 0 && P % 256 == 0,
                "ff_pool_partials_images: the pixels per image must be a positive multiple of 256 (1 <= B <= 65535; got B=%d P=%lld)", B, P);
-  FF_CHECK_ARG(in && part && C > 0 && ld >= C, "ff_pool_partials_images: bad args");
-  int ppc;
-  const int nch = pool_chunks(P, &ppc);
-  FF_CHECK_ARG(part_floats >= (long long)B * nch * C, "ff_pool_partials_images: need %lld floats", (long long)B * nch * C);
-  const bool v4 = (C % 4 == 0) && (ld % 4 == 0) && (C / 4 <= 256) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)part & 15) == 0);
-  if (v4) {
-    const int cv = C / 4, rpi = 256 / cv;
-    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, B), dim3(256), (size_t)rpi * cv * 16, (hipStream_t)stream, in, ld, P, C, ppc, part);
-  } else {
-    hipLaunchKernelGGL(pool_partial_kernel, dim3(nch, B), dim3(256), 0, (hipStream_t)stream, in, ld, P, C, ppc, part);
-  }
-  FF_LAUNCH_CHECK("ff_pool_partials_images");
-  return FF_OK;
+  return pool_partials_launch("ff_pool_partials_images", in, ld, B, P, C, part, part_floats, stream);
 }
 
 // second stage alone: out[c] = inv_count * sum_r part[r][c] over `rows` rows of pitch ld (per-workgroup partials written by a

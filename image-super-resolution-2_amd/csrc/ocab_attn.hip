@@ -313,12 +313,8 @@ static int ocab_launch(OcabParams& p, const char* who, void* stream) {
   const long long nblk = (long long)p.B * p.nwx * p.nwy;
   FF_CHECK_ARG(nblk < (1LL << 31), "%s: grid too large", who);
   static_assert(OC_LDS <= 160 * 1024, "LDS image too large");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ocab_attn_kernel<ROWS16>), hipFuncAttributeMaxDynamicSharedMemorySize, OC_LDS);
-    if (e != hipSuccess) { ff_set_error("%s: cannot raise dynamic LDS: %s", who, hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once;
+  if (!ff_raise_lds(once, who, OC_LDS, FF_LDS_SAY_ERR, &ocab_attn_kernel<ROWS16>)) return FF_ERR_LAUNCH;
   hipLaunchKernelGGL(ocab_attn_kernel<ROWS16>, dim3((unsigned)nblk), dim3(512), OC_LDS, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK(who);
   return FF_OK;

@@ -256,12 +256,8 @@ extern "C" int ff_sgfn_tail(const float* h, int ldh, int c2, const float* stats,
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_sgfn_tail: grid too large");
   static_assert(SG_LDS <= 160 * 1024, "LDS image too large");
   static_assert(8 * 32 * 36 * 4 <= 2 * SG_XBUF, "epilogue patches must fit in the halo buffers");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sgfn_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SG_LDS);
-    if (e != hipSuccess) { ff_set_error("ff_sgfn_tail: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once;
+  if (!ff_raise_lds(once, "ff_sgfn_tail", SG_LDS, FF_LDS_SAY_ERR, &sgfn_tail_kernel)) return FF_ERR_LAUNCH;
   hipLaunchKernelGGL(sgfn_tail_kernel, dim3((unsigned)nblk), dim3(512), SG_LDS, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_sgfn_tail");
   return FF_OK;

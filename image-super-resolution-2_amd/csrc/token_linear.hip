@@ -92,13 +92,8 @@ extern "C" int ff_token_linear(const float* x, int ldx, float* out, int ldo, lon
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_linear: grid too large");
 #define TL_LAUNCH(A, KSV, V4, NTM)                                                                                          \
   do {                                                                                                                      \
-    static bool attr_set = false;                                                                                           \
-    if (!attr_set) {                                                                                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_kernel<A, KSV, V4, false, NTM>),       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
-      if (e != hipSuccess) { ff_set_error("ff_token_linear: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
-      attr_set = true;                                                                                                      \
-    }                                                                                                                       \
+    static ff_device_once once;                                                                                             \
+    if (!ff_raise_lds(once, "ff_token_linear", 160 * 1024, FF_LDS_SAY_ERR, &token_linear_kernel<A, KSV, V4, false, NTM>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((token_linear_kernel<A, KSV, V4, false, NTM>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p); \
   } while (0)
 #define TL_LAUNCH_NT(A, KSV, V4) do { if (nterms == 3) TL_LAUNCH(A, KSV, V4, 3); else TL_LAUNCH(A, KSV, V4, 1); } while (0)
@@ -144,13 +139,8 @@ extern "C" int ff_token_linear_rows16(const float* x, int ldx, void* out16, int 
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_linear_rows16: grid too large");
 #define TL_LAUNCH16(KSV)                                                                                                    \
   do {                                                                                                                      \
-    static bool attr_set = false;                                                                                           \
-    if (!attr_set) {                                                                                                        \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                           \
-      if (e != hipSuccess) { ff_set_error("ff_token_linear_rows16: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
-      attr_set = true;                                                                                                      \
-    }                                                                                                                       \
+    static ff_device_once once;                                                                                             \
+    if (!ff_raise_lds(once, "ff_token_linear_rows16", 160 * 1024, FF_LDS_SAY_ERR, &token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p); \
   } while (0)
   if (ks == 4) TL_LAUNCH16(4); else if (ks == 8) TL_LAUNCH16(8); else TL_LAUNCH16(12);
@@ -163,39 +153,45 @@ extern "C" int ff_token_linear_rows16(const float* x, int ldx, void* out16, int 
 // (channel gate on one branch, spatial gate on the other, dat_arch.py:541-556 spatial blocks / :649-664 channel blocks) + the output
 // projection (:559 / :666) + the block's residual in one launch.  gw1t: [192][12] floats = GW1 transposed and zero padded
 // (11 hidden units, BatchNorm folded), gb1 / gw2: [12].
+// The body of both entry points: B == 0 is ff_token_linear_gated (one cm vector, a grid of 256-token workgroups), B >= 1
+// ff_token_linear_gated_images (cm [B][K], grid (rows_per_image / 256, B)).
+static int token_linear_gated_launch(const char* who, const float* x, int ldx, const float* x2, int ldx2, const float* cm, int B, long long rows_per_image,
+                                     const float* gw1t, const float* gb1, const float* gw2, float gb2, float* out, int ldo, long long M, int K, int N,
+                                     int n_tiles, const void* w_tiles, const float* bias_padded, const float* res, int ldr, int nterms, void* stream) {
+  FF_CHECK_ARG(nterms == 1 || nterms == 3, "%s: nterms must be 1 or 3", who);
+  FF_CHECK_ARG(x && x2 && cm && gb1 && gw2 && out && w_tiles, "%s: null pointer", who);   /* gw1t is unused: GW1 travels as tile n_tiles of w_tiles */
+  FF_CHECK_ARG(M > 0 && K > 0 && K <= 192 && K % 4 == 0 && N > 0 && N % 4 == 0 && n_tiles * 32 >= N, "%s: needs K <= 192, K and N multiples of 4", who);
+  FF_CHECK_ARG(ldx >= K && ldx % 4 == 0 && ldx2 >= K && ldx2 % 4 == 0 && ldo >= N && ldo % 4 == 0 && (!res || (ldr >= N && ldr % 4 == 0)), "%s: rows must be 16-byte aligned", who);
+  FF_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)x2) | ((uintptr_t)cm) | ((uintptr_t)out) | ((uintptr_t)w_tiles) | ((uintptr_t)res)) & 15) == 0, "%s: 16-byte alignment", who);
+  const long long wpi = B ? rows_per_image / 256 : 0, nblk = B ? wpi : (M + 255) / 256;
+  FF_CHECK_ARG(nblk < (1LL << 31), "%s: grid too large", who);
+  TokenLinParams p{};
+  p.x = x; p.out = out; p.w = (const __bf16*)w_tiles; p.bias = bias_padded; p.res = res; p.M = M; p.ldx = ldx; p.ldo = ldo; p.ldr = ldr;
+  p.K = K; p.N = N; p.NT = n_tiles; p.act = ACT_NONE;
+  p.x2 = x2; p.ldx2 = ldx2; p.cm = cm; p.gw1t = gw1t; p.gb1 = gb1; p.gw2 = gw2; p.gb2 = gb2; p.wpi = (int)wpi;
+  const size_t lds = (size_t)2 * 2 * 32 * 25 * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)n_tiles * 32 * 4;
+  FF_CHECK_ARG(lds <= 160 * 1024, "%s: N too large for the LDS image", who);
+  static ff_device_once once[2];
+  if (!(!B ? ff_raise_lds(once[0], who, 160 * 1024, FF_LDS_SAY_ERR, &token_linear_kernel<ACT_NONE, 12, true, true, 3>, &token_linear_kernel<ACT_NONE, 12, true, true, 1>)
+           : ff_raise_lds(once[1], who, 160 * 1024, FF_LDS_SAY_ERR, &token_linear_images_kernel<ACT_NONE, 12, true, true, 3>, &token_linear_images_kernel<ACT_NONE, 12, true, true, 1>)))
+    return FF_ERR_LAUNCH;
+  const dim3 grid((unsigned)nblk, B ? (unsigned)B : 1u);
+  if (!B) {
+    if (nterms == 3) hipLaunchKernelGGL((token_linear_kernel<ACT_NONE, 12, true, true, 3>), grid, dim3(512), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((token_linear_kernel<ACT_NONE, 12, true, true, 1>), grid, dim3(512), lds, (hipStream_t)stream, p);
+  } else {
+    if (nterms == 3) hipLaunchKernelGGL((token_linear_images_kernel<ACT_NONE, 12, true, true, 3>), grid, dim3(512), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((token_linear_images_kernel<ACT_NONE, 12, true, true, 1>), grid, dim3(512), lds, (hipStream_t)stream, p);
+  }
+  FF_LAUNCH_CHECK(who);
+  return FF_OK;
+}
+
 extern "C" int ff_token_linear_gated(const float* x, int ldx, const float* x2, int ldx2, const float* cm, const float* gw1t,
                                      const float* gb1, const float* gw2, float gb2, float* out, int ldo, long long M, int K, int N,
                                      int n_tiles, const void* w_tiles, const float* bias_padded, const float* res, int ldr, int nterms,
                                      void* stream) {
-  FF_CHECK_ARG(nterms == 1 || nterms == 3, "ff_token_linear_gated: nterms must be 1 or 3");
-  FF_CHECK_ARG(x && x2 && cm && gb1 && gw2 && out && w_tiles, "ff_token_linear_gated: null pointer");   /* gw1t is unused: GW1 travels as tile n_tiles of w_tiles */
-  FF_CHECK_ARG(M > 0 && K > 0 && K <= 192 && K % 4 == 0 && N > 0 && N % 4 == 0 && n_tiles * 32 >= N, "ff_token_linear_gated: needs K <= 192, K and N multiples of 4");
-  FF_CHECK_ARG(ldx >= K && ldx % 4 == 0 && ldx2 >= K && ldx2 % 4 == 0 && ldo >= N && ldo % 4 == 0 && (!res || (ldr >= N && ldr % 4 == 0)), "ff_token_linear_gated: rows must be 16-byte aligned");
-  FF_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)x2) | ((uintptr_t)cm) | ((uintptr_t)out) | ((uintptr_t)w_tiles) | ((uintptr_t)res)) & 15) == 0, "ff_token_linear_gated: 16-byte alignment");
-  TokenLinParams p;
-  p.x = x; p.out = out; p.gamma = nullptr; p.beta = nullptr; p.w = (const __bf16*)w_tiles; p.bias = bias_padded;
-  p.res = res; p.res2 = nullptr; p.rs2 = nullptr; p.xn = nullptr; p.ldxn = 0; p.M = M; p.ldx = ldx; p.ldo = ldo; p.ldr = ldr; p.ldr2 = 0;
-  p.K = K; p.N = N; p.NT = n_tiles; p.act = ACT_NONE; p.eps = 0.f;
-  p.stats = nullptr; p.st_lo = 0; p.st_hi = 0; p.st_eps = 0.f;
-  p.x2 = x2; p.ldx2 = ldx2; p.cm = cm; p.gw1t = gw1t; p.gb1 = gb1; p.gw2 = gw2; p.gb2 = gb2; p.wpi = 0;
-  const size_t lds = (size_t)2 * 2 * 32 * 25 * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)n_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_linear_gated: N too large for the LDS image");
-  const long long nblk = (M + 255) / 256;
-  FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_linear_gated: grid too large");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_kernel<ACT_NONE, 12, true, true, 3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_kernel<ACT_NONE, 12, true, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { ff_set_error("ff_token_linear_gated: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
-  if (nterms == 3) hipLaunchKernelGGL((token_linear_kernel<ACT_NONE, 12, true, true, 3>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((token_linear_kernel<ACT_NONE, 12, true, true, 1>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
-  FF_LAUNCH_CHECK("ff_token_linear_gated");
-  return FF_OK;
+  return token_linear_gated_launch("ff_token_linear_gated", x, ldx, x2, ldx2, cm, 0, 0, gw1t, gb1, gw2, gb2, out, ldo, M, K, N, n_tiles, w_tiles, bias_padded, res, ldr, nterms, stream);
 }
 
 // ff_token_linear_gated over B images of rows_per_image tokens each, with one channel gate per image: cm is [B][K] (contiguous rows).  A
@@ -208,34 +204,5 @@ extern "C" int ff_token_linear_gated_images(const float* x, int ldx, const float
   FF_CHECK_ARG(B > 0 && B <= 65535 && rows_per_image > 0 && rows_per_image % 256 == 0 && M == (long long)B * rows_per_image,
                "ff_token_linear_gated_images: rows_per_image must be a positive multiple of 256 and M == B * rows_per_image (1 <= B <= 65535; got B=%d rows_per_image=%lld M=%lld)",
                B, rows_per_image, M);
-  FF_CHECK_ARG(nterms == 1 || nterms == 3, "ff_token_linear_gated_images: nterms must be 1 or 3");
-  FF_CHECK_ARG(x && x2 && cm && gb1 && gw2 && out && w_tiles, "ff_token_linear_gated_images: null pointer");
-  FF_CHECK_ARG(K > 0 && K <= 192 && K % 4 == 0 && N > 0 && N % 4 == 0 && n_tiles * 32 >= N, "ff_token_linear_gated_images: needs K <= 192, K and N multiples of 4");
-  FF_CHECK_ARG(ldx >= K && ldx % 4 == 0 && ldx2 >= K && ldx2 % 4 == 0 && ldo >= N && ldo % 4 == 0 && (!res || (ldr >= N && ldr % 4 == 0)), "ff_token_linear_gated_images: rows must be 16-byte aligned");
-  FF_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)x2) | ((uintptr_t)cm) | ((uintptr_t)out) | ((uintptr_t)w_tiles) | ((uintptr_t)res)) & 15) == 0, "ff_token_linear_gated_images: 16-byte alignment");
-  const long long wpi = rows_per_image / 256;
-  FF_CHECK_ARG(wpi < (1LL << 31), "ff_token_linear_gated_images: grid too large");
-  TokenLinParams p;
-  p.x = x; p.out = out; p.gamma = nullptr; p.beta = nullptr; p.w = (const __bf16*)w_tiles; p.bias = bias_padded;
-  p.res = res; p.res2 = nullptr; p.rs2 = nullptr; p.xn = nullptr; p.ldxn = 0; p.M = M; p.ldx = ldx; p.ldo = ldo; p.ldr = ldr; p.ldr2 = 0;
-  p.K = K; p.N = N; p.NT = n_tiles; p.act = ACT_NONE; p.eps = 0.f;
-  p.stats = nullptr; p.st_lo = 0; p.st_hi = 0; p.st_eps = 0.f;
-  p.x2 = x2; p.ldx2 = ldx2; p.cm = cm; p.gw1t = nullptr; p.gb1 = gb1; p.gw2 = gw2; p.gb2 = gb2; p.wpi = (int)wpi;
-  const size_t lds = (size_t)2 * 2 * 32 * 25 * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)n_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_linear_gated_images: N too large for the LDS image");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_images_kernel<ACT_NONE, 12, true, true, 3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_linear_images_kernel<ACT_NONE, 12, true, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { ff_set_error("ff_token_linear_gated_images: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
-  const dim3 grid((unsigned)wpi, (unsigned)B);
-  if (nterms == 3) hipLaunchKernelGGL((token_linear_images_kernel<ACT_NONE, 12, true, true, 3>), grid, dim3(512), lds, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((token_linear_images_kernel<ACT_NONE, 12, true, true, 1>), grid, dim3(512), lds, (hipStream_t)stream, p);
-  FF_LAUNCH_CHECK("ff_token_linear_gated_images");
-  return FF_OK;
+  return token_linear_gated_launch("ff_token_linear_gated_images", x, ldx, x2, ldx2, cm, B, rows_per_image, nullptr, gb1, gw2, gb2, out, ldo, M, K, N, n_tiles, w_tiles, bias_padded, res, ldr, nterms, stream);
 }

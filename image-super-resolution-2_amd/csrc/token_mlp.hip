@@ -880,21 +880,12 @@ static int token_projmlp_launch(const float* att, int lda, const float* x, int l
   const dim3 grid((unsigned)(nblk / images), (unsigned)images);
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_projmlp: grid too large");
   FF_CHECK_ARG(M * (long long)(ldx > ldc ? ldx : ldc) < (1LL << 31), "ff_token_projmlp: too many tokens for 32-bit row offsets");
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_projmlp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { ff_set_error("ff_token_projmlp: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-    attr_set = true;
-  }
+  static ff_device_once once, once2;
+  if (!ff_raise_lds(once, "ff_token_projmlp", 160 * 1024, FF_LDS_SAY_ERR, &token_projmlp_kernel)) return FF_ERR_LAUNCH;
   if (nterms == 1) {
     const size_t lds2 = (size_t)PM_OFF_VEC + (size_t)(2 * TM_KP + hidden_tiles * 32) * 4;
     FF_CHECK_ARG(lds2 <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
-    static bool attr2 = false;
-    if (!attr2) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_projmlp_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) { ff_set_error("ff_token_projmlp: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; }
-      attr2 = true;
-    }
+    if (!ff_raise_lds(once2, "ff_token_projmlp", 160 * 1024, FF_LDS_SAY_ERR, &token_projmlp_bf16_kernel)) return FF_ERR_LAUNCH;
     hipLaunchKernelGGL(token_projmlp_bf16_kernel, grid, dim3(512), lds2, (hipStream_t)stream, p);
   } else hipLaunchKernelGGL(token_projmlp_kernel, grid, dim3(512), lds, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_token_projmlp");
@@ -943,13 +934,8 @@ extern "C" int ff_token_mlp(const float* x, int ldx, float* out, int ldo, long l
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_mlp: grid too large");
 #define TM_LAUNCH(V4, NTM)                                                                                                 \
   do {                                                                                                                     \
-    static bool attr_set = false;                                                                                          \
-    if (!attr_set) {                                                                                                       \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&token_mlp_kernel<V4, NTM>),                        \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                          \
-      if (e != hipSuccess) { ff_set_error("ff_token_mlp: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
-      attr_set = true;                                                                                                     \
-    }                                                                                                                      \
+    static ff_device_once once;                                                                                            \
+    if (!ff_raise_lds(once, "ff_token_mlp", 160 * 1024, FF_LDS_SAY_ERR, &token_mlp_kernel<V4, NTM>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((token_mlp_kernel<V4, NTM>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);         \
   } while (0)
   if (nterms == 3) { if (vec4) TM_LAUNCH(true, 3); else TM_LAUNCH(false, 3); }

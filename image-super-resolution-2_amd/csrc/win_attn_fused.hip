@@ -456,26 +456,16 @@ extern "C" int ff_win_attn_fused(const float* x, int ldx, float* out, int ldo, i
   static_assert(8 * 32 * WF_XS_ROW * 4 <= 8 * WF_KWAVE + 2 * WF_VPLB, "gather patch must fit in the K / V area");
 #define WF_LAUNCH(WWV)                                                                                                        \
   do {                                                                                                                        \
-    static bool attr_set = false;                                                                                             \
-    if (!attr_set) {                                                                                                          \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&win_attn_fused_kernel<WWV, 3>),                       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, WF_LDS);                                 \
-      if (e != hipSuccess) { ff_set_error("ff_win_attn_fused: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
-      attr_set = true;                                                                                                        \
-    }                                                                                                                         \
+    static ff_device_once once;                                                                                               \
+    if (!ff_raise_lds(once, "ff_win_attn_fused", WF_LDS, FF_LDS_SAY_ERR, &win_attn_fused_kernel<WWV, 3>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((win_attn_fused_kernel<WWV, 3>), dim3((unsigned)nblk), dim3(512), WF_LDS, (hipStream_t)stream, p);     \
   } while (0)
   static_assert(W2_LDS <= 160 * 1024, "LDS image too large");
   static_assert(8 * 32 * WF_XS_ROW * 4 <= 2 * W2_KBUF + 2 * W2_VBUF, "gather patch must fit in the K / V area");
 #define W2_LAUNCH1(WWV, ON)                                                                                                   \
   do {                                                                                                                        \
-    static bool attr_set = false;                                                                                             \
-    if (!attr_set) {                                                                                                          \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&win_attn_fused_v2_kernel<WWV, ON>),                   \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS);                                 \
-      if (e != hipSuccess) { ff_set_error("ff_win_attn_fused: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return FF_ERR_LAUNCH; } \
-      attr_set = true;                                                                                                        \
-    }                                                                                                                         \
+    static ff_device_once once;                                                                                               \
+    if (!ff_raise_lds(once, "ff_win_attn_fused", W2_LDS, FF_LDS_SAY_ERR, &win_attn_fused_v2_kernel<WWV, ON>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((win_attn_fused_v2_kernel<WWV, ON>), dim3((unsigned)nblk), dim3(512), W2_LDS, (hipStream_t)stream, p); \
   } while (0)
 #define W2_LAUNCH(WWV) do { if (d == 30) W2_LAUNCH1(WWV, true); else W2_LAUNCH1(WWV, false); } while (0)

@@ -13,6 +13,7 @@
  *     arguments are row (pixel) strides in floats, so channel slices of wider tensors are addressed in place.
  *   - `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream); every call is asynchronous
  *     on it and graph-capturable (no allocation, no synchronisation inside).
+ *   - entry points may be called with any device current (the stream's) and from several threads at once.
  *   - return 0 on success; otherwise nothing was launched and ff_last_error() describes why.
  */
 #ifndef FF_KERNELS_H

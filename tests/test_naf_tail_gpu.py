@@ -102,6 +102,24 @@ def test_naf_tail_takes_row_views(dev, bf16_mode, C):
 
 
 @pytest.mark.gpu
+def test_naf_tail_runs_on_a_second_device_of_the_process(dev, bf16_mode):
+    """C = 64 takes 69 888 B of dynamic LDS, above the 64 KB default: the limit has to be raised on EVERY device the process launches on.
+    One workgroup's rows (128) on device 0, then the same launch on device 1; the two outputs are bit-equal."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices")
+    C, M = 64, 128
+    outs = []
+    for d in (0, 1):
+        with torch.cuda.device(d):
+            dd = torch.device("cuda", d)
+            k = _block(C, dd, seed=7700)
+            out = _fused(rnd(M, C, dev=dd, seed=7701, scale=1.2), rnd(M, C, dev=dd, seed=7702, scale=1.5) + 0.2, k)
+            torch.cuda.synchronize(d)
+            outs.append(out.cpu())
+    assert torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["bf16x3", "f32"])
 def test_naf_tail_refuses_the_other_modes(dev, mode):
     from isr2_amd import lib, ops
