@@ -50,8 +50,9 @@ the 2^-10 |v| cleanliness threshold (from the bf16 spacing, see branch_round_poi
 Covered elsewhere: the attention kernels of this mode (window_attn_bf16s, ocab_attn, win_attn_fused) round softmax probabilities relative
 to a running maximum; their flip model is tests/golden/attn_ref.py (which imports this module's accounting), checked on the CPU by
 tests/test_attn_ref_cpu.py and held against the kernels by tests/test_lowprec_attn_gpu.py -- win_attn_fused there on fixed-point inputs
-that make its LayerNorm and projections exact.  What remains on the checks of tests/test_ops_gpu.py: chan_qkv, whose reduction spans the
-whole image, and win_attn_fused on generic inputs (a flip model through LayerNorm, projection and softmax together).  The `_images` and
+that make its LayerNorm and projections exact.  chan_qkv, whose reduction spans the whole image, and the fp32 ff_chan_attn_weights are held per
+partial block to tests/golden/chan_ref.py by tests/test_chan_attn_gpu.py.  What remains on the checks of tests/test_ops_gpu.py:
+win_attn_fused on generic inputs (a flip model through LayerNorm, projection and softmax together).  The `_images` and
 batched forms are pinned bit for bit against the single-image forms by tests/test_batched_*_gpu.py.
 
 tests/test_stage_ref_cpu.py checks this module against fp32 stand-ins (and mutants of them) on the CPU; tests/test_lowprec_fused_gpu.py

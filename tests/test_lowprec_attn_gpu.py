@@ -17,7 +17,8 @@ final-maximum rounding, a 0 instead of -inf tail and a shifted head slice all fa
 The stand-alone kernels run on randn q / k / v, flat and sharpened; the fused kernel on FIXED-POINT inputs that make every stage ahead
 of the exponent exact in fp32 (asserted from the reference), so its v_out side output must equal the fp64 value bit for bit, the bf16 xn
 side output the rounded operand, the fp32 one within 2e-6.  The fused kernel on generic inputs stays in tests/test_ops_gpu.py
-(test_win_attn_fused_hat / _dat_branches); chan_qkv stays on its checks there too (its reduction spans the whole image).
+(test_win_attn_fused_hat / _dat_branches); chan_qkv (its reduction spans the whole image) is held per partial block to
+tests/golden/chan_ref.py by tests/test_chan_attn_gpu.py.
 
 Shapes (attn_ref.CASES) are the smallest that reach every path: window_attn HAT 16x16 on 16x16 with shift 8 (one window, every mask
 region) and on 32x48 without, OCAB's 24x24 keys on 32x32 (576 keys = 4.5 chunks: the ragged tail; every window has zero keys), DAT 8x32 and

@@ -15,7 +15,7 @@ Every test sets the contraction mode itself and restores it (and set_halo) in a 
 Elsewhere: the kernels that round an intermediate no test can observe -- token_mlp, token_projmlp, token_linear_gated on unmoved
 inputs, naf_ffn, naf_front, naf_tail, sgfn_tail -- are held to the same fp32 bound by tests/test_lowprec_fused_gpu.py, against
 stage-rounded fp64 references (tests/golden/stage_ref.py) that account for the roundings fp32 noise can flip.  The attention kernels
-are held to tests/golden/attn_ref.py by tests/test_lowprec_attn_gpu.py; chan_qkv keeps the checks of tests/test_ops_gpu.py.  naf_tail's anchor, ops.linear(kmul=...) in plain bf16, is pinned here.
+are held to tests/golden/attn_ref.py by tests/test_lowprec_attn_gpu.py; chan_qkv to tests/golden/chan_ref.py by tests/test_chan_attn_gpu.py.  naf_tail's anchor, ops.linear(kmul=...) in plain bf16, is pinned here.
 
 Two departures from a literal reading of the case list, both forced by ops.conv2d's own rules:
   * 180 -> 180 at 33x20 (one of the five ragged shapes of test_plain_bf16_forms_of_the_fused_kernels) has 660 pixels; conv2d gives the

@@ -23,8 +23,9 @@ fp32 and bf16 att / c2 rows (all three non-zero io_bf16 values).
 
 Covered elsewhere: the attention kernels (win_attn_fused in plain bf16, window_attn_bf16s, ocab_attn), whose rounded intermediate is
 the softmax probability relative to a running maximum, are held to tests/golden/attn_ref.py by tests/test_lowprec_attn_gpu.py
-(win_attn_fused on fixed-point inputs).  What remains on the checks of tests/test_ops_gpu.py: chan_qkv (its reduction spans the whole
-image) and win_attn_fused on generic inputs.  The `_images` and batched forms are pinned bit for bit against the single-image forms by
+(win_attn_fused on fixed-point inputs).  chan_qkv (its reduction spans the whole image) is held per partial block to
+tests/golden/chan_ref.py by tests/test_chan_attn_gpu.py.  What remains on the checks of tests/test_ops_gpu.py: win_attn_fused on
+generic inputs.  The `_images` and batched forms are pinned bit for bit against the single-image forms by
 tests/test_batched_*_gpu.py.
 
 Measured on MI355X (the line this module prints: per kernel the worst err and err - allow, both as fractions of max(1, max|ref|), and
