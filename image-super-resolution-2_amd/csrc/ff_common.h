@@ -194,8 +194,9 @@ __device__ __forceinline__ void ff_wave_rows_to_frags(const float* __restrict__ 
 //   naf_tail.hip            naf_tail_kernel: statistics and step (slower through the helpers)
 //   naf_fused.hip           naf_ffn_kernel: statistics, step and split (through the helpers the output bits moved)
 //   naf_front.inc           naf_front_kernel: statistics, step and split (slower through the helpers)
-//   win_attn_fused_v2.inc   win_attn_fused_v2_kernel: statistics and step (slower through the statistics helper)
-//   token_mlp.hip           token_projmlp_kernel, token_projmlp_bf16_kernel: statistics in the ACCUMULATOR layout (a helper spills)
+//   win_attn_fused_v2_ln.inc      win_attn_fused_v2_kernel, hab_link_kernel: statistics and step (slower through the statistics helper)
+//   token_projmlp_ln_stats.inc    token_projmlp_kernel, token_projmlp_bf16_kernel, hab_link_kernel: statistics in the ACCUMULATOR
+//                                 layout (a helper spills; the bf16 step after it is token_projmlp_bf16_ln.inc)
 // Callers: token_mlp_kernel (all three helpers), win_attn_fused_kernel (the statistics; its own optional-gamma step).
 // Where K is a compile-time 16 KS (NAFNet) the k < K masks and the index clamps fold away.
 // Statistics of a row over its K channels: plain sums in st-major order, the lane pair (l, l ^ 32) holds the row's two halves.

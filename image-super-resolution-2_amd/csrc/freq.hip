@@ -241,35 +241,14 @@ __device__ __forceinline__ void irdft_rows_bands_body(const float* __restrict__ 
   const int r = blockIdx.x, Wf = W / 2 + 1, y = r % H;
   int c = r / H;
   if (IMAGES) { out += (long long)(c / 3) * H * W * ldo; c %= 3; }
-  float* urow = sm; float* cs = sm + 2 * Wf; float* sn = cs + W;
-  for (int i = threadIdx.x; i < 2 * Wf; i += 256) urow[i] = U[(long long)r * Wf * 2 + i];
-  for (int i = threadIdx.x; i < W; i += 256) { cs[i] = tc[i]; sn[i] = ts[i]; }
-  __syncthreads();
-  const float nrm = 1.0f / sqrtf((float)W);
-  const int kmax = (W - 1) / 2;                           // bins with a conjugate partner
-  for (int w = threadIdx.x; w < W; w += 256) {
-    float s0 = urow[0], s1 = 0.f;
-    if ((W & 1) == 0) s0 += ((w & 1) ? -1.f : 1.f) * urow[2 * (W / 2)];
-    int idx = 0, k = 1;
-    for (; k + 1 <= kmax; k += 2) {
-      idx += w;
-      if (idx >= W) idx -= W;
-      s0 += 2.f * (urow[2 * k] * cs[idx] - urow[2 * k + 1] * sn[idx]);
-      idx += w;
-      if (idx >= W) idx -= W;
-      s1 += 2.f * (urow[2 * k + 2] * cs[idx] - urow[2 * k + 3] * sn[idx]);
-    }
-    for (; k <= kmax; ++k) {
-      idx += w;
-      if (idx >= W) idx -= W;
-      s0 += 2.f * (urow[2 * k] * cs[idx] - urow[2 * k + 1] * sn[idx]);
-    }
-    const float s = (s0 + s1) * nrm;
-    const float xv = x[(long long)r * W + w];
-    float* o = out + ((long long)y * W + w) * ldo;
-    o[ch_lo + c] = s * bscale[0];
-    o[ch_hi + c] = (xv - s) * bscale[1];
-  }
+#define IRDFT_ROW_STORE                            \
+  const float s = (s0 + s1) * nrm;                 \
+  const float xv = x[(long long)r * W + w];        \
+  float* o = out + ((long long)y * W + w) * ldo;   \
+  o[ch_lo + c] = s * bscale[0];                    \
+  o[ch_hi + c] = (xv - s) * bscale[1];
+#include "freq_irdft_row.inc"
+#undef IRDFT_ROW_STORE
 }
 __global__ __launch_bounds__(256) void irdft_rows_bands_kernel(const float* __restrict__ U, const float* __restrict__ x, int C,
                                                                int H, int W, const float* __restrict__ tc,
@@ -358,31 +337,9 @@ __global__ __launch_bounds__(256) void irdft_rows_kernel(const float* __restrict
                                                          const float* __restrict__ ts, float* __restrict__ out) {
   extern __shared__ float sm[];                           // urow[Wf][2] | cos[W] | sin[W]
   const int r = blockIdx.x, Wf = W / 2 + 1;
-  float* urow = sm; float* cs = sm + 2 * Wf; float* sn = cs + W;
-  for (int i = threadIdx.x; i < 2 * Wf; i += 256) urow[i] = U[(long long)r * Wf * 2 + i];
-  for (int i = threadIdx.x; i < W; i += 256) { cs[i] = tc[i]; sn[i] = ts[i]; }
-  __syncthreads();
-  const float nrm = 1.0f / sqrtf((float)W);
-  const int kmax = (W - 1) / 2;
-  for (int w = threadIdx.x; w < W; w += 256) {
-    float s0 = urow[0], s1 = 0.f;
-    if ((W & 1) == 0) s0 += ((w & 1) ? -1.f : 1.f) * urow[2 * (W / 2)];
-    int idx = 0, k = 1;
-    for (; k + 1 <= kmax; k += 2) {
-      idx += w;
-      if (idx >= W) idx -= W;
-      s0 += 2.f * (urow[2 * k] * cs[idx] - urow[2 * k + 1] * sn[idx]);
-      idx += w;
-      if (idx >= W) idx -= W;
-      s1 += 2.f * (urow[2 * k + 2] * cs[idx] - urow[2 * k + 3] * sn[idx]);
-    }
-    for (; k <= kmax; ++k) {
-      idx += w;
-      if (idx >= W) idx -= W;
-      s0 += 2.f * (urow[2 * k] * cs[idx] - urow[2 * k + 1] * sn[idx]);
-    }
-    out[(long long)r * W + w] = (s0 + s1) * nrm;
-  }
+#define IRDFT_ROW_STORE out[(long long)r * W + w] = (s0 + s1) * nrm;
+#include "freq_irdft_row.inc"
+#undef IRDFT_ROW_STORE
 }
 
 static int fft2_cols(const float* in, float* out, int C, int H, int Wf, float sign, const float* twH_cos, const float* twH_sin, hipStream_t st) {

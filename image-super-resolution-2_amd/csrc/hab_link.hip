@@ -7,10 +7,15 @@
 // finishes phase A holding the final x of exactly the 32 positions it normalises in phase B, and hands them over through its own LDS
 // patch -- no workgroup barrier, no HBM read.  x_out is still stored (it is block i+1's residual).
 //
-// The arithmetic is the parents', statement for statement: the hidden-tile loop, the LayerNorm sequence and the per-head loop are the
-// SAME TEXT (token_projmlp_bf16_mlp.inc, win_attn_fused_v2_ln.inc, win_attn_fused_v2_heads.inc); the value handed over is what the
-// stand-alone epilogue stores (accumulator + b2 in fp32, zero in the padded channels as the gather leaves them).  Results are bit
-// equal to ff_token_projmlp_images followed by ff_win_attn_fused.
+// The arithmetic is the parents', statement for statement, because every phase they share is the SAME TEXT:
+//   phase A   token_projmlp_bf16_dma.inc (projection image, W1 / W2 slot maps), token_projmlp_bf16_proj.inc (projection MFMAs),
+//             token_projmlp_bf16_ln.inc (norm2 from the accumulators; statistics: token_projmlp_ln_stats.inc), token_projmlp_bf16_mlp.inc
+//             (hidden-tile loop) -- they name a field of TokenProjMlpParams PM_P(f), here p.a_f;
+//   phase B   win_attn_fused_v2_dma.inc (per-head weight image and bias table), win_attn_fused_v2_ln.inc (norm1), win_attn_fused_v2_heads.inc
+//             (per-head loop).
+// What stays inline differs on purpose: the att fragments and residual slices (tok_of, bf16 rows only) and the hand-over.  The value
+// handed over is what the stand-alone epilogue stores (accumulator + b2 in fp32, zero in the padded channels as the gather leaves
+// them).  Results are bit equal to ff_token_projmlp_images followed by ff_win_attn_fused.
 //
 // LDS (one image, both phases; offsets of token_mlp_layout.h and win_attn_layout.h):
 //   phase A   [0, 78 K) projection image, then the W1 / W2 double buffers | [78 K, 146 K) wave patches (residual transposes) | vectors
@@ -48,6 +53,7 @@ struct HabLinkParams {
 static_assert(HL_LDS <= 160 * 1024, "LDS image too large");
 static_assert(W2_LDS <= PM_OFF_VEC, "the attention's tables must stay below phase A's vectors");
 static_assert(W2_WB <= PM_PROJB && W2_OFF_K + 8 * 32 * WF_XS_ROW * 4 <= W2_OFF_REL, "hand-over patches must clear the weight image and the bias tables");
+#define PM_P(f) p.a_##f                                // the shared phase-A texts' name for field f of TokenProjMlpParams
 
 __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   constexpr int WW = 16, WH = 16, RS = 48, TPR = 2, WWM = 16;
@@ -76,47 +82,7 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   FF_STAMP(128, 0);
 
   // ================================================ phase A: block i's projection + residuals + norm2 + MLP ======================
-  // ---- the whole projection (6 tiles x 13 one-KiB pieces, hi plane) by LDS-DMA ----------------------------------------------
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const int pc = wid + 8 * i;
-    if (pc < 78) {
-      const int tile = pc / 13, pw = pc - 13 * tile;
-      int s = pw * 64 + lane;
-      if (s > W1PL - 1) s = W1PL - 1;
-      const int row = s / W1SLOTS;
-      int q = s - row * W1SLOTS;
-      if (q > 23) q = 23;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.a_wp + (long long)tile * (2 * TILE_ELEMS) + row * 192 + q * 8),
-                                       (__attribute__((address_space(3))) void*)(smem + pc * 1024), 16, 0, 0);
-    }
-  }
-  int off1[2], off2[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int s = (wid + 8 * i) * 64 + lane;
-    if (s > W1PL - 1) s = W1PL - 1;
-    int row = s / W1SLOTS, q = s - row * W1SLOTS;
-    if (q > 23) q = 23;
-    off1[i] = row * 192 + q * 8;
-    s = (wid + 8 * i) * 64 + lane;
-    if (s > W2PL - 1) s = W2PL - 1;
-    row = s / W2SLOTS; q = s - row * W2SLOTS;
-    if (q > 3) q = 3;
-    off2[i] = 2 * TILE_ELEMS + row * 32 + q * 8;
-  }
-  auto dma_mlp = [&](int ht, int slot) {
-    const __bf16* rec = p.a_w + (long long)ht * (4 * TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (wid + 8 * i < 13)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off1[i]),
-                                         (__attribute__((address_space(3))) void*)(smem + slot * PM_W1SLOT + (wid + 8 * i) * 1024), 16, 0, 0);
-      if (wid + 8 * i < 15)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off2[i]),
-                                         (__attribute__((address_space(3))) void*)(smem + PM_OFF_W2 + slot * PM_W2SLOT + (wid + 8 * i) * 1024), 16, 0, 0);
-    }
-  };
+#include "token_projmlp_bf16_dma.inc"
   for (int i = tid; i < p.HT * 32; i += 512) B1s[i] = p.a_b1[i];
   if (tid < TM_KP) { Gs[tid] = tid < p.K ? p.a_gamma[tid] : 0.f; Bts[tid] = tid < p.K ? p.a_beta[tid] : 0.f; }
 
@@ -160,25 +126,7 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the projection image, the vectors and the fragments are in place
 
-  f32x16 oacc[6];
-#pragma unroll
-  for (int n = 0; n < 6; ++n) {
-    const float* bpn = p.a_bp + n * 32 + 4 * hh;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[n][r] = bpn[(r & 3) + 8 * (r >> 2)];
-    const unsigned char* ap = smem + n * PM_W1SLOT + l31 * W1ROWB + 16 * hh;
-    bf16x8 fa[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-#pragma unroll
-    for (int st = 0; st < TM_KS; ++st) {
-      const bf16x8 ah = fa[st & 1];
-      if (st + 2 < TM_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-      __builtin_amdgcn_sched_barrier(0);
-      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], oacc[n], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
+#include "token_projmlp_bf16_proj.inc"
   FF_STAMP(128, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // every wave is past the projection image: the MLP's first two tiles may land on it
@@ -207,41 +155,8 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   }
   FF_STAMP(128, 4);
 
-  // ---- LayerNorm(x1) from the accumulators -> fc1 operand (the statement sequence of token_projmlp_bf16_kernel) -----------------
-  {
-    float s = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh < p.K) ? oacc[n][r] : 0.f;
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)p.K;
-    float qv = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh < p.K) ? oacc[n][r] - mean : 0.f;
-        qv += d * d;
-      }
-    qv += __shfl_xor(qv, 32);
-    const float rstd = 1.0f / sqrtf(qv / (float)p.K + p.a_eps);
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-#pragma unroll
-        for (int g2 = 0; g2 < 2; ++g2) {
-          const int c0 = n * 32 + 8 * (2 * s2 + g2) + 4 * hh;
-          const f32x4 g4 = *reinterpret_cast<const f32x4*>(Gs + c0);
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(Bts + c0);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            xh[2 * n + s2][4 * g2 + e] = (__bf16)((oacc[n][8 * s2 + 4 * g2 + e] - mean) * rstd * g4[e] + b4[e]);
-        }
-        asm volatile("" : "+v"(xh[2 * n + s2]) :: "memory");          // (pinned as in the parent: keeps the reads from piling up)
-      }
-  }
+  // ---- LayerNorm(x1) from the accumulators -> fc1 operand --------------------------------------------------------------------
+#include "token_projmlp_bf16_ln.inc"
   FF_STAMP(128, 5);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // tiles 0 and 1 of the MLP have landed
@@ -255,35 +170,7 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   // ================================================ the boundary =================================================================
   // The loop above ended with a workgroup barrier: the W1 / W2 slots and phase A's patches are idle in every wave.  Head 0's weight
   // image (38 one-KiB pieces, 5 per wave), its bias table and the q / k / v biases go out now and land under the hand-over.
-  int woff[5];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    int s = (wid + 8 * i) * 64 + lane;
-    if (s >= W2_HEAD_SLOTS) s = W2_HEAD_SLOTS - 1;
-    const int tile = s / WF_PL, t = s - tile * WF_PL, row = t / WF_SLOTS;
-    int q = t - row * WF_SLOTS;
-    if (q > 2 * WF_KS - 1) q = 2 * WF_KS - 1;
-    woff[i] = tile * (2 * WF_TILE_ELEMS) + row * 192 + q * 8;
-  }
-  const int reln = p.rel_rows * p.rel_stride;           // floats per head table (a multiple of 4)
-  const int relpieces = (reln + 255) >> 8;
-  auto dma_head = [&](int head, int buf) {
-    const __bf16* rec = p.w + (long long)(3 * head) * (2 * WF_TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-      if (wid + 8 * i < W2_PIECES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + woff[i]),
-                                         (__attribute__((address_space(3))) void*)(smem + (wid + 8 * i) * 1024), 16, 0, 0);
-    const float* src = p.rel + (long long)head * reln;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      if (wid + 8 * i < relpieces) {
-        int c = (wid + 8 * i) * 64 + lane;
-        if (c > (reln >> 2) - 1) c = (reln >> 2) - 1;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 4 * c),
-                                         (__attribute__((address_space(3))) void*)(smem + W2_OFF_REL + buf * W2_RELB + WF_REL_PAD * 4 + (wid + 8 * i) * 1024), 16, 0, 0);
-      }
-  };
+#include "win_attn_fused_v2_dma.inc"
   dma_head(0, 0);
   // q / k / v biases; padded V channel 30 is the constant 1 (the denominator channel).  Visible after the head loop's first barrier.
   for (int i = tid; i < 3 * HL_HEADS * 32; i += 512) Bs[i] = (i % 96 == 94) ? 1.0f : p.bias[i];
@@ -363,6 +250,7 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   FF_STAMP(128, 64 + 60);
   FF_STAMP_DRAINED(128, 64 + 61);
 }
+#undef PM_P
 
 extern "C" int ff_hab_link(const float* att, int lda, const float* x, int ldx, const float* c2, int ldc, const float* c2_scale,
                            int scale_ld, int B, long long rows_per_image, float* x_out, int ldxo, long long M, int K, int hidden_tiles,

@@ -46,37 +46,7 @@ __global__ __launch_bounds__(512) void token_mlp_kernel(TokenMlpParams p) {
   const long long tok = (long long)blockIdx.x * 256 + wid * 32 + l31;
   const bool tvalid = tok < p.M;
 
-  // ---- LDS-DMA bookkeeping: this wave fills pieces wid, wid+8, ... of each image; per lane the source offset in a tile record
-  int off1[4], off2[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int s = (wid + 8 * i) * 64 + lane;               // slot in the W1 image (2 planes x 32 rows x 25 slots)
-    if (s >= 2 * W1PL) s = 2 * W1PL - 1;
-    int plane = s / W1PL, t = s - plane * W1PL, row = t / W1SLOTS, q = t - row * W1SLOTS;
-    if (q > 23) q = 23;
-    off1[i] = plane * TILE_ELEMS + row * 192 + q * 8;
-    s = (wid + 8 * i) * 64 + lane;                   // slot in the W2 image (2 planes x 192 rows x 5 slots)
-    if (s >= 2 * W2PL) s = 2 * W2PL - 1;
-    plane = s / W2PL; t = s - plane * W2PL; row = t / W2SLOTS; q = t - row * W2SLOTS;
-    if (q > 3) q = 3;
-    off2[i] = (2 + plane) * TILE_ELEMS + row * 32 + q * 8;
-  }
-  auto dma_w1 = [&](int ht) {
-    const __bf16* rec = p.w + (long long)ht * (4 * TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (wid + 8 * i < W1PIECES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off1[i]),
-                                         (__attribute__((address_space(3))) void*)(W1s + (wid + 8 * i) * 1024), 16, 0, 0);
-  };
-  auto dma_w2 = [&](int ht) {
-    const __bf16* rec = p.w + (long long)ht * (4 * TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (wid + 8 * i < W2PIECES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off2[i]),
-                                         (__attribute__((address_space(3))) void*)(W2s + (wid + 8 * i) * 1024), 16, 0, 0);
-  };
+#include "token_mlp_split_dma.inc"
   dma_w1(0);
   dma_w2(0);
   for (int i = tid; i < p.HT * 32; i += 512) B1s[i] = p.b1[i];
@@ -116,83 +86,11 @@ __global__ __launch_bounds__(512) void token_mlp_kernel(TokenMlpParams p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // tile 0 landed (this wave's pieces)
   __syncthreads();
 
-  for (int ht = 0; ht < p.HT; ++ht) {
-    // ---- H^T tile = b1 + W1 . LN(x)^T ------------------------------------------------------------------------
-    f32x16 hacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hacc[r] = B1s[ht * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
-    {
-      // operands are read TWO k-steps ahead (hipcc otherwise issues ds_read; s_waitcnt lgkmcnt(0); mfma per step and
-      // exposes the LDS latency 24 times per tile); sched_barrier pins the read block in front of the MFMA block
-      const unsigned char* ap = W1s + l31 * W1ROWB + 16 * hh;
-      bf16x8 fa[2], fl[2], fx[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-        fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + W1B);
-        fx[u] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * u);
-      }
-#pragma unroll
-      for (int st = 0; st < TM_KS; ++st) {
-        const bf16x8 ah = fa[st & 1], al = fl[st & 1], xl = fx[st & 1];
-        if (st + 2 < TM_KS) {
-          fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-          fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + W1B);
-          fx[st & 1] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * (st + 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (NTERMS == 3) {
-          hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, hacc, 0, 0, 0);
-          hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], hacc, 0, 0, 0);
-        }
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], hacc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // W2(ht) pieces of this wave have landed
-    __syncthreads();                                    // A: every wave finished reading W1; W2(ht) visible to all
-    if (ht + 1 < p.HT) dma_w1(ht + 1);
-    // ---- GELU, split; registers 8s..8s+7 are the B fragment of k-step s ----------------------------------------
-    bf16x8 gh[2], gl[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float g = ff_gelu_fast(hacc[8 * s + j]);
-        const __bf16 h = (__bf16)g;
-        gh[s][j] = h;
-        gl[s][j] = (__bf16)(g - (float)h);
-      }
-    // ---- OUT^T += W2 . H^T ---------------------------------------------------------------------------------------
-    {
-      const unsigned char* ap = W2s + l31 * W2ROWB + 16 * hh;        // step u = 2n + s: row n*32 + l31, k-step s
-      bf16x8 fa[2], fl[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        fa[u] = *reinterpret_cast<const bf16x8*>(ap + (u >> 1) * 32 * W2ROWB + 32 * (u & 1));
-        fl[u] = *reinterpret_cast<const bf16x8*>(ap + (u >> 1) * 32 * W2ROWB + 32 * (u & 1) + W2B);
-      }
-#pragma unroll
-      for (int u = 0; u < 12; ++u) {
-        const int n = u >> 1, s2 = u & 1;
-        const bf16x8 ah = fa[u & 1], al = fl[u & 1];
-        if (u + 2 < 12) {
-          fa[u & 1] = *reinterpret_cast<const bf16x8*>(ap + ((u + 2) >> 1) * 32 * W2ROWB + 32 * ((u + 2) & 1));
-          fl[u & 1] = *reinterpret_cast<const bf16x8*>(ap + ((u + 2) >> 1) * 32 * W2ROWB + 32 * ((u + 2) & 1) + W2B);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (NTERMS == 3) {
-          oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl[s2], oacc[n], 0, 0, 0);
-          oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh[s2], oacc[n], 0, 0, 0);
-        }
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh[s2], oacc[n], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // W1(ht+1) pieces of this wave have landed
-    __syncthreads();                                    // B: every wave finished reading W2; W1(ht+1) visible to all
-    if (ht + 1 < p.HT) dma_w2(ht + 1);
-  }
+#define TM_NTERMS NTERMS
+#define TM_STAMP(i) do { } while (0)                   // (TokenMlpParams has no stamp member)
+#include "token_mlp_split_tiles.inc"
+#undef TM_STAMP
+#undef TM_NTERMS
 
   // ---- epilogue: all 96 residual loads first (x fragments are dead, registers are free), then per n-tile a
   // transpose through LDS -> coalesced 128-byte row segments.  (out may alias x as far as the compiler knows: a
@@ -306,6 +204,7 @@ struct TokenProjMlpParams {
                           // (wpi workgroups per image, images), so the image index costs no division and no vector register
   FF_STAMP_MEMBER
 };
+#define PM_P(f) p.f                                    // the shared phase texts' name for field f (hab_link.hip: p.a_##f)
 
 __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -318,36 +217,7 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;   // blockIdx.y = image (0 in the single-gate launch)
 
-  int off1[4], off2[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int s = (wid + 8 * i) * 64 + lane;
-    if (s >= 2 * W1PL) s = 2 * W1PL - 1;
-    int plane = s / W1PL, t = s - plane * W1PL, row = t / W1SLOTS, q = t - row * W1SLOTS;
-    if (q > 23) q = 23;
-    off1[i] = plane * TILE_ELEMS + row * 192 + q * 8;
-    s = (wid + 8 * i) * 64 + lane;
-    if (s >= 2 * W2PL) s = 2 * W2PL - 1;
-    plane = s / W2PL; t = s - plane * W2PL; row = t / W2SLOTS; q = t - row * W2SLOTS;
-    if (q > 3) q = 3;
-    off2[i] = (2 + plane) * TILE_ELEMS + row * 32 + q * 8;
-  }
-  auto dma_w1 = [&](int ht) {
-    const __bf16* rec = p.w + (long long)ht * (4 * TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (wid + 8 * i < W1PIECES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off1[i]),
-                                         (__attribute__((address_space(3))) void*)(W1s + (wid + 8 * i) * 1024), 16, 0, 0);
-  };
-  auto dma_w2 = [&](int ht) {
-    const __bf16* rec = p.w + (long long)ht * (4 * TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (wid + 8 * i < W2PIECES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off2[i]),
-                                         (__attribute__((address_space(3))) void*)(W2s + (wid + 8 * i) * 1024), 16, 0, 0);
-  };
+#include "token_mlp_split_dma.inc"
   // projection tile n (a W1-format image) into ring slot 0 = the W1 area, 1 = the W2 area (30 720 B >= 25 600 B)
   auto dma_proj = [&](int n, int slot) {
     const __bf16* rec = p.wp + (long long)n * (2 * TILE_ELEMS);
@@ -456,25 +326,7 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
   FF_STAMP(64, 4);
   // ---- LayerNorm(x1) from the accumulators -> fc1 operand (hi registers, lo rows) -------------------------------------
   {
-    // inline on purpose: through a shared helper (by reference, by value or returning a struct alike) token_projmlp_kernel spills
-    // 28-31 VGPRs (116-128 B of scratch) and token_projmlp_bf16_kernel 6-12 (28-52 B); as written here neither spills
-    float s = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh < p.K) ? oacc[n][r] : 0.f;
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)p.K;
-    float qv = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh < p.K) ? oacc[n][r] - mean : 0.f;
-        qv += d * d;
-      }
-    qv += __shfl_xor(qv, 32);
-    const float rstd = 1.0f / sqrtf(qv / (float)p.K + p.eps);
+#include "token_projmlp_ln_stats.inc"
 #pragma unroll
     for (int n = 0; n < 6; ++n)
 #pragma unroll
@@ -502,79 +354,12 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
   __syncthreads();
   FF_STAMP(64, 6);
 
-  // ---- the MLP over hidden tiles: identical to token_mlp_kernel (W1 columns are permuted to the operand order above) ----
-  for (int ht = 0; ht < p.HT; ++ht) {
-    f32x16 hacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hacc[r] = B1s[ht * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
-    {
-      const unsigned char* ap = W1s + l31 * W1ROWB + 16 * hh;
-      bf16x8 fa[2], fl[2], fx[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-        fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + W1B);
-        fx[u] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * u);
-      }
-#pragma unroll
-      for (int st = 0; st < TM_KS; ++st) {
-        const bf16x8 ah = fa[st & 1], al = fl[st & 1], xl = fx[st & 1];
-        if (st + 2 < TM_KS) {
-          fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-          fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + W1B);
-          fx[st & 1] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * (st + 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, hacc, 0, 0, 0);
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], hacc, 0, 0, 0);
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], hacc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (ht < 3) FF_STAMP(64, 8 + 4 * ht);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (ht < 3) FF_STAMP(64, 9 + 4 * ht);
-    if (ht + 1 < p.HT) dma_w1(ht + 1);
-    bf16x8 gh[2], gl[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float g = ff_gelu_fast(hacc[8 * s + j]);
-        const __bf16 h = (__bf16)g;
-        gh[s][j] = h;
-        gl[s][j] = (__bf16)(g - (float)h);
-      }
-    {
-      const unsigned char* ap = W2s + l31 * W2ROWB + 16 * hh;
-      bf16x8 fa[2], fl[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        fa[u] = *reinterpret_cast<const bf16x8*>(ap + (u >> 1) * 32 * W2ROWB + 32 * (u & 1));
-        fl[u] = *reinterpret_cast<const bf16x8*>(ap + (u >> 1) * 32 * W2ROWB + 32 * (u & 1) + W2B);
-      }
-#pragma unroll
-      for (int u = 0; u < 12; ++u) {
-        const int n = u >> 1, s2 = u & 1;
-        const bf16x8 ah = fa[u & 1], al = fl[u & 1];
-        if (u + 2 < 12) {
-          fa[u & 1] = *reinterpret_cast<const bf16x8*>(ap + ((u + 2) >> 1) * 32 * W2ROWB + 32 * ((u + 2) & 1));
-          fl[u & 1] = *reinterpret_cast<const bf16x8*>(ap + ((u + 2) >> 1) * 32 * W2ROWB + 32 * ((u + 2) & 1) + W2B);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl[s2], oacc[n], 0, 0, 0);
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh[s2], oacc[n], 0, 0, 0);
-        oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh[s2], oacc[n], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (ht < 3) FF_STAMP(64, 10 + 4 * ht);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (ht < 3) FF_STAMP(64, 11 + 4 * ht);
-    if (ht + 1 < p.HT) dma_w2(ht + 1);
-  }
+  // ---- the MLP over hidden tiles (W1 columns are permuted to the operand order above) -----------------------------------
+#define TM_NTERMS 3
+#define TM_STAMP(i) FF_STAMP(64, i)
+#include "token_mlp_split_tiles.inc"
+#undef TM_STAMP
+#undef TM_NTERMS
   FF_STAMP(64, 40);
 
   // ---- epilogue: out = accumulators (x1 + fc2 part) + b2, transposed through LDS into 128-byte row segments ------------
@@ -628,47 +413,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   float* patch = reinterpret_cast<float*>(smem + PM_OFF_PATCH + wid * PM_PATCHB);      // the wave's gather / transpose patch
   FF_STAMP(64, 0);
 
-  // ---- the whole projection (6 tiles x 13 one-KiB pieces, hi plane) by LDS-DMA ----------------------------------------------
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const int pc = wid + 8 * i;
-    if (pc < 78) {
-      const int tile = pc / 13, pw = pc - 13 * tile;
-      int s = pw * 64 + lane;
-      if (s > W1PL - 1) s = W1PL - 1;
-      const int row = s / W1SLOTS;
-      int q = s - row * W1SLOTS;
-      if (q > 23) q = 23;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.wp + (long long)tile * (2 * TILE_ELEMS) + row * 192 + q * 8),
-                                       (__attribute__((address_space(3))) void*)(smem + pc * 1024), 16, 0, 0);
-    }
-  }
-  int off1[2], off2[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int s = (wid + 8 * i) * 64 + lane;
-    if (s > W1PL - 1) s = W1PL - 1;
-    int row = s / W1SLOTS, q = s - row * W1SLOTS;
-    if (q > 23) q = 23;
-    off1[i] = row * 192 + q * 8;
-    s = (wid + 8 * i) * 64 + lane;
-    if (s > W2PL - 1) s = W2PL - 1;
-    row = s / W2SLOTS; q = s - row * W2SLOTS;
-    if (q > 3) q = 3;
-    off2[i] = 2 * TILE_ELEMS + row * 32 + q * 8;
-  }
-  auto dma_mlp = [&](int ht, int slot) {
-    const __bf16* rec = p.w + (long long)ht * (4 * TILE_ELEMS);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (wid + 8 * i < 13)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off1[i]),
-                                         (__attribute__((address_space(3))) void*)(smem + slot * PM_W1SLOT + (wid + 8 * i) * 1024), 16, 0, 0);
-      if (wid + 8 * i < 15)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rec + off2[i]),
-                                         (__attribute__((address_space(3))) void*)(smem + PM_OFF_W2 + slot * PM_W2SLOT + (wid + 8 * i) * 1024), 16, 0, 0);
-    }
-  };
+#include "token_projmlp_bf16_dma.inc"
   for (int i = tid; i < p.HT * 32; i += 512) B1s[i] = p.b1[i];
   if (tid < TM_KP) { Gs[tid] = tid < p.K ? p.gamma[tid] : 0.f; Bts[tid] = tid < p.K ? p.beta[tid] : 0.f; }
 
@@ -724,25 +469,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the projection image, the vectors and the fragments are in place
 
-  f32x16 oacc[6];
-#pragma unroll
-  for (int n = 0; n < 6; ++n) {
-    const float* bpn = p.bp + n * 32 + 4 * hh;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[n][r] = bpn[(r & 3) + 8 * (r >> 2)];
-    const unsigned char* ap = smem + n * PM_W1SLOT + l31 * W1ROWB + 16 * hh;
-    bf16x8 fa[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-#pragma unroll
-    for (int st = 0; st < TM_KS; ++st) {
-      const bf16x8 ah = fa[st & 1];
-      if (st + 2 < TM_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-      __builtin_amdgcn_sched_barrier(0);
-      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], oacc[n], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
+#include "token_projmlp_bf16_proj.inc"
   FF_STAMP(64, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // every wave is past the projection image: the MLP's first two tiles may land on it
@@ -774,44 +501,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   FF_STAMP(64, 4);
 
   // ---- LayerNorm(x1) from the accumulators -> fc1 operand --------------------------------------------------------------------
-  {
-    // inline on purpose: through a shared helper (by reference, by value or returning a struct alike) token_projmlp_kernel spills
-    // 28-31 VGPRs (116-128 B of scratch) and token_projmlp_bf16_kernel 6-12 (28-52 B); as written here neither spills
-    float s = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh < p.K) ? oacc[n][r] : 0.f;
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)p.K;
-    float qv = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh < p.K) ? oacc[n][r] - mean : 0.f;
-        qv += d * d;
-      }
-    qv += __shfl_xor(qv, 32);
-    const float rstd = 1.0f / sqrtf(qv / (float)p.K + p.eps);
-#pragma unroll
-    for (int n = 0; n < 6; ++n)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-#pragma unroll
-        for (int g2 = 0; g2 < 2; ++g2) {
-          const int c0 = n * 32 + 8 * (2 * s2 + g2) + 4 * hh;           // channels of registers 8 s2 + 4 g2 .. + 3 (< 192: the vectors are zero padded)
-          const f32x4 g4 = *reinterpret_cast<const f32x4*>(Gs + c0);
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(Bts + c0);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            xh[2 * n + s2][4 * g2 + e] = (__bf16)((oacc[n][8 * s2 + 4 * g2 + e] - mean) * rstd * g4[e] + b4[e]);
-        }
-        // the fragment is pinned here: left to itself the scheduler issues all 48 vector reads first and sinks the arithmetic
-        // below them (192 live registers, 52 of them spilled)
-        asm volatile("" : "+v"(xh[2 * n + s2]) :: "memory");
-      }
-  }
+#include "token_projmlp_bf16_ln.inc"
   FF_STAMP(64, 5);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // tiles 0 and 1 of the MLP have landed
@@ -850,6 +540,7 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   FF_STAMP(64, 41);
   FF_STAMP_DRAINED(64, 42);
 }
+#undef PM_P
 
 // images == 1: the single-gate launch of ff_token_projmlp, grid (workgroups, 1).  images > 1: grid (workgroups per image, images),
 // image b scales c2 by c2_scale + b * scale_ld.

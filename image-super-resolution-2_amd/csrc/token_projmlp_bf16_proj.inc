@@ -1,0 +1,22 @@
+// Projection of the plain-bf16 token_projmlp phase: the six proj^T tiles (bias as the MFMAs' C-in) into the output accumulators, from
+// the LDS image of token_projmlp_bf16_dma.inc.  A statement sequence of token_projmlp_bf16_kernel, shared as text with hab_link.hip.
+// Expects smem, xh, l31, hh and PM_P(f) (bp); leaves oacc.
+  f32x16 oacc[6];
+#pragma unroll
+  for (int n = 0; n < 6; ++n) {
+    const float* bpn = PM_P(bp) + n * 32 + 4 * hh;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oacc[n][r] = bpn[(r & 3) + 8 * (r >> 2)];
+    const unsigned char* ap = smem + n * PM_W1SLOT + l31 * W1ROWB + 16 * hh;
+    bf16x8 fa[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
+#pragma unroll
+    for (int st = 0; st < TM_KS; ++st) {
+      const bf16x8 ah = fa[st & 1];
+      if (st + 2 < TM_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
+      __builtin_amdgcn_sched_barrier(0);
+      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], oacc[n], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
