@@ -20,6 +20,8 @@
 // LDS (one image, both phases; offsets of token_mlp_layout.h and win_attn_layout.h):
 //   phase A   [0, 78 K) projection image, then the W1 / W2 double buffers | [78 K, 146 K) wave patches (residual transposes) | vectors
 //   phase B   [0, 38 K) a head's weight image | [38 K, 78 K) K x 2 | [78 K, 111 K) V^T x 2 | bias tables x 2 | projection biases
+//   both      above phase A's vectors: gamma1 | beta1 | b2 | the image's gate row | block i's projection bias, copied once in the prologue
+//             (a global read of them later would queue behind the bulk traffic that is in flight by then)
 // Order at the boundary: the hidden-tile loop ends with a workgroup barrier (every wave is past the W1 / W2 slots and, long before,
 // the phase-A patches), so head 0's weight image, its bias table and the projection biases are fetched right there, onto areas no
 // wave touches again in phase A.  The hand-over patch is where the stand-alone attention keeps its gather patch (over the K / V area,
@@ -49,7 +51,8 @@ struct HabLinkParams {
   FF_STAMP_MEMBER
 };
 
-#define HL_LDS (HL_OFF_VEC + (2 * TM_KP + 12 * 32) * 4)
+#define HL_OFF_VEC_B (HL_OFF_VEC + (2 * TM_KP + 12 * 32) * 4)     // gamma1 | beta1 | b2 | gate row | projection bias: read once, in the prologue
+#define HL_LDS (HL_OFF_VEC_B + 5 * TM_KP * 4)
 static_assert(HL_LDS <= 160 * 1024, "LDS image too large");
 static_assert(W2_LDS <= PM_OFF_VEC, "the attention's tables must stay below phase A's vectors");
 static_assert(W2_WB <= PM_PROJB && W2_OFF_K + 8 * 32 * WF_XS_ROW * 4 <= W2_OFF_REL, "hand-over patches must clear the weight image and the bias tables");
@@ -62,6 +65,11 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   float* Gs = reinterpret_cast<float*>(smem + HL_OFF_VEC);
   float* Bts = Gs + TM_KP;
   float* B1s = Bts + TM_KP;
+  float* G1s = reinterpret_cast<float*>(smem + HL_OFF_VEC_B);           // LayerNorm1's gamma / beta, the hand-over's b2, the image's gate row
+  float* Bt1s = G1s + TM_KP;
+  float* B2s = Bt1s + TM_KP;
+  float* Scs = B2s + TM_KP;
+  float* Bps = Scs + TM_KP;                                             // the padded projection bias (token_projmlp_bf16_proj.inc)
   float* Bs = reinterpret_cast<float*>(smem + W2_OFF_BS);
   unsigned* same = reinterpret_cast<unsigned*>(smem + W2_OFF_SAME);     // (the ONES form never reads it)
   const int* ktok = nullptr;                                            // (only the v side output reads it: absent here)
@@ -85,14 +93,24 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
 #include "token_projmlp_bf16_dma.inc"
   for (int i = tid; i < p.HT * 32; i += 512) B1s[i] = p.a_b1[i];
   if (tid < TM_KP) { Gs[tid] = tid < p.K ? p.a_gamma[tid] : 0.f; Bts[tid] = tid < p.K ? p.a_beta[tid] : 0.f; }
+  // phase B's vectors and the gate row, read once here: by the time they are needed every workgroup has its x_out stores in flight, and
+  // a global read would queue behind them.  The padded channels hold zero; the selects that keep them out of a result stay as they are.
+  if (tid >= 256 && tid < 256 + TM_KP) {
+    const int c = tid - 256;
+    const bool cok = c < p.K;
+    G1s[c] = cok ? p.gamma[c] : 0.f; Bt1s[c] = cok ? p.beta[c] : 0.f; B2s[c] = cok ? p.a_b2[c] : 0.f;
+    Scs[c] = cok ? p.a_rs2[(long long)b * p.a_rs2_ld + c] : 0.f;
+    Bps[c] = p.a_bp[c];
+  }
 
   // ---- att rows (bf16) -> fragments: a lane's fragment of k-step st IS 16 bytes of its token's row ---------------------------
   bf16x8 xh[TM_KS];
   {
     const __bf16* arow = p.a_att + tok_of(wid * 32 + l31) * p.a_lda + 8 * hh;
 #pragma unroll
+    for (int st = 0; st < TM_KS; ++st) xh[st] = *reinterpret_cast<const bf16x8*>(arow + 16 * st);      // all twelve in flight, then the masks
+#pragma unroll
     for (int st = 0; st < TM_KS; ++st) {
-      xh[st] = *reinterpret_cast<const bf16x8*>(arow + 16 * st);
       if (16 * st + 8 * hh + 7 >= p.K) {               // the row's padding is never written: mask it
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -102,9 +120,14 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   }
   FF_STAMP(128, 1);
 
-  // ---- residual slices: coalesced float4 loads (lane = window position lane>>3 (+8i) of the wave, channel quad), one slice ahead ----
+  // ---- residual slices: coalesced float4 loads (lane = window position lane>>3 (+8i) of the wave, channel quad), one slice ahead:
+  //      two register sets, slice n + 1 is issued before slice n is consumed; slices 0 and 1 go out right behind the barrier below
+  //      and land under the projection's MFMAs (issued before the wait in front of that barrier, slice 0 only lengthened the wait:
+  //      profiles/hab_link_prefetch.json).  c2 stays the bf16 it is loaded as until it is consumed (the conversion is exact), so that
+  //      nothing waits for a slice before its turn.
   const int tq = lane >> 3, q4 = 4 * (lane & 7);
-  f32x4 rx[4], rc[4];
+  f32x4 rx[2][4];
+  bf16x4 rc[2][4];
   // 32-bit element offsets of the lane's four token rows (entry point: B H W ld < 2^31); channels past K read channel 0 instead --
   // finite values that the zero-padded gamma / beta keep out of fc1 and that the hand-over replaces by zero
   int xo[4], co[4];
@@ -118,13 +141,18 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
     const int cn = (n * 32 + q4 < p.K) ? n * 32 : -q4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      rx[i] = *reinterpret_cast<const f32x4*>(p.a_x + (xo[i] + cn));
-      const bf16x4 h4 = *reinterpret_cast<const bf16x4*>(p.a_c2 + (co[i] + cn));
-      rc[i] = (f32x4){(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
+      rx[n & 1][i] = *reinterpret_cast<const f32x4*>(p.a_x + (xo[i] + cn));
+      rc[n & 1][i] = *reinterpret_cast<const bf16x4*>(p.a_c2 + (co[i] + cn));
     }
   };
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  // vmcnt(0) lgkmcnt(0), as the builtin and not as text: the compiler then knows that nothing is in flight behind it.  After an LDS-DMA
+  // it otherwise makes the next use of a loaded register wait for EVERY load issued before that use -- the slices below included
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0x0070);
+  asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the projection image, the vectors and the fragments are in place
+  load_res(0);                                           // 16.7 MB a slice over all workgroups: they land under the projection's MFMAs
+  load_res(1);
 
 #include "token_projmlp_bf16_proj.inc"
   FF_STAMP(128, 2);
@@ -136,14 +164,14 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
 #pragma unroll
   for (int n = 0; n < 6; ++n) {
     // x1 = proj + shortcut + conv * scale, slice n: through the wave's patch into accumulator order
-    load_res(n);
+    if (n >= 1 && n + 1 < 6) load_res(n + 1);            // (slices 0 and 1 left before the projection)
     const int c4 = n * 32 + q4;
-    f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-    if (c4 < p.K) sc = *reinterpret_cast<const f32x4*>(p.a_rs2 + (long long)b * p.a_rs2_ld + c4);
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(Scs + c4);        // the image's gate, zero in the padded channels
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f32x4 r0 = rx[i];
-      r0 += rc[i] * sc;
+      f32x4 r0 = rx[n & 1][i];
+      const bf16x4 h4 = rc[n & 1][i];
+      r0 += (f32x4){(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]} * sc;
       *reinterpret_cast<f32x4*>(patch + (tq + 8 * i) * 36 + q4) = r0;
     }
 #pragma unroll
@@ -209,7 +237,7 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
         for (int g = 0; g < 4; ++g) {
           const int c0 = n * 32 + 8 * g + 4 * hh;
           const bool cok = c0 < p.K;
-          const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.a_b2 + (cok ? c0 : 0));
+          const f32x4 b4 = *reinterpret_cast<const f32x4*>(B2s + (cok ? c0 : 0));
           f32x4 v4;
 #pragma unroll
           for (int e = 0; e < 4; ++e) v4[e] = cok ? oacc[n][4 * g + e] + b4[e] : 0.f;
@@ -239,7 +267,11 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
     // this wave's pieces of head 0 have landed (and with them the x_out stores issued above)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     FF_STAMP(128, 42);
+#define W2_LN(f) ln1_##f                               // LayerNorm1's gamma / beta come from LDS here
+    const float* const ln1_gamma = G1s;
+    const float* const ln1_beta = Bt1s;
 #include "win_attn_fused_v2_ln.inc"
+#undef W2_LN
   }
   FF_STAMP(128, 64 + 2);
 

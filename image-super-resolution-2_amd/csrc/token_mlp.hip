@@ -406,7 +406,9 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Gs = reinterpret_cast<float*>(smem + PM_OFF_VEC);
   float* Bts = Gs + TM_KP;
-  float* B1s = Bts + TM_KP;
+  float* Scs = Bts + TM_KP;                              // the image's gate row (zero without c2 and in the padded channels)
+  float* Bps = Scs + TM_KP;                              // the padded projection bias (token_projmlp_bf16_proj.inc)
+  float* B1s = Bps + TM_KP;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;   // blockIdx.y = image (0 in the single-gate launch)
@@ -416,6 +418,11 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
 #include "token_projmlp_bf16_dma.inc"
   for (int i = tid; i < p.HT * 32; i += 512) B1s[i] = p.b1[i];
   if (tid < TM_KP) { Gs[tid] = tid < p.K ? p.gamma[tid] : 0.f; Bts[tid] = tid < p.K ? p.beta[tid] : 0.f; }
+  if (tid >= 256 && tid < 256 + TM_KP) {
+    const int c = tid - 256;
+    Scs[c] = (p.c2 && c < p.N) ? p.rs2[(long long)blockIdx.y * p.rs2_ld + c] : 0.f;
+    Bps[c] = p.bp[c];
+  }
 
   // ---- att rows -> bf16 fragments -------------------------------------------------------------------------------------------
   bf16x8 xh[TM_KS];
@@ -424,8 +431,9 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
     const long long tk = tok0 + l31 < p.M ? tok0 + l31 : 0;
     const __bf16* arow = reinterpret_cast<const __bf16*>(p.att) + tk * p.lda + 8 * hh;
 #pragma unroll
+    for (int st = 0; st < TM_KS; ++st) xh[st] = *reinterpret_cast<const bf16x8*>(arow + 16 * st);      // all twelve in flight, then the masks
+#pragma unroll
     for (int st = 0; st < TM_KS; ++st) {
-      xh[st] = *reinterpret_cast<const bf16x8*>(arow + 16 * st);
       if (16 * st + 8 * hh + 7 >= p.K) {               // the row's padding is never written: mask it
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -442,7 +450,12 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   }
   FF_STAMP(64, 1);
 
-  // ---- residual slices: coalesced float4 loads (lane = token row lane>>3 (+8i), channel quad), one slice ahead ----------------
+  // ---- residual slices: coalesced float4 loads (lane = token row lane>>3 (+8i), channel quad), one slice ahead: slice 0 goes out
+  //      right behind the barrier below and lands under the projection's MFMAs, slice n + 1 as soon as slice n has left its registers
+  //      for the wave's patch, under slice n's transpose.  ONE register set: a second one (32 registers, c2 may be fp32 here) spills
+  //      (hab_link.hip, whose c2 is always bf16, has two).  rc holds
+  //      c2 as loaded (bf16 rows: the quad's four bf16 in the first two words, converted -- exactly -- when the slice is consumed), so
+  //      that nothing waits for a slice before its turn.
   const int tq = lane >> 3, q4 = 4 * (lane & 7);
   f32x4 rx[4], rc[4];
   // 32-bit element offsets of the lane's four token rows (launcher: M * ld < 2^31); rows past M read row 0 and channels past N
@@ -461,13 +474,18 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
     for (int i = 0; i < 4; ++i) {
       rx[i] = *reinterpret_cast<const f32x4*>(p.x + (xo[i] + cn));
       if (p.c2 && (p.io_bf16 & 2)) {
-        const bf16x4 h4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(p.c2) + (co[i] + cn));
-        rc[i] = (f32x4){(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
+        const f32x2 w2 = *reinterpret_cast<const f32x2*>(reinterpret_cast<const __bf16*>(p.c2) + (co[i] + cn));
+        rc[i][0] = w2[0]; rc[i][1] = w2[1];
       } else if (p.c2) rc[i] = *reinterpret_cast<const f32x4*>(p.c2 + (co[i] + cn));
     }
   };
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  // vmcnt(0) lgkmcnt(0), as the builtin and not as text: the compiler then knows that nothing is in flight behind it.  After an LDS-DMA
+  // it otherwise makes the next use of a loaded register wait for EVERY load issued before that use -- the slices below included
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0x0070);
+  asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();                          // the projection image, the vectors and the fragments are in place
+  load_res(0);                                           // lands under the projection's MFMAs
 
 #include "token_projmlp_bf16_proj.inc"
   FF_STAMP(64, 2);
@@ -480,16 +498,20 @@ __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpPar
   for (int n = 0; n < 6; ++n) {
     // x1 = proj + shortcut + conv * scale, slice n: through the wave's patch into accumulator order
     {
-      load_res(n);
       const int c4 = n * 32 + q4;
-      f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-      if (p.c2 && c4 < p.N) sc = *reinterpret_cast<const f32x4*>(p.rs2 + (long long)blockIdx.y * p.rs2_ld + c4);
+      const f32x4 sc = *reinterpret_cast<const f32x4*>(Scs + c4);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         f32x4 r0 = rx[i];
-        if (p.c2) r0 += rc[i] * sc;
+        f32x4 c2v = rc[i];
+        if (p.io_bf16 & 2) {
+          const bf16x4 h4 = __builtin_bit_cast(bf16x4, (f32x2){c2v[0], c2v[1]});
+          c2v = (f32x4){(float)h4[0], (float)h4[1], (float)h4[2], (float)h4[3]};
+        }
+        if (p.c2) r0 += c2v * sc;
         *reinterpret_cast<f32x4*>(patch + (tq + 8 * i) * 36 + q4) = r0;
       }
+      if (n + 1 < 6) load_res(n + 1);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 u = *reinterpret_cast<const f32x4*>(patch + l31 * 36 + 8 * g + 4 * hh);
@@ -574,7 +596,7 @@ static int token_projmlp_launch(const float* att, int lda, const float* x, int l
   static ff_device_once once, once2;
   if (!ff_raise_lds(once, "ff_token_projmlp", 160 * 1024, FF_LDS_SAY_ERR, &token_projmlp_kernel)) return FF_ERR_LAUNCH;
   if (nterms == 1) {
-    const size_t lds2 = (size_t)PM_OFF_VEC + (size_t)(2 * TM_KP + hidden_tiles * 32) * 4;
+    const size_t lds2 = (size_t)PM_OFF_VEC + (size_t)(4 * TM_KP + hidden_tiles * 32) * 4;     // gamma | beta | gate row | projection bias | b1
     FF_CHECK_ARG(lds2 <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
     if (!ff_raise_lds(once2, "ff_token_projmlp", 160 * 1024, FF_LDS_SAY_ERR, &token_projmlp_bf16_kernel)) return FF_ERR_LAUNCH;
     hipLaunchKernelGGL(token_projmlp_bf16_kernel, grid, dim3(512), lds2, (hipStream_t)stream, p);

@@ -107,7 +107,9 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
     // every load of this wave has returned (the x rows were consumed above; the head-0 DMA left long before them): the
     // side-output stores below are then the only traffic in flight and nothing later has to wait for them
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#define W2_LN(f) p.f
 #include "win_attn_fused_v2_ln.inc"
+#undef W2_LN
   }
   FF_STAMP(64, 2);
 

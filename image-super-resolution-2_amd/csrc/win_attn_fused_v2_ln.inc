@@ -1,6 +1,7 @@
 // LayerNorm of the fragment rows v[][] -> bf16 operand fragments xh[] (+ the normalised side output): a statement sequence of
 // win_attn_fused_v2_kernel, shared as text with hab_link.hip (the reduction order is part of the result).  Expects p (gamma, beta, K, eps, xn, xn_bf16,
-// ldxn), v, xh, hh, mytok, tvalid.
+// ldxn), v, xh, hh, mytok, tvalid, and W2_LN(f): where the vector f (gamma, beta) is read from -- p.f in the stand-alone kernels, an LDS
+// copy in hab_link.hip, whose LayerNorm runs while every workgroup's x_out stores are in flight (p.gamma stays the "has a norm" test).
     // ff_frag_ln_stats, inline on purpose: with the helper every instantiation goes from 171 / 196 to 246 VGPRs and
     // win_attn_fused_v2_kernel<32, true> from 46.17 / 45.91 us to 46.36 / 47.23 us under the bench
     float mean = 0.f, rstd = 1.f;
@@ -29,8 +30,8 @@
       f32x4 g0 = {1.f, 1.f, 1.f, 1.f}, g1 = g0, b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
       if (p.gamma) {
         const int ka = k0 < p.K ? k0 : 0, kb = k0 + 4 < p.K ? k0 + 4 : 0;
-        g0 = *reinterpret_cast<const f32x4*>(p.gamma + ka); b0 = *reinterpret_cast<const f32x4*>(p.beta + ka);
-        g1 = *reinterpret_cast<const f32x4*>(p.gamma + kb); b1 = *reinterpret_cast<const f32x4*>(p.beta + kb);
+        g0 = *reinterpret_cast<const f32x4*>(W2_LN(gamma) + ka); b0 = *reinterpret_cast<const f32x4*>(W2_LN(beta) + ka);
+        g1 = *reinterpret_cast<const f32x4*>(W2_LN(gamma) + kb); b1 = *reinterpret_cast<const f32x4*>(W2_LN(beta) + kb);
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
