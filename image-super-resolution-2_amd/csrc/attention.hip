@@ -16,6 +16,7 @@
 //     'An accumulator tile as the next MFMA's operand'): P never touches LDS.
 // Keys are processed in chunks of NKT*32 = 128 with an online softmax (2 chunks for 256 keys, 5 for OCAB's 576).
 #include "ff_common.h"
+#include "win_geometry.h"
 
 struct AttnParams {
   const float* qkv;
@@ -44,11 +45,9 @@ __global__ __launch_bounds__(512) void window_attn_kernel(AttnParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
 
-  int bid = blockIdx.x;
-  const int head = bid % p.heads; bid /= p.heads;
-  const int wx = bid % p.nwx; bid /= p.nwx;
-  const int wy = bid % p.nwy;
-  const int b = bid / p.nwy;
+  const int head = (int)blockIdx.x % p.heads;
+  const FFWinId win = ff_win_decode((int)blockIdx.x / p.heads, p.nwx, p.nwy);
+  const int wx = win.wx, wy = win.wy, b = win.b;
 
   const int nk = p.kh * p.kw;
   const int koy = wy * p.wh - (p.kh - p.wh) / 2, kox = wx * p.ww - (p.kw - p.ww) / 2;
@@ -56,17 +55,11 @@ __global__ __launch_bounds__(512) void window_attn_kernel(AttnParams p) {
   // ---- this lane's query token ------------------------------------------------------------
   const int qi = wid * 32 + l31;
   const int qy = wy * p.wh + qi / p.ww, qx = wx * p.ww + qi % p.ww;     // coords in the shifted grid
-  int oy = qy + p.sh, ox = qx + p.sw;
-  if (oy >= p.Hp) oy -= p.Hp;
-  if (ox >= p.Wp) ox -= p.Wp;
-  const bool qvalid = oy < p.H && ox < p.W;
-  const long long qtok = ((long long)b * p.H + oy) * p.W + ox;
+  const FFWinYX qo = ff_win_unshift(qy, qx, p.sh, p.sw, p.Hp, p.Wp);
+  const bool qvalid = qo.y < p.H && qo.x < p.W;
+  const long long qtok = ((long long)b * p.H + qo.y) * p.W + qo.x;
   int qreg_id = 0;
-  if (p.use_mask) {
-    const int ry = qy < p.Hp - p.wh ? 0 : (qy < p.Hp - p.sh ? 1 : 2);
-    const int rx = qx < p.Wp - p.ww ? 0 : (qx < p.Wp - p.sw ? 1 : 2);
-    qreg_id = 3 * ry + rx;
-  }
+  if (p.use_mask) qreg_id = ff_win_region(qy, qx, p.Hp, p.Wp, p.wh, p.ww, p.sh, p.sw);
   float qv[16];
 #pragma unroll
   for (int s = 0; s < 16; ++s) {
@@ -90,20 +83,14 @@ __global__ __launch_bounds__(512) void window_attn_kernel(AttnParams p) {
       int rid = 0;
       if (kidx < nk) {
         const int ky = koy + kidx / p.kw, kx = kox + kidx % p.kw;       // shifted-grid coords
-        if (ky >= 0 && kx >= 0 && ky < p.Hp && kx < p.Wp) {
-          int yy = ky + p.sh, xx = kx + p.sw;
-          if (yy >= p.Hp) yy -= p.Hp;
-          if (xx >= p.Wp) xx -= p.Wp;
-          if (yy < p.H && xx < p.W && l31 < p.d) {
-            const long long tok = ((long long)b * p.H + yy) * p.W + xx;
+        if (FF_WIN_IN_GRID(ky, kx, p.Hp, p.Wp)) {         // (the text form: as a function it swaps the operands of one v_or)
+          const FFWinYX ko = ff_win_unshift(ky, kx, p.sh, p.sw, p.Hp, p.Wp);
+          if (ko.y < p.H && ko.x < p.W && l31 < p.d) {
+            const long long tok = ((long long)b * p.H + ko.y) * p.W + ko.x;
             kval = p.qkv[tok * p.ldq + p.k_off + head * p.d + l31];
             vval = p.qkv[tok * p.ldq + p.v_off + head * p.d + l31];
           }
-          if (p.use_mask) {
-            const int ry = ky < p.Hp - p.wh ? 0 : (ky < p.Hp - p.sh ? 1 : 2);
-            const int rx = kx < p.Wp - p.ww ? 0 : (kx < p.Wp - p.sw ? 1 : 2);
-            rid = 3 * ry + rx;
-          }
+          if (p.use_mask) rid = ff_win_region(ky, kx, p.Hp, p.Wp, p.wh, p.ww, p.sh, p.sw);
         }
       }
       Kt[l31 * KTS + kk] = kval;

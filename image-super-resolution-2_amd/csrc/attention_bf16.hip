@@ -9,6 +9,7 @@
 // NTERMS = 3: every product is hi*hi + lo*hi + hi*lo of bf16 splits (fp32-grade); NTERMS = 1: plain bf16.
 // Softmax in base 2: p = exp2(fma(s, log2e, -m*log2e)) -- one v_fma + one v_exp_f32 per element.
 #include "ff_common.h"
+#include "win_geometry.h"
 
 struct AttnBfParams {
   const float* qkv;
@@ -50,27 +51,19 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
 
-  int bid = blockIdx.x;
-  const int head = bid % p.heads; bid /= p.heads;
-  const int wx = bid % p.nwx; bid /= p.nwx;
-  const int wy = bid % p.nwy;
-  const int b = bid / p.nwy;
+  const int head = (int)blockIdx.x % p.heads;
+  const FFWinId win = ff_win_decode((int)blockIdx.x / p.heads, p.nwx, p.nwy);
+  const int wx = win.wx, wy = win.wy, b = win.b;
   const int nk = p.kh * p.kw;
   const int koy = wy * p.wh - (p.kh - p.wh) / 2, kox = wx * p.ww - (p.kw - p.ww) / 2;
 
   const int qi = wid * 32 + l31;
   const int qy = wy * p.wh + qi / p.ww, qx = wx * p.ww + qi % p.ww;
-  int oy = qy + p.sh, ox = qx + p.sw;
-  if (oy >= p.Hp) oy -= p.Hp;
-  if (ox >= p.Wp) ox -= p.Wp;
-  const bool qvalid = oy < p.H && ox < p.W;
-  const long long qtok = ((long long)b * p.H + oy) * p.W + ox;
+  const FFWinYX qo = ff_win_unshift(qy, qx, p.sh, p.sw, p.Hp, p.Wp);
+  const bool qvalid = qo.y < p.H && qo.x < p.W;
+  const long long qtok = ((long long)b * p.H + qo.y) * p.W + qo.x;
   int qreg_id = 0;
-  if (p.use_mask) {
-    const int ry = qy < p.Hp - p.wh ? 0 : (qy < p.Hp - p.sh ? 1 : 2);
-    const int rx = qx < p.Wp - p.ww ? 0 : (qx < p.Wp - p.sw ? 1 : 2);
-    qreg_id = 3 * ry + rx;
-  }
+  if (p.use_mask) qreg_id = ff_win_region(qy, qx, p.Hp, p.Wp, p.wh, p.ww, p.sh, p.sw);
   bf16x8 qh[2], ql[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -111,16 +104,10 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
     int tk = -1, rid = 0;
     if (kidx < nk) {
       const int ky = koy + kidx / p.kw, kx = kox + kidx % p.kw;
-      if (ky >= 0 && kx >= 0 && ky < p.Hp && kx < p.Wp) {
-        int yy = ky + p.sh, xx = kx + p.sw;
-        if (yy >= p.Hp) yy -= p.Hp;
-        if (xx >= p.Wp) xx -= p.Wp;
+      if (FF_WIN_IN_GRID(ky, kx, p.Hp, p.Wp)) {        // (the text forms: the calls move this kernel's scalar registers)
+        FF_WIN_UNSHIFT_DECL(yy, xx, ky, kx, p.sh, p.sw, p.Hp, p.Wp);
         if (yy < p.H && xx < p.W) tk = (b * p.H + yy) * p.W + xx;
-        if (p.use_mask) {
-          const int ry = ky < p.Hp - p.wh ? 0 : (ky < p.Hp - p.sh ? 1 : 2);
-          const int rx = kx < p.Wp - p.ww ? 0 : (kx < p.Wp - p.sw ? 1 : 2);
-          rid = 3 * ry + rx;
-        }
+        if (p.use_mask) rid = ff_win_region(ky, kx, p.Hp, p.Wp, p.wh, p.ww, p.sh, p.sw);
       }
     }
     ktok[kidx] = tk;
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
     for (int i = tid; i < p.rel_n; i += 512) Tl[i] = p.rel[(long long)head * p.rel_n + i];
   __syncthreads();
   // only windows in the last window row / column contain more than one shift region (mask is all zero elsewhere)
-  const bool blk_mask = p.use_mask && (wy == p.nwy - 1 || wx == p.nwx - 1);
+  const bool blk_mask = p.use_mask && ff_win_has_regions(wx, wy, p.nwx, p.nwy);
   // K/V rows of chunk c+1 are fetched while chunk c is computed; the bias of chunk c is fetched straight into the
   // S^T accumulators before the staging barrier -- one exposed L2 latency per chunk instead of three.
   float kv[8], vv[8];

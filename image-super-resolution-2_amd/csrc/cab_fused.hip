@@ -240,13 +240,7 @@ void cab_fused_kernel(CabParams p) {
   FF_STAMP(8, 3);
 
   // ---- phase 3: conv2, the tap loop of conv3x3_halo_kernel<4,2,2,3,32,.,.,1> on the c1 tile -------------------------------------------------------
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#include "gemm_acc_zero.inc"
   int aoff[MI], boff[NI];
 #pragma unroll
   for (int i = 0; i < MI; ++i) aoff[i] = ((wr * MI + i) * 2 + (l31 >> 4)) * PROW + (l31 & 15) * ROWB + 16 * hh;

@@ -111,35 +111,7 @@ __global__ __launch_bounds__(512) void chan_qkv_kernel(ChanQkvParams p) {
 
   auto gemm_tile = [&](int buf, bool swap, f32x16& acc) {
     const unsigned char* ap = smem + buf * CQ_BUFB + l31 * CQ_ROWB + 16 * hh;
-    bf16x8 fa[2], fl[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-      fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + CQ_PLB);
-    }
-#pragma unroll
-    for (int st = 0; st < CQ_KS; ++st) {
-      const bf16x8 ah = fa[st & 1], al = fl[st & 1];
-      if (st + 2 < CQ_KS) {
-        fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-        fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + CQ_PLB);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (!swap) {
-        if (NTERMS == 3) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl[st], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], acc, 0, 0, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], acc, 0, 0, 0);
-      } else {
-        if (NTERMS == 3) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[st], ah, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], al, acc, 0, 0, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], ah, acc, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ff_tile_mfma<CQ_KS, NTERMS>(ap, CQ_PLB, xh, xl, swap, acc);
   };
   int it = 0;
   auto ring_step = [&]() {

@@ -178,13 +178,7 @@ void conv3x3_halo_kernel(HaloParams p) {
   store_x();
   FF_STAMP(8, 1);
 
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#include "gemm_acc_zero.inc"
 
   // per-lane LDS byte offsets (tap (0,0)): pixel row of m-tile i, weight row of n-tile j
   int aoff[MI], boff[NI];

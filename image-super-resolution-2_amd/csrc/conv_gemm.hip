@@ -145,13 +145,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     }
   };
 
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#include "gemm_acc_zero.inc"
 
   const int nchunks = (p.K + BK - 1) / BK;
   load_chunk(0);

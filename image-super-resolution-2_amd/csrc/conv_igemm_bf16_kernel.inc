@@ -157,13 +157,7 @@ __global__ __launch_bounds__(WM * WN * 64) void CIG_KERNEL(ConvBfParams p) {
     }
   };
 
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#include "gemm_acc_zero.inc"
 
   const int nchunks = p.Kp / BKB;
   load_chunk(0);

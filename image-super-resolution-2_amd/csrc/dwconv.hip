@@ -8,6 +8,12 @@
 //   out = act( (sum_taps w*x + bias) * post_scale + post_shift ) * mul_in      (mul_in optional: the SGFN gate, dat_arch.py:123)
 #include "ff_common.h"
 
+// grid of the grid-stride kernels below: one thread per item, capped at 32 workgroups for each of the 256 CUs
+static inline unsigned dw_grid(long long total) {
+  const long long nb = (total + 255) / 256;
+  return (unsigned)(nb > 256 * 32 ? 256 * 32 : nb);
+}
+
 struct DwParams {
   const float* in; float* out; const float* w; const float* bias; const float* ps; const float* pt; const float* mulin;
   int ldm, ldi, ldo, B, H, W, C, Ho, Wo, KH, KW, sy, sx, py, px, act;
@@ -18,22 +24,16 @@ __global__ __launch_bounds__(256) void dwconv_vec4_kernel(DwParams p) {
   const long long total = (long long)p.B * p.Ho * p.Wo * c4n;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
     const int c = (int)(idx % c4n) * 4;
-    long long pix = idx / c4n;
-    const int ox = (int)(pix % p.Wo); pix /= p.Wo;
-    const int oy = (int)(pix % p.Ho);
-    const int b = (int)(pix / p.Ho);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int ky = 0; ky < p.KH; ++ky) {
-      const int iy = oy * p.sy - p.py + ky;
-      if ((unsigned)iy >= (unsigned)p.H) continue;
-      for (int kx = 0; kx < p.KW; ++kx) {
-        const int ix = ox * p.sx - p.px + kx;
-        if ((unsigned)ix >= (unsigned)p.W) continue;
-        const f32x4 x = *reinterpret_cast<const f32x4*>(p.in + ((long long)(b * p.H + iy) * p.W + ix) * p.ldi + c);
-        const f32x4 w = *reinterpret_cast<const f32x4*>(p.w + (long long)(ky * p.KW + kx) * p.C + c);
-        acc += x * w;
-      }
-    }
+#define DW_CN c4n
+#define DW_ACC_INIT f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#define DW_TAP                                                                                                        \
+  const f32x4 x = *reinterpret_cast<const f32x4*>(p.in + ((long long)(b * p.H + iy) * p.W + ix) * p.ldi + c);         \
+  const f32x4 w = *reinterpret_cast<const f32x4*>(p.w + (long long)(ky * p.KW + kx) * p.C + c);                       \
+  acc += x * w;
+#include "dwconv_generic_taps.inc"
+#undef DW_CN
+#undef DW_ACC_INIT
+#undef DW_TAP
     f32x4 r;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -46,67 +46,33 @@ __global__ __launch_bounds__(256) void dwconv_vec4_kernel(DwParams p) {
   }
 }
 
-// 3x3 / stride 1 / pad 1 specialisation (DAT's two depth-wise convs, dat_arch.py:109,403): a thread owns 4 channels of a
-// 4-row output strip, keeps the 9 tap weights in registers and slides a 3-column window down 6 input rows, so each
-// output costs 4.5 float4 loads instead of 9 and no per-tap weight loads or bounds branches.
+// 3x3 / stride 1 / pad 1 specialisation (DAT's two depth-wise convs, dat_arch.py:109,403): the strip body of dwconv3x3_strip.inc with
+// plain taps;  out = act((acc + bias) * post_scale + post_shift) * mul_in.
 template <int ACT>
 __global__ __launch_bounds__(256, 4) void dwconv3x3_strip_kernel(DwParams p) {
-  const int c4n = p.C >> 2;
-  const int nstrip = (p.H + 3) >> 2;
-  const long long total = (long long)p.B * nstrip * p.W * c4n;
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-    const int c = (int)(idx % c4n) * 4;
-    long long t = idx / c4n;
-    const int ox = (int)(t % p.W); t /= p.W;
-    const int y0 = (int)(t % nstrip) * 4;
-    const int b = (int)(t / nstrip);
-    f32x4 w[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) w[k] = *reinterpret_cast<const f32x4*>(p.w + (long long)k * p.C + c);
-    f32x4 bias = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + c) : z4;
-    f32x4 ps = {1.f, 1.f, 1.f, 1.f}, pt = z4;
-    if (p.ps) { ps = *reinterpret_cast<const f32x4*>(p.ps + c); pt = *reinterpret_cast<const f32x4*>(p.pt + c); }
-    // one input row at a time feeding up to three output rows (see dwconv3x3_ln_strip_kernel): same (ky, kx) accumulation order per
-    // output, a third fewer live registers, four waves per SIMD
-    f32x4 acc4[4] = {z4, z4, z4, z4};
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const int iy = y0 - 1 + r;
-      const bool oky = (unsigned)iy < (unsigned)p.H;
-      f32x4 t[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int ix = ox - 1 + k;
-        const bool ok = oky && (unsigned)ix < (unsigned)p.W;
-        const f32x4 u = *reinterpret_cast<const f32x4*>(p.in + (ok ? ((long long)(b * p.H + iy) * p.W + ix) * p.ldi + c : 0));
-        t[k] = ok ? u : z4;
-      }
-#pragma unroll
-      for (int ky = 2; ky >= 0; --ky) {
-        const int o = r - ky;
-        if (o >= 0 && o < 4) {
-          acc4[o] += t[0] * w[ky * 3];
-          acc4[o] += t[1] * w[ky * 3 + 1];
-          acc4[o] += t[2] * w[ky * 3 + 2];
-        }
-      }
-      asm volatile("" : "+v"(acc4[0]), "+v"(acc4[1]), "+v"(acc4[2]), "+v"(acc4[3]) : : "memory");
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (y0 + r >= p.H) break;
-      const long long pix = (long long)(b * p.H + y0 + r) * p.W + ox;
-      const f32x4 acc = (acc4[r] + bias) * ps + pt;
-      const f32x4 m = p.mulin ? *reinterpret_cast<const f32x4*>(p.mulin + pix * p.ldm + c) : (f32x4){1.f, 1.f, 1.f, 1.f};
-      f32x4 o;
-#pragma unroll
-      // GELU through the 1.5e-7-accurate erf of ff_gelu_fast: the libm erff costs ~55 VALU ops with divergent branches and made
-      // this HBM-bound kernel VALU-bound (66 us for 94 MB at 65 536 x 180; r2)
-      for (int e = 0; e < 4; ++e) o[e] = ff_act_c<ACT, true>(acc[e]) * m[e];
-      *reinterpret_cast<f32x4*>(p.out + pix * p.ldo + c) = o;
-    }
+#define DW_STRIP_VECS                                                                                                     \
+  f32x4 bias = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + c) : z4;                                                 \
+  f32x4 ps = {1.f, 1.f, 1.f, 1.f}, pt = z4;                                                                               \
+  if (p.ps) { ps = *reinterpret_cast<const f32x4*>(p.ps + c); pt = *reinterpret_cast<const f32x4*>(p.pt + c); }
+#define DW_STRIP_TAP                                                                                                      \
+  const f32x4 u = *reinterpret_cast<const f32x4*>(p.in + (ok ? ((long long)(b * p.H + iy) * p.W + ix) * p.ldi + c : 0)); \
+  t[k] = ok ? u : z4;
+  // ff_act_c<ACT, true>: GELU through the 1.5e-7-accurate erf of ff_gelu_fast -- the libm erff costs ~55 VALU ops with divergent branches
+  // and made this HBM-bound kernel VALU-bound (66 us for 94 MB at 65 536 x 180; r2)
+#define DW_STRIP_STORE                                                                                                    \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                         \
+    if (y0 + r >= p.H) break;                                                                                             \
+    const long long pix = (long long)(b * p.H + y0 + r) * p.W + ox;                                                       \
+    const f32x4 acc = (acc4[r] + bias) * ps + pt;                                                                         \
+    const f32x4 m = p.mulin ? *reinterpret_cast<const f32x4*>(p.mulin + pix * p.ldm + c) : (f32x4){1.f, 1.f, 1.f, 1.f};   \
+    f32x4 o;                                                                                                              \
+    _Pragma("unroll") for (int e = 0; e < 4; ++e) o[e] = ff_act_c<ACT, true>(acc[e]) * m[e];                              \
+    *reinterpret_cast<f32x4*>(p.out + pix * p.ldo + c) = o;                                                               \
   }
+#include "dwconv3x3_strip.inc"
+#undef DW_STRIP_VECS
+#undef DW_STRIP_TAP
+#undef DW_STRIP_STORE
 }
 
 // Register-tiled depth-wise convolution, stride 1, "same" padding, for the large kernels of the LKA chain
@@ -182,62 +148,28 @@ struct DwLnParams {
 };
 
 __global__ __launch_bounds__(256, 4) void dwconv3x3_ln_strip_kernel(DwLnParams p) {
-  const int c4n = p.C >> 2;
-  const int nstrip = (p.H + 3) >> 2;
-  const long long total = (long long)p.B * nstrip * p.W * c4n;
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-    const int c = (int)(idx % c4n) * 4;
-    long long t = idx / c4n;
-    const int ox = (int)(t % p.W); t /= p.W;
-    const int y0 = (int)(t % nstrip) * 4;
-    const int b = (int)(t / nstrip);
-    f32x4 w[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) w[k] = *reinterpret_cast<const f32x4*>(p.w + (long long)k * p.C + c);
-    const f32x4 bias = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + c) : z4;
-    const f32x4 g4 = *reinterpret_cast<const f32x4*>(p.gamma + c), b4 = *reinterpret_cast<const f32x4*>(p.beta + c);
-    // One input row at a time (three normalised elements) feeding up to three output rows: the whole 6 x 3 window never sits in
-    // registers next to the nine taps (136 VGPRs -> under 128 = four waves per SIMD for this bandwidth-bound kernel); each output
-    // still accumulates its taps in (ky, kx) order, so the result is bit-identical to the windowed form.
-    f32x4 acc4[4] = {z4, z4, z4, z4};
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const int iy = y0 - 1 + r;
-      const bool oky = (unsigned)iy < (unsigned)p.H;
-      f32x4 t[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int ix = ox - 1 + k;
-        const bool ok = oky && (unsigned)ix < (unsigned)p.W;
-        const long long tk = ok ? (long long)(b * p.H + iy) * p.W + ix : 0;
-        const f32x4 u = *reinterpret_cast<const f32x4*>(p.in + tk * p.ldi + c);
-        const float2 ms = *reinterpret_cast<const float2*>(p.stats + 2 * tk);
-        t[k] = ok ? (u - ms.x) * ms.y * g4 + b4 : z4;
-      }
-#pragma unroll
-      for (int ky = 2; ky >= 0; --ky) {                          // output row o = r - ky receives its tap row ky
-        const int o = r - ky;
-        if (o >= 0 && o < 4) {
-          acc4[o] += t[0] * w[ky * 3];
-          acc4[o] += t[1] * w[ky * 3 + 1];
-          acc4[o] += t[2] * w[ky * 3 + 2];
-        }
-      }
-      asm volatile("" : "+v"(acc4[0]), "+v"(acc4[1]), "+v"(acc4[2]), "+v"(acc4[3]) : : "memory");
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc4[r] += bias;
-    // the gate operand is fetched only now (window and taps are dead): 128 VGPRs = four waves per SIMD for this bandwidth-bound kernel
-    asm volatile("" : "+v"(acc4[0]), "+v"(acc4[1]), "+v"(acc4[2]), "+v"(acc4[3]) : : "memory");
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (y0 + r >= p.H) break;
-      const long long pix = (long long)(b * p.H + y0 + r) * p.W + ox;
-      const f32x4 m = p.mulin ? *reinterpret_cast<const f32x4*>(p.mulin + pix * p.ldm + c) : (f32x4){1.f, 1.f, 1.f, 1.f};
-      *reinterpret_cast<f32x4*>(p.out + pix * p.ldo + c) = acc4[r] * m;
-    }
+#define DW_STRIP_VECS                                                                                                     \
+  const f32x4 bias = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + c) : z4;                                           \
+  const f32x4 g4 = *reinterpret_cast<const f32x4*>(p.gamma + c), b4 = *reinterpret_cast<const f32x4*>(p.beta + c);
+#define DW_STRIP_TAP                                                                                                      \
+  const long long tk = ok ? (long long)(b * p.H + iy) * p.W + ix : 0;                                                     \
+  const f32x4 u = *reinterpret_cast<const f32x4*>(p.in + tk * p.ldi + c);                                                 \
+  const float2 ms = *reinterpret_cast<const float2*>(p.stats + 2 * tk);                                                   \
+  t[k] = ok ? (u - ms.x) * ms.y * g4 + b4 : z4;
+  // the gate operand is fetched only after the bias (window and taps are dead): 128 VGPRs = four waves per SIMD
+#define DW_STRIP_STORE                                                                                                    \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r) acc4[r] += bias;                                                          \
+  asm volatile("" : "+v"(acc4[0]), "+v"(acc4[1]), "+v"(acc4[2]), "+v"(acc4[3]) : : "memory");                             \
+  _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                         \
+    if (y0 + r >= p.H) break;                                                                                             \
+    const long long pix = (long long)(b * p.H + y0 + r) * p.W + ox;                                                       \
+    const f32x4 m = p.mulin ? *reinterpret_cast<const f32x4*>(p.mulin + pix * p.ldm + c) : (f32x4){1.f, 1.f, 1.f, 1.f};   \
+    *reinterpret_cast<f32x4*>(p.out + pix * p.ldo + c) = acc4[r] * m;                                                     \
   }
+#include "dwconv3x3_strip.inc"
+#undef DW_STRIP_VECS
+#undef DW_STRIP_TAP
+#undef DW_STRIP_STORE
 }
 
 extern "C" int ff_dwconv3x3_ln(const float* in, int ldi, float* out, int ldo, int B, int H, int W, int C, const float* w_tapmajor,
@@ -252,31 +184,24 @@ extern "C" int ff_dwconv3x3_ln(const float* in, int ldi, float* out, int ldo, in
   p.in = in; p.out = out; p.w = w_tapmajor; p.bias = bias; p.stats = stats; p.gamma = gamma; p.beta = beta; p.mulin = mul_in;
   p.ldm = ldm; p.ldi = ldi; p.ldo = ldo; p.B = B; p.H = H; p.W = W; p.C = C;
   const long long tot = (long long)B * ((H + 3) / 4) * W * (C / 4);
-  long long nbs = (tot + 255) / 256;
-  if (nbs > 256 * 32) nbs = 256 * 32;
-  hipLaunchKernelGGL(dwconv3x3_ln_strip_kernel, dim3((unsigned)nbs), dim3(256), 0, (hipStream_t)stream, p);
+  const unsigned nbs = dw_grid(tot);
+  hipLaunchKernelGGL(dwconv3x3_ln_strip_kernel, dim3(nbs), dim3(256), 0, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_dwconv3x3_ln");
   return FF_OK;
 }
 
+// dwconv_vec4_kernel one channel at a time
 __global__ __launch_bounds__(256) void dwconv_scalar_kernel(DwParams p) {
   const long long total = (long long)p.B * p.Ho * p.Wo * p.C;
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
     const int c = (int)(idx % p.C);
-    long long pix = idx / p.C;
-    const int ox = (int)(pix % p.Wo); pix /= p.Wo;
-    const int oy = (int)(pix % p.Ho);
-    const int b = (int)(pix / p.Ho);
-    float acc = 0.f;
-    for (int ky = 0; ky < p.KH; ++ky) {
-      const int iy = oy * p.sy - p.py + ky;
-      if ((unsigned)iy >= (unsigned)p.H) continue;
-      for (int kx = 0; kx < p.KW; ++kx) {
-        const int ix = ox * p.sx - p.px + kx;
-        if ((unsigned)ix >= (unsigned)p.W) continue;
-        acc += p.in[((long long)(b * p.H + iy) * p.W + ix) * p.ldi + c] * p.w[(long long)(ky * p.KW + kx) * p.C + c];
-      }
-    }
+#define DW_CN p.C
+#define DW_ACC_INIT float acc = 0.f;
+#define DW_TAP acc += p.in[((long long)(b * p.H + iy) * p.W + ix) * p.ldi + c] * p.w[(long long)(ky * p.KW + kx) * p.C + c];
+#include "dwconv_generic_taps.inc"
+#undef DW_CN
+#undef DW_ACC_INIT
+#undef DW_TAP
     float v = acc + (p.bias ? p.bias[c] : 0.f);
     if (p.ps) v = v * p.ps[c] + p.pt[c];
     float rr = ff_act(v, p.act);
@@ -300,10 +225,9 @@ extern "C" int ff_dwconv2d(const float* in, int ldi, float* out, int ldo, int B,
                   (((uintptr_t)out & 15) == 0) && (((uintptr_t)w_tapmajor & 15) == 0);
   if (v4 && KH == 3 && KW == 3 && sy == 1 && sx == 1 && py == 1 && px == 1 && Ho == H && Wo == W && out != in) {
     const long long tot = (long long)B * ((H + 3) / 4) * W * (C / 4);
-    long long nbs = (tot + 255) / 256;
-    if (nbs > 256 * 32) nbs = 256 * 32;
+    const unsigned nbs = dw_grid(tot);
     auto go = [&](auto A) {
-      hipLaunchKernelGGL((dwconv3x3_strip_kernel<decltype(A)::value>), dim3((unsigned)nbs), dim3(256), 0, (hipStream_t)stream, p);
+      hipLaunchKernelGGL((dwconv3x3_strip_kernel<decltype(A)::value>), dim3(nbs), dim3(256), 0, (hipStream_t)stream, p);
     };
     FF_DISPATCH_ACT(act, go);
     FF_LAUNCH_CHECK("ff_dwconv2d");
@@ -313,21 +237,19 @@ extern "C" int ff_dwconv2d(const float* in, int ldi, float* out, int ldo, int B,
       ((KH == 1 && KW == 21) || (KH == 21 && KW == 1) || (KH == 5 && KW == 5))) {
     const int ry = KH == 21 ? 8 : (KH == 5 ? 2 : 1), rx = KW == 21 ? 8 : (KW == 5 ? 2 : 1);
     const long long tot = (long long)B * ((H + ry - 1) / ry) * ((W + rx - 1) / rx) * (C / 4);
-    long long nbt = (tot + 255) / 256;
-    if (nbt > 256 * 32) nbt = 256 * 32;
-    if (KW == 21) hipLaunchKernelGGL((dwconv_tile_kernel<1, 21, 1, 8>), dim3((unsigned)nbt), dim3(256), 0, (hipStream_t)stream, p);
-    else if (KH == 21) hipLaunchKernelGGL((dwconv_tile_kernel<21, 1, 8, 1>), dim3((unsigned)nbt), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((dwconv_tile_kernel<5, 5, 2, 2>), dim3((unsigned)nbt), dim3(256), 0, (hipStream_t)stream, p);
+    const unsigned nbt = dw_grid(tot);
+    if (KW == 21) hipLaunchKernelGGL((dwconv_tile_kernel<1, 21, 1, 8>), dim3(nbt), dim3(256), 0, (hipStream_t)stream, p);
+    else if (KH == 21) hipLaunchKernelGGL((dwconv_tile_kernel<21, 1, 8, 1>), dim3(nbt), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((dwconv_tile_kernel<5, 5, 2, 2>), dim3(nbt), dim3(256), 0, (hipStream_t)stream, p);
     FF_LAUNCH_CHECK("ff_dwconv2d");
     return FF_OK;
   }
   const long long total = (long long)B * Ho * Wo * (v4 ? C / 4 : C);
-  long long nb = (total + 255) / 256;
-  if (nb > 256 * 32) nb = 256 * 32;
+  const unsigned nb = dw_grid(total);
   if (v4)
-    hipLaunchKernelGGL(dwconv_vec4_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(dwconv_vec4_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
   else
-    hipLaunchKernelGGL(dwconv_scalar_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(dwconv_scalar_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_dwconv2d");
   return FF_OK;
 }

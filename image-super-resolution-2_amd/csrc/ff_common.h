@@ -189,15 +189,18 @@ __device__ __forceinline__ void ff_wave_rows_to_frags(const float* __restrict__ 
 // ---- LayerNorm on MFMA B fragments (the layout ff_wave_rows_to_frags leaves: v[st][j] = x[row l31][16 st + 8 hh + j]) ----------
 // A LayerNorm or split change is made HERE -- and then carried to the sites that repeat this arithmetic inline, each for a
 // measured reason stated at the site (registers, spills or time moved when the code went through the helpers):
-//   token_linear.hip        token_linear_kernel: statistics and step (optional gamma; the statistics helper costs an occupancy step)
+//   token_linear_kernel.inc token_linear_kernel: statistics (the statistics helper costs an occupancy step)
+//   frag_ln_opt_step.inc    token_linear_kernel, win_attn_fused_kernel: the step where gamma may be absent, the split and the xn side
+//                           store -- ONE text for both
 //   chan_qkv.hip            chan_qkv_kernel: statistics, step and split (slower through the helpers)
 //   naf_tail.hip            naf_tail_kernel: statistics and step (slower through the helpers)
 //   naf_fused.hip           naf_ffn_kernel: statistics, step and split (through the helpers the output bits moved)
 //   naf_front.inc           naf_front_kernel: statistics, step and split (slower through the helpers)
+//   naf_ln_stats.inc        the statistics of the three NAFNet kernels above with the compile-time channel count -- ONE text for them
 //   win_attn_fused_v2_ln.inc      win_attn_fused_v2_kernel, hab_link_kernel: statistics and step (slower through the statistics helper)
 //   token_projmlp_ln_stats.inc    token_projmlp_kernel, token_projmlp_bf16_kernel, hab_link_kernel: statistics in the ACCUMULATOR
 //                                 layout (a helper spills; the bf16 step after it is token_projmlp_bf16_ln.inc)
-// Callers: token_mlp_kernel (all three helpers), win_attn_fused_kernel (the statistics; its own optional-gamma step).
+// Callers: token_mlp_kernel (all three helpers), win_attn_fused_kernel (the statistics; its step is frag_ln_opt_step.inc).
 // Where K is a compile-time 16 KS (NAFNet) the k < K masks and the index clamps fold away.
 // Statistics of a row over its K channels: plain sums in st-major order, the lane pair (l, l ^ 32) holds the row's two halves.
 template <int KS>
@@ -239,6 +242,51 @@ __device__ __forceinline__ void ff_frag_ln_step(const float (&v)[8], const float
 __device__ __forceinline__ void ff_bf16_split(float f, __bf16& h, __bf16& l) {
   h = (__bf16)f;
   l = (__bf16)(f - (float)h);
+}
+
+// ---- the weight-tile MFMA loop of the token-stationary kernels ------------------------------------------------------------------
+// A change to this loop is made HERE and carried to the three texts that repeat it for kernels whose assembly moved through the function:
+//   token_linear_tile_mfma.inc          token_linear_kernel: gate GEMM and main tile loop
+//   token_projmlp_bf16_tile_mfma.inc    token_projmlp_bf16_kernel, hab_link_kernel: projection and fc1 tile (hi plane only)
+//   token_mlp_split_tile_mfma.inc       token_mlp_kernel, token_projmlp_kernel: the tokens' lo fragments read from LDS
+// One 32-row weight tile in LDS times the wave's KS fragment steps, accumulated into acc.  ap is the lane's 16 bytes of k-step 0 in
+// the tile's hi plane (row l31, + 16 hh; a k-step is 32 bytes further), the lo plane lies plane_bytes behind it.  NTERMS = 3 is the
+// split-bf16 product hi.lo + lo.hi + hi.hi, NTERMS = 1 reads the hi plane only (xl and plane_bytes are then unused: pass xh, 0).
+// swap = false: acc[weight row][token] (lane = token); true: acc[token][weight row].
+// Operands are read TWO k-steps ahead (hipcc otherwise issues ds_read; s_waitcnt lgkmcnt(0); mfma per step and exposes the LDS
+// latency at every step); the sched_barrier pair pins the read block in front of the MFMA block.
+template <int KS, int NTERMS>
+__device__ __forceinline__ void ff_tile_mfma(const unsigned char* ap, int plane_bytes, const bf16x8 (&xh)[KS], const bf16x8 (&xl)[KS],
+                                             bool swap, f32x16& acc) {
+  bf16x8 fa[2], fl[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
+    if (NTERMS == 3) fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + plane_bytes);
+  }
+#pragma unroll
+  for (int st = 0; st < KS; ++st) {
+    const bf16x8 ah = fa[st & 1], al = fl[st & 1];
+    if (st + 2 < KS) {
+      fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
+      if (NTERMS == 3) fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + plane_bytes);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (!swap) {
+      if (NTERMS == 3) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl[st], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], acc, 0, 0, 0);
+      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], acc, 0, 0, 0);
+    } else {
+      if (NTERMS == 3) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[st], ah, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], al, acc, 0, 0, 0);
+      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], ah, acc, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 // ---- small helpers shared by several files ---------------------------------------------------------------------------------

@@ -126,13 +126,7 @@ __device__ __forceinline__ void gemm_rows_bf16_body(const RowsGemmParams& p) {
                                        (__attribute__((address_space(3))) void*)(dst + ABYTES + (wid + NW * i) * 1024), 16, 0, 0);
   };
 
-  f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#include "gemm_acc_zero.inc"
 
   const int sw = (l31 >> 1) & 7;                    // tile rows are multiples of 32 apart: the swizzle depends on l31 only
   const int arow = (wr * TM + l31) * 128, brow = ABYTES + (wc * TN + l31) * 128;

@@ -27,6 +27,7 @@
 // wave touches again in phase A.  The hand-over patch is where the stand-alone attention keeps its gather patch (over the K / V area,
 // clear of all three), and the per-head loop's first barrier orders every wave's last patch read before the first K / V^T write.
 #include "ff_common.h"
+#include "win_geometry.h"
 #include "token_mlp_layout.h"
 #include "win_attn_layout.h"
 
@@ -75,16 +76,12 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   const int* ktok = nullptr;                                            // (only the v side output reads it: absent here)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  int bid = blockIdx.x;
-  const int wx = bid % p.nwx; bid /= p.nwx;
-  const int wy = bid % p.nwy;
-  const int b = bid / p.nwy;                                            // image: its gate row, its tokens
+  const FFWinId win = ff_win_decode(blockIdx.x, p.nwx, p.nwy);
+  const int wx = win.wx, wy = win.wy, b = win.b;            // image: its gate row, its tokens
   float* patch = reinterpret_cast<float*>(smem + PM_OFF_PATCH + wid * PM_PATCHB);
   // window position -> token (the cyclic shift is index arithmetic; H and W are multiples of 16, so every position is a token)
   auto tok_of = [&](int pos) {
-    int oy = wy * WH + (pos >> 4) + p.sh, ox = wx * WW + (pos & 15) + p.sw;
-    if (oy >= p.H) oy -= p.H;
-    if (ox >= p.W) ox -= p.W;
+    FF_WIN_UNSHIFT_DECL(oy, ox, wy * WH + (pos >> 4), wx * WW + (pos & 15), p.sh, p.sw, p.H, p.W);      // (the text form: a call moves registers)
     return (b * p.H + oy) * p.W + ox;
   };
   FF_STAMP(128, 0);
@@ -203,18 +200,12 @@ __global__ __launch_bounds__(512) void hab_link_kernel(HabLinkParams p) {
   // q / k / v biases; padded V channel 30 is the constant 1 (the denominator channel).  Visible after the head loop's first barrier.
   for (int i = tid; i < 3 * HL_HEADS * 32; i += 512) Bs[i] = (i % 96 == 94) ? 1.0f : p.bias[i];
 
-  const bool blk_mask = p.use_mask && (wy == p.nwy - 1 || wx == p.nwx - 1);
+  const bool blk_mask = p.use_mask && ff_win_has_regions(wx, wy, p.nwx, p.nwy);
   const int qi = wid * 32 + 31 - l31;                  // this lane's window position in phase B (query; also one of the wave's keys)
   const int mytok = tok_of(qi);
   constexpr bool tvalid = true, kill_pad = false;
   constexpr unsigned vmask = 0xffffffffu;
-  int qreg_id = 0;
-  if (p.use_mask) {
-    const int qy = wy * WH + qi / WW, qx = wx * WW + qi % WW;
-    const int ry = qy < p.H - WH ? 0 : (qy < p.H - p.sh ? 1 : 2);
-    const int rx2 = qx < p.W - WW ? 0 : (qx < p.W - p.sw ? 1 : 2);
-    qreg_id = 3 * ry + rx2;
-  }
+  const int qreg_id = p.use_mask ? ff_win_region(wy * WH + qi / WW, wx * WW + qi % WW, p.H, p.W, WH, WW, p.sh, p.sw) : 0;
   const float msy = (qreg_id / 3 == 2) ? -7.0625f : 7.0625f, msx = (qreg_id % 3 == 2) ? -7.0625f : 7.0625f;
 
   // ---- hand-over: x_out = accumulators + b2 leaves through the wave's patch twice -- as 128-byte row segments to memory (block

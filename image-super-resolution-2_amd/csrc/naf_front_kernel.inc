@@ -100,20 +100,7 @@ __global__ __launch_bounds__(512, KS == 4 ? 4 : 2) void NF_KERNEL(NafFrontParams
     }
     // the LayerNorm of ff_common.h (ff_frag_ln_stats / _step / ff_bf16_split), inline on purpose: through the helpers
     // naf_front_kernel<4, 1> measured 293.2 / 279.3 us against 278.8 / 272.5 us under the bench
-    float s = 0.f;
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[st][j];
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)C;
-    float qv = 0.f;
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float d = v[st][j] - mean; qv += d * d; }
-    qv += __shfl_xor(qv, 32);
-    const float rstd = 1.0f / sqrtf(qv / (float)C + p.eps);
+#include "naf_ln_stats.inc"
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
       const int k0 = 16 * st + 8 * hh;

@@ -155,20 +155,7 @@ __global__ __launch_bounds__(512) void naf_ffn_kernel(NafFfnParams p) {
     // through the helpers ops.naf_ffn came out different in the last bits from the inline form (sha256 of the output, c = 64 and
     // 128, split and plain bf16; which instruction rounds differently was not found), and with the step as well
     // naf_ffn_kernel<8, 1> went from 166 to 170 VGPRs, reported occupancy 3 -> 2
-    float s = 0.f;
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[st][j];
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)C;
-    float qv = 0.f;
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float d = v[st][j] - mean; qv += d * d; }
-    qv += __shfl_xor(qv, 32);
-    const float rstd = 1.0f / sqrtf(qv / (float)C + p.eps);
+#include "naf_ln_stats.inc"
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
       const int k0 = 16 * st + 8 * hh;

@@ -151,20 +151,7 @@ __global__ __launch_bounds__(NW * 64, (KS == 4 ? 2 : 1)) void NAF_TAIL_KERNEL(Na
     {
       // the LayerNorm of ff_common.h (ff_frag_ln_stats / _step), inline on purpose: through the helpers naf_tail_kernel<8, 4> goes
       // from 202 to 214 AGPRs and from 110.94 / 110.39 us to 112.22 / 111.89 us under the bench
-      float s = 0.f;
-#pragma unroll
-      for (int st = 0; st < KS; ++st)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += v[st][j];
-      s += __shfl_xor(s, 32);
-      const float mean = s / (float)C;
-      float qv = 0.f;
-#pragma unroll
-      for (int st = 0; st < KS; ++st)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float d = v[st][j] - mean; qv += d * d; }
-      qv += __shfl_xor(qv, 32);
-      const float rstd = 1.0f / sqrtf(qv / (float)C + p.eps);
+#include "naf_ln_stats.inc"
 #pragma unroll
       for (int st = 0; st < KS; ++st) {
         const int k0 = 16 * st + 8 * hh;

@@ -19,6 +19,7 @@
 // fp32 form rounds the same values to bf16 as they arrive, so both forms feed the MFMAs the same operands; the rows form fetches them
 // with 5 sixteen-byte loads per lane and stage instead of 18 eight-byte ones and converts nothing.
 #include "ff_common.h"
+#include "win_geometry.h"
 
 #define OC_NK 576
 #define OC_RELW 39
@@ -49,10 +50,8 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
   int* ktok = reinterpret_cast<int*>(smem + OC_OFF_TOK);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  int bid = blockIdx.x;
-  const int wx = bid % p.nwx; bid /= p.nwx;
-  const int wy = bid % p.nwy;
-  const int b = bid / p.nwy;
+  const FFWinId win = ff_win_decode(blockIdx.x, p.nwx, p.nwy);
+  const int wx = win.wx, wy = win.wy, b = win.b;
   FF_STAMP(64, 0);
 
   // ---- key table in TILE order: key index 32 T + kappa, T = 3 tr + tc, is window position (4 tr + kappa / 8, 8 tc + kappa % 8) ---
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(512) void ocab_attn_kernel(OcabParams p) {
     const int T = kidx >> 5, kap = kidx & 31;
     const int ky = 4 * (T / 3) + (kap >> 3), kx = 8 * (T % 3) + (kap & 7);
     const int y = wy * 16 - 4 + ky, x = wx * 16 - 4 + kx;
-    ktok[kidx] = ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W) ? (b * p.H + y) * p.W + x : -1;
+    ktok[kidx] = FF_WIN_IN_IMAGE(y, x, p.H, p.W) ? (b * p.H + y) * p.W + x : -1;      // (the text form: a token function moved the assembly)
   }
   // constant parts of both stage buffers: K channels 30 / 31 = 0, V^T row 30 = 1 (the denominator channel), row 31 = 0
   for (int i = tid; i < 2 * OC_STK; i += 512)

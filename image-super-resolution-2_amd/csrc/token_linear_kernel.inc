@@ -84,27 +84,13 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
       f32x16 ga;
 #pragma unroll
       for (int r = 0; r < 16; ++r) ga[r] = p.gb1[(r & 3) + 8 * (r >> 2) + 4 * hh];       // gb1 padded to 32
-      bf16x8 fa[2], fl[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-        if (NTERMS == 3) fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + WB);
-      }
-#pragma unroll
-      for (int st = 0; st < TL_KS; ++st) {
-        const bf16x8 ah = fa[st & 1], al = fl[st & 1];
-        if (st + 2 < TL_KS) {
-          fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-          if (NTERMS == 3) fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + WB);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (NTERMS == 3) {
-          ga = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, tl[st], ga, 0, 0, 0);
-          ga = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, th[st], ga, 0, 0, 0);
-        }
-        ga = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, th[st], ga, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+#define TL_XH th
+#define TL_XL tl
+#define TL_ACC ga
+#include "token_linear_tile_mfma.inc"
+#undef TL_XH
+#undef TL_XL
+#undef TL_ACC
       float sacc = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) sacc += p.gw2[(r & 3) + 8 * (r >> 2) + 4 * hh] * ff_gelu_fast(ga[r]);   // gw2 padded with zeros
@@ -188,33 +174,11 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
       qv += __shfl_xor(qv, 32);
       rstd = 1.0f / sqrtf(qv / (float)p.K + p.eps);
     }
-#pragma unroll
-    for (int st = 0; st < TL_KS; ++st) {
-      const int k0 = 16 * st + 8 * hh;
-      f32x4 g0 = {1.f, 1.f, 1.f, 1.f}, g1 = g0, b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
-      if (p.gamma) {
-        const int ka = k0 < p.K ? k0 : 0, kb = k0 + 4 < p.K ? k0 + 4 : 0;
-        g0 = *reinterpret_cast<const f32x4*>(p.gamma + ka); b0 = *reinterpret_cast<const f32x4*>(p.beta + ka);
-        g1 = *reinterpret_cast<const f32x4*>(p.gamma + kb); b1 = *reinterpret_cast<const f32x4*>(p.beta + kb);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float gg = j < 4 ? g0[j & 3] : g1[j & 3], bb = j < 4 ? b0[j & 3] : b1[j & 3];
-        const float f = (k0 + j < p.K) ? (p.gamma ? (v[st][j] - mean) * rstd * gg + bb : v[st][j]) : 0.f;
-        const __bf16 h = (__bf16)f;
-        xh[st][j] = h;
-        if (NTERMS == 3) xl[st][j] = (__bf16)(f - (float)h);
-        v[st][j] = f;
-      }
-      // side output of the normalised rows (HAT feeds them to the CAB convolution, hat_arch.py:272-274): the separate
-      // LayerNorm pass (read 47 MB, write 47 MB) becomes 47 MB of extra stores here.  A lane holds 8 consecutive channels
-      // of its row: two float4 stores; the 12 steps of a wave complete whole lines in L2 before they are evicted.
-      if (p.xn && tvalid) {
-        float* xr = p.xn + tok * p.ldxn + k0;
-        if (k0 < p.K) *reinterpret_cast<f32x4*>(xr) = (f32x4){v[st][0], v[st][1], v[st][2], v[st][3]};
-        if (k0 + 4 < p.K) *reinterpret_cast<f32x4*>(xr + 4) = (f32x4){v[st][4], v[st][5], v[st][6], v[st][7]};
-      }
-    }
+#define LN_OPT_KS TL_KS
+#define LN_OPT_TOK tok
+#include "frag_ln_opt_step.inc"
+#undef LN_OPT_KS
+#undef LN_OPT_TOK
   }
 
   // LayerNorm statistics of a channel range of the (activated) OUTPUT, taken from the accumulators on their way out: the
@@ -270,27 +234,13 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = Bs[nb + (r & 3) + 8 * (r >> 2)];
     }
-    bf16x8 fa[2], fl[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-      if (NTERMS == 3) fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + WB);
-    }
-#pragma unroll
-    for (int st = 0; st < TL_KS; ++st) {
-      const bf16x8 ah = fa[st & 1], al = fl[st & 1];
-      if (st + 2 < TL_KS) {
-        fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-        if (NTERMS == 3) fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + WB);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (NTERMS == 3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl[st], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], acc, 0, 0, 0);
-      }
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+#define TL_XH xh
+#define TL_XL xl
+#define TL_ACC acc
+#include "token_linear_tile_mfma.inc"
+#undef TL_XH
+#undef TL_XL
+#undef TL_ACC
     // ---- epilogue of this tile: act, transpose through the wave's LDS patch, coalesced row-segment stores --------
     // accumulator register r of lane (l31 = token, hh) is channel (r & 3) + 8 (r >> 2) + 4 hh: four consecutive channels
     // per r >> 2 -> one ds_write_b128 each

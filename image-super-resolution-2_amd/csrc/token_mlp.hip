@@ -264,27 +264,11 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[n][r] = bpn[(r & 3) + 8 * (r >> 2)];
     const unsigned char* ap = ((n & 1) ? W2s : W1s) + l31 * W1ROWB + 16 * hh;
-    bf16x8 fa[2], fl[2], fx[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-      fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + W1B);
-      fx[u] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * u);
-    }
-#pragma unroll
-    for (int st = 0; st < TM_KS; ++st) {
-      const bf16x8 ah = fa[st & 1], al = fl[st & 1], xl = fx[st & 1];
-      if (st + 2 < TM_KS) {
-        fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-        fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + W1B);
-        fx[st & 1] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * (st + 2));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, oacc[n], 0, 0, 0);
-      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], oacc[n], 0, 0, 0);
-      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], oacc[n], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+#define TM_NTERMS 3
+#define TM_ACC oacc[n]
+#include "token_mlp_split_tile_mfma.inc"
+#undef TM_ACC
+#undef TM_NTERMS
   }
   FF_STAMP(64, 2);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -8,32 +8,10 @@
 #pragma unroll
     for (int r = 0; r < 16; ++r) hacc[r] = B1s[ht * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
     {
-      // operands are read TWO k-steps ahead (hipcc otherwise issues ds_read; s_waitcnt lgkmcnt(0); mfma per step and
-      // exposes the LDS latency 24 times per tile); sched_barrier pins the read block in front of the MFMA block
       const unsigned char* ap = W1s + l31 * W1ROWB + 16 * hh;
-      bf16x8 fa[2], fl[2], fx[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-        fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + W1B);
-        fx[u] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * u);
-      }
-#pragma unroll
-      for (int st = 0; st < TM_KS; ++st) {
-        const bf16x8 ah = fa[st & 1], al = fl[st & 1], xl = fx[st & 1];
-        if (st + 2 < TM_KS) {
-          fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-          fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + W1B);
-          fx[st & 1] = *reinterpret_cast<const bf16x8*>(xl_row + 32 * (st + 2));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (TM_NTERMS == 3) {
-          hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, hacc, 0, 0, 0);
-          hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], hacc, 0, 0, 0);
-        }
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], hacc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+#define TM_ACC hacc
+#include "token_mlp_split_tile_mfma.inc"
+#undef TM_ACC
     }
     if (ht < 3) TM_STAMP(8 + 4 * ht);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // W2(ht) pieces of this wave have landed

@@ -8,17 +8,9 @@
     for (int r = 0; r < 16; ++r) hacc[r] = B1s[ht * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
     {
       const unsigned char* ap = smem + slot * PM_W1SLOT + l31 * W1ROWB + 16 * hh;
-      bf16x8 fa[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-#pragma unroll
-      for (int st = 0; st < TM_KS; ++st) {
-        const bf16x8 ah = fa[st & 1];
-        if (st + 2 < TM_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-        __builtin_amdgcn_sched_barrier(0);
-        hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], hacc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+#define PM_ACC hacc
+#include "token_projmlp_bf16_tile_mfma.inc"
+#undef PM_ACC
     }
     if (ht < 3) PM_STAMP(8 + 4 * ht);
     bf16x8 gh[2];

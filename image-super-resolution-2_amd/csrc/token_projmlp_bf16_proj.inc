@@ -9,15 +9,7 @@
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[n][r] = bpn[(r & 3) + 8 * (r >> 2)];
     const unsigned char* ap = smem + n * PM_W1SLOT + l31 * W1ROWB + 16 * hh;
-    bf16x8 fa[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-#pragma unroll
-    for (int st = 0; st < TM_KS; ++st) {
-      const bf16x8 ah = fa[st & 1];
-      if (st + 2 < TM_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-      __builtin_amdgcn_sched_barrier(0);
-      oacc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], oacc[n], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+#define PM_ACC oacc[n]
+#include "token_projmlp_bf16_tile_mfma.inc"
+#undef PM_ACC
   }

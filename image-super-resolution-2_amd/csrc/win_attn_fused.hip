@@ -17,6 +17,7 @@
 //              O^T is transposed through the wave's own (now idle) K rows and stored as 120-byte row segments.
 // HBM traffic per launch: x in, attention out (+ the optional side output): 2-3 x 47 MB instead of 47+141+47 | 141+180+47.
 #include "ff_common.h"
+#include "win_geometry.h"
 
 struct WinFusedParams {
   const float* x; float* out;
@@ -53,10 +54,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  int bid = blockIdx.x;
-  const int wx = bid % p.nwx; bid /= p.nwx;
-  const int wy = bid % p.nwy;
-  const int b = bid / p.nwy;
+  const FFWinId win = ff_win_decode(blockIdx.x, p.nwx, p.nwy);
+  const int wx = win.wx, wy = win.wy, b = win.b;
   FF_STAMP(64, 0);
 
   // ---- weight-tile DMA: piece (wid + 8 i) of the 25 one-KiB pieces of a tile image --------------------------------------
@@ -85,22 +84,13 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
   //      shift-mask region; the padded bias vector of this head group --------------------------------------------------
   if (tid < 256) {
     const int qy = wy * WH + tid / WW, qx = wx * WW + tid % WW;
-    int oy = qy + p.sh, ox = qx + p.sw;
-    if (oy >= p.Hp) oy -= p.Hp;
-    if (ox >= p.Wp) ox -= p.Wp;
-    ktok[tid] = (oy < p.H && ox < p.W) ? (b * p.H + oy) * p.W + ox : -1;
-    int rid = 0;
-    if (p.use_mask) {
-      const int ry = qy < p.Hp - WH ? 0 : (qy < p.Hp - p.sh ? 1 : 2);
-      const int rx = qx < p.Wp - WW ? 0 : (qx < p.Wp - p.sw ? 1 : 2);
-      rid = 3 * ry + rx;
-    }
-    kreg[tid] = rid;
+    ktok[tid] = ff_win_token(b, qy, qx, p.sh, p.sw, p.Hp, p.Wp, p.H, p.W);
+    kreg[tid] = p.use_mask ? ff_win_region(qy, qx, p.Hp, p.Wp, WH, WW, p.sh, p.sw) : 0;
   }
   for (int i = tid; i < ntiles * 32; i += 512) Bs[i] = p.bias ? p.bias[tile0 * 32 + i] : 0.f;
   __syncthreads();
 
-  const bool blk_mask = p.use_mask && (wy == p.nwy - 1 || wx == p.nwx - 1);
+  const bool blk_mask = p.use_mask && ff_win_has_regions(wx, wy, p.nwx, p.nwy);
   if (blk_mask) {                                      // key-region bit masks: the shift mask becomes one LDS word per key tile
     for (int i = wid; i < 72; i += 8) {
       const int region = i >> 3, t = i & 7;
@@ -122,6 +112,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
   bf16x8 xh[WF_KS], xl[WF_KS];
   {
     float* xs = reinterpret_cast<float*>(smem + WF_OFF_K) + wid * (32 * WF_XS_ROW);    // gather patch over the idle K/V area
+    // the gather below is win_attn_fused_v2.inc's, written out in both: as a function with the read-back row as a parameter both kernels
+    // moved, as one text this one did (it forms the read-back address as xs + l31 * ROW + 16 s4 + 8 hh, the other as xrow + 16 s4)
     const int rr = lane >> 4, cq = (lane & 15) * 4;
     float v[WF_KS][8];
     f32x4 t[3][8];
@@ -149,30 +141,11 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
     }
     float mean = 0.f, rstd = 1.f;
     if (p.gamma) ff_frag_ln_stats<WF_KS>(v, p.K, hh, p.eps, mean, rstd);
-#pragma unroll
-    for (int st = 0; st < WF_KS; ++st) {
-      const int k0 = 16 * st + 8 * hh;
-      f32x4 g0 = {1.f, 1.f, 1.f, 1.f}, g1 = g0, b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
-      if (p.gamma) {                                   // optional LayerNorm: this site keeps its own form of ff_frag_ln_step
-        const int ka = k0 < p.K ? k0 : 0, kb = k0 + 4 < p.K ? k0 + 4 : 0;
-        g0 = *reinterpret_cast<const f32x4*>(p.gamma + ka); b0 = *reinterpret_cast<const f32x4*>(p.beta + ka);
-        g1 = *reinterpret_cast<const f32x4*>(p.gamma + kb); b1 = *reinterpret_cast<const f32x4*>(p.beta + kb);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float gg = j < 4 ? g0[j & 3] : g1[j & 3], bb = j < 4 ? b0[j & 3] : b1[j & 3];
-        const float f = (k0 + j < p.K) ? (p.gamma ? (v[st][j] - mean) * rstd * gg + bb : v[st][j]) : 0.f;
-        const __bf16 h = (__bf16)f;
-        xh[st][j] = h;
-        if (NTERMS == 3) xl[st][j] = (__bf16)(f - (float)h);
-        v[st][j] = f;
-      }
-      if (p.xn && tvalid) {                          // side output: the normalised rows (two float4 per step and lane)
-        float* xr = p.xn + (long long)mytok * p.ldxn + k0;
-        if (k0 < p.K) *reinterpret_cast<f32x4*>(xr) = (f32x4){v[st][0], v[st][1], v[st][2], v[st][3]};
-        if (k0 + 4 < p.K) *reinterpret_cast<f32x4*>(xr + 4) = (f32x4){v[st][4], v[st][5], v[st][6], v[st][7]};
-      }
-    }
+#define LN_OPT_KS WF_KS
+#define LN_OPT_TOK (long long)mytok
+#include "frag_ln_opt_step.inc"
+#undef LN_OPT_KS
+#undef LN_OPT_TOK
   }
 
   FF_STAMP(64, 2);
@@ -187,35 +160,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
   // one 32-row weight tile times the wave's tokens.  SWAP = false: acc[ch][token] (lane = token); true: acc[token][ch]
   auto gemm_tile = [&](int buf, bool swap, f32x16& acc) {
     const unsigned char* ap = smem + buf * WF_BUFB + l31 * WF_ROWB + 16 * hh;
-    bf16x8 fa[2], fl[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-      if (NTERMS == 3) fl[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u + WF_PLB);
-    }
-#pragma unroll
-    for (int st = 0; st < WF_KS; ++st) {
-      const bf16x8 ah = fa[st & 1], al = fl[st & 1];
-      if (st + 2 < WF_KS) {
-        fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-        if (NTERMS == 3) fl[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2) + WF_PLB);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (!swap) {
-        if (NTERMS == 3) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl[st], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh[st], acc, 0, 0, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], acc, 0, 0, 0);
-      } else {
-        if (NTERMS == 3) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[st], ah, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], al, acc, 0, 0, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], ah, acc, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ff_tile_mfma<WF_KS, NTERMS>(ap, WF_PLB, xh, xl, swap, acc);
   };
   // ring hand-over: own DMA pieces of tile `it` have landed, every wave is past its reads of the other slot
   auto ring_step = [&]() {

@@ -27,10 +27,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  int bid = blockIdx.x;
-  const int wx = bid % p.nwx; bid /= p.nwx;
-  const int wy = bid % p.nwy;
-  const int b = bid / p.nwy;
+  const FFWinId win = ff_win_decode(blockIdx.x, p.nwx, p.nwy);
+  const int wx = win.wx, wy = win.wy, b = win.b;
   FF_STAMP(64, 0);
 
   // ---- LDS-DMA: a head's weight image (38 one-KiB pieces, 5 per wave) and its bias table (<= 10 pieces) ---------------------
@@ -39,23 +37,14 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
 
   if (tid < 256) {
     const int qy = wy * WH + tid / WW, qx = wx * WW + tid % WW;
-    int oy = qy + p.sh, ox = qx + p.sw;
-    if (oy >= p.Hp) oy -= p.Hp;
-    if (ox >= p.Wp) ox -= p.Wp;
-    ktok[tid] = (oy < p.H && ox < p.W) ? (b * p.H + oy) * p.W + ox : -1;
-    int rid = 0;
-    if (p.use_mask) {
-      const int ry = qy < p.Hp - WH ? 0 : (qy < p.Hp - p.sh ? 1 : 2);
-      const int rx = qx < p.Wp - WW ? 0 : (qx < p.Wp - p.sw ? 1 : 2);
-      rid = 3 * ry + rx;
-    }
-    kreg[tid] = rid;
+    ktok[tid] = ff_win_token(b, qy, qx, p.sh, p.sw, p.Hp, p.Wp, p.H, p.W);
+    kreg[tid] = p.use_mask ? ff_win_region(qy, qx, p.Hp, p.Wp, WH, WW, p.sh, p.sw) : 0;
   }
   for (int i = tid; i < 3 * p.nheads * 32; i += 512) Bs[i] = p.bias ? p.bias[3 * p.head0 * 32 + i] : 0.f;
   __syncthreads();
   if (ONES && tid < p.nheads) Bs[(3 * tid + 2) * 32 + 30] = 1.0f;       // the denominator channel of V (visible after the first barrier below)
 
-  const bool blk_mask = p.use_mask && (wy == p.nwy - 1 || wx == p.nwx - 1);
+  const bool blk_mask = p.use_mask && ff_win_has_regions(wx, wy, p.nwx, p.nwy);
   if (!ONES && blk_mask) {                             // key-region bit masks, bit i of tile t = key 32 t + 31 - i
     for (int i = wid; i < 72; i += 8) {
       const int region = i >> 3, t = i & 7;
@@ -78,6 +67,8 @@ __global__ __launch_bounds__(512) void win_attn_fused_v2_kernel(WinFusedParams p
   bf16x8 xh[WF_KS];
   {
     float* xs = reinterpret_cast<float*>(smem + W2_OFF_K) + wid * (32 * WF_XS_ROW);    // gather patch over the idle K/V area
+    // the gather below is win_attn_fused_kernel's with the read-back row reversed, written out in both: as a function and as one text
+    // the assembly moved (see the note there)
     const int rr = lane >> 4, cq = (lane & 15) * 4;
     float v[WF_KS][8];
     f32x4 t[3][8];

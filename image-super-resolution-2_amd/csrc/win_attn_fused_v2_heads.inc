@@ -8,18 +8,7 @@
 
   auto gemm_tile = [&](int j, bool swap, f32x16& acc) {
     const unsigned char* ap = smem + j * W2_TILEB + l31 * WF_ROWB + 16 * hh;
-    bf16x8 fa[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) fa[u] = *reinterpret_cast<const bf16x8*>(ap + 32 * u);
-#pragma unroll
-    for (int st = 0; st < WF_KS; ++st) {
-      const bf16x8 ah = fa[st & 1];
-      if (st + 2 < WF_KS) fa[st & 1] = *reinterpret_cast<const bf16x8*>(ap + 32 * (st + 2));
-      __builtin_amdgcn_sched_barrier(0);
-      if (!swap) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh[st], acc, 0, 0, 0);
-      else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[st], ah, acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    ff_tile_mfma<WF_KS, 1>(ap, 0, xh, xh, swap, acc);
   };
 
   for (int hi = 0; hi < p.nheads; ++hi) {

@@ -25,6 +25,30 @@ def _ceil_to(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
+def _forward_batch(who: str, name: str, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], nb_bound, feat_shape, chunk) -> T:
+    """The batch driver of the experts' forward(): B == 1 (or a batch that fits one chunk) is one chunk(lr, taps, feats, out, None, B);
+    a larger batch runs in chunks of nb images, every chunk writing its slice of the one output (and feature) buffer, feats[name] = the
+    feature buffer.  nb_bound(): the expert's images-per-chunk bound in the fused modes (the f32 mode loops per image); feat_shape: the
+    hooked feature's shape for the whole batch; chunk(lr, taps, feats, out, feat_out, cap): the expert's _forward_chunk, cap = the
+    largest chunk's images."""
+    B, _, h, w = lr.shape
+    if B > 1:
+        if taps is not None:
+            raise ops._lib.FFError(f"{who}.forward: taps are recorded for B == 1 only")
+        nb = max(1, nb_bound()) if ops.fused_modes() else 1      # images per chunk
+        if nb < B:
+            if out is None:
+                out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
+            fall = ops.empty_rows(feat_shape, lr.device) if feats is not None else None
+            for b0 in range(0, B, nb):
+                chunk(lr[b0:b0 + nb], None, {} if feats is not None else None, out[b0:b0 + nb],
+                      fall[b0:b0 + nb] if feats is not None else None, nb)
+            if feats is not None:
+                feats[name] = fall
+            return out
+    return chunk(lr, taps, feats, out, None, B)
+
+
 class _Weights:
     """Small helper: fetch tensors by reference key, move to the device once."""
 
@@ -304,26 +328,13 @@ class HatHIP(_Trunk):
         loop in f32 mode; either way bit-equal to B single forwards.  taps are recorded for B == 1 only."""
         B, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, self.ws), _ceil_to(w, self.ws)
-        if B > 1:
-            if taps is not None:
-                raise ops._lib.FFError("HatHIP.forward: taps are recorded for B == 1 only")
-            nb = 1                                          # images per chunk
-            if ops.fused_modes():
-                # ops.conv2d keeps the LDS-resident 3x3 kernel to inputs of fewer than 2^31 elements (32-bit offsets), counted over the
-                # whole launch.  The largest 3x3 input here is the last convolution's, 16 Hp Wp pixels at a pitch of 64: a chunk stays
-                # under that bound whatever max_batch_tokens says, so a batch never leaves the route its images take alone.
-                nb = max(1, min(int(self.max_batch_tokens) // (Hp * Wp), (2 ** 31 - 1) // (16 * Hp * Wp * 64)))
-            if nb < B:                                      # every chunk writes its slice of the one output (and feature) buffer
-                if out is None:
-                    out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
-                fall = ops.empty_rows((B, Hp, Wp, self.after[0].shape[0]), lr.device) if feats is not None else None
-                for b0 in range(0, B, nb):
-                    self._forward_chunk(lr[b0:b0 + nb], None, {} if feats is not None else None, out[b0:b0 + nb],
-                                        fall[b0:b0 + nb] if feats is not None else None)
-                if feats is not None:
-                    feats["hat"] = fall
-                return out
-        return self._forward_chunk(lr, taps, feats, out, None)
+        # ops.conv2d keeps the LDS-resident 3x3 kernel to inputs of fewer than 2^31 elements (32-bit offsets), counted over the whole
+        # launch.  The largest 3x3 input here is the last convolution's, 16 Hp Wp pixels at a pitch of 64: a chunk stays under that
+        # bound whatever max_batch_tokens says, so a batch never leaves the route its images take alone.
+        return _forward_batch("HatHIP", "hat", lr, taps, feats, out,
+                              lambda: min(int(self.max_batch_tokens) // (Hp * Wp), (2 ** 31 - 1) // (16 * Hp * Wp * 64)),
+                              (B, Hp, Wp, self.after[0].shape[0]),
+                              lambda x, tp, ft, o, fo, cap: self._forward_chunk(x, tp, ft, o, fo))
 
     def _forward_chunk(self, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], feat_out: Optional[T]) -> T:
         """One launch per op for all of lr [B,3,h,w]; feat_out: where the hooked feature goes (a slice of the batch's buffer)."""
@@ -520,28 +531,16 @@ class DatHIP(_Trunk):
         taps are recorded for B == 1 only."""
         B, _, h, w = lr.shape
         Hp, Wp = _ceil_to(h, 16), _ceil_to(w, 16)
-        if B > 1:
-            if taps is not None:
-                raise ops._lib.FFError("DatHIP.forward: taps are recorded for B == 1 only")
-            nb = 1                                          # images per chunk
-            if ops.fused_modes():
-                # Two launches index the whole chunk in 32 bits: the LDS-resident 3x3 kernel (ops.conv2d keeps it to inputs of fewer
-                # than 2^31 elements; the largest is the last convolution's, 16 Hp Wp pixels at a pitch of 64) and ff_sgfn_tail (B H W
-                # rows of fc1's output at its pitch).  A chunk stays under both whatever max_batch_tokens says, so a batch never
-                # leaves the route its images take alone.
-                ldh = _ceil_to(self.blocks[0][0]["fc1"][0].shape[0], 32)
-                nb = max(1, min(int(self.max_batch_tokens) // (Hp * Wp), (2 ** 31 - 1) // (16 * Hp * Wp * 64), (2 ** 31 - 1) // (Hp * Wp * ldh)))
-            if nb < B:                                      # every chunk writes its slice of the one output (and feature) buffer
-                if out is None:
-                    out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
-                fall = ops.empty_rows((B, Hp, Wp, self.after[0].shape[0]), lr.device) if feats is not None else None
-                for b0 in range(0, B, nb):
-                    self._forward_chunk(lr[b0:b0 + nb], None, {} if feats is not None else None, out[b0:b0 + nb],
-                                        fall[b0:b0 + nb] if feats is not None else None)
-                if feats is not None:
-                    feats["dat"] = fall
-                return out
-        return self._forward_chunk(lr, taps, feats, out, None)
+
+        def nb_bound():
+            # Two launches index the whole chunk in 32 bits: the LDS-resident 3x3 kernel (ops.conv2d keeps it to inputs of fewer than
+            # 2^31 elements; the largest is the last convolution's, 16 Hp Wp pixels at a pitch of 64) and ff_sgfn_tail (B H W rows of
+            # fc1's output at its pitch).  A chunk stays under both whatever max_batch_tokens says, so a batch never leaves the route
+            # its images take alone.
+            ldh = _ceil_to(self.blocks[0][0]["fc1"][0].shape[0], 32)
+            return min(int(self.max_batch_tokens) // (Hp * Wp), (2 ** 31 - 1) // (16 * Hp * Wp * 64), (2 ** 31 - 1) // (Hp * Wp * ldh))
+        return _forward_batch("DatHIP", "dat", lr, taps, feats, out, nb_bound, (B, Hp, Wp, self.after[0].shape[0]),
+                              lambda x, tp, ft, o, fo, cap: self._forward_chunk(x, tp, ft, o, fo))
 
     def _forward_chunk(self, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], feat_out: Optional[T]) -> T:
         """One launch per op for all of lr [B,3,h,w]; feat_out: where the hooked feature goes (a slice of the batch's buffer)."""
@@ -673,26 +672,16 @@ class NafnetHIP:
         loop in f32 mode (its conv3 folds sca into a dynamic weight); either way bit-equal to B single forwards.  taps are recorded
         for B == 1 only."""
         B, _, h, w = lr.shape
-        if B > 1:
-            if taps is not None:
-                raise ops._lib.FFError("NafnetHIP.forward: taps are recorded for B == 1 only")
-            m = 2 ** len(self.enc_n)
-            Hp, Wp = _ceil_to(4 * h, m), _ceil_to(4 * w, m)
-            nb = 1                                          # images per chunk
-            if ops.fused_modes():
-                nb = max(1, min(int(self.max_batch_pixels) // (Hp * Wp), (2 ** 31 - 1) // (Hp * Wp * 64)))
-            if nb < B:                                      # every chunk writes its slice of the one output (and feature) buffer
-                if out is None:
-                    out = torch.empty((B, 3, 4 * h, 4 * w), device=lr.device, dtype=torch.float32)
-                fall = ops.empty_rows((B, Hp, Wp, self.ending[0].shape[1] // 9), lr.device) if feats is not None else None
-                for b0 in range(0, B, nb):
-                    t = lr[b0:b0 + nb]                      # (the kernels take 16-byte aligned images: odd image sizes are copied)
-                    self._forward_chunk(t.clone() if t.data_ptr() % 16 else t, None, {} if feats is not None else None, out[b0:b0 + nb], nb,
-                                        fall[b0:b0 + nb] if feats is not None else None)
-                if feats is not None:
-                    feats["nafnet"] = fall
-                return out
-        return self._forward_chunk(lr, taps, feats, out, B, None)
+        m = 2 ** len(self.enc_n)
+        Hp, Wp = _ceil_to(4 * h, m), _ceil_to(4 * w, m)
+
+        def chunk(x, tp, ft, o, fo, cap):
+            # the kernels take 16-byte aligned images: a slice of the batch at an odd offset is copied.  cap < B exactly when x is
+            # such a slice (_forward_batch passes the whole batch with cap == B); the whole batch is never copied, as before
+            return self._forward_chunk(x.clone() if cap < B and x.data_ptr() % 16 else x, tp, ft, o, cap, fo)
+        return _forward_batch("NafnetHIP", "nafnet", lr, taps, feats, out,
+                              lambda: min(int(self.max_batch_pixels) // (Hp * Wp), (2 ** 31 - 1) // (Hp * Wp * 64)),
+                              (B, Hp, Wp, self.ending[0].shape[1] // 9), chunk)
 
     def _forward_chunk(self, lr: T, taps: Optional[dict], feats: Optional[dict], out: Optional[T], cap: int, feat_out: Optional[T]) -> T:
         """One launch per op for all of lr [B,3,h,w] (per_image matters for B > 1 only: ops.conv2d); cap: the largest chunk's images;
