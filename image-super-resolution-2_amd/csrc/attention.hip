@@ -39,8 +39,8 @@ __global__ __launch_bounds__(512) void window_attn_kernel(AttnParams p) {
   constexpr int KTS = KC + 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Kt = smem;                         // [32][KTS]
-  float* Vs = smem + 32 * KTS;              // [KC][32]
-  int* kreg = reinterpret_cast<int*>(Vs + KC * 32);   // [KC] region id of each key (mask)
+  float* Vs = smem + wat_off_v_f(NKT);      // [KC][32]          (the map: lds_layout.h)
+  int* kreg = reinterpret_cast<int*>(smem + wat_off_reg_f(NKT));   // [KC] region id of each key (mask)
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
@@ -202,7 +202,8 @@ extern "C" int ff_window_attn(const float* qkv, int ldq, int q_off, int k_off, i
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_window_attn: grid too large");
   hipStream_t st = (hipStream_t)stream;
   constexpr int NKT = 4;   // 128-key chunks: 64 accumulator registers, 2 waves/SIMD without in-loop spills
-  const size_t lds = (size_t)(32 * (NKT * 32 + 1) + NKT * 32 * 32) * 4 + NKT * 32 * 4;
+  constexpr size_t lds = wat_lds(NKT);
+  static_assert(lds <= FF_LDS_DEFAULT_MAX, "LDS budget");
   hipLaunchKernelGGL(window_attn_kernel<NKT>, dim3((unsigned)nblk), dim3(512), lds, st, p);
   FF_LAUNCH_CHECK("ff_window_attn");
   return FF_OK;

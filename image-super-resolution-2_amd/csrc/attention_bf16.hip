@@ -32,19 +32,18 @@ struct AttnBfParams {
   int vec_q;       // float2 query loads: d, q_off, ldq even and qkv 8-byte aligned
 };
 
-#define AKC 128            // keys per chunk
-#define KROWB 80           // K row: 32 bf16 + 16 B pad
-#define VROWB 272          // V^T row: 128 bf16 + 16 B pad
+// WAB_AKC (keys per chunk), WAB_KROWB / WAB_VROWB (bytes per K / V^T row) and the map of the image: lds_layout.h
 
 template <int NTERMS>
 __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* Kh = smem;                          // [AKC][KROWB]
-  unsigned char* Kl = Kh + AKC * KROWB;
-  unsigned char* Vh = Kl + AKC * KROWB;              // [32][VROWB]
-  unsigned char* Vl = Vh + 32 * VROWB;
-  int* ktok = reinterpret_cast<int*>(Vl + 32 * VROWB);   // [nchunks*AKC] token index of every key (or -1: zero key)
-  int* kregAll = ktok + p.nkpad;                         // [nchunks*AKC] shift-region id of every key
+  unsigned char* Kh = smem;                          // [WAB_AKC][WAB_KROWB]
+  unsigned char* Kl = smem + WAB_OFF_KL;
+  unsigned char* Vh = smem + WAB_OFF_VH;             // [32][WAB_VROWB]
+  unsigned char* Vl = smem + WAB_OFF_VL;
+  int* ktok = reinterpret_cast<int*>(smem + WAB_OFF_KTOK);   // [nchunks*WAB_AKC] token index of every key (or -1: zero key)
+  // the three run-time offsets wab_off_kreg / wab_off_rel / wab_off_kofs, written out: through the functions the kernel's scalar code moved
+  int* kregAll = ktok + p.nkpad;                         // [nchunks*WAB_AKC] shift-region id of every key
   float* Tl = reinterpret_cast<float*>(kregAll + p.nkpad);   // [rel_n] this head's relative-position table (rel path)
   int* kofs = reinterpret_cast<int*>(Tl + (p.rel ? p.rel_n : 0));   // [nkpad] ky * rel_w + kx of every key (rel_gen path)
 
@@ -98,9 +97,9 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
   float m_run = -INFINITY, l_run = 0.f;
   const float LOG2E = 1.4426950408889634f;
 
-  const int nchunks = (nk + AKC - 1) / AKC;
+  const int nchunks = (nk + WAB_AKC - 1) / WAB_AKC;
   // ---- per-block key tables: token index (or -1 for the zero keys outside the image) and mask region of every key ------
-  for (int kidx = tid; kidx < nchunks * AKC; kidx += 512) {
+  for (int kidx = tid; kidx < nchunks * WAB_AKC; kidx += 512) {
     int tk = -1, rid = 0;
     if (kidx < nk) {
       const int ky = koy + kidx / p.kw, kx = kox + kidx % p.kw;
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
   auto fetch_kv = [&](int c) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int tk = ktok[c * AKC + wid * 2 + hh + 16 * i];
+      const int tk = ktok[c * WAB_AKC + wid * 2 + hh + 16 * i];
       const bool ok = tk >= 0 && l31 < p.d;
       const float* src = p.qkv + (long long)(ok ? tk : 0) * p.ldq + hoff;
       const float a = src[p.k_off], bq = src[p.v_off];
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
   };
   fetch_kv(0);
   for (int c = 0; c < nchunks; ++c) {
-    const bool full = (c + 1) * AKC <= nk;            // every key of this chunk exists: no per-element tail handling
+    const bool full = (c + 1) * WAB_AKC <= nk;            // every key of this chunk exists: no per-element tail handling
     // ---- bias of this chunk -> accumulators (C-in of the QK^T MFMAs) ---------------------------------------------
     f32x16 st[4];
     {
@@ -153,7 +152,7 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            const int4 ko = *reinterpret_cast<const int4*>(kofs + c * AKC + t * 32 + 8 * g + 4 * hh);
+            const int4 ko = *reinterpret_cast<const int4*>(kofs + c * WAB_AKC + t * 32 + 8 * g + 4 * hh);
             st[t][4 * g + 0] = Tl[lane_base + ko.x];
             st[t][4 * g + 1] = Tl[lane_base + ko.y];
             st[t][4 * g + 2] = Tl[lane_base + ko.z];
@@ -169,11 +168,11 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int key0 = c * AKC + t * 32 + (r & 3) + 8 * (r >> 2);        // uniform; lane half hh adds 4 to kx
+            const int key0 = c * WAB_AKC + t * 32 + (r & 3) + 8 * (r >> 2);        // uniform; lane half hh adds 4 to kx
             st[t][r] = Tl[lane_base - (key0 >> p.lkw) * p.rel_w - (key0 & (p.kw - 1))];
           }
       } else {
-      const float* bbase = p.biasT + ((long long)head * nk + (long long)c * AKC) * 256;      // wave-uniform
+      const float* bbase = p.biasT + ((long long)head * nk + (long long)c * WAB_AKC) * 256;      // wave-uniform
       const int lo = hh * 1024 + 4 * qi;                                                      // floats: key half + query
       if (full) {
 #pragma unroll
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            int k0 = c * AKC + t * 32 + 8 * g + 4 * hh;
+            int k0 = c * WAB_AKC + t * 32 + 8 * g + 4 * hh;
             k0 = k0 < nk ? k0 : nk - 4;
             const f32x4 u = *reinterpret_cast<const f32x4*>(p.biasT + ((long long)head * nk + k0) * 256 + 4 * qi);
 #pragma unroll
@@ -203,12 +202,12 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
     for (int i = 0; i < 8; ++i) {
       const int kk = wid * 2 + hh + 16 * i;
       const __bf16 k_h = (__bf16)kv[i], v_h = (__bf16)vv[i];
-      *reinterpret_cast<__bf16*>(Kh + kk * KROWB + 2 * l31) = k_h;
+      *reinterpret_cast<__bf16*>(Kh + kk * WAB_KROWB + 2 * l31) = k_h;
       const int vp = ff_swap23(kk);
-      *reinterpret_cast<__bf16*>(Vh + l31 * VROWB + 2 * vp) = v_h;
+      *reinterpret_cast<__bf16*>(Vh + l31 * WAB_VROWB + 2 * vp) = v_h;
       if (NTERMS == 3) {
-        *reinterpret_cast<__bf16*>(Kl + kk * KROWB + 2 * l31) = (__bf16)(kv[i] - (float)k_h);
-        *reinterpret_cast<__bf16*>(Vl + l31 * VROWB + 2 * vp) = (__bf16)(vv[i] - (float)v_h);
+        *reinterpret_cast<__bf16*>(Kl + kk * WAB_KROWB + 2 * l31) = (__bf16)(kv[i] - (float)k_h);
+        *reinterpret_cast<__bf16*>(Vl + l31 * WAB_VROWB + 2 * vp) = (__bf16)(vv[i] - (float)v_h);
       }
     }
     __syncthreads();
@@ -219,9 +218,9 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(Kh + (t * 32 + l31) * KROWB + 32 * s + 16 * hh);
+        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(Kh + (t * 32 + l31) * WAB_KROWB + 32 * s + 16 * hh);
         if (NTERMS == 3) {
-          const bf16x8 al = *reinterpret_cast<const bf16x8*>(Kl + (t * 32 + l31) * KROWB + 32 * s + 16 * hh);
+          const bf16x8 al = *reinterpret_cast<const bf16x8*>(Kl + (t * 32 + l31) * WAB_KROWB + 32 * s + 16 * hh);
           st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[s], st[t], 0, 0, 0);
           st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[s], st[t], 0, 0, 0);
         }
@@ -235,14 +234,14 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (kregAll[c * AKC + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh] != qreg_id) st[t][r] += -100.0f;
+          if (kregAll[c * WAB_AKC + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh] != qreg_id) st[t][r] += -100.0f;
     }
     if (!full) {
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (c * AKC + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh >= nk) st[t][r] = -INFINITY;
+          if (c * WAB_AKC + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh >= nk) st[t][r] = -INFINITY;
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -269,9 +268,9 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
           ph[j] = h;
           if (NTERMS == 3) pl[j] = (__bf16)(e - (float)h);
         }
-        const bf16x8 vh = *reinterpret_cast<const bf16x8*>(Vh + l31 * VROWB + 2 * (t * 32 + 16 * s + 8 * hh));
+        const bf16x8 vh = *reinterpret_cast<const bf16x8*>(Vh + l31 * WAB_VROWB + 2 * (t * 32 + 16 * s + 8 * hh));
         if (NTERMS == 3) {
-          const bf16x8 vl = *reinterpret_cast<const bf16x8*>(Vl + l31 * VROWB + 2 * (t * 32 + 16 * s + 8 * hh));
+          const bf16x8 vl = *reinterpret_cast<const bf16x8*>(Vl + l31 * WAB_VROWB + 2 * (t * 32 + 16 * s + 8 * hh));
           o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, o, 0, 0, 0);
           o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, o, 0, 0, 0);
         }
@@ -289,8 +288,8 @@ __global__ __launch_bounds__(512) void window_attn_bf16_kernel(AttnBfParams p) {
     // O^T sits with the query in the lane and 16 head channels in registers: stored directly, every instruction would
     // scatter 64 dwords over 32 token rows.  The K/V staging buffers are idle after the loop's last barrier, so each wave
     // transposes its 32 x 32 tile through a private patch and writes 120-byte row segments as float2 (16 lanes per query).
-    float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 34);
-    int* tokq = reinterpret_cast<int*>(smem + 8 * 32 * 34 * 4) + wid * 32;
+    float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 34);      // both over the idle K / V staging: asserted at the map
+    int* tokq = reinterpret_cast<int*>(smem + WAB_OFF_TOKQ) + wid * 32;
 #pragma unroll
     for (int r = 0; r < 16; ++r) tr[l31 * 34 + (r & 3) + 8 * (r >> 2) + 4 * hh] = o[r] * inv;
     if (hh == 0) tokq[l31] = qvalid ? (int)qtok : -1;
@@ -347,12 +346,12 @@ extern "C" int ff_window_attn_bf16s(const float* qkv, int ldq, int q_off, int k_
   p.nwx = Wp / ww; p.nwy = Hp / wh;
   p.vec_q = (d % 2 == 0) && (q_off % 2 == 0) && (ldq % 2 == 0) && ((((uintptr_t)qkv) & 7) == 0);
   p.vec_out = (d % 2 == 0) && (o_off % 2 == 0) && (ldo % 2 == 0) && ((((uintptr_t)out) & 7) == 0);
-  p.nkpad = (kh * kw + AKC - 1) / AKC * AKC;
+  p.nkpad = (kh * kw + WAB_AKC - 1) / WAB_AKC * WAB_AKC;
   const long long nblk = (long long)B * p.nwx * p.nwy * heads;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_window_attn_bf16s: grid too large");
   FF_CHECK_ARG((long long)B * H * W < (1LL << 31), "ff_window_attn_bf16s: too many tokens");
-  const size_t lds = (size_t)2 * AKC * KROWB + (size_t)2 * 32 * VROWB + (size_t)2 * p.nkpad * 4 + (rel_table ? (size_t)p.rel_n * 4 : 0) + (rel_gen ? (size_t)p.nkpad * 4 : 0);
-  FF_CHECK_ARG(lds <= 64 * 1024, "ff_window_attn_bf16s: window too large for the LDS image");
+  const size_t lds = wab_lds(p.nkpad, p.rel_n, rel_table != nullptr, rel_gen);
+  FF_CHECK_ARG(lds <= FF_LDS_DEFAULT_MAX, "ff_window_attn_bf16s: window too large for the LDS image");
   if (nterms == 3)
     hipLaunchKernelGGL(window_attn_bf16_kernel<3>, dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);
   else

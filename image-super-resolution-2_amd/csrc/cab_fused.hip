@@ -40,9 +40,8 @@ struct CabParams {
 #define CAB_W2SLOT 15360                // 192 rows x 80 B
 #define CAB_W2SLOTS 4
 #define CAB_LDS (CAB_XBYTES + CAB_CBYTES + CAB_W1SLOTS * CAB_W1SLOT)
-static_assert(CAB_LDS <= 160 * 1024, "LDS budget");
+static_assert(CAB_LDS <= FF_LDS_MAX, "LDS budget");
 static_assert(CAB_W2SLOTS * CAB_W2SLOT <= CAB_XBYTES, "conv2's weight ring lives in the input chunk's space");
-static_assert(8192 + 8 * 32 * 36 * 4 <= CAB_XBYTES, "the epilogue's pool row and patches live in the input chunk's space");
 static_assert(CAB_XPROW % 16 == 0 && (CAB_XPROW / 4) % 64 == (18 * 36) % 64, "input rows continue the 36-dword pixel step across the row wrap");
 
 // s_waitcnt vmcnt(N); the count is an immediate, so every wait is an instantiation and a count the field cannot hold does not compile
@@ -64,6 +63,7 @@ void cab_fused_kernel(CabParams p) {
   constexpr int WM = 4, WN = 2, MI = 2, NI = 3, NTERMS = 1, ACT = ACT_NONE;
   constexpr int NW = WM * WN, NT = NW * 64, BN = WN * NI * 32, TN = NI * 32;
   constexpr bool TWO_PER_CU = false;
+  constexpr int VEC_EPI_SPACE = CAB_XBYTES;   // the epilogue's pool row and patches live in the input chunk's space (the .inc asserts that they fit)
   constexpr int ROWB = CAB_ROWB, PROW = CAB_CPROW;
   constexpr int W2ROW = 80, W1ROW = 144;
   constexpr int NPX = 400, PPP = NT / 8, NPASS = (NPX + PPP - 1) / PPP;      // staging: 8 lanes (16 B = 8 channels each) per pixel, 64 pixels per pass

@@ -233,7 +233,7 @@ extern "C" int ff_chan_qkv(const float* x, int ldx, long long M, int K, const fl
   ChanQkvParams p;
   p.x = x; p.gamma = gamma; p.beta = beta; p.w = (const __bf16*)w_tiles; p.bias = bias_padded; p.v = v_out; p.part = work;
   p.M = M; p.ldx = ldx; p.ldv = ldv; p.K = K; p.C = 180; p.eps = eps;
-  static_assert(CQ_LDS <= 160 * 1024, "LDS image too large");
+  static_assert(CQ_LDS <= FF_LDS_MAX, "LDS image too large");
   static_assert(8 * 32 * FF_XS_ROW * 4 <= 8 * CQ_RED * 4 + 8 * 32 * CQ_TR * 4, "gather patch must fit in the reduction + transpose area");
   static ff_device_once once;
   if (!ff_raise_lds(once, "ff_chan_qkv", CQ_LDS, FF_LDS_SAY_ERR, &chan_qkv_kernel<3>, &chan_qkv_kernel<1>)) return FF_ERR_LAUNCH;

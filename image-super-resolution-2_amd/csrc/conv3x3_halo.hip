@@ -67,13 +67,14 @@ void conv3x3_halo_kernel(HaloParams p) {
   constexpr int PPP = NT / 16;                         // pixels staged per pass (16 lanes per pixel)
   constexpr int TH = WM * MI * 2, NPX = (TH + 2) * HX_W, NPASS = (NPX + PPP - 1) / PPP;
   constexpr int BN = WN * NI * 32, TN = NI * 32;
-  constexpr int XBYTES = (TH + 2) * PROW;
-  constexpr int WROW = (NTERMS == 1 ? WK * 2 : WK * 4) + 16, NH = 64 / WK, KSTEPS = WK / 16;
+  constexpr int XBYTES = halo_off_w(TH, PROW);         // the map: lds_layout.h
+  constexpr int WROW = halo_wrow(WK, NTERMS), NH = 64 / WK, KSTEPS = WK / 16;
   constexpr bool BLK = NSLOT == 9;           // blocked schedule: a chunk's nine weight tiles resident, two barriers per chunk (below)
   constexpr bool TWO_PER_CU = NTERMS == 1 && MI * NI <= 2 && WM * WN == 8 && !BLK;   // 128-register budget: the partner workgroup hides the chunk load instead
   constexpr bool PAIR_4W = NTERMS == 1 && MI * NI == 6 && WM * WN == 4;      // 8 x 16 pixels x 192: two 4-wave workgroups per CU, 256 registers
   constexpr bool XPREF = MI * NI <= 6 && !TWO_PER_CU && !PAIR_4W;   // prefetch the next chunk's input rows into registers during tap 7
-  constexpr int WPIECES = (BN * WROW + 1023) / 1024, WSLOT = WPIECES * 1024;
+  constexpr int WPIECES = (BN * WROW + 1023) / 1024, WSLOT = halo_wslot(BN, WK, NTERMS);
+  constexpr int VEC_EPI_SPACE = halo_lds(TH, PROW, NSLOT, WSLOT);   // the whole image is idle staging in the epilogue
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Xs = smem;
   unsigned char* Ws = smem + XBYTES;
@@ -355,6 +356,7 @@ void conv3x3_halo_kernel(HaloParams p) {
       if (p.pool_part) {
         psum += __shfl_xor(psum, 32);
         float* ps = reinterpret_cast<float*>(smem);              // [WM][BN]: staging buffers are idle in the epilogue
+        static_assert(WM * BN * 4 <= XBYTES, "the pool row must fit in the idle input tile");
         if (j == 0) __syncthreads();                              // (first use: every wave has left the tap loop)
         if (hh == 0) ps[wr * BN + wc * TN + j * 32 + l31] = psum;
       }
@@ -377,10 +379,8 @@ void conv3x3_halo_kernel(HaloParams p) {
 template <int WM, int WN, int MI, int NI, int WK, int NSLOT, int NTERMS>
 static int launch_halo(HaloParams& p, hipStream_t st) {
   constexpr int TH = WM * MI * 2, BN = WN * NI * 32;
-  constexpr int WSLOT = ((BN * ((NTERMS == 1 ? WK * 2 : WK * 4) + 16) + 1023) / 1024) * 1024;
-  constexpr size_t lds = (size_t)(TH + 2) * HaloGeom<NTERMS>::PROW + NSLOT * WSLOT;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static_assert(lds >= 8192 + (size_t)WM * WN * 32 * 36 * 4, "the vector epilogue's pool row + patches must fit in the staging area");
+  constexpr size_t lds = halo_lds(TH, HaloGeom<NTERMS>::PROW, NSLOT, halo_wslot(BN, WK, NTERMS));
+  static_assert(lds <= FF_LDS_MAX, "LDS budget");
   p.tiles_x = (p.W + 15) / 16;
   p.tiles_y = (p.H + TH - 1) / TH;
   p.nblk = (p.Cout + BN - 1) / BN;

@@ -1,11 +1,13 @@
 // Vector epilogue of the LDS-resident 3x3 convolutions, shared as text by conv3x3_halo_kernel (conv3x3_halo.hip) and cab_fused_kernel
 // (cab_fused.hip): bias + activation, the transposition through the wave's LDS patch, 16-byte stores and the per-workgroup pool partial row.
 // The including scope provides p (res, mul, bias, alpha, out, ldo, ldr, io_bf16, pool_part, H, W, Cout), smem, acc[MI][NI], the wave's
-// coordinates (wid, lane, l31, hh, wr, wc), the tile origin (b, y0, x0, n0) and the constants WM, WN, MI, NI, TN, BN, NT, NTERMS, ACT, TWO_PER_CU.
+// coordinates (wid, lane, l31, hh, wr, wc), the tile origin (b, y0, x0, n0) and the constants WM, WN, MI, NI, TN, BN, NT, NTERMS, ACT, TWO_PER_CU,
+// and VEC_EPI_SPACE: the bytes from smem on that are idle staging in the epilogue.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                        // every wave has left the tap loop: the staging area is free
-    float* ps = reinterpret_cast<float*>(smem);          // [WM][BN] pool partials (first 8 KB), then the waves' 32 x 36 patches
-    float* patch = reinterpret_cast<float*>(smem + 8192) + wid * (32 * 36);
+    float* ps = reinterpret_cast<float*>(smem);          // [WM][BN] pool partials below HALO_OFF_PATCH, then the waves' 32 x 36 patches
+    float* patch = reinterpret_cast<float*>(smem + HALO_OFF_PATCH) + wid * (32 * 36);
+    static_assert(halo_epilogue_fits(WM, WN, BN, VEC_EPI_SPACE), "pool row under HALO_OFF_PATCH, patches inside the idle staging");
     const int tq = lane >> 3, q4 = 4 * (lane & 7);
     const bool has_res = p.res != nullptr;
     // residual quads are requested one n-tile ahead of their use (fetched right before the add, each tile exposed an HBM latency: the

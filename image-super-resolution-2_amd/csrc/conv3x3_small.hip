@@ -17,7 +17,7 @@ struct SmallConvParams {
 
 template <int CT>
 __global__ __launch_bounds__(256) void conv3x3_small_kernel(SmallConvParams p) {
-  extern __shared__ __attribute__((aligned(16))) float tile[];         // [18][18][CinP + 4]
+  extern __shared__ __attribute__((aligned(16))) float tile[];         // [18][18][CinP + 4]: c3s_lds
   const int PS = p.CinP + 4;
   const int tid = threadIdx.x;
   const int tx = blockIdx.x, ty = blockIdx.y, b = blockIdx.z;
@@ -78,11 +78,11 @@ extern "C" int ff_conv3x3_small(const float* in, int ldi, const float* w_small, 
   p.in = in; p.w = w_small; p.bias = bias; p.res = res; p.out = out; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.CinP = (Cin + 3) / 4 * 4;
   p.ldi = ldi; p.Cout = Cout; p.ldo = ldo; p.ldr = ldr; p.act = act; p.alpha = alpha;
   const dim3 grid((W + 15) / 16, (H + 15) / 16, B);
-  const size_t lds = (size_t)324 * (p.CinP + 4) * 4;
+  const size_t lds = c3s_lds(p.CinP);
 #define SC_LAUNCH(CTV)                                                                                                      \
   do {                                                                                                                      \
     static ff_device_once once;                                                                                             \
-    if (!ff_raise_lds(once, "ff_conv3x3_small", 324 * 68 * 4, FF_LDS_SAY_ERR, &conv3x3_small_kernel<CTV>)) return FF_ERR_LAUNCH; \
+    if (!ff_raise_lds(once, "ff_conv3x3_small", c3s_lds(64), FF_LDS_SAY_ERR, &conv3x3_small_kernel<CTV>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL(conv3x3_small_kernel<CTV>, grid, dim3(256), lds, (hipStream_t)stream, p);                            \
   } while (0)
   if (ct == 1) SC_LAUNCH(1); else if (ct == 4) SC_LAUNCH(4); else SC_LAUNCH(16);

@@ -10,7 +10,7 @@
 // nafnet_arch.py:77-96,174,184; hierarchical_fusion.py:96-127; enhanced_fusion.py:266-290).
 //
 // Tiling: workgroup = 4 waves (256 threads), BM x BN output tile, BK = 16.  LDS rows are
-// k-contiguous with a 4-float pad (LDK = 20): the lane's operand for 8 consecutive k-steps is two
+// k-contiguous with a 4-float pad (CG_LDK = 20): the lane's operand for 8 consecutive k-steps is two
 // ds_read_b128 (lane half h owns k = 8h..8h+7 of the chunk -- the k order inside a chunk is free as
 // long as A and B agree), and rows r, r+1, ... start 20 dwords apart, which puts the 16 rows of a
 // ds_read_b128 lane group on 16 distinct 4-bank slots (conflict free).  Global->LDS goes through
@@ -34,7 +34,7 @@ struct ConvParams {
   int shuffle;  // 0 or 2: PixelShuffle(2) folded into the store
 };
 
-#define LDK 20
+// CG_LDK = 20 floats per LDS row and the map [2][BM][CG_LDK] | [2][BN][CG_LDK]: lds_layout.h
 #define BK 16
 
 template <int BM, int BN, int WM, int WN, bool VEC4>
@@ -44,8 +44,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
   constexpr int AR = BM / 64;                    // A rows staged per thread
   constexpr int BR = (BN + 63) / 64;             // B rows staged per thread
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* As = smem;                              // [2][BM][LDK]
-  float* Bs = smem + 2 * BM * LDK;               // [2][BN][LDK]
+  float* As = smem;                              // [2][BM][CG_LDK]
+  float* Bs = smem + gemm_off_b(BM, CG_LDK);        // [2][BN][CG_LDK]   (float offset: rowb = CG_LDK floats)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
@@ -137,11 +137,11 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
   auto store_chunk = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < AR; ++i)
-      *reinterpret_cast<f32x4*>(As + (buf * BM + srow + 64 * i) * LDK + 4 * kq) = ra[i];
+      *reinterpret_cast<f32x4*>(As + (buf * BM + srow + 64 * i) * CG_LDK + 4 * kq) = ra[i];
 #pragma unroll
     for (int i = 0; i < BR; ++i) {
       const int r = srow + 64 * i;
-      if (r < BN) *reinterpret_cast<f32x4*>(Bs + (buf * BN + r) * LDK + 4 * kq) = rb[i];
+      if (r < BN) *reinterpret_cast<f32x4*>(Bs + (buf * BN + r) * CG_LDK + 4 * kq) = rb[i];
     }
   };
 
@@ -158,13 +158,13 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
     f32x4 fa[MI][2], fb[NI][2];
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-      const float* ap = As + (buf * BM + wr * TM + i * 32 + l31) * LDK + 8 * hh;
+      const float* ap = As + (buf * BM + wr * TM + i * 32 + l31) * CG_LDK + 8 * hh;
       fa[i][0] = *reinterpret_cast<const f32x4*>(ap);
       fa[i][1] = *reinterpret_cast<const f32x4*>(ap + 4);
     }
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      const float* bp = Bs + (buf * BN + wc * TN + j * 32 + l31) * LDK + 8 * hh;
+      const float* bp = Bs + (buf * BN + wc * TN + j * 32 + l31) * CG_LDK + 8 * hh;
       fb[j][0] = *reinterpret_cast<const f32x4*>(bp);
       fb[j][1] = *reinterpret_cast<const f32x4*>(bp + 4);
     }
@@ -193,7 +193,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const ConvParams& p, bool vec4, hipStream_t st) {
   const int mt = ff_cdiv(p.M, BM), nt = ff_cdiv(p.Cout, BN);
-  const size_t lds = (size_t)2 * (BM + BN) * LDK * sizeof(float);
+  constexpr size_t lds = gemm_lds(BM, BN, CG_LDK * 4);
+  static_assert(lds <= FF_LDS_DEFAULT_MAX, "LDS budget");
   dim3 grid((unsigned)(mt * nt)), block(256);
   if (vec4)
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true>), grid, block, lds, st, p);

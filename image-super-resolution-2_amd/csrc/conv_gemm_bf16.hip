@@ -71,14 +71,14 @@ template <bool WIMG, int BM, int BN, int WM, int WN, int NT>
 static int launch_bf_images(const ConvBfParams& p, hipStream_t st) {
   const char* const who = bf_images_who<WIMG>();
   const int mt = ff_cdiv(p.M, BM), nt = ff_cdiv(p.Cout, BN);
-  constexpr size_t lds = (size_t)2 * (BM + BN) * (32 * 4 + 16);
-  static_assert(lds <= 160 * 1024 && lds >= (size_t)WM * WN * 32 * 36 * 4, "LDS budget");
+  constexpr size_t lds = gemm_lds(BM, BN, cig_rowb(32));
+  static_assert(lds <= FF_LDS_MAX, "LDS budget");
   static_assert(!WIMG || 256 % BM == 0, "an m-tile must not straddle two images of a multiple of 256 rows");
   void (*kernel)(ConvBfParams);
   if constexpr (WIMG) kernel = &conv_igemm_bf16_wimg_kernel<BM, BN, WM, WN, true, NT, 32>;
   else kernel = &conv_igemm_bf16_kmimg_kernel<BM, BN, WM, WN, true, NT, 32>;
   static ff_device_once once;
-  if (lds > 64 * 1024 && !ff_raise_lds(once, who, lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, kernel)) return FF_ERR_LAUNCH;
+  if (lds > FF_LDS_DEFAULT_MAX && !ff_raise_lds(once, who, lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, kernel)) return FF_ERR_LAUNCH;
   hipLaunchKernelGGL(kernel, dim3((unsigned)(mt * nt)), dim3(WM * WN * 64), lds, st, p);
   FF_LAUNCH_CHECK(who);
   return FF_OK;
@@ -99,11 +99,11 @@ static int dispatch_bf_images(const ConvBfParams& p, int cfg, hipStream_t st) {
 template <int BM, int BN, int WM, int WN, int NT, int BKB = 32>
 static int launch_bf(const ConvBfParams& p, bool vec4, hipStream_t st) {
   const int mt = ff_cdiv(p.M, BM), nt = ff_cdiv(p.Cout, BN);
-  constexpr size_t lds = (size_t)2 * (BM + BN) * (BKB * 4 + 16);
-  static_assert(lds <= 160 * 1024 && lds >= (size_t)WM * WN * 32 * 36 * 4, "LDS budget (staging ring; the epilogue patch reuses it)");
+  constexpr size_t lds = gemm_lds(BM, BN, cig_rowb(BKB));
+  static_assert(lds <= FF_LDS_MAX, "LDS budget (staging ring; the epilogue patches reuse it: asserted in the kernel)");
   dim3 grid((unsigned)(mt * nt)), block(WM * WN * 64);
   static ff_device_once once[2];       // [vec4]
-  if (lds > 64 * 1024 && !(vec4 ? ff_raise_lds(once[1], "ff_conv2d_bf16s", lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &conv_igemm_bf16_kernel<BM, BN, WM, WN, true, NT, BKB>)
+  if (lds > FF_LDS_DEFAULT_MAX && !(vec4 ? ff_raise_lds(once[1], "ff_conv2d_bf16s", lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &conv_igemm_bf16_kernel<BM, BN, WM, WN, true, NT, BKB>)
                                 : ff_raise_lds(once[0], "ff_conv2d_bf16s", lds, FF_LDS_SAY_SIZE | FF_LDS_SAY_ERR, &conv_igemm_bf16_kernel<BM, BN, WM, WN, false, NT, BKB>)))
     return FF_ERR_LAUNCH;
   if (vec4)

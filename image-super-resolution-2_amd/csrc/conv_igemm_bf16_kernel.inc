@@ -10,7 +10,7 @@
 //   LDS row = [BKB hi | BKB lo | 16 B pad]: 144 B (36 dwords) or 272 B (68 dwords), both = 4 (mod 32) dwords: conflict-free b128 reads.
 template <int BM, int BN, int WM, int WN, bool VEC4, int NTERMS, int BKB>
 __global__ __launch_bounds__(WM * WN * 64) void CIG_KERNEL(ConvBfParams p) {
-  constexpr int ROWB = BKB * 4 + 16, PLB = BKB * 2;   // bytes per LDS row / per plane of a row
+  constexpr int ROWB = cig_rowb(BKB), PLB = BKB * 2;  // bytes per LDS row / per plane of a row (the map: lds_layout.h)
   constexpr int KQ = BKB / 4, QB = BKB / 8;       // 4-float quads / 16-byte bf16 items per row and plane
   constexpr int NT = WM * WN * 64;                // threads
   constexpr int TM = BM / WM, TN = BN / WN;
@@ -21,7 +21,8 @@ __global__ __launch_bounds__(WM * WN * 64) void CIG_KERNEL(ConvBfParams p) {
   static_assert(BM % RPP == 0, "A staging must tile the rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* As = smem;                       // [2][BM][ROWB]
-  unsigned char* Bs = smem + 2 * BM * ROWB;       // [2][BN][ROWB]
+  unsigned char* Bs = smem + gemm_off_b(BM, ROWB);   // [2][BN][ROWB]
+  static_assert(gemm_patches_fit(BM, BN, ROWB, WM * WN), "the epilogues' 32 x 36 patches must fit in the idle staging ring");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(WM * WN * 64) void CIG_KERNEL(ConvBfParams p) {
       // SimpleGate (nafnet_arch.py:28-31, 100-104) on interleaved columns: the caller orders the weight rows so that the two halves of
       // the reference's chunk(2, dim=1) alternate (2j <- j, 2j+1 <- j + C); a lane then multiplies adjacent columns of the
       // transposed 32 x 32 tile and stores four consecutive product channels: the 2C-wide tensor never reaches memory.
-      float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);
+      float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);    // over the idle ring (asserted at the carve-up)
       const int grow = lane >> 2, seg = lane & 3;
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(WM * WN * 64) void CIG_KERNEL(ConvBfParams p) {
       // 16-byte form: each 32(m) x 32(n) accumulator tile goes through a wave-private LDS patch (the staging buffers are
       // idle now) so a lane owns four consecutive channels of one row: float4 residual loads and stores, 8 whole
       // 128-byte row segments per instruction instead of 2 with dword accesses.
-      float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);
+      float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);    // over the idle ring (asserted at the carve-up)
       const int tq = lane >> 3, q4 = 4 * (lane & 7);
 #pragma unroll
       for (int j = 0; j < NI; ++j) {

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "ff_device_once.h"
+#include "lds_layout.h"       // the older kernels' LDS maps (host + device; token_mlp_layout.h and win_attn_layout.h hold the newer ones)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -35,6 +36,10 @@ void ff_set_error(const char* fmt, ...);
       return FF_ERR_LAUNCH;                                                \
     }                                                                      \
   } while (0)
+
+// what a workgroup can ask for on gfx950, and what it gets without hipFuncAttributeMaxDynamicSharedMemorySize
+#define FF_LDS_MAX (160 * 1024)
+#define FF_LDS_DEFAULT_MAX (64 * 1024)
 
 // ---- dynamic LDS above the 64 KB default ----------------------------------------------------------------------------------------
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to a (kernel, device) pair.  A launch site keeps one `static ff_device_once` -- one
@@ -154,8 +159,7 @@ template <int V> struct ff_ic { static constexpr int value = V; };
 // and redistributes them through a wave-private LDS patch (32 rows x 68 dwords: 4-bank row shift, conflict-free
 // ds_read_b128) into the MFMA B-operand order: v[st][j] = x[row l31][16 st + 8 hh + j].  Per-lane strided row reads
 // (two lanes per row, 32 B per instruction and row) reach only ~1.7 TB/s; this form streams at the HBM rate.
-#define FF_XS_ROW 68
-template <int NPASS>
+template <int NPASS>   // (FF_XS_ROW: lds_layout.h)
 __device__ __forceinline__ void ff_wave_rows_to_frags(const float* __restrict__ x, int ldx, long long tok0, long long M, int K,
                                                       float* xs, int lane, float (&v)[4 * NPASS][8]) {
   const int l31 = lane & 31, hh = lane >> 5;

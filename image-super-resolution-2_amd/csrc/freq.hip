@@ -137,7 +137,7 @@ extern "C" int ff_dwt_pass(const float* in, int C, int H, int W, int axis, const
 __global__ __launch_bounds__(256) void rdft_rows_kernel(const float* __restrict__ x, int R, int W, const float* __restrict__ tc,
                                                         const float* __restrict__ ts, float* __restrict__ Y) {
   extern __shared__ float sm[];                            // row[W] | cos[W] | sin[W]
-  float* row = sm; float* cs = sm + W; float* sn = sm + 2 * W;
+  float* row = sm; float* cs = sm + rdft_off_cos_f(W); float* sn = sm + rdft_off_sin_f(W);      // the map: lds_layout.h, rdft_lds(W)
   const int r = blockIdx.x, Wf = W / 2 + 1;
   for (int i = threadIdx.x; i < W; i += 256) { row[i] = x[(long long)r * W + i]; cs[i] = tc[i]; sn[i] = ts[i]; }
   __syncthreads();
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void cdft_cols_kernel(const float* __restrict_
                                                         const float* __restrict__ mask_logits, int msz, float temp,
                                                         float* __restrict__ Z) {
   extern __shared__ float sm[];                           // tile [H][CB][2] | cos[H] | sin[H]
-  float* tile = sm; float* cs = sm + 2 * H * CB; float* sn = cs + H;
+  float* tile = sm; float* cs = sm + cdft_off_cos_f(H, CB); float* sn = sm + cdft_off_sin_f(H, CB);      // cdft_lds(H, CB)
   const int c = blockIdx.y, col0 = blockIdx.x * CB;
   for (int i = threadIdx.x; i < H * CB; i += 256) {
     const int h = i / CB, cc = i % CB;
@@ -275,12 +275,12 @@ static int fft_bands_launch(const char* who, const float* x, int C, int split_pl
   const long long spec = (long long)C * H * Wf * 2;
   FF_CHECK_ARG(work_floats >= 2 * spec, "%s: workspace too small (need %lld floats)", who, 2 * spec);
   const int CB = H <= 512 ? 16 : 4;
-  const size_t clds = (size_t)H * CB * 8 + (size_t)H * 8;
-  FF_CHECK_ARG(clds <= 64 * 1024, "%s: H too large for the column tile", who);
+  const size_t clds = cdft_lds(H, CB);
+  FF_CHECK_ARG(clds <= FF_LDS_DEFAULT_MAX, "%s: H too large for the column tile", who);
   float* Y = work;
   float* Z = work + spec;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), (size_t)W * 12, st, x, C * H, W, twW_cos, twW_sin, Y);
+  hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), rdft_lds(W), st, x, C * H, W, twW_cos, twW_sin, Y);
   // split the output rows of a column block over workgroups until the grid has a few per CU
   const int ncb = (Wf + CB - 1) / CB;
   int ksplit = 1;
@@ -291,7 +291,7 @@ static int fft_bands_launch(const char* who, const float* x, int C, int split_pl
                      msz, temp, Z);
   hipLaunchKernelGGL(cdft_cols_kernel, gc, dim3(256), clds, st, Z, H, Wf, CB, KH, 1.f, twH_cos, twH_sin,
                      (const float*)nullptr, 0, 0.f, Y);
-  const size_t rlds = (size_t)Wf * 8 + (size_t)W * 8;
+  const size_t rlds = irdft_lds(Wf, W);
   if (images)
     hipLaunchKernelGGL(irdft_rows_bands_images_kernel, dim3(C * H), dim3(256), rlds, st, Y, x, C, H, W, twW_cos, twW_sin, band_scale2, out, ldo, ch_lo, ch_hi);
   else
@@ -311,7 +311,7 @@ extern "C" int ff_fft_bands(const float* x, int C, int H, int W, const float* tw
 // B images in one run of the same four kernels over 3 B planes: x [B][3][H][W] -> out [B][H][W][ldo].  The planes index gridDim.y of the
 // column passes and gridDim.x = 3 B H of the row passes, hence 3 B <= 65535.  H is one ff_fft_bands takes: the column tile of a workgroup within 64 KiB of LDS (H <= 481 or 513 <= H <= 1638).
 static bool fft_bands_images_geometry(int B, int H, int W) {
-  return B > 0 && 3LL * B <= 65535 && H > 1 && W > 1 && W <= 8192 && H <= 8192 && (size_t)H * (H <= 512 ? 16 : 4) * 8 + (size_t)H * 8 <= 64 * 1024;
+  return B > 0 && 3LL * B <= 65535 && H > 1 && W > 1 && W <= 8192 && H <= 8192 && cdft_lds(H, H <= 512 ? 16 : 4) <= FF_LDS_DEFAULT_MAX;
 }
 extern "C" long long ff_fft_bands_images_workspace(int B, int H, int W) {
   if (!fft_bands_images_geometry(B, H, W)) return -1;
@@ -344,8 +344,8 @@ __global__ __launch_bounds__(256) void irdft_rows_kernel(const float* __restrict
 
 static int fft2_cols(const float* in, float* out, int C, int H, int Wf, float sign, const float* twH_cos, const float* twH_sin, hipStream_t st) {
   const int CB = H <= 512 ? 16 : 4;
-  const size_t clds = (size_t)H * CB * 8 + (size_t)H * 8;
-  if (clds > 64 * 1024) { ff_set_error("fft2: H too large for the column tile"); return FF_ERR_ARG; }
+  const size_t clds = cdft_lds(H, CB);
+  if (clds > FF_LDS_DEFAULT_MAX) { ff_set_error("fft2: H too large for the column tile"); return FF_ERR_ARG; }
   const int ncb = (Wf + CB - 1) / CB;
   int ksplit = 1;
   while (ncb * C * ksplit < 512 && (H + ksplit - 1) / ksplit > 256 / CB) ksplit *= 2;
@@ -362,7 +362,7 @@ extern "C" int ff_rfft2(const float* x, int C, int H, int W, const float* twW_co
   const int Wf = W / 2 + 1;
   FF_CHECK_ARG(work_floats >= (long long)C * H * Wf * 2, "ff_rfft2: workspace too small (need %lld floats)", (long long)C * H * Wf * 2);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), (size_t)W * 12, st, x, C * H, W, twW_cos, twW_sin, work);
+  hipLaunchKernelGGL(rdft_rows_kernel, dim3(C * H), dim3(256), rdft_lds(W), st, x, C * H, W, twW_cos, twW_sin, work);
   if (int rc = fft2_cols(work, spec, C, H, Wf, -1.f, twH_cos, twH_sin, st)) return rc;
   FF_LAUNCH_CHECK("ff_rfft2");
   return FF_OK;
@@ -376,7 +376,7 @@ extern "C" int ff_irfft2(const float* spec, int C, int H, int W, const float* tw
   FF_CHECK_ARG(work_floats >= (long long)C * H * Wf * 2, "ff_irfft2: workspace too small (need %lld floats)", (long long)C * H * Wf * 2);
   hipStream_t st = (hipStream_t)stream;
   if (int rc = fft2_cols(spec, work, C, H, Wf, 1.f, twH_cos, twH_sin, st)) return rc;
-  hipLaunchKernelGGL(irdft_rows_kernel, dim3(C * H), dim3(256), (size_t)Wf * 8 + (size_t)W * 8, st, work, H, W, twW_cos, twW_sin, out);
+  hipLaunchKernelGGL(irdft_rows_kernel, dim3(C * H), dim3(256), irdft_lds(Wf, W), st, work, H, W, twW_cos, twW_sin, out);
   FF_LAUNCH_CHECK("ff_irfft2");
   return FF_OK;
 }

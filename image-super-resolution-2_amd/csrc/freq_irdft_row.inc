@@ -2,7 +2,7 @@
 // interleaved partial sums.  Shared as text by irdft_rows_bands_body and irdft_rows_kernel (freq.hip includes this file twice).
 // Expects sm (urow[Wf][2] | cos[W] | sin[W]), U, r, W, Wf, tc, ts and IRDFT_ROW_STORE, the including kernel's statements for
 // sample w (they read w, s0, s1 and nrm; the sample is (s0 + s1) * nrm).
-  float* urow = sm; float* cs = sm + 2 * Wf; float* sn = cs + W;
+  float* urow = sm; float* cs = sm + irdft_off_cos_f(Wf); float* sn = cs + W;      // sn at irdft_off_sin_f(Wf, W), written over cs: from sm the kernels' scalar registers moved
   for (int i = threadIdx.x; i < 2 * Wf; i += 256) urow[i] = U[(long long)r * Wf * 2 + i];
   for (int i = threadIdx.x; i < W; i += 256) { cs[i] = tc[i]; sn[i] = ts[i]; }
   __syncthreads();

@@ -42,7 +42,7 @@ __device__ __forceinline__ void gemm_rows_bf16_body(const RowsGemmParams& p) {
   constexpr int MI = TM / 32, NI = TN / 32;
   constexpr int AI = A32 ? 0 : BM / 8 / NW, BI = BN / 8 / NW;    // 1-KiB DMA pieces (8 rows x 128 B) per wave and chunk
   constexpr int AS = A32 ? BM / (8 * NW) : 0;                    // A32: 16-byte LDS slots (8 k-values, 32 B of fp32) per thread and chunk
-  constexpr int ABYTES = BM * 128, BUFB = (BM + BN) * 128;
+  constexpr int ABYTES = BM * RG_ROWB, BUFB = gemm_bufb(BM, BN, RG_ROWB);     // the map [2][A tile | B tile]: lds_layout.h
   static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "DMA pieces must tile the waves");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2][A tile | B tile]; the epilogue patch reuses it
 
@@ -162,6 +162,7 @@ __device__ __forceinline__ void gemm_rows_bf16_body(const RowsGemmParams& p) {
   // Epilogues: the expressions of conv_igemm_bf16_kernel's gate and 16-byte forms, operation for operation.  Each 32(m) x 32(n)
   // accumulator tile is transposed through a wave-private LDS patch so a lane owns consecutive channels of one row.
   float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);
+  static_assert(gemm_patches_fit(BM, BN, RG_ROWB, NW), "the epilogues' 32 x 36 patches must fit in the idle staging buffers");
   if (GATE) {
     // SimpleGate on interleaved columns: out[m][j] = y[m][2j] * y[m][2j+1], rounded to the bf16 its only consumer (conv5's A
     // operand) would round it to
@@ -242,7 +243,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_rows_bf16_kmimg_kernel(Rows
 
 template <int BM, int BN, int WM, int WN>
 static int launch_rows_kmimg(const RowsGemmParams& p, hipStream_t st) {
-  constexpr size_t lds = (size_t)2 * (BM + BN) * 128;
+  constexpr size_t lds = gemm_lds(BM, BN, RG_ROWB);
+  static_assert(lds <= FF_LDS_DEFAULT_MAX, "LDS budget");
   dim3 grid((unsigned)(ff_cdiv(p.M, BM) * ff_cdiv(p.N, BN))), block(WM * WN * 64);
   hipLaunchKernelGGL((gemm_rows_bf16_kmimg_kernel<BM, BN, WM, WN>), grid, block, lds, st, p);
   FF_LAUNCH_CHECK("ff_gemm_rows_bf16_kmul_images");
@@ -251,8 +253,8 @@ static int launch_rows_kmimg(const RowsGemmParams& p, hipStream_t st) {
 
 template <int BM, int BN, int WM, int WN>
 static int launch_rows(const RowsGemmParams& p, bool gate, bool a32, hipStream_t st) {
-  constexpr size_t lds = (size_t)2 * (BM + BN) * 128;
-  static_assert(lds <= 64 * 1024 && lds >= (size_t)WM * WN * 32 * 36 * 4, "LDS budget (two staging buffers; the epilogue patches reuse them)");
+  constexpr size_t lds = gemm_lds(BM, BN, RG_ROWB);
+  static_assert(lds <= FF_LDS_DEFAULT_MAX, "LDS budget (two staging buffers; the epilogue patches reuse them: asserted in the kernel)");
   dim3 grid((unsigned)(ff_cdiv(p.M, BM) * ff_cdiv(p.N, BN))), block(WM * WN * 64);
   if (a32)                                                 // conv3: residual epilogue only
     hipLaunchKernelGGL((gemm_rows_bf16_kernel<BM, BN, WM, WN, false, true>), grid, block, lds, st, p);

@@ -54,7 +54,7 @@ struct HabLinkParams {
 
 #define HL_OFF_VEC_B (HL_OFF_VEC + (2 * TM_KP + 12 * 32) * 4)     // gamma1 | beta1 | b2 | gate row | projection bias: read once, in the prologue
 #define HL_LDS (HL_OFF_VEC_B + 5 * TM_KP * 4)
-static_assert(HL_LDS <= 160 * 1024, "LDS image too large");
+static_assert(HL_LDS <= FF_LDS_MAX, "LDS image too large");
 static_assert(W2_LDS <= PM_OFF_VEC, "the attention's tables must stay below phase A's vectors");
 static_assert(W2_WB <= PM_PROJB && W2_OFF_K + 8 * 32 * WF_XS_ROW * 4 <= W2_OFF_REL, "hand-over patches must clear the weight image and the bias tables");
 #define PM_P(f) p.a_##f                                // the shared phase-A texts' name for field f of TokenProjMlpParams

@@ -27,8 +27,7 @@ struct NafFrontParams {
 #define NF_TX 16
 #define NF_HW (NF_TX + 2)                 // halo tile width
 #define NF_NTOK ((NF_TY + 2) * NF_HW)     // 180 halo tokens
-#define NF_MT 6                           // m-tiles of 32 tokens (192 >= 180)
-#define NF_TS 68                          // floats per token row of the LDS tile (64 + 4: conflict-free 16-byte rows)
+// NF_MT = 6 m-tiles of 32 tokens (192 >= 180) and NF_TS = 68 floats per token row of the LDS tile: lds_layout.h, with the map
 #define NF_BAD (-2147483647 - 1)          // row-offset sentinel: token outside the image / beyond the 180 halo tokens
 
 #define NF_KERNEL naf_front_kernel
@@ -72,7 +71,7 @@ static int naf_front_launch(const char* who, const float* x, int ldx, int B, int
   const long long nb = (long long)p.tiles_x * p.tiles_y;
   FF_CHECK_ARG(nb < (1LL << 31) && work_floats >= (B ? B : 1) * nb * C, "%s: workspace too small (%s_workspace)", who, who);
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)NF_MT * 32 * NF_TS * 4 + (size_t)2 * 32 * (4 * C + 16) + 8 * 8 * 4 * 4 + (size_t)11 * 2 * C * 4;
+  const size_t lds = nfr_lds(C);
   const float inv_hw = 1.0f / ((float)H * (float)W);
 #define NF_LAUNCH(KERNEL, GRID, KSV, NTM)                                                                                    \
   do {                                                                                                                       \

@@ -5,14 +5,14 @@ template <int KS, int NTERMS>
 __global__ __launch_bounds__(512, KS == 4 ? 4 : 2) void NF_KERNEL(NafFrontParams p) {   // C = 64: two workgroups per CU (70 KB of LDS each)
   constexpr int C = 16 * KS, NCH = C / 32;                      // channels, gated 32-channel chunks
   constexpr int WROWB = 4 * C + 16;                             // LDS weight row: [C hi | C lo | 16 B pad]
-  constexpr int WTILEB = 32 * WROWB;
+  constexpr int WTILEB = nfr_wtileb(C);                         // the map: lds_layout.h
   constexpr int ITEMS = 32 * C * 2 * 2 / 16;                    // 16-byte items per weight tile (hi + lo)
   constexpr int IPT = (2 * ITEMS + 511) / 512;                  // items per thread for the two tiles of a chunk
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Tt = reinterpret_cast<float*>(smem);                   // [192][NF_TS]: phase 0 row staging, then the conv1 output tile
-  unsigned char* Ws = smem + NF_MT * 32 * NF_TS * 4;            // [2 tiles][32][WROWB]
-  float* red = reinterpret_cast<float*>(Ws + 2 * WTILEB);       // [8 waves][8 quads][4]
-  float* Wd = red + 8 * 8 * 4;                                  // [9][2C] depth-wise taps, [2C] depth-wise bias, [2C] conv1 bias
+  unsigned char* Ws = smem + nfr_off_w();                       // [2 tiles][32][WROWB]
+  float* red = reinterpret_cast<float*>(smem + nfr_off_red(C)); // [8 waves][8 quads][4]
+  float* Wd = reinterpret_cast<float*>(smem + nfr_off_wd(C));   // [9][2C] depth-wise taps, [2C] depth-wise bias, [2C] conv1 bias
 
 #if NF_IMAGES
   {                                                              // image blockIdx.y: its pixels, and its rows of part [B][tiles][C]

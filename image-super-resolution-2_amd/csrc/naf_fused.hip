@@ -47,7 +47,7 @@ static int dwconv3_gate_pool_launch(const char* who, const float* in, int ldi, f
   if (nb > 1024) nb = 1024;      // 4 workgroups per CU: enough to stream at HBM rate, few enough partials to reduce
   FF_CHECK_ARG(work_floats >= (B ? B : 1) * nb * C, "%s: workspace too small", who);
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)ppb * cv * 16;
+  const size_t lds = pool4_lds(ppb, cv);
   if (!B) {
     hipLaunchKernelGGL(dwconv3_gate_pool_kernel, dim3((unsigned)nb), dim3(256), lds, st, in, ldi, out, ldo, H, W, C, w_tapmajor, bias, work);
     hipLaunchKernelGGL(pool_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, st, work, (int)nb, C, inv_p, pooled);
@@ -90,18 +90,18 @@ __global__ __launch_bounds__(512) void naf_ffn_kernel(NafFfnParams p) {
   constexpr int C = 16 * KS, GT = C / 32, NTO = C / 32;
   constexpr int W1SLOTS = 2 * KS + 1, W1ROWB = W1SLOTS * 16, W1PL = 32 * W1SLOTS;      // per plane (one 32-row tile)
   constexpr int W2ROWB = 80, W2PL = C * 5;
-  constexpr int W1B = W1PL * 16, W2B = W2PL * 16;
+  constexpr int W1B = nffn_w1b(KS), W2B = nffn_w2b(KS);          // the map: lds_layout.h
   constexpr int W1PIECES = 4 * W1PL / 64, W2PIECES = 2 * W2PL / 64;
   constexpr int W1ELEMS = 32 * C, W2ELEMS = C * 32;
   constexpr int REC = 4 * W1ELEMS + 2 * W2ELEMS;
-  constexpr int XLROWB = KS * 32 + 16;
+  constexpr int XLROWB = nffn_xlrowb(KS);
   constexpr int N1 = (W1PIECES + 7) / 8, N2 = (W2PIECES + 7) / 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* W1s = smem;                          // [4 planes: a_hi, a_lo, b_hi, b_lo][32][W1ROWB]
-  unsigned char* W2s = smem + 4 * W1B;                // [2 planes][C][80]
-  unsigned char* XLs = W2s + 2 * W2B;                 // [8 waves][32][XLROWB]
-  float* B4s = reinterpret_cast<float*>(XLs + 8 * 32 * XLROWB);        // [2C]
-  float* XSt = B4s + 2 * C;                           // x staging patches (KS == 4 only: the x_lo rows are too small to alias)
+  unsigned char* W2s = smem + nffn_off_w2(KS);        // [2 planes][C][80]
+  unsigned char* XLs = smem + nffn_off_xl(KS);        // [8 waves][32][XLROWB]
+  float* B4s = reinterpret_cast<float*>(smem + nffn_off_b4(KS));       // [2C]
+  float* XSt = reinterpret_cast<float*>(smem + nffn_off_xst(KS));      // x staging patches, where the x_lo rows are too small to alias (!nffn_xs_in_xl: KS == 4)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok0 = (long long)blockIdx.x * 256 + wid * 32;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(512) void naf_ffn_kernel(NafFfnParams p) {
   unsigned char* xl_row = XLs + (size_t)(wid * 32 + l31) * XLROWB + 16 * hh;
   {
     float v[KS][8];
-    float* xs = (KS >= 8) ? reinterpret_cast<float*>(XLs + (size_t)wid * 32 * XLROWB) : XSt + wid * (32 * FF_XS_ROW);
+    float* xs = nffn_xs_in_xl(KS) ? reinterpret_cast<float*>(XLs + (size_t)wid * 32 * XLROWB) : XSt + wid * (32 * FF_XS_ROW);
     ff_wave_rows_to_frags<KS / 4>(p.y, p.ldy, tok0, p.M, C, xs, lane, v);
     // the LayerNorm of ff_common.h (ff_frag_ln_stats / _step / ff_bf16_split), inline on purpose: with the statistics and the split
     // through the helpers ops.naf_ffn came out different in the last bits from the inline form (sha256 of the output, c = 64 and
@@ -243,7 +243,10 @@ __global__ __launch_bounds__(512) void naf_ffn_kernel(NafFfnParams p) {
   }
 
   // ---- epilogue: out = y + oscale[n] * (acc + b5[n]); residual loads first, transpose through LDS, coalesced stores ----
+  // per-wave [token][33] patches over the W4 / W5 images and, at KS == 4, the first 5 KB of the x_lo rows (waves 6 and 7 write into the
+  // rows of waves 0 and 1).  All of it is idle: the last x_lo read (GEMM1 of the last g) lies before that iteration's barriers A and B
   float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 33);
+  static_assert(ff_patches_bytes(8, 33) <= nffn_off_b4(KS), "the transpose patches must stay below the b4 vector");
   float rv[NTO][16];
 #pragma unroll
   for (int n = 0; n < NTO; ++n) {
@@ -277,11 +280,10 @@ __global__ __launch_bounds__(512) void naf_ffn_kernel(NafFfnParams p) {
 
 template <int KS, int NTERMS>
 static int launch_naf_ffn(const NafFfnParams& p, hipStream_t st) {
-  constexpr int C = 16 * KS;
-  const size_t lds = (size_t)4 * 32 * (2 * KS + 1) * 16 + (size_t)2 * C * 5 * 16 + (size_t)8 * 32 * (KS * 32 + 16) + (size_t)2 * C * 4 +
-                     (KS >= 8 ? 0 : (size_t)8 * 32 * FF_XS_ROW * 4);
+  constexpr size_t lds = nffn_lds(KS);
+  static_assert(lds <= FF_LDS_MAX, "LDS budget");
   static ff_device_once once;
-  if (!ff_raise_lds(once, "ff_naf_ffn", 160 * 1024, FF_LDS_SAY_ERR, &naf_ffn_kernel<KS, NTERMS>)) return FF_ERR_LAUNCH;
+  if (!ff_raise_lds(once, "ff_naf_ffn", FF_LDS_MAX, FF_LDS_SAY_ERR, &naf_ffn_kernel<KS, NTERMS>)) return FF_ERR_LAUNCH;
   const long long nblk = (p.M + 255) / 256;
   if (nblk >= (1LL << 31)) { ff_set_error("ff_naf_ffn: grid too large"); return FF_ERR_ARG; }
   hipLaunchKernelGGL((naf_ffn_kernel<KS, NTERMS>), dim3((unsigned)nblk), dim3(512), lds, st, p);

@@ -4,7 +4,7 @@
 __global__ __launch_bounds__(256) void NP_DW_KERNEL(const float* __restrict__ in, int ldi, float* __restrict__ out, int ldo,
                                                                 int H, int W, int C, const float* __restrict__ w, const float* __restrict__ bias,
                                                                 float* __restrict__ part) {
-  extern __shared__ float4 red[];                      // [ppb][C/4]
+  extern __shared__ float4 red[];                      // [ppb][C/4]: pool4_lds
 #if NP_IMAGES
   {                                                    // image blockIdx.y: its pixels, and its rows of part [B][gridDim.x][C]
     const long long P = (long long)H * W, b = blockIdx.y;

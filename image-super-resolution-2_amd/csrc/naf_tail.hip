@@ -65,9 +65,8 @@ struct NafTailParams {
 //   naf_tail_images<8, 4>  256  208  0        156 160 B      1           1
 template <int KS, int NW, int WGPC, bool IMG = false>
 static int launch_naf_tail(NafTailParams& p, hipStream_t st) {
-  constexpr int C = 16 * KS;
-  constexpr size_t lds = (size_t)8 * C * C + (size_t)9 * C * 4 + (size_t)NW * 32 * ((KS == 4 ? 64 : 32) + 4) * 4 + (IMG ? (size_t)NW * C * 4 : 0);
-  static_assert(lds <= 160 * 1024, "LDS budget");
+  constexpr size_t lds = ntl_lds(KS, NW, IMG);
+  static_assert(lds <= FF_LDS_MAX, "LDS budget");
   static ff_device_once once;
   if (!(IMG ? ff_raise_lds(once, "ff_naf_tail", lds, FF_LDS_SAY_ERR, &naf_tail_images_kernel<KS, NW>)
             : ff_raise_lds(once, "ff_naf_tail", lds, FF_LDS_SAY_ERR, &naf_tail_kernel<KS, NW>))) return FF_ERR_LAUNCH;

@@ -17,20 +17,21 @@ __global__ __launch_bounds__(NW * 64, (KS == 4 ? 2 : 1)) void NAF_TAIL_KERNEL(Na
   constexpr int NT = NW * 64;
   // row gather: CPP channels per pass.  64 at c = 64 (whole 256-byte rows, four per load instruction); 32 at c = 128 (eight
   // 128-byte segments per instruction) -- the patch is then 4.5 KB per wave and FOUR waves fit next to the 128 KB of weights
-  constexpr int CPP = KS == 4 ? 64 : 32, NPASS = C / CPP, XROW = CPP + 4;   // patch row: CPP + 4 dwords = 4 (mod 32): conflict-free b128
+  constexpr int CPP = KS == 4 ? 64 : 32, NPASS = C / CPP, XROW = ntl_xrow(KS);   // patch row: CPP + 4 dwords = 4 (mod 32): conflict-free b128 (the map: lds_layout.h)
   constexpr int LPR = CPP / 4, RPI = 64 / LPR, LPP = 32 / RPI, FPP = CPP / 16;   // lanes per row, rows per instruction, loads / fragments per pass
   constexpr bool EARLY = KS == 8;                      // c = 128 (one wave per SIMD, 512 registers): next tile's loads in flight during conv3 too
   constexpr int WPIECES = 4 * C * C / 8;               // 16-byte pieces of the weight image
   constexpr int F4 = NTO * KS, F5 = F4 + 2 * GT * KS;  // first fragment of W4 / W5
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const bf16x8* Wl = reinterpret_cast<const bf16x8*>(smem);            // [fragment][64 lanes]
-  float* cs = reinterpret_cast<float*>(smem + 8 * C * C);               // sca | b3 | beta | ln_g | ln_b | b4 (2C) | b5 | gamma
+  float* cs = reinterpret_cast<float*>(smem + ntl_off_cs(KS));          // sca | b3 | beta | ln_g | ln_b | b4 (2C) | b5 | gamma
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: scalar row bases
   const int l31 = lane & 31, hh = lane >> 5;
   const int rr = lane / LPR, cq = (lane % LPR) * 4;
-  float* xs = cs + 9 * C + wid * (32 * XROW);                           // wave-private patch: row gather, later the 32 x 33 transposes
+  float* xs = reinterpret_cast<float*>(smem + ntl_off_xs(KS)) + wid * (32 * XROW);   // wave-private patch: row gather, later the 32 x 33 transposes
+  static_assert(33 <= XROW, "the 32 x 33 transpose must fit in the wave's gather patch");
 #if NAF_TAIL_IMG
-  float* scw = cs + 9 * C + NW * (32 * XROW) + wid * C;                 // the wave's slot for its image's sca vector
+  float* scw = reinterpret_cast<float*>(smem + ntl_off_sca(KS, NW)) + wid * C;   // the wave's slot for its image's sca vector
   float nsca[C / 64];                                                   // the next tile's vector, lane l holds channels l (+ 64)
 #endif
 

@@ -82,7 +82,7 @@ extern "C" int ff_layernorm_bf16out(const float* in, int ldi, void* out, int ldo
 // Stage 1 (C % 4 == 0): a thread owns one float4 column and walks pixels with 4 independent loads in flight.
 __global__ __launch_bounds__(256) void pool_partial_v4_kernel(const float* __restrict__ in, int ld, long long P, int C,
                                                               int pix_per_chunk, float* __restrict__ part) {
-  extern __shared__ float4 red4[];                           // [rpi][cv]
+  extern __shared__ float4 red4[];                           // [rpi][cv]: pool4_lds
   const int cv = C >> 2, rpi = 256 / cv;                     // float4 columns, pixel rows per iteration
   const int col = threadIdx.x % cv, row = threadIdx.x / cv;
   const int chunk = blockIdx.x, b = blockIdx.y, nch = gridDim.x;
@@ -175,7 +175,7 @@ extern "C" int ff_pool_mean(const float* in, int ld, int B, long long P, int C, 
   const bool v4 = (C % 4 == 0) && (ld % 4 == 0) && (C / 4 <= 256) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)work & 15) == 0);
   if (v4) {
     const int cv = C / 4, rpi = 256 / cv;
-    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, B), dim3(256), (size_t)rpi * cv * 16, st, in, ld, P, C, ppc, work);
+    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, B), dim3(256), pool4_lds(rpi, cv), st, in, ld, P, C, ppc, work);
   } else {
     hipLaunchKernelGGL(pool_partial_kernel, dim3(nch, B), dim3(256), 0, st, in, ld, P, C, ppc, work);
   }
@@ -203,7 +203,7 @@ static int pool_partials_launch(const char* who, const float* in, int ld, int im
   const bool v4 = (C % 4 == 0) && (ld % 4 == 0) && (C / 4 <= 256) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)part & 15) == 0);
   if (v4) {
     const int cv = C / 4, rpi = 256 / cv;
-    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, images), dim3(256), (size_t)rpi * cv * 16, (hipStream_t)stream, in, ld, P, C, ppc, part);
+    hipLaunchKernelGGL(pool_partial_v4_kernel, dim3(nch, images), dim3(256), pool4_lds(rpi, cv), (hipStream_t)stream, in, ld, P, C, ppc, part);
   } else {
     hipLaunchKernelGGL(pool_partial_kernel, dim3(nch, images), dim3(256), 0, (hipStream_t)stream, in, ld, P, C, ppc, part);
   }
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256) void vec_mlp_kernel(const float* __restrict__ 
                                                       int Cout, int act2, float post, float* __restrict__ out) {
   extern __shared__ float sm[];
   float* xin = sm;            // [Cin]
-  float* hid = sm + Cin;      // [Ch]
+  float* hid = sm + vmlp_off_hid_f(Cin);      // [Ch]; the map: lds_layout.h, vmlp_lds(Cin, Ch)
   const int b = blockIdx.y, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < Cin; i += 256) xin[i] = in[(long long)b * Cin + i];
   __syncthreads();
@@ -296,7 +296,7 @@ extern "C" int ff_vec_mlp(const float* in, int B, int Cin, const float* W1, cons
   const int nout = W2 ? Cout : Ch;
   int gx = (nout + 3) / 4;
   if (gx > 256) gx = 256;                          // one wave per output row up to 1024 rows: the 4 MB SCA matrix is read by every CU at once
-  hipLaunchKernelGGL(vec_mlp_kernel, dim3(gx, B), dim3(256), (size_t)(Cin + Ch) * 4, (hipStream_t)stream, in, Cin, W1, b1, Ch,
+  hipLaunchKernelGGL(vec_mlp_kernel, dim3(gx, B), dim3(256), vmlp_lds(Cin, Ch), (hipStream_t)stream, in, Cin, W1, b1, Ch,
                      act1, W2, b2, Cout, act2, post, out);
   FF_LAUNCH_CHECK("ff_vec_mlp");
   return FF_OK;
@@ -312,10 +312,10 @@ __global__ __launch_bounds__(1024) void pool_vec_mlp_kernel(const float* __restr
                                                             const float* __restrict__ W2, const float* __restrict__ b2, int Cout, int act2,
                                                             float post, float* __restrict__ out, float* __restrict__ pooled) {
   extern __shared__ float sm[];
-  float* red = sm;                       // [16][CP]  (CP = Cin rounded up to 64)
-  const int CP = (Cin + 63) & ~63;
-  float* xin = sm + 16 * CP;             // [Cin]
-  float* hid = xin + Cin;                // [Ch]
+  float* red = sm;                       // [16][CP]  (CP = Cin rounded up to 64); the map: lds_layout.h, pvm_lds(Cin, Ch)
+  const int CP = pvm_cp(Cin);
+  float* xin = sm + 16 * CP;             // [Cin]: at pvm_off_xin_f(Cin), written over CP (through the function the address arithmetic moved)
+  float* hid = xin + Cin;                // [Ch]: at pvm_off_hid_f(Cin), behind the written-out xin
   const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
   // one workgroup per image (ff_pool_vec_mlp_images; blockIdx.x == 0 in the single-image launch): its own rows, its own output row
   part += (long long)blockIdx.x * rows * ld;
@@ -374,7 +374,7 @@ extern "C" int ff_pool_vec_mlp(const float* part, int rows, int ld, float inv_co
                                float* pooled_out, void* stream) {
   FF_CHECK_ARG(part && W1 && W2 && out, "ff_pool_vec_mlp: null pointer");
   FF_CHECK_ARG(rows > 0 && Cin > 0 && ld >= Cin && Ch > 0 && Ch <= 64 && Cout > 0 && Cin <= 512, "ff_pool_vec_mlp: bad dims (Cin <= 512, hidden width <= 64)");
-  hipLaunchKernelGGL(pool_vec_mlp_kernel, dim3(1), dim3(1024), (size_t)(16 * ((Cin + 63) & ~63) + Cin + Ch) * 4, (hipStream_t)stream, part, rows, ld,
+  hipLaunchKernelGGL(pool_vec_mlp_kernel, dim3(1), dim3(1024), pvm_lds(Cin, Ch), (hipStream_t)stream, part, rows, ld,
                      inv_count, Cin, W1, b1, Ch, act1, W2, b2, Cout, act2, post, out, pooled_out);
   FF_LAUNCH_CHECK("ff_pool_vec_mlp");
   return FF_OK;
@@ -387,7 +387,7 @@ extern "C" int ff_pool_vec_mlp_images(const float* part, int B, int rows, int ld
                                       float* pooled_out, void* stream) {
   FF_CHECK_ARG(part && W1 && W2 && out, "ff_pool_vec_mlp_images: null pointer");
   FF_CHECK_ARG(B > 0 && rows > 0 && Cin > 0 && ld >= Cin && Ch > 0 && Ch <= 64 && Cout > 0 && Cin <= 512, "ff_pool_vec_mlp_images: bad dims (Cin <= 512, hidden width <= 64)");
-  hipLaunchKernelGGL(pool_vec_mlp_kernel, dim3(B), dim3(1024), (size_t)(16 * ((Cin + 63) & ~63) + Cin + Ch) * 4, (hipStream_t)stream, part, rows, ld,
+  hipLaunchKernelGGL(pool_vec_mlp_kernel, dim3(B), dim3(1024), pvm_lds(Cin, Ch), (hipStream_t)stream, part, rows, ld,
                      inv_count, Cin, W1, b1, Ch, act1, W2, b2, Cout, act2, post, out, pooled_out);
   FF_LAUNCH_CHECK("ff_pool_vec_mlp_images");
   return FF_OK;

@@ -311,7 +311,7 @@ static int ocab_launch(OcabParams& p, const char* who, void* stream) {
   FF_STAMP_ARM(p);
   const long long nblk = (long long)p.B * p.nwx * p.nwy;
   FF_CHECK_ARG(nblk < (1LL << 31), "%s: grid too large", who);
-  static_assert(OC_LDS <= 160 * 1024, "LDS image too large");
+  static_assert(OC_LDS <= FF_LDS_MAX, "LDS image too large");
   static ff_device_once once;
   if (!ff_raise_lds(once, who, OC_LDS, FF_LDS_SAY_ERR, &ocab_attn_kernel<ROWS16>)) return FF_ERR_LAUNCH;
   hipLaunchKernelGGL(ocab_attn_kernel<ROWS16>, dim3((unsigned)nblk), dim3(512), OC_LDS, (hipStream_t)stream, p);

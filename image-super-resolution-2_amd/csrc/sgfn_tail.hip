@@ -198,6 +198,7 @@ __global__ __launch_bounds__(512) void sgfn_tail_kernel(SgfnParams p) {
   // ---- epilogue: + b2 + residual, through the wave's LDS patch (the halo buffers are idle) into 128-byte row segments ---------
   {
     float* patch = reinterpret_cast<float*>(smem) + wid * (32 * 36);
+    static_assert(8 * 32 * 36 * 4 <= SG_OFF_W, "the epilogue patches must fit in the idle halo buffers");
     const int tq = lane >> 3, q4 = 4 * (lane & 7);
     const bool rowok = cy < p.H;
     const long long tok0 = (long long)(b * p.H + (rowok ? cy : 0)) * p.W + x0;
@@ -254,7 +255,7 @@ extern "C" int ff_sgfn_tail(const float* h, int ldh, int c2, const float* stats,
   FF_STAMP_ARM(p);
   const long long nblk = (long long)B * p.ntx * p.nty;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_sgfn_tail: grid too large");
-  static_assert(SG_LDS <= 160 * 1024, "LDS image too large");
+  static_assert(SG_LDS <= FF_LDS_MAX, "LDS image too large");
   static_assert(8 * 32 * 36 * 4 <= 2 * SG_XBUF, "epilogue patches must fit in the halo buffers");
   static ff_device_once once;
   if (!ff_raise_lds(once, "ff_sgfn_tail", SG_LDS, FF_LDS_SAY_ERR, &sgfn_tail_kernel)) return FF_ERR_LAUNCH;

@@ -31,8 +31,6 @@ struct TokenLinParams {
   int wpi;                                 // token_linear_images_kernel: 256-token workgroups per image (grid (wpi, images), cm [images][K])
 };
 
-#define TL_TR 36   // floats per row of the transpose patch: 144 B keeps rows 16-byte aligned and ds_*_b128 conflict-free
-
 // NTERMS = 3: split-bf16 products hi*lo + lo*hi + hi*hi (fp32-grade); NTERMS = 1: plain bf16 (hi*hi only: a third of the MFMAs, no lo
 // fragments built or read; the weight image keeps its lo plane, unused).
 #ifndef TL_GELU_SIG
@@ -85,15 +83,15 @@ extern "C" int ff_token_linear(const float* x, int ldx, float* out, int ldo, lon
   const bool vec4 = (N % 4 == 0) && (ldo % 4 == 0) && ((((uintptr_t)out) & 15) == 0) && (!res || (ldr % 4 == 0 && (((uintptr_t)res) & 15) == 0)) &&
            (!res2 || (ldr2 % 4 == 0 && (((uintptr_t)res2) & 15) == 0 && (((uintptr_t)res2_scale) & 15) == 0));
   const int ks = kpad / 16;
-  const size_t lds = (size_t)2 * 2 * 32 * (2 * ks + 1) * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)n_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_linear: N too large for the LDS image");
+  const size_t lds = tl_lds(ks, n_tiles, 1);      // bias only
+  FF_CHECK_ARG(lds <= FF_LDS_MAX, "ff_token_linear: N too large for the LDS image");
   FF_CHECK_ARG(act == ACT_NONE || act == ACT_GELU, "ff_token_linear: act must be none or gelu");
   const long long nblk = (M + 255) / 256;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_linear: grid too large");
 #define TL_LAUNCH(A, KSV, V4, NTM)                                                                                          \
   do {                                                                                                                      \
     static ff_device_once once;                                                                                             \
-    if (!ff_raise_lds(once, "ff_token_linear", 160 * 1024, FF_LDS_SAY_ERR, &token_linear_kernel<A, KSV, V4, false, NTM>)) return FF_ERR_LAUNCH; \
+    if (!ff_raise_lds(once, "ff_token_linear", FF_LDS_MAX, FF_LDS_SAY_ERR, &token_linear_kernel<A, KSV, V4, false, NTM>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((token_linear_kernel<A, KSV, V4, false, NTM>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p); \
   } while (0)
 #define TL_LAUNCH_NT(A, KSV, V4) do { if (nterms == 3) TL_LAUNCH(A, KSV, V4, 3); else TL_LAUNCH(A, KSV, V4, 1); } while (0)
@@ -133,14 +131,14 @@ extern "C" int ff_token_linear_rows16(const float* x, int ldx, void* out16, int 
   p.stats = nullptr; p.st_lo = 0; p.st_hi = 0; p.st_eps = 0.f;
   p.x2 = nullptr; p.ldx2 = 0; p.cm = nullptr; p.gw1t = nullptr; p.gb1 = nullptr; p.gw2 = nullptr; p.gb2 = 0.f; p.wpi = 0;
   const int ks = kpad / 16;
-  const size_t lds = (size_t)2 * 2 * 32 * (2 * ks + 1) * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)2 * n_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_linear_rows16: N too large for the LDS image");
+  const size_t lds = tl_lds(ks, n_tiles, 2);      // bias | column scale
+  FF_CHECK_ARG(lds <= FF_LDS_MAX, "ff_token_linear_rows16: N too large for the LDS image");
   const long long nblk = (M + 255) / 256;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_linear_rows16: grid too large");
 #define TL_LAUNCH16(KSV)                                                                                                    \
   do {                                                                                                                      \
     static ff_device_once once;                                                                                             \
-    if (!ff_raise_lds(once, "ff_token_linear_rows16", 160 * 1024, FF_LDS_SAY_ERR, &token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>)) return FF_ERR_LAUNCH; \
+    if (!ff_raise_lds(once, "ff_token_linear_rows16", FF_LDS_MAX, FF_LDS_SAY_ERR, &token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((token_linear_rows16_kernel<ACT_NONE, KSV, true, false, 1>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p); \
   } while (0)
   if (ks == 4) TL_LAUNCH16(4); else if (ks == 8) TL_LAUNCH16(8); else TL_LAUNCH16(12);
@@ -169,11 +167,11 @@ static int token_linear_gated_launch(const char* who, const float* x, int ldx, c
   p.x = x; p.out = out; p.w = (const __bf16*)w_tiles; p.bias = bias_padded; p.res = res; p.M = M; p.ldx = ldx; p.ldo = ldo; p.ldr = ldr;
   p.K = K; p.N = N; p.NT = n_tiles; p.act = ACT_NONE;
   p.x2 = x2; p.ldx2 = ldx2; p.cm = cm; p.gw1t = gw1t; p.gb1 = gb1; p.gw2 = gw2; p.gb2 = gb2; p.wpi = (int)wpi;
-  const size_t lds = (size_t)2 * 2 * 32 * 25 * 16 + (size_t)8 * 32 * TL_TR * 4 + (size_t)8 * 32 * FF_XS_ROW * 4 + (size_t)n_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "%s: N too large for the LDS image", who);
+  const size_t lds = tl_lds(12, n_tiles, 1);      // the gated kernels are the KS = 12 instantiations; bias only
+  FF_CHECK_ARG(lds <= FF_LDS_MAX, "%s: N too large for the LDS image", who);
   static ff_device_once once[2];
-  if (!(!B ? ff_raise_lds(once[0], who, 160 * 1024, FF_LDS_SAY_ERR, &token_linear_kernel<ACT_NONE, 12, true, true, 3>, &token_linear_kernel<ACT_NONE, 12, true, true, 1>)
-           : ff_raise_lds(once[1], who, 160 * 1024, FF_LDS_SAY_ERR, &token_linear_images_kernel<ACT_NONE, 12, true, true, 3>, &token_linear_images_kernel<ACT_NONE, 12, true, true, 1>)))
+  if (!(!B ? ff_raise_lds(once[0], who, FF_LDS_MAX, FF_LDS_SAY_ERR, &token_linear_kernel<ACT_NONE, 12, true, true, 3>, &token_linear_kernel<ACT_NONE, 12, true, true, 1>)
+           : ff_raise_lds(once[1], who, FF_LDS_MAX, FF_LDS_SAY_ERR, &token_linear_images_kernel<ACT_NONE, 12, true, true, 3>, &token_linear_images_kernel<ACT_NONE, 12, true, true, 1>)))
     return FF_ERR_LAUNCH;
   const dim3 grid((unsigned)nblk, B ? (unsigned)B : 1u);
   if (!B) {

@@ -10,13 +10,12 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
   constexpr int TL_SLOTS = 2 * TL_KS + 1, TL_ROWB = TL_SLOTS * 16, TL_PL = 32 * TL_SLOTS, TL_PIECES = 2 * TL_PL / 64;
   constexpr int TL_TILE_ELEMS = 32 * 16 * TL_KS, KPAD = 16 * TL_KS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int WB = TL_PL * 16;                     // bytes per plane
-  constexpr int BUFB = 2 * WB;                       // one ring slot (hi + lo)
+  constexpr int BUFB = tl_bufb(TL_KS), WB = BUFB / 2;   // one ring slot (hi + lo planes of WB bytes); the map: lds_layout.h
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
-  float* tr = reinterpret_cast<float*>(smem + 2 * BUFB) + wid * (32 * TL_TR);   // wave-private transpose patch [token][36]
-  float* xs = reinterpret_cast<float*>(smem + 2 * BUFB + 8 * 32 * TL_TR * 4) + wid * (32 * FF_XS_ROW);   // wave-private x staging
-  float* Bs = reinterpret_cast<float*>(smem + 2 * BUFB + 8 * 32 * TL_TR * 4 + 8 * 32 * FF_XS_ROW * 4);   // [NT*32] bias
+  float* tr = reinterpret_cast<float*>(smem + tl_off_tr(TL_KS)) + wid * (32 * TL_TR);   // wave-private transpose patch [token][36]
+  float* xs = reinterpret_cast<float*>(smem + tl_off_xs(TL_KS)) + wid * (32 * FF_XS_ROW);   // wave-private x staging
+  float* Bs = reinterpret_cast<float*>(smem + tl_off_vec(TL_KS, p.NT, 0));   // [NT*32] bias
 #if TL_IMAGES
   const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;
   const float* cmrow = p.cm + (long long)blockIdx.y * p.K;
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
   dma(0, 0);
   for (int i = tid; i < p.NT * 32; i += 512) Bs[i] = p.bias ? p.bias[i] : 0.f;
 #if TL_OUT16
-  float* Ss = Bs + p.NT * 32;                        // [NT*32] column scale
+  float* Ss = Bs + p.NT * 32;                        // [NT*32] column scale = tl_off_vec(TL_KS, p.NT, 1), written out: through the function the kernel's scalar code moved
   for (int i = tid; i < p.NT * 32; i += 512) Ss[i] = p.rs2[i];
 #endif
 

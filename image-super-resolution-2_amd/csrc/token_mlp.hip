@@ -36,11 +36,11 @@ struct TokenMlpParams {
 template <bool VEC4, int NTERMS>
 __global__ __launch_bounds__(512) void token_mlp_kernel(TokenMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int W1B = W1PL * 16, W2B = W2PL * 16;
+  constexpr int W1B = TM_W1B, W2B = TM_W2B;          // the map: token_mlp_layout.h
   unsigned char* W1s = smem;                         // [2 planes][32][400]
-  unsigned char* W2s = smem + 2 * W1B;               // [2 planes][192][80]
-  unsigned char* XLs = smem + 2 * W1B + 2 * W2B;     // [8 waves][32 tokens][400]
-  float* B1s = reinterpret_cast<float*>(XLs + 8 * 32 * XLROWB);   // [HT*32] fc1 bias (read every hidden tile)
+  unsigned char* W2s = smem + TM_OFF_W2;             // [2 planes][192][80]
+  unsigned char* XLs = smem + TM_OFF_XL;             // [8 waves][32 tokens][400]
+  float* B1s = reinterpret_cast<float*>(smem + TM_OFF_B1);   // [HT*32] fc1 bias (read every hidden tile)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok = (long long)blockIdx.x * 256 + wid * 32 + l31;
@@ -100,7 +100,8 @@ __global__ __launch_bounds__(512) void token_mlp_kernel(TokenMlpParams p) {
     // 16-byte form: the accumulator's four consecutive channels per r >> 2 go to the patch as one ds_write_b128, a lane
     // then owns (token row lane >> 3 (+8 per step), channel quad lane & 7): one float4 residual load and one float4
     // store per step = 8 whole 128-byte row segments per instruction (2 with dword accesses)
-    float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);    // per-wave [token][36] inside the (now idle) W images
+    float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);    // per-wave [token][36] over the (now idle) W images
+    static_assert(TM_TRB(36) <= TM_OFF_XL, "the transpose patches must stay inside the W images");
     const int tq = lane >> 3, q4 = 4 * (lane & 7);
     f32x4 rq[6][4];
 #pragma unroll
@@ -142,7 +143,8 @@ __global__ __launch_bounds__(512) void token_mlp_kernel(TokenMlpParams p) {
     }
     return;
   }
-  float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 33);      // per-wave [token][33] inside the (now idle) W images
+  float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 33);    // per-wave [token][33] over the (now idle) W images
+  static_assert(TM_TRB(33) <= TM_OFF_XL, "the transpose patches must stay inside the W images");
   float rv[6][16];
 #pragma unroll
   for (int n = 0; n < 6; ++n) {
@@ -208,11 +210,11 @@ struct TokenProjMlpParams {
 
 __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int W1B = W1PL * 16, W2B = W2PL * 16;
+  constexpr int W1B = TM_W1B, W2B = TM_W2B;
   unsigned char* W1s = smem;
-  unsigned char* W2s = smem + 2 * W1B;
-  unsigned char* XLs = smem + 2 * W1B + 2 * W2B;
-  float* B1s = reinterpret_cast<float*>(XLs + 8 * 32 * XLROWB);
+  unsigned char* W2s = smem + TM_OFF_W2;
+  unsigned char* XLs = smem + TM_OFF_XL;
+  float* B1s = reinterpret_cast<float*>(smem + TM_OFF_B1);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;   // blockIdx.y = image (0 in the single-gate launch)
@@ -280,7 +282,8 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
   // ---- residuals: coalesced float4 loads (lane = token row lane>>3 (+8i), channel quad) go through the wave's own LDS rows
   //      (the att_lo image is dead) and come back in accumulator order: x1 = proj + shortcut + conv * scale ------------
   {
-    float* tr = reinterpret_cast<float*>(XLs + (size_t)wid * 32 * XLROWB);      // [32 tokens][36]
+    float* tr = reinterpret_cast<float*>(XLs + (size_t)wid * 32 * XLROWB);    // [32 tokens][36] over the wave's own x_lo rows
+    static_assert(32 * 36 * 4 <= 32 * XLROWB, "the wave's patch must fit in its x_lo rows");
     const int tq = lane >> 3, q4 = 4 * (lane & 7);
 #pragma unroll
     for (int n = 0; n < 6; ++n) {
@@ -348,7 +351,8 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
 
   // ---- epilogue: out = accumulators (x1 + fc2 part) + b2, transposed through LDS into 128-byte row segments ------------
   {
-    float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);
+    float* tr = reinterpret_cast<float*>(smem) + wid * (32 * 36);    // per-wave [token][36] over the (now idle) W images
+    static_assert(TM_TRB(36) <= TM_OFF_XL, "the transpose patches must stay inside the W images");
     const int tq = lane >> 3, q4 = 4 * (lane & 7);
 #pragma unroll
     for (int n = 0; n < 6; ++n) {
@@ -389,10 +393,10 @@ __global__ __launch_bounds__(512) void token_projmlp_kernel(TokenProjMlpParams p
 __global__ __launch_bounds__(512) void token_projmlp_bf16_kernel(TokenProjMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Gs = reinterpret_cast<float*>(smem + PM_OFF_VEC);
-  float* Bts = Gs + TM_KP;
-  float* Scs = Bts + TM_KP;                              // the image's gate row (zero without c2 and in the padded channels)
-  float* Bps = Scs + TM_KP;                              // the padded projection bias (token_projmlp_bf16_proj.inc)
-  float* B1s = Bps + TM_KP;
+  float* Bts = reinterpret_cast<float*>(smem + PM_OFF_BT);
+  float* Scs = reinterpret_cast<float*>(smem + PM_OFF_SC);   // the image's gate row (zero without c2 and in the padded channels)
+  float* Bps = reinterpret_cast<float*>(smem + PM_OFF_BP);   // the padded projection bias (token_projmlp_bf16_proj.inc)
+  float* B1s = reinterpret_cast<float*>(smem + PM_OFF_B1);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hh = lane >> 5;
   const long long tok0 = ((long long)blockIdx.y * p.wpi + blockIdx.x) * 256 + wid * 32;   // blockIdx.y = image (0 in the single-gate launch)
@@ -571,18 +575,18 @@ static int token_projmlp_launch(const float* att, int lda, const float* x, int l
   p.M = M; p.lda = lda; p.ldx = ldx; p.ldc = ldc; p.ldo = ldo; p.K = K; p.N = K; p.HT = hidden_tiles; p.eps = eps; p.io_bf16 = io_bf16;
   p.wpi = (int)(((M + 255) / 256) / images); p.rs2_ld = images > 1 ? scale_ld : 0;
   FF_STAMP_ARM(p);
-  const size_t lds = (size_t)(2 * W1PL + 2 * W2PL) * 16 + (size_t)8 * 32 * XLROWB + (size_t)hidden_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
+  const size_t lds = TM_LDS(hidden_tiles);
+  FF_CHECK_ARG(lds <= FF_LDS_MAX, "ff_token_projmlp: hidden too large for the LDS image");
   const long long nblk = (M + 255) / 256;
   const dim3 grid((unsigned)(nblk / images), (unsigned)images);
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_projmlp: grid too large");
   FF_CHECK_ARG(M * (long long)(ldx > ldc ? ldx : ldc) < (1LL << 31), "ff_token_projmlp: too many tokens for 32-bit row offsets");
   static ff_device_once once, once2;
-  if (!ff_raise_lds(once, "ff_token_projmlp", 160 * 1024, FF_LDS_SAY_ERR, &token_projmlp_kernel)) return FF_ERR_LAUNCH;
+  if (!ff_raise_lds(once, "ff_token_projmlp", FF_LDS_MAX, FF_LDS_SAY_ERR, &token_projmlp_kernel)) return FF_ERR_LAUNCH;
   if (nterms == 1) {
-    const size_t lds2 = (size_t)PM_OFF_VEC + (size_t)(4 * TM_KP + hidden_tiles * 32) * 4;     // gamma | beta | gate row | projection bias | b1
-    FF_CHECK_ARG(lds2 <= 160 * 1024, "ff_token_projmlp: hidden too large for the LDS image");
-    if (!ff_raise_lds(once2, "ff_token_projmlp", 160 * 1024, FF_LDS_SAY_ERR, &token_projmlp_bf16_kernel)) return FF_ERR_LAUNCH;
+    const size_t lds2 = PM_LDS(hidden_tiles);
+    FF_CHECK_ARG(lds2 <= FF_LDS_MAX, "ff_token_projmlp: hidden too large for the LDS image");
+    if (!ff_raise_lds(once2, "ff_token_projmlp", FF_LDS_MAX, FF_LDS_SAY_ERR, &token_projmlp_bf16_kernel)) return FF_ERR_LAUNCH;
     hipLaunchKernelGGL(token_projmlp_bf16_kernel, grid, dim3(512), lds2, (hipStream_t)stream, p);
   } else hipLaunchKernelGGL(token_projmlp_kernel, grid, dim3(512), lds, (hipStream_t)stream, p);
   FF_LAUNCH_CHECK("ff_token_projmlp");
@@ -625,14 +629,14 @@ extern "C" int ff_token_mlp(const float* x, int ldx, float* out, int ldo, long l
   p.x = x; p.out = out; p.gamma = gamma; p.beta = beta; p.w = (const __bf16*)w_tiles;
   p.b1 = b1_padded; p.b2 = b2; p.M = M; p.ldx = ldx; p.ldo = ldo; p.K = K; p.N = N; p.HT = hidden_tiles; p.eps = eps;
   const bool vec4 = (N % 4 == 0) && (ldo % 4 == 0) && ((((uintptr_t)out) & 15) == 0) && ((((uintptr_t)b2) & 15) == 0);
-  const size_t lds = (size_t)(2 * W1PL + 2 * W2PL) * 16 + (size_t)8 * 32 * XLROWB + (size_t)hidden_tiles * 32 * 4;
-  FF_CHECK_ARG(lds <= 160 * 1024, "ff_token_mlp: hidden too large for the LDS image");
+  const size_t lds = TM_LDS(hidden_tiles);
+  FF_CHECK_ARG(lds <= FF_LDS_MAX, "ff_token_mlp: hidden too large for the LDS image");
   const long long nblk = (M + 255) / 256;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_token_mlp: grid too large");
 #define TM_LAUNCH(V4, NTM)                                                                                                 \
   do {                                                                                                                     \
     static ff_device_once once;                                                                                            \
-    if (!ff_raise_lds(once, "ff_token_mlp", 160 * 1024, FF_LDS_SAY_ERR, &token_mlp_kernel<V4, NTM>)) return FF_ERR_LAUNCH; \
+    if (!ff_raise_lds(once, "ff_token_mlp", FF_LDS_MAX, FF_LDS_SAY_ERR, &token_mlp_kernel<V4, NTM>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((token_mlp_kernel<V4, NTM>), dim3((unsigned)nblk), dim3(512), lds, (hipStream_t)stream, p);         \
   } while (0)
   if (nterms == 3) { if (vec4) TM_LAUNCH(true, 3); else TM_LAUNCH(false, 3); }

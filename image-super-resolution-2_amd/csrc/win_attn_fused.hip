@@ -397,7 +397,7 @@ extern "C" int ff_win_attn_fused(const float* x, int ldx, float* out, int ldo, i
   FF_STAMP_ARM(p);
   const long long nblk = (long long)B * p.nwx * p.nwy;
   FF_CHECK_ARG(nblk < (1LL << 31), "ff_win_attn_fused: grid too large");
-  static_assert(WF_LDS <= 160 * 1024, "LDS image too large");
+  static_assert(WF_LDS <= FF_LDS_MAX, "LDS image too large");
   static_assert(8 * 32 * WF_XS_ROW * 4 <= 8 * WF_KWAVE + 2 * WF_VPLB, "gather patch must fit in the K / V area");
 #define WF_LAUNCH(WWV)                                                                                                        \
   do {                                                                                                                        \
@@ -405,7 +405,7 @@ extern "C" int ff_win_attn_fused(const float* x, int ldx, float* out, int ldo, i
     if (!ff_raise_lds(once, "ff_win_attn_fused", WF_LDS, FF_LDS_SAY_ERR, &win_attn_fused_kernel<WWV, 3>)) return FF_ERR_LAUNCH; \
     hipLaunchKernelGGL((win_attn_fused_kernel<WWV, 3>), dim3((unsigned)nblk), dim3(512), WF_LDS, (hipStream_t)stream, p);     \
   } while (0)
-  static_assert(W2_LDS <= 160 * 1024, "LDS image too large");
+  static_assert(W2_LDS <= FF_LDS_MAX, "LDS image too large");
   static_assert(8 * 32 * WF_XS_ROW * 4 <= 2 * W2_KBUF + 2 * W2_VBUF, "gather patch must fit in the K / V area");
 #define W2_LAUNCH1(WWV, ON)                                                                                                   \
   do {                                                                                                                        \
