@@ -5,6 +5,7 @@
 // The library owns its weight copies and one workspace (packed by buffer lifetime at export time); the caller owns the input
 // and output tensors; every launch goes to the caller's stream in plan order, so ff_forward is asynchronous and
 // graph-capturable like the per-operator entry points it drives.  No internal threads; one handle per host thread.
+// ff_forward_image_u8 serves images of any size at least the tile's from ONE tile plan: uint8 in, overlap tiles B at a time, uint8 out.
 #include "ff_common.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -12,6 +13,7 @@
 #include <vector>
 
 extern "C" int ff_abi_version(void);
+extern "C" int ff_tile_positions(int n, int tile, int step, int* out, int cap);      // csrc/tile_image.hip (pure host)
 union FFVal { long long i; double f; void* p; };
 #include "ff_dispatch_gen.h"      // generated from include/ff_kernels.h by build.py: FF_DISPATCH_NAMES[], ff_dispatch(id, vals)
 
@@ -147,11 +149,8 @@ extern "C" int ff_finalize(void* handle) {
   return FF_OK;
 }
 
-extern "C" int ff_forward(void* handle, const float* lr_dev, int B, int H, int W, float* out_dev, void* stream) {
-  ff_model* m = (ff_model*)handle;
-  FF_CHECK_ARG(m && lr_dev && out_dev, "ff_forward: null argument");
-  FF_CHECK_ARG(m->finalized, "ff_forward: ff_finalize has not succeeded on this handle");
-  FF_CHECK_ARG(B == m->in[0] && H == m->in[2] && W == m->in[3], "ff_forward: this plan is for input [%d,3,%d,%d], got [%d,3,%d,%d]", m->in[0], m->in[2], m->in[3], B, H, W);
+// One replay of the plan: lr_dev / out_dev stand for the plan's input / output space.  `who` names the entry point in a fork / join error.
+static int replay_plan(ff_model* m, const float* lr_dev, float* out_dev, void* stream, const char* who) {
   FFVal v[64];
   hipStream_t main_st = (hipStream_t)stream;
   for (const PlanCall& c : m->calls) {
@@ -165,7 +164,7 @@ extern "C" int ff_forward(void* handle, const float* lr_dev, int B, int H, int W
           for (int i = 0; i < 2 && ok; ++i)
             ok = hipEventRecord(m->ev_join[i], m->side[i]) == hipSuccess && hipStreamWaitEvent(main_st, m->ev_join[i], 0) == hipSuccess;
         }
-        if (!ok) { ff_set_error("ff_forward: stream fork / join failed: %s", hipGetErrorString(hipGetLastError())); return FF_ERR_LAUNCH; }
+        if (!ok) { ff_set_error("%s: stream fork / join failed: %s", who, hipGetErrorString(hipGetLastError())); return FF_ERR_LAUNCH; }
       }
       continue;
     }
@@ -187,6 +186,97 @@ extern "C" int ff_forward(void* handle, const float* lr_dev, int B, int H, int W
     if (rc != FF_OK) return rc;               // ff_last_error() carries the failing entry point's message
   }
   return FF_OK;
+}
+
+extern "C" int ff_forward(void* handle, const float* lr_dev, int B, int H, int W, float* out_dev, void* stream) {
+  ff_model* m = (ff_model*)handle;
+  FF_CHECK_ARG(m && lr_dev && out_dev, "ff_forward: null argument");
+  FF_CHECK_ARG(m->finalized, "ff_forward: ff_finalize has not succeeded on this handle");
+  FF_CHECK_ARG(B == m->in[0] && H == m->in[2] && W == m->in[3], "ff_forward: this plan is for input [%d,3,%d,%d], got [%d,3,%d,%d]", m->in[0], m->in[2], m->in[3], B, H, W);
+  return replay_plan(m, lr_dev, out_dev, stream, "ff_forward");
+}
+
+// ---- any-size images through a TILE plan ([B,3,t,t] -> [B,3,4t,4t], B <= 16): the plugin's _tiled_forward (models/team29_FreqFusion/
+// io.py:116-164) on uint8 images, B tiles per replay.  The caller's work buffer, every part 256-byte aligned, in this order:
+//     acc [3][4H][4W] fp32 | wsum [4H][4W] fp32 | tile input [B,3,t,t] fp32 | tile output [B,3,4t,4t] fp32 | ramp table [4][4t] fp32
+// After the call acc and wsum hold the un-normalised canvas (ff_tile_finish_u8 only reads them).
+enum { IW_ACC = 0, IW_WSUM, IW_TIN, IW_TOUT, IW_RAMPS, IW_PARTS };
+static const int IMAGE_SCALE = 4, IMAGE_MAX_BATCH = 16;
+
+static bool tile_plan_ok(const ff_model* m) {
+  const int* a = m->in; const int* b = m->out;
+  return a[0] >= 1 && a[0] <= IMAGE_MAX_BATCH && a[1] == 3 && a[2] >= 1 && a[2] == a[3] && b[0] == a[0] && b[1] == 3 &&
+         b[2] == IMAGE_SCALE * a[2] && b[3] == IMAGE_SCALE * a[3];
+}
+
+static long long image_layout(const ff_model* m, int H, int W, long long (&off)[IW_PARTS]) {
+  const long long B = m->in[0], t = m->in[2], P = (long long)IMAGE_SCALE * H * IMAGE_SCALE * W, st = IMAGE_SCALE * t;
+  const long long bytes[IW_PARTS] = {12 * P, 4 * P, 12 * B * t * t, 12 * B * st * st, 16 * st};
+  long long at = 0;
+  for (int i = 0; i < IW_PARTS; ++i) { off[i] = at; at += (bytes[i] + 255) / 256 * 256; }
+  return at;
+}
+
+extern "C" long long ff_image_workspace_bytes(void* handle, int H, int W) {
+  ff_model* m = (ff_model*)handle;
+  if (!m) { ff_set_error("ff_image_workspace_bytes: null handle"); return -1; }
+  if (!tile_plan_ok(m)) { ff_set_error("ff_image_workspace_bytes: not a tile plan (input [%d,%d,%d,%d], output [%d,%d,%d,%d])", m->in[0], m->in[1], m->in[2], m->in[3], m->out[0], m->out[1], m->out[2], m->out[3]); return -1; }
+  if (H < m->in[2] || W < m->in[3]) { ff_set_error("ff_image_workspace_bytes: a %dx%d image is smaller than the plan's %dx%d tile", H, W, m->in[2], m->in[3]); return -1; }
+  long long off[IW_PARTS];
+  return image_layout(m, H, W, off);
+}
+
+extern "C" int ff_forward_image_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, unsigned char* out_dev, void* work,
+                                   long long work_bytes, void* stream) {
+  ff_model* m = (ff_model*)handle;
+  FF_CHECK_ARG(m && img_dev && out_dev && work, "ff_forward_image_u8: null argument");
+  FF_CHECK_ARG(m->finalized, "ff_forward_image_u8: ff_finalize has not succeeded on this handle");
+  FF_CHECK_ARG(tile_plan_ok(m), "ff_forward_image_u8: the handle's plan must map square tiles [B,3,t,t] to [B,3,4t,4t] with B <= %d; this one maps [%d,%d,%d,%d] to [%d,%d,%d,%d]",
+               IMAGE_MAX_BATCH, m->in[0], m->in[1], m->in[2], m->in[3], m->out[0], m->out[1], m->out[2], m->out[3]);
+  const int B = m->in[0], t = m->in[2], st = IMAGE_SCALE * t;
+  FF_CHECK_ARG(H <= (1 << 28) && W <= (1 << 28), "ff_forward_image_u8: a %dx%d image is beyond the 2^28 samples per side that 4H and 4W as int allow", H, W);
+  FF_CHECK_ARG(H >= t && W >= t, "ff_forward_image_u8: a %dx%d image does not hold one full %dx%d tile of this plan (ragged tiles, as the reference "
+               "cuts from images smaller than the tile, are out of scope)", H, W, t, t);
+  FF_CHECK_ARG(overlap >= 0 && overlap < t, "ff_forward_image_u8: overlap %d must lie in [0, tile = %d)", overlap, t);
+  long long off[IW_PARTS];
+  const long long need = image_layout(m, H, W, off);
+  FF_CHECK_ARG(work_bytes >= need, "ff_forward_image_u8: a %dx%d image needs %lld bytes of work space, got %lld", H, W, need, work_bytes);
+  const int step = t - overlap, blend = IMAGE_SCALE * overlap < st / 4 ? IMAGE_SCALE * overlap : st / 4;
+  std::vector<int> ys((H - t) / step + 2), xs((W - t) / step + 2);
+  const int ny = ff_tile_positions(H, t, step, ys.data(), (int)ys.size()), nx = ff_tile_positions(W, t, step, xs.data(), (int)xs.size());
+  FF_CHECK_ARG(ny > 0 && nx > 0, "ff_forward_image_u8: cannot place %dx%d tiles with step %d on a %dx%d image", t, t, step, H, W);
+
+  float* acc = (float*)((char*)work + off[IW_ACC]);
+  float* wsum = (float*)((char*)work + off[IW_WSUM]);
+  float* tin = (float*)((char*)work + off[IW_TIN]);
+  float* tout = (float*)((char*)work + off[IW_TOUT]);
+  float* tab = (float*)((char*)work + off[IW_RAMPS]);
+  const int HS = IMAGE_SCALE * H, WS = IMAGE_SCALE * W;
+  const long long P = (long long)HS * WS;
+  if (hipMemsetAsync(acc, 0, (size_t)(12 * P), (hipStream_t)stream) != hipSuccess || hipMemsetAsync(wsum, 0, (size_t)(4 * P), (hipStream_t)stream) != hipSuccess) {
+    ff_set_error("ff_forward_image_u8: clearing the canvas failed: %s", hipGetErrorString(hipGetLastError()));
+    return FF_ERR_LAUNCH;
+  }
+  int rc = ff_tile_ramps(tab, st, blend, stream);
+  if (rc != FF_OK) return rc;
+  const long long ntiles = (long long)ny * nx;
+  for (long long g0 = 0; g0 < ntiles; g0 += B) {
+    for (int s = 0; s < B; ++s) {                            // a short last group repeats its last tile: the forward reads no stale slot
+      const long long k = g0 + s < ntiles ? g0 + s : ntiles - 1;
+      rc = ff_tile_cut_u8(img_dev, H, W, ys[k / nx], xs[k % nx], t, t, tin + (long long)s * 3 * t * t, stream);
+      if (rc != FF_OK) return rc;
+    }
+    rc = replay_plan(m, tin, tout, stream, "ff_forward_image_u8");
+    if (rc != FF_OK) return rc;
+    for (int s = 0; s < B && g0 + s < ntiles; ++s) {         // in tile order (y outer, x inner), as the plugin accumulates
+      const int y = ys[(g0 + s) / nx], x = xs[(g0 + s) % nx];
+      const float* wy = tab + (long long)((y > 0 ? 1 : 0) + (y + t < H ? 2 : 0)) * st;
+      const float* wx = tab + (long long)((x > 0 ? 1 : 0) + (x + t < W ? 2 : 0)) * st;
+      rc = ff_tile_accum(tout + (long long)s * 3 * st * st, 3, st, st, wy, wx, acc, wsum, HS, WS, IMAGE_SCALE * y, IMAGE_SCALE * x, stream);
+      if (rc != FF_OK) return rc;
+    }
+  }
+  return ff_tile_finish_u8(acc, wsum, HS, WS, out_dev, stream);
 }
 
 extern "C" int ff_destroy(void* handle) {

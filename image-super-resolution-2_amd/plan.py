@@ -363,6 +363,30 @@ class NativeModel:
                                      torch.cuda.current_stream().cuda_stream))
         return out
 
+    def image_workspace_bytes(self, H: int, W: int) -> int:
+        """Bytes of `work` that forward_image_u8 needs for an H x W image (the handle's plan is the tile plan)."""
+        n = int(self.L.ff_image_workspace_bytes(self.h, int(H), int(W)))
+        if n < 0:
+            raise _lib.FFError(self.L.ff_last_error().decode())
+        return n
+
+    def forward_image_u8(self, img_u8: torch.Tensor, overlap: int = 32, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 HWC [H,W,3] on the device -> uint8 [4H,4W,3] through the tile plan (ff_forward_image_u8): the plugin's overlap-tile
+        result, the plan's batch of tiles per replay.  `work` is a contiguous CUDA uint8 buffer of at least image_workspace_bytes(H, W)
+        bytes (allocated here when None); afterwards it holds the un-normalised canvas in the layout include/ff_kernels.h states."""
+        if not (isinstance(img_u8, torch.Tensor) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3
+                and img_u8.shape[2] == 3 and img_u8.is_contiguous()):
+            raise _lib.FFError("NativeModel.forward_image_u8: expected a contiguous CUDA uint8 [H,W,3] tensor")
+        H, W, _ = img_u8.shape
+        if work is None:
+            work = torch.empty(self.image_workspace_bytes(H, W), device=img_u8.device, dtype=torch.uint8)
+        elif not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+            raise _lib.FFError("NativeModel.forward_image_u8: work must be a contiguous CUDA uint8 tensor")
+        out = torch.empty((4 * H, 4 * W, 3), device=img_u8.device, dtype=torch.uint8)
+        _lib.check(self.L.ff_forward_image_u8(self.h, img_u8.data_ptr(), H, W, int(overlap), out.data_ptr(), work.data_ptr(), work.numel(),
+                                              torch.cuda.current_stream().cuda_stream))
+        return out
+
     def close(self):
         if self.h:
             self.L.ff_destroy(self.h)

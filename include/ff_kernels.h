@@ -497,6 +497,23 @@ int ff_tile_accum(const float* tile, int C, int th, int tw, const float* wy, con
                   int H, int W, int sy, int sx, void* stream);
 int ff_tile_normalize(float* acc, const float* wsum, int C, int H, int W, void* stream);
 
+/* The image side of the tiled executor (csrc/tile_image.hip; ff_forward_image_u8 below drives them, each is usable alone).
+ *   ff_tile_positions  pure host, no GPU call: the tile origins along an axis of n samples (io.py:87-91) --
+ *                      range(0, max(n - tile + 1, 1), step), plus n - tile when the last tile stops short of the border -- into
+ *                      out[0..count); returns the count, or -1 for n < tile, step < 1, tile < 1, a null out or count > cap.
+ *   ff_tile_cut_u8     img uint8 HWC [H][W][3] -> out fp32 planar [3][th][tw], the tile at (y, x): u8 / 255 by IEEE division, the
+ *                      bits of ff_u8hwc_to_f32nchw followed by a slice copy.  The tile must lie inside the image.
+ *   ff_tile_ramps      tab [4][st], the edge weights of io.py:97-113: row v is ones; with bit 0 of v the first `blend` samples are
+ *                      ramp = np.linspace(0, 1, blend, dtype=float32), with bit 1 the last `blend` are 1 - ramp (fp32).  blend 0
+ *                      gives ones, blend 1 the ramp [0]; 0 <= blend <= st.
+ *   ff_tile_finish_u8  acc [3][H][W], wsum [H][W] (the un-normalised canvas, only read) -> out uint8 HWC [H][W][3]:
+ *                      acc / max(wsum, 1e-8), clamp to [0,1], * 255, round half to even -- the bytes of ff_tile_normalize
+ *                      followed by ff_f32nchw_to_u8hwc, in one pass.  Four pixels per thread when out is 4-byte aligned. */
+int ff_tile_positions(int n, int tile, int step, int* out, int cap);
+int ff_tile_cut_u8(const unsigned char* img, int H, int W, int y, int x, int th, int tw, float* out, void* stream);
+int ff_tile_ramps(float* tab, int st, int blend, void* stream);
+int ff_tile_finish_u8(const float* acc, const float* wsum, int H, int W, unsigned char* out, void* stream);
+
 /* Bilinear (mode 0) / bicubic A=-0.75 (mode 1) resize, align_corners=False, generic element strides.
  * scale_* = source step per destination pixel exactly as ATen computes it. */
 int ff_resize(const float* in, long long isb, long long isc, long long isy, long long isx, int Hi, int Wi, float* out,
@@ -753,7 +770,23 @@ int ff_d4_rect_nchw(const float* src, float* dst, int B, int C, int Hs, int Ws, 
  *   ff_forward   lr_dev [B,3,H,W] fp32 -> out_dev [B,3,4H,4W]; all launches go to `stream` in plan order (asynchronous,
  *                graph-capturable); B, H, W must be the plan's
  *   ff_destroy   frees everything the handle owns
- * Handles are not thread-safe; use one per host thread (kernels of different handles may run on different streams). */
+ * Handles are not thread-safe; use one per host thread (kernels of different handles may run on different streams).
+ *
+ * Images of ANY size through one TILE plan (a plan exported on [B,3,t,t] -> [B,3,4t,4t], square tiles, B <= 16): the plugin's
+ * overlap-tile path (models/team29_FreqFusion/io.py:116-164, _tiled_forward) with its exact result, B tiles per replay, uint8 in and out.
+ *   ff_image_workspace_bytes  the size of `work` for an H x W image; -1 (and a message) for a null handle, a plan that is no tile
+ *                             plan, or an image smaller than the tile
+ *   ff_forward_image_u8       img_dev uint8 HWC [H][W][3] -> out_dev uint8 HWC [4H][4W][3], tiles of step t - overlap blended with
+ *                             linear ramps of min(4 overlap, t) samples.  Needs a finalized handle, H >= t and W >= t (every tile
+ *                             is then full-size; ragged tiles are out of scope), 0 <= overlap < t, work_bytes >= the size above;
+ *                             all of it is checked before the first launch.  Everything runs on `stream`: no allocation, no host
+ *                             synchronisation, no host-to-device copy -- asynchronous and graph-capturable like ff_forward.
+ * `work` is the caller's device buffer; its parts, each starting on a multiple of 256 bytes, in this order (fp32):
+ *     acc [3][4H][4W] | wsum [4H][4W] | tile input [B,3,t,t] | tile output [B,3,4t,4t] | ramp table [4][4t]
+ * acc and wsum hold the un-normalised canvas when the call has run (ff_tile_normalize(acc, wsum) gives the fp32 image). */
+long long ff_image_workspace_bytes(void* handle, int H, int W);
+int ff_forward_image_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, unsigned char* out_dev, void* work,
+                        long long work_bytes, void* stream);
 int ff_create(const char* plan_path, void** out_handle);
 int ff_upload(void* handle, const char* slot_name, const void* host_or_dev_ptr, long long nbytes);
 int ff_finalize(void* handle);
