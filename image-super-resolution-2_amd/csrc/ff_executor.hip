@@ -6,6 +6,7 @@
 // and output tensors; every launch goes to the caller's stream in plan order, so ff_forward is asynchronous and
 // graph-capturable like the per-operator entry points it drives.  No internal threads; one handle per host thread.
 // ff_forward_image_u8 serves images of any size at least the tile's from ONE tile plan: uint8 in, overlap tiles B at a time, uint8 out.
+// ff_forward_image_ens_u8 is its x8 geometric self-ensemble: the same loop once per symmetry, folded into one fp32 accumulator.
 #include "ff_common.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -217,66 +218,164 @@ static long long image_layout(const ff_model* m, int H, int W, long long (&off)[
   return at;
 }
 
+// what the two workspace queries refuse (with a message that names `who`): a null handle, a plan that is no tile plan, an image smaller than the tile
+static bool workspace_query_ok(const ff_model* m, int H, int W, const char* who) {
+  if (!m) { ff_set_error("%s: null handle", who); return false; }
+  if (!tile_plan_ok(m)) { ff_set_error("%s: not a tile plan (input [%d,%d,%d,%d], output [%d,%d,%d,%d])", who, m->in[0], m->in[1], m->in[2], m->in[3], m->out[0], m->out[1], m->out[2], m->out[3]); return false; }
+  if (H < m->in[2] || W < m->in[3]) { ff_set_error("%s: a %dx%d image is smaller than the plan's %dx%d tile", who, H, W, m->in[2], m->in[3]); return false; }
+  return true;
+}
+
 extern "C" long long ff_image_workspace_bytes(void* handle, int H, int W) {
   ff_model* m = (ff_model*)handle;
-  if (!m) { ff_set_error("ff_image_workspace_bytes: null handle"); return -1; }
-  if (!tile_plan_ok(m)) { ff_set_error("ff_image_workspace_bytes: not a tile plan (input [%d,%d,%d,%d], output [%d,%d,%d,%d])", m->in[0], m->in[1], m->in[2], m->in[3], m->out[0], m->out[1], m->out[2], m->out[3]); return -1; }
-  if (H < m->in[2] || W < m->in[3]) { ff_set_error("ff_image_workspace_bytes: a %dx%d image is smaller than the plan's %dx%d tile", H, W, m->in[2], m->in[3]); return -1; }
+  if (!workspace_query_ok(m, H, W, "ff_image_workspace_bytes")) return -1;
   long long off[IW_PARTS];
   return image_layout(m, H, W, off);
 }
 
-extern "C" int ff_forward_image_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, unsigned char* out_dev, void* work,
-                                   long long work_bytes, void* stream) {
-  ff_model* m = (ff_model*)handle;
-  FF_CHECK_ARG(m && img_dev && out_dev && work, "ff_forward_image_u8: null argument");
-  FF_CHECK_ARG(m->finalized, "ff_forward_image_u8: ff_finalize has not succeeded on this handle");
-  FF_CHECK_ARG(tile_plan_ok(m), "ff_forward_image_u8: the handle's plan must map square tiles [B,3,t,t] to [B,3,4t,4t] with B <= %d; this one maps [%d,%d,%d,%d] to [%d,%d,%d,%d]",
-               IMAGE_MAX_BATCH, m->in[0], m->in[1], m->in[2], m->in[3], m->out[0], m->out[1], m->out[2], m->out[3]);
-  const int B = m->in[0], t = m->in[2], st = IMAGE_SCALE * t;
-  FF_CHECK_ARG(H <= (1 << 28) && W <= (1 << 28), "ff_forward_image_u8: a %dx%d image is beyond the 2^28 samples per side that 4H and 4W as int allow", H, W);
-  FF_CHECK_ARG(H >= t && W >= t, "ff_forward_image_u8: a %dx%d image does not hold one full %dx%d tile of this plan (ragged tiles, as the reference "
-               "cuts from images smaller than the tile, are out of scope)", H, W, t, t);
-  FF_CHECK_ARG(overlap >= 0 && overlap < t, "ff_forward_image_u8: overlap %d must lie in [0, tile = %d)", overlap, t);
-  long long off[IW_PARTS];
-  const long long need = image_layout(m, H, W, off);
-  FF_CHECK_ARG(work_bytes >= need, "ff_forward_image_u8: a %dx%d image needs %lld bytes of work space, got %lld", H, W, need, work_bytes);
-  const int step = t - overlap, blend = IMAGE_SCALE * overlap < st / 4 ? IMAGE_SCALE * overlap : st / 4;
-  std::vector<int> ys((H - t) / step + 2), xs((W - t) / step + 2);
-  const int ny = ff_tile_positions(H, t, step, ys.data(), (int)ys.size()), nx = ff_tile_positions(W, t, step, xs.data(), (int)xs.size());
-  FF_CHECK_ARG(ny > 0 && nx > 0, "ff_forward_image_u8: cannot place %dx%d tiles with step %d on a %dx%d image", t, t, step, H, W);
+// The checks the two image entry points share, in ff_forward_image_u8's order and wording; `who` names the entry point.
+static int image_args_ok(const ff_model* m, int H, int W, int overlap, const char* who) {
+  FF_CHECK_ARG(m->finalized, "%s: ff_finalize has not succeeded on this handle", who);
+  FF_CHECK_ARG(tile_plan_ok(m), "%s: the handle's plan must map square tiles [B,3,t,t] to [B,3,4t,4t] with B <= %d; this one maps [%d,%d,%d,%d] to [%d,%d,%d,%d]",
+               who, IMAGE_MAX_BATCH, m->in[0], m->in[1], m->in[2], m->in[3], m->out[0], m->out[1], m->out[2], m->out[3]);
+  const int t = m->in[2];
+  FF_CHECK_ARG(H <= (1 << 28) && W <= (1 << 28), "%s: a %dx%d image is beyond the 2^28 samples per side that 4H and 4W as int allow", who, H, W);
+  FF_CHECK_ARG(H >= t && W >= t, "%s: a %dx%d image does not hold one full %dx%d tile of this plan (ragged tiles, as the reference "
+               "cuts from images smaller than the tile, are out of scope)", who, H, W, t, t);
+  FF_CHECK_ARG(overlap >= 0 && overlap < t, "%s: overlap %d must lie in [0, tile = %d)", who, overlap, t);
+  return FF_OK;
+}
 
+// The canvas of ONE image from its tiles, the loop both image entry points run: clear acc and wsum, (write the ramp table,) then per
+// group of B tiles B cuts, one replay and one ff_tile_accum per real tile in tile order.  The image the tiles are cut from is
+// T_code(img), Ht x Wt, with ys / xs its tile origins; code < 0 is the plain image through ff_tile_cut_u8 (ff_forward_image_u8's
+// launches), code >= 0 goes through ff_tile_cut_u8_d4 and never materialises T_code(img).  Rows of the ramp table are chosen from
+// the TRANSFORMED image's neighbours, as _tiled_forward would on d4_rect(lr, code).
+static int canvas_from_tiles(ff_model* m, const unsigned char* img_dev, int H, int W, int code, int overlap, const std::vector<int>& ys,
+                             const std::vector<int>& xs, void* work, const long long (&off)[IW_PARTS], bool write_ramps, void* stream,
+                             const char* who) {
+  const int B = m->in[0], t = m->in[2], st = IMAGE_SCALE * t;
+  const int odd = code >= 0 && ((code >> 2) & 1);
+  const int Ht = odd ? W : H, Wt = odd ? H : W;
+  const int blend = IMAGE_SCALE * overlap < st / 4 ? IMAGE_SCALE * overlap : st / 4;
+  const int nx = (int)xs.size();
   float* acc = (float*)((char*)work + off[IW_ACC]);
   float* wsum = (float*)((char*)work + off[IW_WSUM]);
   float* tin = (float*)((char*)work + off[IW_TIN]);
   float* tout = (float*)((char*)work + off[IW_TOUT]);
   float* tab = (float*)((char*)work + off[IW_RAMPS]);
-  const int HS = IMAGE_SCALE * H, WS = IMAGE_SCALE * W;
+  const int HS = IMAGE_SCALE * Ht, WS = IMAGE_SCALE * Wt;
   const long long P = (long long)HS * WS;
   if (hipMemsetAsync(acc, 0, (size_t)(12 * P), (hipStream_t)stream) != hipSuccess || hipMemsetAsync(wsum, 0, (size_t)(4 * P), (hipStream_t)stream) != hipSuccess) {
-    ff_set_error("ff_forward_image_u8: clearing the canvas failed: %s", hipGetErrorString(hipGetLastError()));
+    ff_set_error("%s: clearing the canvas failed: %s", who, hipGetErrorString(hipGetLastError()));
     return FF_ERR_LAUNCH;
   }
-  int rc = ff_tile_ramps(tab, st, blend, stream);
+  int rc = write_ramps ? ff_tile_ramps(tab, st, blend, stream) : FF_OK;
   if (rc != FF_OK) return rc;
-  const long long ntiles = (long long)ny * nx;
+  const long long ntiles = (long long)ys.size() * nx;
   for (long long g0 = 0; g0 < ntiles; g0 += B) {
     for (int s = 0; s < B; ++s) {                            // a short last group repeats its last tile: the forward reads no stale slot
       const long long k = g0 + s < ntiles ? g0 + s : ntiles - 1;
-      rc = ff_tile_cut_u8(img_dev, H, W, ys[k / nx], xs[k % nx], t, t, tin + (long long)s * 3 * t * t, stream);
+      float* slot = tin + (long long)s * 3 * t * t;
+      rc = code < 0 ? ff_tile_cut_u8(img_dev, H, W, ys[k / nx], xs[k % nx], t, t, slot, stream)
+                    : ff_tile_cut_u8_d4(img_dev, H, W, code, ys[k / nx], xs[k % nx], t, t, slot, stream);
       if (rc != FF_OK) return rc;
     }
-    rc = replay_plan(m, tin, tout, stream, "ff_forward_image_u8");
+    rc = replay_plan(m, tin, tout, stream, who);
     if (rc != FF_OK) return rc;
     for (int s = 0; s < B && g0 + s < ntiles; ++s) {         // in tile order (y outer, x inner), as the plugin accumulates
       const int y = ys[(g0 + s) / nx], x = xs[(g0 + s) % nx];
-      const float* wy = tab + (long long)((y > 0 ? 1 : 0) + (y + t < H ? 2 : 0)) * st;
-      const float* wx = tab + (long long)((x > 0 ? 1 : 0) + (x + t < W ? 2 : 0)) * st;
+      const float* wy = tab + (long long)((y > 0 ? 1 : 0) + (y + t < Ht ? 2 : 0)) * st;
+      const float* wx = tab + (long long)((x > 0 ? 1 : 0) + (x + t < Wt ? 2 : 0)) * st;
       rc = ff_tile_accum(tout + (long long)s * 3 * st * st, 3, st, st, wy, wx, acc, wsum, HS, WS, IMAGE_SCALE * y, IMAGE_SCALE * x, stream);
       if (rc != FF_OK) return rc;
     }
   }
-  return ff_tile_finish_u8(acc, wsum, HS, WS, out_dev, stream);
+  return FF_OK;
+}
+
+// the tile origins along an axis of n samples (ff_tile_positions into a vector); empty when they cannot be placed
+static std::vector<int> axis_positions(int n, int t, int step) {
+  std::vector<int> p((n - t) / step + 2);
+  const int cnt = ff_tile_positions(n, t, step, p.data(), (int)p.size());
+  p.resize(cnt > 0 ? cnt : 0);
+  return p;
+}
+
+extern "C" int ff_forward_image_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, unsigned char* out_dev, void* work,
+                                   long long work_bytes, void* stream) {
+  static const char* const who = "ff_forward_image_u8";
+  ff_model* m = (ff_model*)handle;
+  FF_CHECK_ARG(m && img_dev && out_dev && work, "ff_forward_image_u8: null argument");
+  int rc = image_args_ok(m, H, W, overlap, who);
+  if (rc != FF_OK) return rc;
+  const int t = m->in[2], step = t - overlap;
+  long long off[IW_PARTS];
+  const long long need = image_layout(m, H, W, off);
+  FF_CHECK_ARG(work_bytes >= need, "ff_forward_image_u8: a %dx%d image needs %lld bytes of work space, got %lld", H, W, need, work_bytes);
+  const std::vector<int> ys = axis_positions(H, t, step), xs = axis_positions(W, t, step);
+  FF_CHECK_ARG(!ys.empty() && !xs.empty(), "ff_forward_image_u8: cannot place %dx%d tiles with step %d on a %dx%d image", t, t, step, H, W);
+  rc = canvas_from_tiles(m, img_dev, H, W, -1, overlap, ys, xs, work, off, true, stream, who);
+  if (rc != FF_OK) return rc;
+  return ff_tile_finish_u8((const float*)((char*)work + off[IW_ACC]), (const float*)((char*)work + off[IW_WSUM]), IMAGE_SCALE * H,
+                           IMAGE_SCALE * W, out_dev, stream);
+}
+
+// ---- the x8 geometric self-ensemble of an image through the same tile plan (model.FreqFusionHIP.self_ensemble with
+// run = _tiled_forward): per code the canvas of T_code(img) from canvas_from_tiles, then ONE ff_tile_fold_d4 that normalises it, maps it
+// back by the inverse code and folds it into ens.  `work` = the parts of ff_forward_image_u8 for an H x W image (a W x H canvas has
+// the same element count) followed by ens [3][4H][4W] fp32, which starts on a multiple of 256 bytes.
+static long long image_ens_layout(const ff_model* m, int H, int W, long long (&off)[IW_PARTS], long long& ens_off) {
+  ens_off = image_layout(m, H, W, off);                      // every part is padded to 256 bytes, so is their sum
+  const long long P = (long long)IMAGE_SCALE * H * IMAGE_SCALE * W;
+  return ens_off + (12 * P + 255) / 256 * 256;
+}
+
+// ops.d4_inverse_code / ops.d4_canonical_code: exactly one flip = a reflection, its own inverse; otherwise a rotation, k' = (4 - k) % 4.
+// A half turn is both flips, so codes 8..15 name the symmetries of 0..7: toggle both flips and keep k - 2.
+static int d4_inverse_code(int c) { return (c & 1) != ((c >> 1) & 1) ? c : (c & 3) | (((4 - (c >> 2)) % 4) << 2); }
+static int d4_canonical_code(int c) { return c < 8 ? c : ((c & 3) ^ 3) | (((c >> 2) - 2) << 2); }
+
+extern "C" long long ff_image_ens_workspace_bytes(void* handle, int H, int W) {
+  ff_model* m = (ff_model*)handle;
+  if (!workspace_query_ok(m, H, W, "ff_image_ens_workspace_bytes")) return -1;
+  long long off[IW_PARTS], ens_off;
+  return image_ens_layout(m, H, W, off, ens_off);
+}
+
+extern "C" int ff_forward_image_ens_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, const int* codes, int ncodes,
+                                       unsigned char* out_dev, void* work, long long work_bytes, void* stream) {
+  static const char* const who = "ff_forward_image_ens_u8";
+  ff_model* m = (ff_model*)handle;
+  FF_CHECK_ARG(m && img_dev && codes && out_dev && work, "ff_forward_image_ens_u8: null argument");
+  int rc = image_args_ok(m, H, W, overlap, who);             // H >= t and W >= t: both orientations hold a full tile
+  if (rc != FF_OK) return rc;
+  FF_CHECK_ARG(ncodes >= 1, "ff_forward_image_ens_u8: ncodes = %d, at least one symmetry code is needed", ncodes);
+  for (int i = 0; i < ncodes; ++i) {
+    FF_CHECK_ARG(codes[i] >= 0 && codes[i] < 16, "ff_forward_image_ens_u8: codes[%d] = %d outside 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)", i, codes[i]);
+    for (int j = 0; j < i; ++j)
+      FF_CHECK_ARG(d4_canonical_code(codes[j]) != d4_canonical_code(codes[i]),
+                   "ff_forward_image_ens_u8: codes[%d] = %d and codes[%d] = %d name the same symmetry (codes 8..15 repeat 0..7)", j, codes[j], i, codes[i]);
+  }
+  const int t = m->in[2], step = t - overlap;
+  long long off[IW_PARTS], ens_off;
+  const long long need = image_ens_layout(m, H, W, off, ens_off);
+  FF_CHECK_ARG(work_bytes >= need, "ff_forward_image_ens_u8: the ensemble of a %dx%d image needs %lld bytes of work space, got %lld", H, W, need, work_bytes);
+  const std::vector<int> pH = axis_positions(H, t, step), pW = axis_positions(W, t, step);
+  FF_CHECK_ARG(!pH.empty() && !pW.empty(), "ff_forward_image_ens_u8: cannot place %dx%d tiles with step %d on a %dx%d image", t, t, step, H, W);
+
+  const float* acc = (const float*)((char*)work + off[IW_ACC]);
+  const float* wsum = (const float*)((char*)work + off[IW_WSUM]);
+  float* ens = (float*)((char*)work + ens_off);
+  for (int i = 0; i < ncodes; ++i) {
+    const int odd = (codes[i] >> 2) & 1;                     // odd k: T(img) is W x H, its rows are placed like the image's columns
+    rc = canvas_from_tiles(m, img_dev, H, W, codes[i], overlap, odd ? pW : pH, odd ? pH : pW, work, off, i == 0, stream, who);
+    if (rc != FF_OK) return rc;
+    const float scale = i == ncodes - 1 ? (float)(1.0 / ncodes) : 1.0f;      // the double quotient narrowed once, as the Python host passes it
+    rc = ff_tile_fold_d4(acc, wsum, IMAGE_SCALE * (odd ? W : H), IMAGE_SCALE * (odd ? H : W), d4_inverse_code(codes[i]), ens, i > 0, scale, stream);
+    if (rc != FF_OK) return rc;
+  }
+  return ff_f32nchw_to_u8hwc(ens, out_dev, IMAGE_SCALE * H, IMAGE_SCALE * W, stream);
 }
 
 extern "C" int ff_destroy(void* handle) {

@@ -1665,6 +1665,62 @@ def d4_rect(x: T, code: int, out: Optional[T] = None, accum: bool = False, scale
     return out
 
 
+def tile_cut_u8_d4(img_u8: T, code: int, y: int, x: int, th: int, tw: int, out: Optional[T] = None) -> T:
+    """The th x tw tile at (y, x) of the TRANSFORMED image d4_rect(u8_to_f32_image(img_u8), code), which is never built: uint8 HWC
+    [H,W,3] on the device -> fp32 [1,3,th,tw].  The transformed image is H x W for even k = code >> 2 and W x H for odd k; the tile
+    must lie inside it.  Everything is checked here, before the launch."""
+    if not (isinstance(img_u8, torch.Tensor) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3
+            and img_u8.shape[2] == 3 and img_u8.is_contiguous() and img_u8.numel() > 0):
+        raise _lib.FFError("tile_cut_u8_d4: expected a non-empty contiguous CUDA(HIP) uint8 [H,W,3] tensor")
+    c, y, x, th, tw = int(code), int(y), int(x), int(th), int(tw)
+    if not 0 <= c < D4_CODES:
+        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    H, W, _ = img_u8.shape
+    Ht, Wt = (W, H) if (c >> 2) & 1 else (H, W)
+    if th < 1 or tw < 1 or y < 0 or x < 0 or y + th > Ht or x + tw > Wt:
+        raise _lib.FFError(f"tile_cut_u8_d4: the {th}x{tw} tile at ({y},{x}) leaves the {Ht}x{Wt} transformed image (code {c} of a {H}x{W} image)")
+    if out is None:
+        out = torch.empty((1, 3, th, tw), device=img_u8.device, dtype=torch.float32)
+    else:
+        _chk(out, "tile_cut_u8_d4.out")
+        if out.numel() != 3 * th * tw or not out.is_contiguous() or out.device != img_u8.device:
+            raise _lib.FFError(f"tile_cut_u8_d4: out must be a contiguous float32 tensor of 3x{th}x{tw} elements on the image's device")
+    _lib.check(_L().ff_tile_cut_u8_d4(img_u8.data_ptr(), H, W, c, y, x, th, tw, out.data_ptr(), _stream()))
+    return out
+
+
+def tile_fold_d4(acc: T, wsum: T, code: int, ens: Optional[T] = None, accum: bool = False, scale: float = 1.0) -> T:
+    """One variant's un-normalised canvas folded into the ensemble accumulator in one pass: with v = acc / max(wsum, 1e-8)
+    (tile_normalize's arithmetic) and t = d4_rect(v, code):  accum=False: ens = t * scale;  accum=True: ens = (ens + t) * scale, the
+    add rounded before the multiply.  acc [1,3,Hc,Wc] and wsum [1,1,Hc,Wc] are only read; ens is [1,3,Hc,Wc] for even k = code >> 2 and
+    [1,3,Wc,Hc] for odd k, and must overlap neither.  Everything is checked here, before the launch."""
+    _chk(acc, "tile_fold_d4.acc")
+    _chk(wsum, "tile_fold_d4.wsum")
+    if acc.dim() != 4 or acc.shape[0] != 1 or acc.shape[1] != 3 or not acc.is_contiguous() or acc.numel() == 0:
+        raise _lib.FFError("tile_fold_d4: acc must be a non-empty contiguous [1,3,Hc,Wc] tensor")
+    _, _, Hc, Wc = acc.shape
+    if wsum.numel() != Hc * Wc or tuple(wsum.shape[-2:]) != (Hc, Wc) or not wsum.is_contiguous() or wsum.device != acc.device:
+        raise _lib.FFError(f"tile_fold_d4: wsum must be a contiguous [1,1,{Hc},{Wc}] tensor on acc's device, got {list(wsum.shape)}")
+    c = int(code)
+    if not 0 <= c < D4_CODES:
+        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    oshape = (1, 3, Wc, Hc) if (c >> 2) & 1 else (1, 3, Hc, Wc)
+    if ens is None:
+        if accum:
+            raise _lib.FFError("tile_fold_d4: accum=True needs the tensor to accumulate into (ens)")
+        ens = torch.empty(oshape, device=acc.device, dtype=torch.float32)
+    else:
+        _chk(ens, "tile_fold_d4.ens")
+        if tuple(ens.shape) != oshape or not ens.is_contiguous() or ens.device != acc.device:
+            raise _lib.FFError(f"tile_fold_d4: ens must be a contiguous {list(oshape)} tensor on acc's device, got {list(ens.shape)}")
+        e0, e1 = ens.data_ptr(), ens.data_ptr() + 4 * ens.numel()
+        for t_, n_ in ((acc, "acc"), (wsum, "wsum")):
+            if e0 < t_.data_ptr() + 4 * t_.numel() and t_.data_ptr() < e1:
+                raise _lib.FFError(f"tile_fold_d4: ens overlaps {n_} (the fold is not in place)")
+    _lib.check(_L().ff_tile_fold_d4(acc.data_ptr(), wsum.data_ptr(), Hc, Wc, c, ens.data_ptr(), 1 if accum else 0, float(scale), _stream()))
+    return ens
+
+
 # ---- cached-expert data-set builder (cache.build_from_folders): patch pairs and the x1/4 degradation ---------------------------------
 def crop_pairs_u8(lr_u8: T, hr_u8: T, positions, patch: int) -> Tuple[T, T]:
     """K aligned patch pairs out of one uploaded image pair, one launch: lr_u8 [h,w,3], hr_u8 [4h,4w,3] uint8 HWC on the device,

@@ -387,6 +387,43 @@ class NativeModel:
                                               torch.cuda.current_stream().cuda_stream))
         return out
 
+    def image_ens_workspace_bytes(self, H: int, W: int) -> int:
+        """Bytes of `work` that forward_image_ens_u8 needs for an H x W image: image_workspace_bytes(H, W) plus the fp32 ensemble
+        accumulator [3,4H,4W], padded to 256 bytes."""
+        n = int(self.L.ff_image_ens_workspace_bytes(self.h, int(H), int(W)))
+        if n < 0:
+            raise _lib.FFError(self.L.ff_last_error().decode())
+        return n
+
+    def forward_image_ens_u8(self, img_u8: torch.Tensor, overlap: int = 32, codes=None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 HWC [H,W,3] on the device -> uint8 [4H,4W,3]: the geometric self-ensemble over the symmetries `codes` (default
+        ops.D4_ENSEMBLE, the x8 ensemble) of the image through the tile plan (ff_forward_image_ens_u8) -- the bytes of
+        f32_to_u8_image(model.self_ensemble(lr, codes=codes, run=<the plugin's tiled forward>)).  `work` is a contiguous CUDA uint8
+        buffer of at least image_ens_workspace_bytes(H, W) bytes (allocated here when None); afterwards its last part holds the fp32
+        ensemble image, in the layout include/ff_kernels.h states."""
+        if not (isinstance(img_u8, torch.Tensor) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3
+                and img_u8.shape[2] == 3 and img_u8.is_contiguous()):
+            raise _lib.FFError("NativeModel.forward_image_ens_u8: expected a contiguous CUDA uint8 [H,W,3] tensor")
+        if codes is None:
+            from . import ops as _ops
+            codes = _ops.D4_ENSEMBLE
+        try:
+            cl = [int(c) for c in codes]
+        except (TypeError, ValueError):
+            raise _lib.FFError("NativeModel.forward_image_ens_u8: codes must be a sequence of ints") from None
+        if any(not -2 ** 31 <= c < 2 ** 31 for c in cl):
+            raise _lib.FFError(f"NativeModel.forward_image_ens_u8: codes {cl} do not fit a C int")
+        H, W, _ = img_u8.shape
+        if work is None:
+            work = torch.empty(self.image_ens_workspace_bytes(H, W), device=img_u8.device, dtype=torch.uint8)
+        elif not (isinstance(work, torch.Tensor) and work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+            raise _lib.FFError("NativeModel.forward_image_ens_u8: work must be a contiguous CUDA uint8 tensor")
+        out = torch.empty((4 * H, 4 * W, 3), device=img_u8.device, dtype=torch.uint8)
+        carr = (ctypes.c_int * max(len(cl), 1))(*cl)               # a HOST array: the entry point reads it before its first launch
+        _lib.check(self.L.ff_forward_image_ens_u8(self.h, img_u8.data_ptr(), H, W, int(overlap), ctypes.cast(carr, ctypes.c_void_p), len(cl),
+                                                  out.data_ptr(), work.data_ptr(), work.numel(), torch.cuda.current_stream().cuda_stream))
+        return out
+
     def close(self):
         if self.h:
             self.L.ff_destroy(self.h)

@@ -514,6 +514,22 @@ int ff_tile_cut_u8(const unsigned char* img, int H, int W, int y, int x, int th,
 int ff_tile_ramps(float* tab, int st, int blend, void* stream);
 int ff_tile_finish_u8(const float* acc, const float* wsum, int H, int W, unsigned char* out, void* stream);
 
+/* The two kernels of the tiled executor's x8 self-ensemble (csrc/tile_image.hip; ff_forward_image_ens_u8 below drives them, each is
+ * usable alone).  `code` (0..15, a HOST int) has ff_d4_nchw's meaning and order: bit 0 flip(-1), then bit 1 flip(-2), then
+ * rot90(k = code >> 2, dims (-2, -1)).  Both added under ABI version 7 (additive entry points: no existing prototype changed).
+ *   ff_tile_cut_u8_d4  the tile at (y, x) of the TRANSFORMED image T_code(img), which is never materialised: img uint8 HWC [H][W][3]
+ *                      -> out fp32 planar [3][th][tw].  T_code(img) is H x W for even k and W x H for odd k; the tile must lie inside
+ *                      THAT shape.  The bits of ff_d4_rect_nchw(ff_u8hwc_to_f32nchw(img), code)[..., y:y+th, x:x+tw]: u8 / 255 by
+ *                      IEEE division, then the permutation.  One pixel per thread, the fp32 stores coalesced for every code.
+ *   ff_tile_fold_d4    acc [3][Hc][Wc], wsum [Hc][Wc] (one variant's un-normalised canvas, only read) folded into ens [3][Hd][Wd],
+ *                      (Hd, Wd) = (Hc, Wc) for even k and (Wc, Hc) for odd k.  With v = acc / max(wsum, 1e-8) (ff_tile_normalize's
+ *                      arithmetic, one rounding) and t = T_code(v):  accum 0: ens = t * scale;  accum 1: ens = (ens + t) * scale,
+ *                      the add rounded first, then the multiply, no contraction -- the bits of ff_tile_normalize on a copy of acc
+ *                      followed by ff_d4_rect_nchw(..., code, accum, scale), in one pass (40 instead of 64 bytes per pixel).  No
+ *                      atomics; ens may overlap neither acc nor wsum. */
+int ff_tile_cut_u8_d4(const unsigned char* img, int H, int W, int code, int y, int x, int th, int tw, float* out, void* stream);
+int ff_tile_fold_d4(const float* acc, const float* wsum, int Hc, int Wc, int code, float* ens, int accum, float scale, void* stream);
+
 /* Bilinear (mode 0) / bicubic A=-0.75 (mode 1) resize, align_corners=False, generic element strides.
  * scale_* = source step per destination pixel exactly as ATen computes it. */
 int ff_resize(const float* in, long long isb, long long isc, long long isy, long long isx, int Hi, int Wi, float* out,
@@ -783,10 +799,30 @@ int ff_d4_rect_nchw(const float* src, float* dst, int B, int C, int Hs, int Ws, 
  *                             synchronisation, no host-to-device copy -- asynchronous and graph-capturable like ff_forward.
  * `work` is the caller's device buffer; its parts, each starting on a multiple of 256 bytes, in this order (fp32):
  *     acc [3][4H][4W] | wsum [4H][4W] | tile input [B,3,t,t] | tile output [B,3,4t,4t] | ramp table [4][4t]
- * acc and wsum hold the un-normalised canvas when the call has run (ff_tile_normalize(acc, wsum) gives the fp32 image). */
+ * acc and wsum hold the un-normalised canvas when the call has run (ff_tile_normalize(acc, wsum) gives the fp32 image).
+ *
+ * The x8 geometric self-ensemble of such an image (isr2_amd.model.FreqFusionHIP.self_ensemble with the tiled forward as `run`), added
+ * under ABI version 7:
+ *   ff_image_ens_workspace_bytes  the size of `work` for the ensemble of an H x W image; -1 (and a message) in the cases of
+ *                                 ff_image_workspace_bytes
+ *   ff_forward_image_ens_u8       img_dev uint8 HWC [H][W][3] -> out_dev uint8 HWC [4H][4W][3], the average of the model's outputs over
+ *                                 the symmetries codes[0..ncodes) -- a HOST array of ff_d4_nchw codes (0..15), no symmetry named twice
+ *                                 (codes 8..15 repeat 0..7); 0..7 is the x8 ensemble.  Per code, in the order given: the canvas of
+ *                                 T_code(img) from its tiles exactly as ff_forward_image_u8 builds the plain one (an odd quarter turn
+ *                                 makes it W x H; tiles come from ff_tile_cut_u8_d4), then one ff_tile_fold_d4 with the inverse code,
+ *                                 accum = (i > 0) and scale = 1, the last one scale = (float)(1.0 / ncodes); at the end
+ *                                 ff_f32nchw_to_u8hwc(ens).  Same requirements and guarantees as ff_forward_image_u8 (H >= t and
+ *                                 W >= t cover both orientations), all checked before the first launch.
+ * Its `work`: the parts of ff_forward_image_u8 for an H x W image, in the same order (a W x H canvas has the same element count),
+ * followed by ens [3][4H][4W] fp32, which starts on a multiple of 256 bytes and is padded to one:
+ *     acc | wsum | tile input | tile output | ramp table | ens [3][4H][4W]
+ * ens holds the fp32 ensemble image when the call has run; acc and wsum the last variant's un-normalised canvas. */
 long long ff_image_workspace_bytes(void* handle, int H, int W);
 int ff_forward_image_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, unsigned char* out_dev, void* work,
                         long long work_bytes, void* stream);
+long long ff_image_ens_workspace_bytes(void* handle, int H, int W);
+int ff_forward_image_ens_u8(void* handle, const unsigned char* img_dev, int H, int W, int overlap, const int* codes, int ncodes,
+                            unsigned char* out_dev, void* work, long long work_bytes, void* stream);
 int ff_create(const char* plan_path, void** out_handle);
 int ff_upload(void* handle, const char* slot_name, const void* host_or_dev_ptr, long long nbytes);
 int ff_finalize(void* handle);
