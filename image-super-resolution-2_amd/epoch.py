@@ -8,7 +8,8 @@
 
 The host side of an epoch is file reads and ONE upload per micro-batch: a reader thread fills pinned staging slots (no GPU call
 on that thread), the stepping thread copies a slot to the device on a side stream one micro-batch ahead and permutes its eight
-tensors with ops.d4_nchw (csrc/augment.hip) -- one launch per tensor per batch.
+tensors with ops.d4_nchw (csrc/augment.hip) -- one launch per tensor per batch.  Opt-in, ResidentCache / ResidentEpoch read every
+sample ONCE into one device buffer and assemble each augmented micro-batch with one launch (csrc/gather_batch.hip), the same bits.
 
 Two things cannot be bit-compared with the reference, both "parity unpinned (RNG stream)": the attention-dropout masks (train.py
 of this package) and the shuffle / augmentation draws, which here come from numpy's counter-based Philox keyed by (seed, epoch) so
@@ -266,6 +267,160 @@ def read_samples(cache_dir: str) -> Iterable[dict]:
 
 
 # ======================================================================================================================
+# the cache resident on the device: every sample loaded ONCE, a micro-batch assembled by one launch (csrc/gather_batch.hip)
+FIELDS = ("lr", "hr") + tuple("out_" + k for k in EXPERTS) + tuple("feat_" + k for k in EXPERTS)      # CachedEpoch.layout's order
+RESIDENT_ALIGN = 64                                                   # floats: every field starts on a 256-byte boundary
+
+
+def resident_layout(shapes: Sequence[Tuple[int, ...]], n: int) -> Tuple[np.ndarray, int]:
+    """The field-major layout of n samples: shapes = one (C, H, W) per field -> (offsets int64 [F] in floats, total floats).  Field f
+    is a contiguous [n, C, H, W] array at offsets[f]; every field starts on a multiple of 64 floats, so a field whose W is a multiple
+    of 4 takes the kernel's 16-byte form whatever came before it.  total = the end of the last field (no padding after it)."""
+    n = int(n)
+    if n < 1 or not len(shapes):
+        raise _lib.FFError(f"resident_layout: need fields and n >= 1, got {len(shapes)} fields and n = {n}")
+    offs, end = np.zeros(len(shapes), dtype=np.int64), 0
+    for f, shp in enumerate(shapes):
+        if len(shp) != 3 or min(int(v) for v in shp) < 1:
+            raise _lib.FFError(f"resident_layout: field {f} has shape {tuple(shp)}, expected (C, H, W) >= 1")
+        offs[f] = -(-end // RESIDENT_ALIGN) * RESIDENT_ALIGN
+        end = int(offs[f]) + n * int(shp[0]) * int(shp[1]) * int(shp[2])
+    return offs, end
+
+
+def _sample_fields(s: dict) -> Dict[str, T]:
+    """The eight tensors of a cache.read_sample dict under FIELDS' names."""
+    d = {"lr": s["lr"], "hr": s["hr"]}
+    d.update({"out_" + k: s["expert_imgs"][k] for k in EXPERTS})
+    d.update({"feat_" + k: s["expert_feats"][k] for k in EXPERTS})
+    return d
+
+
+class ResidentCache:
+    """Every sample of a cache directory, loaded once and resident on the device as ONE field-major fp32 buffer.
+
+        pool = ResidentCache(cache_dir, device="cuda:0", readers=8, max_bytes=200 << 30)
+        pool.buf [total_floats] fp32, pool.shapes {field: (C, H, W)}, pool.offsets int64 [8], pool.stems, pool.load_s
+
+    The eight field shapes come from the first sample (as CachedEpoch takes them) and the pool is laid out from them by
+    resident_layout; more than max_bytes is an error naming the bytes needed, raised before anything is allocated -- there is no
+    second route.  Then `readers` host threads (at most 16) run cache.read_sample into pinned one-sample slots and make no GPU call;
+    the calling thread uploads each sample into its eight places (_fill_from_readers, ImagePool's pattern).  A sample whose shapes
+    differ from the first one's is an error naming the file.  `load_s`: seconds the loading took."""
+
+    def __init__(self, cache_dir: str, device="cuda:0", readers: int = 8, max_bytes: int = 200 << 30):
+        self.dir, self.dev = cache_dir, torch.device(device)
+        if int(readers) < 1:
+            raise _lib.FFError(f"ResidentCache: readers must be >= 1, got {readers}")
+        self.stems = cache.list_stems(cache_dir)
+        if not self.stems:
+            raise _lib.FFError(f"{cache_dir}: no cached samples (*{cache.PRIMARY_SUFFIX} + *{cache.REST_SUFFIX})")
+        t0 = time.perf_counter()
+        first = _sample_fields(cache.read_sample(cache_dir, self.stems[0]))
+        self.shapes = {k: tuple(int(v) for v in first[k].shape) for k in FIELDS}
+        n = len(self.stems)
+        self.offsets, self.total_floats = resident_layout([self.shapes[k] for k in FIELDS], n)
+        self.total_bytes = 4 * self.total_floats
+        if self.total_bytes > int(max_bytes):
+            raise _lib.FFError(f"ResidentCache: {n} samples need {self.total_bytes} bytes on the device, max_bytes allows {int(max_bytes)}")
+        if self.dev.type != "cuda" or not torch.cuda.is_available():
+            raise _lib.FFError("ResidentCache needs an MI355X (torch device 'cuda'): the samples live on the device")
+        self.readers = max(1, min(16, int(readers)))
+        with torch.cuda.device(self.dev):
+            self.buf = torch.empty(self.total_floats, dtype=torch.float32, device=self.dev)
+            self._fill()
+        self.load_s = time.perf_counter() - t0
+
+    def _fill(self):
+        sizes = [int(np.prod(self.shapes[k])) for k in FIELDS]
+        soffs, slot_floats = resident_layout([self.shapes[k] for k in FIELDS], 1)      # one sample: the slot's own layout
+
+        def read(i, slot):
+            s = cache.read_sample(self.dir, self.stems[i])
+            for k, so, t in zip(FIELDS, soffs, _sample_fields(s).values()):
+                if tuple(t.shape) != self.shapes[k]:
+                    raise _lib.FFError(f"{os.path.join(self.dir, self.stems[i] + cache.PRIMARY_SUFFIX)}: {k} has shape {tuple(t.shape)}, the pool "
+                                       f"holds {self.shapes[k]} (the shapes of {self.stems[0]})")
+                slot[int(so):int(so) + t.numel()].view(t.shape).copy_(t)
+
+        def upload(i, slot):
+            for po, so, sz in zip(self.offsets, soffs, sizes):
+                self.buf[int(po) + i * sz:int(po) + (i + 1) * sz].copy_(slot[int(so):int(so) + sz], non_blocking=True)
+
+        _fill_from_readers(len(self.stems), self.readers, lambda: torch.empty(slot_floats, dtype=torch.float32, pin_memory=True), read, upload,
+                           self.dev, name="ff-cache-reader")
+
+    def __len__(self) -> int:
+        return len(self.stems)
+
+    def field(self, name: str) -> T:
+        """[n, C, H, W]: the view of one field inside the pool."""
+        f = FIELDS.index(name)
+        C, H, W = self.shapes[name]
+        return self.buf[int(self.offsets[f]):int(self.offsets[f]) + len(self) * C * H * W].view(len(self), C, H, W)
+
+    def sample(self, i: int) -> dict:
+        """Sample i in cache.read_sample's shape; its tensors are views of the pool."""
+        v = {k: self.field(k)[i] for k in FIELDS}
+        return {"lr": v["lr"], "hr": v["hr"], "expert_imgs": {k: v["out_" + k] for k in EXPERTS},
+                "expert_feats": {k: v["feat_" + k] for k in EXPERTS}, "filename": self.stems[i]}
+
+    def samples(self) -> Iterable[dict]:
+        """Every sample as read_samples yields them, from the pool: validate() takes them unchanged (its .to(device) is a no-op)."""
+        for i in range(len(self)):
+            yield self.sample(i)
+
+
+class ResidentEpoch:
+    """Micro-batches of a ResidentCache, epoch by epoch; interchangeable with CachedEpoch in train_epoch and fit, and bit-equal to it.
+
+        data = ResidentEpoch(pool, batch_size=14, repeat_factor=20, augment=True, seed=0)
+        for lr, hr, outs, feats in data.batches(epoch): ...           # device tensors, augmented, len(data) of them
+
+    plan() is epoch_plan itself: order and codes are CachedEpoch's for the same (seed, epoch).  An epoch uploads its descriptor table
+    (int32 [nb, B, 2] = {sample index, d4 code}) once; a micro-batch is then one fresh flat buffer from the caching allocator and ONE
+    ops.gather_d4_fields launch on the current stream, and the eight yielded tensors are views of that buffer.  No thread, no side
+    stream, no copy and nothing read from disk during an epoch: `wait_s` stays 0."""
+
+    def __init__(self, pool: ResidentCache, batch_size: int, repeat_factor: int = 1, augment: bool = True, seed: int = 0, shuffle: bool = True):
+        self.pool, self.B, self.repeat, self.augment, self.seed, self.shuffle = pool, int(batch_size), int(repeat_factor), bool(augment), int(seed), shuffle
+        self.stems, self.dev = pool.stems, pool.dev
+        if self.B < 1 or self.repeat < 1:
+            raise _lib.FFError(f"ResidentEpoch: batch_size and repeat_factor must be >= 1, got {batch_size}, {repeat_factor}")
+        if len(self.stems) * self.repeat < self.B:
+            raise _lib.FFError(f"{pool.dir}: {len(self.stems)} samples x repeat {self.repeat} do not fill one batch of {self.B} (drop_last)")
+        if self.augment:                                              # refuse before any launch: odd quarter turns need square planes
+            from . import ops
+            for k in FIELDS:
+                ops.d4_check_codes([4], pool.shapes[k][-2], pool.shapes[k][-1])
+        shapes = [pool.shapes[k] for k in FIELDS]
+        self.out_offsets, self.out_floats = resident_layout(shapes, self.B)
+        self.fields = np.array([[int(po), int(oo), *shp] for po, oo, shp in zip(pool.offsets, self.out_offsets, shapes)], dtype=np.int64)
+        self.wait_s = 0.0
+
+    def __len__(self) -> int:
+        return len(self.stems) * self.repeat // self.B
+
+    def plan(self, epoch: int):
+        return epoch_plan(len(self.stems), self.repeat, self.B, self.seed, epoch, self.augment, self.shuffle)
+
+    def descriptors(self, epoch: int) -> np.ndarray:
+        """The epoch's gather table, int32 [nb, B, 2] = {sample index, d4 code} (ops.gather_d4_fields)."""
+        idx, codes = self.plan(epoch)
+        return np.ascontiguousarray(np.stack((idx % len(self.stems), codes), axis=-1).astype(np.int32))
+
+    def batches(self, epoch: int):
+        from . import ops
+        desc = self.descriptors(epoch)
+        with torch.cuda.device(self.dev):
+            desc_dev = torch.from_numpy(desc).to(self.dev)            # ONE upload per epoch
+            for b in range(desc.shape[0]):
+                flat = torch.empty(self.out_floats, dtype=torch.float32, device=self.dev)
+                v = dict(zip(FIELDS, ops.gather_d4_fields(self.pool.buf, len(self.stems), self.fields, desc_dev[b], flat, desc_host=desc[b])))
+                yield (v["lr"], v["hr"], {e: v["out_" + e] for e in EXPERTS}, {e: v["feat_" + e] for e in EXPERTS})
+
+
+# ======================================================================================================================
 # epoch, validation, driver
 def train_epoch(trainer, epoch_data, epoch: int, accumulation_steps: int = 1, lr_now: Optional[float] = None, grad_hook=None) -> dict:
     """train_epoch_cached (train.py:262-383): -> {'loss', 'stage', component means..., 'lr', 'micro_batches', 'optimizer_steps', 'discarded'}.
@@ -497,6 +652,68 @@ def live_jitter_plan(nb: int, batch_size: int, seed: int, epoch: int, prob: floa
     return t.reshape(nb, B, 4)
 
 
+def _fill_from_readers(n_items: int, n_readers: int, make_slot, read, upload, dev, name: str = "ff-pool-reader"):
+    """How a resident pool (ImagePool, ResidentCache) is filled: n_readers host threads take the items 0 .. n_items in turn and call
+    read(i, slot) -- decode or load item i into a pinned slot, NO GPU call -- and the calling thread calls upload(i, slot), which queues
+    the copies of that slot into the pool on the current stream.  n_readers + 2 slots from make_slot(), made here (pinning is a GPU
+    call); a slot goes back to the readers once an event recorded after its copies has completed.  A reader's exception ends the fill
+    and is re-raised here.  Returns after the device has finished."""
+    free, ready, stop, nxt, lock = queue.Queue(), queue.Queue(), threading.Event(), [0], threading.Lock()
+    for _ in range(n_readers + 2):                                    # pinned here: the readers make no GPU call
+        free.put(make_slot())
+
+    def reader():
+        try:
+            while not stop.is_set():
+                with lock:
+                    i = nxt[0]
+                    nxt[0] += 1
+                if i >= n_items:
+                    break
+                slot = free.get()
+                if slot is None:
+                    return
+                read(i, slot)
+                ready.put((i, slot))
+            ready.put(None)
+        except BaseException as e:                                    # noqa: BLE001 -- re-raised on the calling thread
+            ready.put(e)
+
+    threads = [threading.Thread(target=reader, name=f"{name}{i}", daemon=True) for i in range(n_readers)]
+    for t in threads:
+        t.start()
+    pending, done = [], 0                                             # (event of the last copy out of a slot, slot)
+    try:
+        while done < n_readers:
+            for ent in [e for e in pending if e[0].query()]:
+                pending.remove(ent)
+                free.put(ent[1])
+            try:
+                item = ready.get(timeout=0.05 if pending else None)
+            except queue.Empty:                                       # the readers may be out of slots: hand the oldest one back
+                ev, slot = pending.pop(0)
+                ev.synchronize()
+                free.put(slot)
+                continue
+            if isinstance(item, BaseException):
+                raise item
+            if item is None:
+                done += 1
+                continue
+            i, slot = item
+            upload(i, slot)
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append((ev, slot))
+    finally:
+        stop.set()
+        for _ in threads:
+            free.put(None)
+        for t in threads:
+            t.join(timeout=60)
+        torch.cuda.synchronize(dev)
+
+
 class ImagePool:
     """Every image pair of a folder (or two), decoded once and resident on the device as ONE packed uint8 buffer.
 
@@ -552,76 +769,30 @@ class ImagePool:
         from . import ops
         from PIL import Image
         slot_bytes = max(51 * h * w for h, w in self.sizes)
-        free, ready, stop, nxt, lock = queue.Queue(), queue.Queue(), threading.Event(), [0], threading.Lock()
-        for _ in range(n_readers + 2):                                # pinned here: the readers make no GPU call
-            free.put(torch.empty(slot_bytes, dtype=torch.uint8, pin_memory=True))
 
-        def reader():
-            try:
-                while not stop.is_set():
-                    with lock:
-                        i = nxt[0]
-                        nxt[0] += 1
-                    if i >= len(items):
-                        break
-                    slot = free.get()
-                    if slot is None:
-                        return
-                    (h, w), (_, hr_path, lr_path) = self.sizes[i], items[i]
-                    hr = np.asarray(Image.open(hr_path).convert("RGB"), dtype=np.uint8)[:4 * h, :4 * w]
-                    if hr.shape != (4 * h, 4 * w, 3):
-                        raise _lib.FFError(f"{hr_path}: decoded to {hr.shape[0]}x{hr.shape[1]}, its header said {4 * h}x{4 * w} or more")
-                    slot[3 * h * w:51 * h * w].view(4 * h, 4 * w, 3).numpy()[...] = hr
-                    if lr_path is not None:
-                        lr = np.asarray(Image.open(lr_path).convert("RGB"), dtype=np.uint8)
-                        if lr.shape != (h, w, 3):
-                            raise _lib.FFError(f"{lr_path}: decoded to {lr.shape[0]}x{lr.shape[1]}, its header said {h}x{w}")
-                        slot[:3 * h * w].view(h, w, 3).numpy()[...] = lr
-                    ready.put((i, slot))
-                ready.put(None)
-            except BaseException as e:                                # noqa: BLE001 -- re-raised on the calling thread
-                ready.put(e)
+        def read(i, slot):
+            (h, w), (_, hr_path, lr_path) = self.sizes[i], items[i]
+            hr = np.asarray(Image.open(hr_path).convert("RGB"), dtype=np.uint8)[:4 * h, :4 * w]
+            if hr.shape != (4 * h, 4 * w, 3):
+                raise _lib.FFError(f"{hr_path}: decoded to {hr.shape[0]}x{hr.shape[1]}, its header said {4 * h}x{4 * w} or more")
+            slot[3 * h * w:51 * h * w].view(4 * h, 4 * w, 3).numpy()[...] = hr
+            if lr_path is not None:
+                lr = np.asarray(Image.open(lr_path).convert("RGB"), dtype=np.uint8)
+                if lr.shape != (h, w, 3):
+                    raise _lib.FFError(f"{lr_path}: decoded to {lr.shape[0]}x{lr.shape[1]}, its header said {h}x{w}")
+                slot[:3 * h * w].view(h, w, 3).numpy()[...] = lr
 
-        threads = [threading.Thread(target=reader, name=f"ff-pool-reader{i}", daemon=True) for i in range(n_readers)]
-        for t in threads:
-            t.start()
-        pending, done = [], 0                                         # (event of the last copy out of a slot, slot)
-        try:
-            while done < n_readers:
-                for ent in [e for e in pending if e[0].query()]:
-                    pending.remove(ent)
-                    free.put(ent[1])
-                try:
-                    item = ready.get(timeout=0.05 if pending else None)
-                except queue.Empty:                                   # the readers may be out of slots: hand the oldest one back
-                    ev, slot = pending.pop(0)
-                    ev.synchronize()
-                    free.put(slot)
-                    continue
-                if isinstance(item, BaseException):
-                    raise item
-                if item is None:
-                    done += 1
-                    continue
-                i, slot = item
-                (h, w), (lo, ho) = self.sizes[i], (int(v) for v in self.offsets[i])
-                if hr_only:                                           # the LR image is made here, from the uploaded HR image
-                    hr_u8 = slot[3 * h * w:51 * h * w].view(4 * h, 4 * w, 3).to(self.dev, non_blocking=True)
-                    self.buf[ho:ho + 48 * h * w].copy_(hr_u8.view(-1))
-                    lr_u8 = ops.f32_to_u8_image(ops.resize_aa(ops.u8_to_f32_image(hr_u8), (h, w)))
-                    self.buf[lo:lo + 3 * h * w].copy_(lr_u8.view(-1))
-                else:                                                 # LR and HR are adjacent in the slot as they are in the pool
-                    self.buf[lo:lo + 51 * h * w].copy_(slot[:51 * h * w], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                pending.append((ev, slot))
-        finally:
-            stop.set()
-            for _ in threads:
-                free.put(None)
-            for t in threads:
-                t.join(timeout=60)
-            torch.cuda.synchronize(self.dev)
+        def upload(i, slot):
+            (h, w), (lo, ho) = self.sizes[i], (int(v) for v in self.offsets[i])
+            if hr_only:                                               # the LR image is made here, from the uploaded HR image
+                hr_u8 = slot[3 * h * w:51 * h * w].view(4 * h, 4 * w, 3).to(self.dev, non_blocking=True)
+                self.buf[ho:ho + 48 * h * w].copy_(hr_u8.view(-1))
+                lr_u8 = ops.f32_to_u8_image(ops.resize_aa(ops.u8_to_f32_image(hr_u8), (h, w)))
+                self.buf[lo:lo + 3 * h * w].copy_(lr_u8.view(-1))
+            else:                                                     # LR and HR are adjacent in the slot as they are in the pool
+                self.buf[lo:lo + 51 * h * w].copy_(slot[:51 * h * w], non_blocking=True)
+
+        _fill_from_readers(len(items), n_readers, lambda: torch.empty(slot_bytes, dtype=torch.uint8, pin_memory=True), read, upload, self.dev)
 
     def __len__(self) -> int:
         return len(self.sizes)

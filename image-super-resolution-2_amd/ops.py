@@ -1796,6 +1796,57 @@ def sample_pairs_u8(pool: T, desc_host, patch: int, desc_dev: Optional[T] = None
     return lr, hr
 
 
+# ---- resident cached-expert training (epoch.ResidentCache / ResidentEpoch): one micro-batch out of the resident sample pool ----------
+GATHER_MAX_FIELDS = 8
+
+
+def gather_d4_fields(pool: T, n_samples: int, fields, desc_dev: T, out: T, desc_host=None):
+    """One augmented micro-batch out of a field-major pool of cached samples, every field in one launch (csrc/gather_batch.hip).
+    pool: 1-D fp32 device tensor; field f is a contiguous [n_samples, C, H, W] array that starts fields[f][0] floats into it.  fields:
+    host int64 [F][5] rows {pool_off, out_off, C, H, W}, 1 <= F <= 8.  desc_dev: int32 [B, 2] device rows {sample index, d4 code}.  out:
+    flat fp32 device tensor; field f of the batch is [B, C, H, W] at out[fields[f][1]:] = the bits of d4_nchw(field_f[index], codes).
+    -> the F views of `out`.  Shapes, dtypes, extents and overlapping output fields are checked here before the launch; desc_host, the
+    same table on the host, is checked too when given: indices in [0, n_samples), codes in 0..15, odd quarter turns only when every field
+    is square.  (Without it the kernel's own guards hold: it clamps the index and drops the odd turn of a non-square field.)"""
+    import numpy as np
+    for t, name in ((pool, "pool"), (out, "out")):
+        _chk(t, "gather_d4_fields." + name)
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() < 1:
+            raise _lib.FFError(f"gather_d4_fields: {name} must be a non-empty contiguous 1-D fp32 tensor")
+    if out.device != pool.device:
+        raise _lib.FFError("gather_d4_fields: out must be on the pool's device")
+    n = int(n_samples)
+    fl = np.ascontiguousarray(np.asarray(fields, dtype=np.int64))
+    if fl.ndim != 2 or fl.shape[1] != 5 or not 1 <= fl.shape[0] <= GATHER_MAX_FIELDS or n < 1:
+        raise _lib.FFError(f"gather_d4_fields: need 1..{GATHER_MAX_FIELDS} rows of 5 fields and n_samples >= 1, got a table of shape {fl.shape} and {n}")
+    if not (isinstance(desc_dev, torch.Tensor) and desc_dev.is_cuda and desc_dev.dtype == torch.int32 and desc_dev.dim() == 2
+            and desc_dev.shape[1] == 2 and desc_dev.shape[0] >= 1 and desc_dev.is_contiguous() and desc_dev.device == pool.device):
+        raise _lib.FFError("gather_d4_fields: desc_dev must be a contiguous int32 [B, 2] tensor (B >= 1) on the pool's device")
+    B = int(desc_dev.shape[0])
+    spans = []
+    for f, (po, oo, C, H, W) in enumerate(fl.tolist()):
+        if C < 1 or H < 1 or W < 1 or po < 0 or oo < 0:
+            raise _lib.FFError(f"gather_d4_fields: field {f}: shape {C}x{H}x{W} at offsets {po} / {oo}")
+        if po + n * C * H * W > pool.numel() or oo + B * C * H * W > out.numel():
+            raise _lib.FFError(f"gather_d4_fields: field {f}: {n} samples of {C}x{H}x{W} at {po} leave the pool of {pool.numel()} floats, or "
+                               f"{B} of them at {oo} the output of {out.numel()}")
+        spans.append((oo, oo + B * C * H * W))
+    spans.sort()
+    if any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+        raise _lib.FFError("gather_d4_fields: output fields overlap")
+    if desc_host is not None:
+        d = np.asarray(desc_host)
+        if d.shape != (B, 2):
+            raise _lib.FFError(f"gather_d4_fields: desc_host has shape {d.shape}, desc_dev [{B}, 2]")
+        if ((d[:, 0] < 0) | (d[:, 0] >= n)).any():
+            raise _lib.FFError(f"gather_d4_fields: sample index {int(d[:, 0].min())}..{int(d[:, 0].max())} outside the pool's 0..{n - 1}")
+        for f in range(fl.shape[0]):                                  # odd quarter turns need square planes, in every field
+            d4_check_codes(d[:, 1], int(fl[f, 3]), int(fl[f, 4]))
+    _lib.check(_L().ff_gather_d4_fields(pool.data_ptr(), n, fl.ctypes.data, int(fl.shape[0]), desc_dev.data_ptr(), B, out.data_ptr(), _stream()))
+    _note(0.0, 8.0 * B * float((fl[:, 2] * fl[:, 3] * fl[:, 4]).sum()))
+    return [out[oo:oo + B * C * H * W].view(B, C, H, W) for _, oo, C, H, W in fl.tolist()]
+
+
 def color_jitter_pairs(lr: T, hr: T, table_host, table_dev: Optional[T] = None) -> Tuple[T, T]:
     """The reference's paired colour jitter on a sampled micro-batch, IN PLACE, two launches (csrc/color_jitter.hip): lr [B,3,p,p] and
     hr [B,3,4p,4p] contiguous fp32 device tensors holding u8 / 255 (what sample_pairs_u8 writes); table_host: host fp32 [B][4] rows

@@ -563,6 +563,20 @@ int ff_resize_aa(const float* in, float* out, int planes, int Hi, int Wi, int Ho
  * First check: null pointers, B < 1, p < 1.  Added under ABI version 7 (additive). */
 int ff_sample_pairs_u8(const unsigned char* pool, const long long* desc, int B, int p, float* lr_out, float* hr_out, void* stream);
 
+/* One cached-expert micro-batch out of a resident sample pool (isr2_amd.epoch.ResidentCache / ResidentEpoch; csrc/gather_batch.hip): the
+ * B samples desc names, every field of them, gathered and D4-augmented in one launch.  pool: one device fp32 buffer, FIELD-major --
+ * field f is a contiguous [n_samples][C_f][H_f][W_f] array that starts fields[f][0] floats into pool.  fields: HOST int64 [F][5] =
+ * {pool_off, out_off, C, H, W}, 1 <= F <= 8, read before the launch (as codes is in ff_forward_image_ens_u8).  desc: DEVICE int32
+ * [B][2] = {sample index, code}, code as ff_d4_nchw (bit 0 flip(-1), bit 1 flip(-2), bits 2-3 rot90 k).  out: flat; field f of the
+ * micro-batch is [B][C_f][H_f][W_f] starting at out + fields[f][1] = the bits of ff_d4_nchw(field_f[index], codes).  A pure copy: NaN
+ * payloads, -0 and denormals pass through.  The 16-byte form is chosen per field (W_f % 4 == 0 and both of its bases 16-byte aligned),
+ * the dword form otherwise.  The caller checks indices and codes (ops.gather_d4_fields); the kernel clamps the index into
+ * [0, n_samples), masks the code to 4 bits and clears its odd-turn bit on a non-square field all the same, so no descriptor reads outside
+ * the pool.  First check, before any launch: null pointers, B < 1, F outside 1..8, n_samples < 1, a non-positive dimension, a negative
+ * offset, 2^31 tiles or more.  Added under ABI version 7 (an additive entry point: no existing prototype changed). */
+int ff_gather_d4_fields(const float* pool, long long n_samples, const long long* fields, int F, const int* desc, int B, float* out,
+                        void* stream);
+
 /* The reference's paired colour jitter (augmentations.py:207-264) on a sampled micro-batch, in place (csrc/color_jitter.hip;
  * ops.color_jitter_pairs, epoch.LiveEpoch(color_jitter=...)).  lr [B][3][p][p], hr [B][3][4p][4p] fp32 = u / 255 as ff_sample_pairs_u8 writes
  * them; table: DEVICE fp32 [B][4] = {apply, bf, cf, sf} -- apply == 0 leaves both patches of that sample untouched bit for bit.  Per patch
