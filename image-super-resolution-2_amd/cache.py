@@ -23,6 +23,24 @@ import torch
 
 T = torch.Tensor
 PRIMARY_SUFFIX, REST_SUFFIX = "_hat_part.pt", "_rest_part.pt"
+EXPERTS = ("hat", "dat", "nafnet")
+FIELDS = ("lr", "hr") + tuple("out_" + k for k in EXPERTS) + tuple("feat_" + k for k in EXPERTS)      # the eight tensors of a cached sample
+
+
+def sample_fields(sample: dict) -> Dict[str, T]:
+    """The eight tensors of a read_sample dict under FIELDS' names, in FIELDS' order."""
+    return dict(zip(FIELDS, (sample["lr"], sample["hr"], *(sample["expert_imgs"][k] for k in EXPERTS), *(sample["expert_feats"][k] for k in EXPERTS))))
+
+
+def fields_batch(v: Dict[str, T]) -> Tuple[T, T, Dict[str, T], Dict[str, T]]:
+    """The inverse: {field: tensor} of a sample or a batch -> (lr, hr, outs, feats), the arguments of write_sample and of a training step."""
+    return v["lr"], v["hr"], {k: v["out_" + k] for k in EXPERTS}, {k: v["feat_" + k] for k in EXPERTS}
+
+
+def fields_sample(v: Dict[str, T], filename: str) -> dict:
+    """{field: tensor} of one sample -> the dict read_sample returns."""
+    lr, hr, outs, feats = fields_batch(v)
+    return {"lr": lr, "hr": hr, "expert_imgs": outs, "expert_feats": feats, "filename": filename}
 
 
 def write_sample(cache_dir: str, stem: str, lr: T, hr: T, outputs: Dict[str, T], features: Dict[str, T]) -> Tuple[str, str]:
@@ -30,7 +48,7 @@ def write_sample(cache_dir: str, stem: str, lr: T, hr: T, outputs: Dict[str, T],
     os.makedirs(cache_dir, exist_ok=True)
     cpu = lambda t: t.detach().to("cpu", torch.float32).contiguous()      # noqa: E731
     sq = lambda t: t.squeeze(0) if t.dim() == 4 else t                    # noqa: E731
-    for k in ("hat", "dat", "nafnet"):
+    for k in EXPERTS:
         if k not in outputs or k not in features:
             raise KeyError(f"cache sample {stem}: missing expert {k}")
     p1 = os.path.join(cache_dir, stem + PRIMARY_SUFFIX)
@@ -114,160 +132,109 @@ def _image_stems(folder: str) -> Dict[str, str]:
     return out
 
 
+def list_pairs(hr_dir: str, lr_dir: Optional[str] = None):
+    """-> [(stem, hr_path, lr_path or None)] sorted by stem: the images of hr_dir, each with its partner of the same stem in lr_dir.
+    An image without a partner, in either folder, is a FileNotFoundError naming it."""
+    hr_files = _image_stems(hr_dir)
+    lr_files = {} if lr_dir is None else _image_stems(lr_dir)
+    missing = sorted(set(hr_files) ^ set(lr_files)) if lr_dir is not None else []
+    if missing:
+        raise FileNotFoundError(f"{missing[0]} has no partner in {lr_dir if missing[0] in hr_files else hr_dir}")
+    return [(stem, hr_files[stem], lr_files.get(stem)) for stem in sorted(hr_files)]
+
+
+def recorded_event() -> "torch.cuda.Event":
+    """An event recorded on the current stream: behind the copies just queued out of (or into) a staging slot."""
+    ev = torch.cuda.Event()
+    ev.record()
+    return ev
+
+
+def pinned_u8(slot: dict, key: str, nbytes: int) -> T:
+    """slot[key]: a pinned uint8 buffer of at least nbytes, grown (never below 1 MiB) when an image needs more."""
+    if slot[key] is None or slot[key].numel() < nbytes:
+        slot[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
+    return slot[key]
+
+
 class _BuildPipeline:
-    """Host side of build_from_folders, after the plugin's image pipeline: a reader thread decodes the images into pinned uint8
-    slots, writer threads run write_sample (and save the optional LR PNGs) from pinned result slots; the calling thread owns every
-    GPU call.  A slot goes back to its free queue only after the event of the last copy that touched it.  An exception on a worker
-    thread is kept and re-raised on the calling thread."""
+    """Host side of build_from_folders on isr2_amd.staging: one reader decodes the images into pinned uint8 slots (_read), writers run
+    write_sample from pinned result slots and save the optional LR PNGs (_write); the calling thread owns every GPU call."""
 
     def __init__(self, items, out_dir, tmp_dir, patch, hr_only, write_lr, device, n_writers, n_in_slots=3):
-        import queue
-        import threading
+        from .staging import ReadAhead, WriteBehind
         self.items, self.out_dir, self.tmp_dir, self.patch, self.hr_only = items, out_dir, tmp_dir, patch, hr_only
         self.write_lr, self.device = write_lr, device
-        self.err = None
-        self.lock = threading.Lock()
-        self.t = {"decode": 0.0, "write": 0.0}
-        self.skipped = 0
         self.written = 0
-        self.in_free, self.in_ready = queue.Queue(), queue.Queue()
-        self.out_free, self.out_ready = queue.Queue(), queue.Queue()
-        for _ in range(n_in_slots):
-            self.in_free.put({"lr": None, "hr": None, "ev": None})
         p = patch
-        shapes = {"lr": (1, 3, p, p), "hr": (3, 4 * p, 4 * p), "o_hat": (1, 3, 4 * p, 4 * p), "o_dat": (1, 3, 4 * p, 4 * p),
-                  "o_nafnet": (1, 3, 4 * p, 4 * p), "f_hat": (1, 180, p, p), "f_dat": (1, 180, p, p), "f_nafnet": (1, 64, p, p)}
-        self.shapes = shapes
-        for _ in range(n_writers + 2):                 # every tensor owns its pinned storage: torch.save writes whole storages
-            self.out_free.put({k: torch.empty(s, dtype=torch.float32).pin_memory() for k, s in shapes.items()})
-        self.reader = threading.Thread(target=self._read_loop, name="ff-cache-reader", daemon=True)
-        self.writers = [threading.Thread(target=self._write_loop, name=f"ff-cache-writer{i}", daemon=True) for i in range(n_writers)]
-        self.reader.start()
-        for t in self.writers:
-            t.start()
+        img, feat = (1, 3, 4 * p, 4 * p), (1, 180, p, p)
+        shapes = dict(zip(FIELDS, ((1, 3, p, p), (3, 4 * p, 4 * p), img, img, img, feat, feat, (1, 64, p, p))))
+        # every tensor owns its pinned storage: torch.save writes whole storages
+        self.writes = WriteBehind(self._write, lambda: {k: torch.empty(s, dtype=torch.float32).pin_memory() for k, s in shapes.items()},
+                                  n_writers, n_writers + 2, name="ff-cache-writer")
+        self.reads = ReadAhead(len(items), self._read, lambda: {"lr": None, "hr": None}, n_slots=n_in_slots, name="ff-cache-reader")
 
-    @staticmethod
-    def _pinned(slot, key, nbytes):
-        if slot[key] is None or slot[key].numel() < nbytes:
-            slot[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
-        return slot[key]
-
-    def _read_loop(self):
-        import time
+    def _read(self, index, slot):
         import numpy as np
         from PIL import Image
-        try:
-            for index, (stem, hr_path, lr_path) in enumerate(self.items):
-                t0 = time.perf_counter()
-                hr_img = Image.open(hr_path)
-                W, H = hr_img.size
-                if lr_path is None:
-                    H, W = H - H % 4, W - W % 4                       # HR-only: crop top-left to multiples of 4
-                    h, w = H // 4, W // 4
-                else:
-                    lr_img = Image.open(lr_path)
-                    w, h = lr_img.size
-                    if (H, W) != (4 * h, 4 * w):
-                        raise ValueError(f"{hr_path}: HR is {H}x{W}, not exactly 4x its LR {lr_path} ({h}x{w})")
-                if h < self.patch or w < self.patch:
-                    self.skipped += 1
-                    self.t["decode"] += time.perf_counter() - t0
-                    continue
-                slot = self.in_free.get()
-                if slot is None:
-                    return
-                if slot["ev"] is not None:
-                    slot["ev"].synchronize()                          # the previous uploads out of this slot have finished
-                hr = np.asarray(hr_img.convert("RGB"), dtype=np.uint8)[:H, :W]
-                self._pinned(slot, "hr", hr.size)[:hr.size].view(H, W, 3).numpy()[...] = hr
-                if lr_path is not None:
-                    lr = np.asarray(lr_img.convert("RGB"), dtype=np.uint8)
-                    self._pinned(slot, "lr", lr.size)[:lr.size].view(h, w, 3).numpy()[...] = lr
-                self.t["decode"] += time.perf_counter() - t0
-                self.in_ready.put((slot, index, stem, h, w))
-        except BaseException as e:                                   # noqa: BLE001 -- handed to the calling thread
-            self.err = e
-        finally:
-            self.in_ready.put(None)
+        from .staging import SKIP
+        stem, hr_path, lr_path = self.items[index]
+        hr_img = Image.open(hr_path)
+        W, H = hr_img.size
+        if lr_path is None:
+            H, W = H - H % 4, W - W % 4                               # HR-only: crop top-left to multiples of 4
+            h, w = H // 4, W // 4
+        else:
+            lr_img = Image.open(lr_path)
+            w, h = lr_img.size
+            if (H, W) != (4 * h, 4 * w):
+                raise ValueError(f"{hr_path}: HR is {H}x{W}, not exactly 4x its LR {lr_path} ({h}x{w})")
+        if h < self.patch or w < self.patch:
+            return SKIP
+        hr = np.asarray(hr_img.convert("RGB"), dtype=np.uint8)[:H, :W]
+        pinned_u8(slot, "hr", hr.size)[:hr.size].view(H, W, 3).numpy()[...] = hr
+        if lr_path is not None:
+            lr = np.asarray(lr_img.convert("RGB"), dtype=np.uint8)
+            pinned_u8(slot, "lr", lr.size)[:lr.size].view(h, w, 3).numpy()[...] = lr
+        return stem, h, w
 
-    def _write_loop(self):
-        import time
-        try:
-            while True:
-                item = self.out_ready.get()
-                if item is None:
-                    return
-                kind, slot, ev, name = item
-                ev.synchronize()                                     # the device-to-host copies into this slot have finished
-                t0 = time.perf_counter()
-                if kind == "png":
-                    from PIL import Image
-                    h, w = slot["shape"]
-                    Image.fromarray(slot["buf"][:h * w * 3].view(h, w, 3).numpy()).save(os.path.join(self.write_lr, name + ".png"), format="PNG")
-                else:
-                    outs = {k: slot["o_" + k] for k in ("hat", "dat", "nafnet")}
-                    feats = {k: slot["f_" + k] for k in ("hat", "dat", "nafnet")}
-                    p1, p2 = write_sample(self.tmp_dir, name, slot["lr"], slot["hr"], outs, feats)
-                    os.replace(p2, os.path.join(self.out_dir, os.path.basename(p2)))    # the rest part first: a primary part file
-                    os.replace(p1, os.path.join(self.out_dir, os.path.basename(p1)))    # never exists without its partner
-                    self.out_free.put(slot)
-                with self.lock:
-                    self.t["write"] += time.perf_counter() - t0
-                    self.written += kind == "sample"
-        except BaseException as e:                                   # noqa: BLE001
-            self.err = e
-            self.out_free.put(None)                                  # keep the producer from blocking forever
-
-    def check(self):
-        if self.err is not None:
-            raise self.err
+    def _write(self, slot, job):
+        if slot is None:                                              # an LR PNG, from the one-off buffer it came with
+            from PIL import Image
+            name, buf, h, w = job
+            Image.fromarray(buf.view(h, w, 3).numpy()).save(os.path.join(self.write_lr, name + ".png"), format="PNG")
+            return
+        p1, p2 = write_sample(self.tmp_dir, job, *fields_batch(slot))
+        os.replace(p2, os.path.join(self.out_dir, os.path.basename(p2)))    # the rest part first: a primary part file
+        os.replace(p1, os.path.join(self.out_dir, os.path.basename(p1)))    # never exists without its partner
 
     def images(self):
         """Yields (index, stem, lr_u8 or None, hr_u8) with the uint8 images on the device, in list order."""
-        while True:
-            item = self.in_ready.get()
-            self.check()
-            if item is None:
-                return
-            slot, index, stem, h, w = item
+        for index, slot, (stem, h, w) in self.reads:
             hr_u8 = slot["hr"][:48 * h * w].view(4 * h, 4 * w, 3).to(self.device, non_blocking=True)
             lr_u8 = None if self.hr_only else slot["lr"][:3 * h * w].view(h, w, 3).to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            slot["ev"] = ev
-            self.in_free.put(slot)
+            self.reads.release(slot, recorded_event())
             yield index, stem, lr_u8, hr_u8
 
     def save_sample(self, stem, lr, hr, outs, feats):
         """Queue one patch's tensors (device) for write_sample: copied into a pinned slot, written once the copies' event is done."""
-        self.check()
-        slot = self.out_free.get()
-        self.check()
-        slot["lr"].copy_(lr, non_blocking=True)
-        slot["hr"].copy_(hr, non_blocking=True)
-        for k in ("hat", "dat", "nafnet"):
-            slot["o_" + k].copy_(outs[k], non_blocking=True)
-            slot["f_" + k].copy_(feats[k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.out_ready.put(("sample", slot, ev, stem))
+        slot = self.writes.take()
+        for k, t in sample_fields({"lr": lr, "hr": hr, "expert_imgs": outs, "expert_feats": feats}).items():
+            slot[k].copy_(t, non_blocking=True)
+        self.writes.submit(slot, recorded_event(), stem)
+        self.written += 1
 
     def save_png(self, stem, u8):
-        self.check()
         h, w, _ = u8.shape
         buf = torch.empty(u8.numel(), dtype=torch.uint8).pin_memory()
         buf.view(h, w, 3).copy_(u8, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.out_ready.put(("png", {"buf": buf, "shape": (h, w)}, ev, stem))
+        self.writes.submit(None, recorded_event(), (stem, buf, h, w))
 
     def close(self):
-        for _ in self.writers:
-            self.out_ready.put(None)
-        for t in self.writers:
-            t.join()
-        self.in_free.put(None)
-        self.reader.join(timeout=5)
+        try:
+            self.writes.close()
+        finally:
+            self.reads.close()
 
 
 class _GraphedExperts:
@@ -352,7 +319,9 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
 
     Returns {graph, batch, images, images_skipped, patches_written, seconds: {total, decode, device, write, wait_reader, wait_writer},
     patches_per_s}: decode / write are the worker threads' busy time (write summed over the writers), device is GPU time between
-    the upload and the last result copy of each image (events), the waits are the calling thread's stalls on the queues."""
+    the upload and the last result copy of each image (events), the waits are the calling thread's stalls for a decoded image and
+    for a free result slot (staging.ReadAhead.wait_s, WriteBehind.wait_s)."""
+    import contextlib
     import shutil
     import time
     from . import ops
@@ -360,13 +329,7 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
     patch, crops, writers, batch = int(patch), int(crops), int(writers), int(batch)
     if patch < 1 or crops < 1 or writers < 1 or batch < 1:
         raise FFError(f"build_from_folders: patch, crops, writers and batch must be >= 1, got {patch}, {crops}, {writers}, {batch}")
-    hr_files = _image_stems(hr_dir)
-    if lr_dir is not None:
-        lr_files = _image_stems(lr_dir)
-        missing = sorted(set(hr_files) ^ set(lr_files))
-        if missing:
-            raise FileNotFoundError(f"build_from_folders: {missing[0]} has no partner in {lr_dir if missing[0] in hr_files else hr_dir}")
-    items = [(stem, hr_files[stem], None if lr_dir is None else lr_files[stem]) for stem in sorted(hr_files)]
+    items = list_pairs(hr_dir, lr_dir)
     os.makedirs(out_dir, exist_ok=True)
     if write_lr is not None:
         os.makedirs(write_lr, exist_ok=True)
@@ -374,56 +337,39 @@ def build_from_folders(model, hr_dir: str, out_dir: str, lr_dir: Optional[str] =
     os.makedirs(tmp_dir, exist_ok=True)
     dev = model.dev
     t_start = time.perf_counter()
-    wait_r = wait_w = 0.0
     spans = []
-    n_img = 0
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), contextlib.ExitStack() as stack:     # left in reverse: the pipeline, the device, the graphs, the directory
+        stack.callback(shutil.rmtree, tmp_dir, ignore_errors=True)
         n_patch = 1 if center else crops                      # patches per image: whole groups of `batch`, then the remainder
         sizes = sorted({min(batch, n_patch)} | ({n_patch % batch} if n_patch % batch else set()))
         experts = _GraphedExperts(model, patch, sizes) if graph else (lambda t: model.experts_with_features(t, streams=True))
-        pipe = None
-        try:
-            pipe = _BuildPipeline(items, out_dir, tmp_dir, patch, lr_dir is None, write_lr, dev, writers)
-            it = pipe.images()
-            while True:
-                t0 = time.perf_counter()
-                nxt = next(it, None)
-                wait_r += time.perf_counter() - t0
-                if nxt is None:
-                    break
-                index, stem, lr_u8, hr_u8 = nxt
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                if lr_u8 is None:
-                    h, w = hr_u8.shape[0] // 4, hr_u8.shape[1] // 4
-                    lr_u8 = ops.f32_to_u8_image(ops.resize_aa(ops.u8_to_f32_image(hr_u8), (h, w)))
-                    if write_lr is not None:
-                        pipe.save_png(stem, lr_u8)
-                plan = crop_plan(lr_u8.shape[0], lr_u8.shape[1], patch, crops, seed, index, center)
-                lr, hr = ops.crop_pairs_u8(lr_u8, hr_u8, plan, patch)
-                for k0 in range(0, len(plan), batch):
-                    lr_g = lr[k0:k0 + batch]
-                    if lr_g.data_ptr() % 16:                          # odd patch sizes: the kernels take 16-byte aligned images
-                        lr_g = lr_g.clone()
-                    outs, feats = experts(lr_g)
-                    for j in range(lr_g.shape[0]):
-                        t0 = time.perf_counter()
-                        pipe.save_sample(stem if center else f"{stem}_p{k0 + j}", lr_g[j:j + 1], hr[k0 + j],
-                                         {k: v[j:j + 1] for k, v in outs.items()}, {k: v[j:j + 1] for k, v in feats.items()})
-                        wait_w += time.perf_counter() - t0
-                e1.record()
-                spans.append((e0, e1))
-                n_img += 1
-        finally:
-            if pipe is not None:
-                pipe.close()
-            torch.cuda.synchronize(dev)
-            shutil.rmtree(tmp_dir, ignore_errors=True)
-            if graph:
-                experts.close()
-        pipe.check()
+        if graph:
+            stack.callback(experts.close)
+        stack.callback(torch.cuda.synchronize, dev)
+        pipe = _BuildPipeline(items, out_dir, tmp_dir, patch, lr_dir is None, write_lr, dev, writers)
+        stack.callback(pipe.close)                            # a reader's or writer's exception is re-raised here at the latest
+        for index, stem, lr_u8, hr_u8 in pipe.images():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            if lr_u8 is None:
+                h, w = hr_u8.shape[0] // 4, hr_u8.shape[1] // 4
+                lr_u8 = ops.f32_to_u8_image(ops.resize_aa(ops.u8_to_f32_image(hr_u8), (h, w)))
+                if write_lr is not None:
+                    pipe.save_png(stem, lr_u8)
+            plan = crop_plan(lr_u8.shape[0], lr_u8.shape[1], patch, crops, seed, index, center)
+            lr, hr = ops.crop_pairs_u8(lr_u8, hr_u8, plan, patch)
+            for k0 in range(0, len(plan), batch):
+                lr_g = lr[k0:k0 + batch]
+                if lr_g.data_ptr() % 16:                          # odd patch sizes: the kernels take 16-byte aligned images
+                    lr_g = lr_g.clone()
+                outs, feats = experts(lr_g)
+                for j in range(lr_g.shape[0]):
+                    pipe.save_sample(stem if center else f"{stem}_p{k0 + j}", lr_g[j:j + 1], hr[k0 + j],
+                                     {k: v[j:j + 1] for k, v in outs.items()}, {k: v[j:j + 1] for k, v in feats.items()})
+            e1.record()
+            spans.append((e0, e1))
     total = time.perf_counter() - t_start
-    secs = {"total": total, "decode": pipe.t["decode"], "device": sum(a.elapsed_time(b) for a, b in spans) / 1e3,
-            "write": pipe.t["write"], "wait_reader": wait_r, "wait_writer": wait_w}
-    return {"graph": bool(graph), "batch": batch, "images": n_img, "images_skipped": pipe.skipped, "patches_written": pipe.written,
+    secs = {"total": total, "decode": pipe.reads.busy_s, "device": sum(a.elapsed_time(b) for a, b in spans) / 1e3,
+            "write": pipe.writes.busy_s, "wait_reader": pipe.reads.wait_s, "wait_writer": pipe.writes.wait_s}
+    return {"graph": bool(graph), "batch": batch, "images": len(spans), "images_skipped": len(items) - len(spans), "patches_written": pipe.written,
             "seconds": {k: round(v, 6) for k, v in secs.items()}, "patches_per_s": pipe.written / total if total > 0 else 0.0}

@@ -7,8 +7,8 @@
     src/data/cached_dataset.py:147-149, :240-268, :306-315   repeat_factor, paired flips / rotations, shuffle + drop_last -> epoch_plan(), CachedEpoch
 
 The host side of an epoch is file reads and ONE upload per micro-batch: a reader thread fills pinned staging slots (no GPU call
-on that thread), the stepping thread copies a slot to the device on a side stream one micro-batch ahead and permutes its eight
-tensors with ops.d4_nchw (csrc/augment.hip) -- one launch per tensor per batch.  Opt-in, ResidentCache / ResidentEpoch read every
+on that thread: staging.ReadAhead, which the pools and the cache builder use too), the stepping thread copies a slot to the device
+on a side stream one micro-batch ahead and permutes its eight tensors with ops.d4_nchw (csrc/augment.hip) -- one launch per tensor per batch.  Opt-in, ResidentCache / ResidentEpoch read every
 sample ONCE into one device buffer and assemble each augmented micro-batch with one launch (csrc/gather_batch.hip), the same bits.
 
 Two things cannot be bit-compared with the reference, both "parity unpinned (RNG stream)": the attention-dropout masks (train.py
@@ -32,9 +32,7 @@ from __future__ import annotations
 import json
 import math
 import os
-import queue
 import shutil
-import threading
 import time
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -43,9 +41,10 @@ import torch
 
 from . import lib as _lib
 from . import cache
+from .cache import EXPERTS, FIELDS                                    # the eight tensors of a cached sample, in CachedEpoch.layout's order
+from .staging import ReadAhead
 
 T = torch.Tensor
-EXPERTS = ("hat", "dat", "nafnet")
 SCHEDULE = dict(base_lr=1.5e-4, warmup_epochs=5, warmup_lr=5e-7, T_0=50, T_mult=2, eta_min=5e-8)     # configs/train_config.yaml:102-120
 
 
@@ -154,10 +153,7 @@ class CachedEpoch:
         self.dev = torch.device(device)
         if self.dev.type != "cuda" or not torch.cuda.is_available():
             raise _lib.FFError("CachedEpoch needs an MI355X (torch device 'cuda'): the batch is assembled and augmented on the device")
-        s = cache.read_sample(cache_dir, self.stems[0])
-        shapes = {"lr": tuple(s["lr"].shape), "hr": tuple(s["hr"].shape)}
-        shapes.update({"out_" + k: tuple(s["expert_imgs"][k].shape) for k in EXPERTS})
-        shapes.update({"feat_" + k: tuple(s["expert_feats"][k].shape) for k in EXPERTS})
+        shapes = {k: tuple(t.shape) for k, t in cache.sample_fields(cache.read_sample(cache_dir, self.stems[0])).items()}
         self.layout, n = {}, 0
         for k, shp in shapes.items():
             self.layout[k] = (n, (self.B,) + shp)
@@ -180,25 +176,12 @@ class CachedEpoch:
     def _fill(self, slot: _Slot, idx, codes):
         for j, i in enumerate(idx):
             s = cache.read_sample(self.dir, self.stems[int(i) % len(self.stems)])
-            for k, t in (("lr", s["lr"]), ("hr", s["hr"]), *(("out_" + e, s["expert_imgs"][e]) for e in EXPERTS),
-                         *(("feat_" + e, s["expert_feats"][e]) for e in EXPERTS)):
+            for k, t in cache.sample_fields(s).items():
                 if tuple(t.shape) != tuple(slot.views_h[k].shape[1:]):
                     raise _lib.FFError(f"cache sample {s['filename']}: {k} has shape {tuple(t.shape)}, the batch holds {tuple(slot.views_h[k].shape[1:])}")
                 slot.views_h[k][j].copy_(t)
         slot.codes_h.copy_(torch.from_numpy(np.ascontiguousarray(codes, dtype=np.int32)))
         slot.codes = [int(c) for c in codes]
-
-    def _reader(self, idx, codes, free: "queue.Queue", ready: "queue.Queue", stop: threading.Event):
-        try:
-            for b in range(len(idx)):
-                slot = free.get()
-                if slot is None or stop.is_set():
-                    return
-                self._fill(slot, idx[b], codes[b])
-                ready.put(slot)
-            ready.put(None)
-        except BaseException as e:                                    # surfaces on the stepping thread
-            ready.put(e)
 
     def batches(self, epoch: int):
         from . import ops
@@ -207,31 +190,15 @@ class CachedEpoch:
             if self._slots is None:
                 self._slots = [_Slot(self.layout, self.n_floats, self.B, self.dev) for _ in range(self.prefetch)]
                 self._copy_stream = torch.cuda.Stream(device=self.dev)
-            free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()
-            for s in self._slots:
-                free.put(s)
-            th = threading.Thread(target=self._reader, args=(idx, codes, free, ready, stop), daemon=True)
-            th.start()
             main = torch.cuda.current_stream()
-            pending: List[_Slot] = []                                 # uploaded, host side not yet known to be free
+            slots = iter(self._slots)
+            reads = ReadAhead(len(idx), lambda b, slot: self._fill(slot, idx[b], codes[b]), lambda: next(slots), n_slots=self.prefetch,
+                              name="ff-epoch-reader")                 # items are micro-batches: one reader, so they arrive in order
+            filled = iter(reads)
 
             def upload():
                 """Take the next filled slot and start its copy on the side stream -> the slot, or None at the end of the epoch."""
-                for s in [p for p in pending if p.copied.query()]:
-                    pending.remove(s)
-                    free.put(s)
-                t0 = time.perf_counter()
-                while True:
-                    try:
-                        slot = ready.get(timeout=0.0 if pending else None)
-                        break
-                    except queue.Empty:                               # the reader may be out of slots: hand the oldest one back
-                        s = pending.pop(0)
-                        s.copied.synchronize()
-                        free.put(s)
-                self.wait_s += time.perf_counter() - t0
-                if isinstance(slot, BaseException):
-                    raise slot
+                slot = next(filled, (None, None, None))[1]
                 if slot is None:
                     return None
                 if slot.consumed is not None:
@@ -239,7 +206,7 @@ class CachedEpoch:
                 with torch.cuda.stream(self._copy_stream):
                     slot.dev.copy_(slot.host, non_blocking=True)      # ONE upload per micro-batch
                     slot.copied.record(self._copy_stream)
-                pending.append(slot)
+                reads.release(slot, slot.copied)                      # the host side is free once the upload has finished
                 return slot
 
             try:
@@ -251,13 +218,10 @@ class CachedEpoch:
                     cur.consumed = torch.cuda.Event()
                     cur.consumed.record(main)
                     nxt = upload()                                    # one micro-batch ahead of the step about to be queued
-                    yield (out["lr"], out["hr"], {e: out["out_" + e] for e in EXPERTS}, {e: out["feat_" + e] for e in EXPERTS})
+                    yield cache.fields_batch(out)
             finally:
-                stop.set()
-                free.put(None)
-                for s in pending:
-                    s.copied.synchronize()
-                th.join(timeout=60)
+                reads.close()                                         # an abandoned epoch too: the reader ended, the uploads finished
+                self.wait_s += reads.wait_s
 
 
 def read_samples(cache_dir: str) -> Iterable[dict]:
@@ -268,7 +232,6 @@ def read_samples(cache_dir: str) -> Iterable[dict]:
 
 # ======================================================================================================================
 # the cache resident on the device: every sample loaded ONCE, a micro-batch assembled by one launch (csrc/gather_batch.hip)
-FIELDS = ("lr", "hr") + tuple("out_" + k for k in EXPERTS) + tuple("feat_" + k for k in EXPERTS)      # CachedEpoch.layout's order
 RESIDENT_ALIGN = 64                                                   # floats: every field starts on a 256-byte boundary
 
 
@@ -288,14 +251,6 @@ def resident_layout(shapes: Sequence[Tuple[int, ...]], n: int) -> Tuple[np.ndarr
     return offs, end
 
 
-def _sample_fields(s: dict) -> Dict[str, T]:
-    """The eight tensors of a cache.read_sample dict under FIELDS' names."""
-    d = {"lr": s["lr"], "hr": s["hr"]}
-    d.update({"out_" + k: s["expert_imgs"][k] for k in EXPERTS})
-    d.update({"feat_" + k: s["expert_feats"][k] for k in EXPERTS})
-    return d
-
-
 class ResidentCache:
     """Every sample of a cache directory, loaded once and resident on the device as ONE field-major fp32 buffer.
 
@@ -305,7 +260,7 @@ class ResidentCache:
     The eight field shapes come from the first sample (as CachedEpoch takes them) and the pool is laid out from them by
     resident_layout; more than max_bytes is an error naming the bytes needed, raised before anything is allocated -- there is no
     second route.  Then `readers` host threads (at most 16) run cache.read_sample into pinned one-sample slots and make no GPU call;
-    the calling thread uploads each sample into its eight places (_fill_from_readers, ImagePool's pattern).  A sample whose shapes
+    the calling thread uploads each sample into its eight places (staging.ReadAhead, as ImagePool does).  A sample whose shapes
     differ from the first one's is an error naming the file.  `load_s`: seconds the loading took."""
 
     def __init__(self, cache_dir: str, device="cuda:0", readers: int = 8, max_bytes: int = 200 << 30):
@@ -316,7 +271,7 @@ class ResidentCache:
         if not self.stems:
             raise _lib.FFError(f"{cache_dir}: no cached samples (*{cache.PRIMARY_SUFFIX} + *{cache.REST_SUFFIX})")
         t0 = time.perf_counter()
-        first = _sample_fields(cache.read_sample(cache_dir, self.stems[0]))
+        first = cache.sample_fields(cache.read_sample(cache_dir, self.stems[0]))
         self.shapes = {k: tuple(int(v) for v in first[k].shape) for k in FIELDS}
         n = len(self.stems)
         self.offsets, self.total_floats = resident_layout([self.shapes[k] for k in FIELDS], n)
@@ -337,7 +292,7 @@ class ResidentCache:
 
         def read(i, slot):
             s = cache.read_sample(self.dir, self.stems[i])
-            for k, so, t in zip(FIELDS, soffs, _sample_fields(s).values()):
+            for k, so, t in zip(FIELDS, soffs, cache.sample_fields(s).values()):
                 if tuple(t.shape) != self.shapes[k]:
                     raise _lib.FFError(f"{os.path.join(self.dir, self.stems[i] + cache.PRIMARY_SUFFIX)}: {k} has shape {tuple(t.shape)}, the pool "
                                        f"holds {self.shapes[k]} (the shapes of {self.stems[0]})")
@@ -347,8 +302,12 @@ class ResidentCache:
             for po, so, sz in zip(self.offsets, soffs, sizes):
                 self.buf[int(po) + i * sz:int(po) + (i + 1) * sz].copy_(slot[int(so):int(so) + sz], non_blocking=True)
 
-        _fill_from_readers(len(self.stems), self.readers, lambda: torch.empty(slot_floats, dtype=torch.float32, pin_memory=True), read, upload,
-                           self.dev, name="ff-cache-reader")
+        with ReadAhead(len(self.stems), read, lambda: torch.empty(slot_floats, dtype=torch.float32, pin_memory=True), self.readers,
+                       name="ff-cache-reader") as reads:
+            for i, slot, _ in reads:                                  # arrival order: every sample has its own place in the pool
+                upload(i, slot)
+                reads.release(slot, cache.recorded_event())
+        torch.cuda.synchronize(self.dev)
 
     def __len__(self) -> int:
         return len(self.stems)
@@ -361,9 +320,7 @@ class ResidentCache:
 
     def sample(self, i: int) -> dict:
         """Sample i in cache.read_sample's shape; its tensors are views of the pool."""
-        v = {k: self.field(k)[i] for k in FIELDS}
-        return {"lr": v["lr"], "hr": v["hr"], "expert_imgs": {k: v["out_" + k] for k in EXPERTS},
-                "expert_feats": {k: v["feat_" + k] for k in EXPERTS}, "filename": self.stems[i]}
+        return cache.fields_sample({k: self.field(k)[i] for k in FIELDS}, self.stems[i])
 
     def samples(self) -> Iterable[dict]:
         """Every sample as read_samples yields them, from the pool: validate() takes them unchanged (its .to(device) is a no-op)."""
@@ -416,8 +373,8 @@ class ResidentEpoch:
             desc_dev = torch.from_numpy(desc).to(self.dev)            # ONE upload per epoch
             for b in range(desc.shape[0]):
                 flat = torch.empty(self.out_floats, dtype=torch.float32, device=self.dev)
-                v = dict(zip(FIELDS, ops.gather_d4_fields(self.pool.buf, len(self.stems), self.fields, desc_dev[b], flat, desc_host=desc[b])))
-                yield (v["lr"], v["hr"], {e: v["out_" + e] for e in EXPERTS}, {e: v["feat_" + e] for e in EXPERTS})
+                yield cache.fields_batch(dict(zip(FIELDS, ops.gather_d4_fields(self.pool.buf, len(self.stems), self.fields, desc_dev[b], flat,
+                                                                                desc_host=desc[b]))))
 
 
 # ======================================================================================================================
@@ -652,75 +609,13 @@ def live_jitter_plan(nb: int, batch_size: int, seed: int, epoch: int, prob: floa
     return t.reshape(nb, B, 4)
 
 
-def _fill_from_readers(n_items: int, n_readers: int, make_slot, read, upload, dev, name: str = "ff-pool-reader"):
-    """How a resident pool (ImagePool, ResidentCache) is filled: n_readers host threads take the items 0 .. n_items in turn and call
-    read(i, slot) -- decode or load item i into a pinned slot, NO GPU call -- and the calling thread calls upload(i, slot), which queues
-    the copies of that slot into the pool on the current stream.  n_readers + 2 slots from make_slot(), made here (pinning is a GPU
-    call); a slot goes back to the readers once an event recorded after its copies has completed.  A reader's exception ends the fill
-    and is re-raised here.  Returns after the device has finished."""
-    free, ready, stop, nxt, lock = queue.Queue(), queue.Queue(), threading.Event(), [0], threading.Lock()
-    for _ in range(n_readers + 2):                                    # pinned here: the readers make no GPU call
-        free.put(make_slot())
-
-    def reader():
-        try:
-            while not stop.is_set():
-                with lock:
-                    i = nxt[0]
-                    nxt[0] += 1
-                if i >= n_items:
-                    break
-                slot = free.get()
-                if slot is None:
-                    return
-                read(i, slot)
-                ready.put((i, slot))
-            ready.put(None)
-        except BaseException as e:                                    # noqa: BLE001 -- re-raised on the calling thread
-            ready.put(e)
-
-    threads = [threading.Thread(target=reader, name=f"{name}{i}", daemon=True) for i in range(n_readers)]
-    for t in threads:
-        t.start()
-    pending, done = [], 0                                             # (event of the last copy out of a slot, slot)
-    try:
-        while done < n_readers:
-            for ent in [e for e in pending if e[0].query()]:
-                pending.remove(ent)
-                free.put(ent[1])
-            try:
-                item = ready.get(timeout=0.05 if pending else None)
-            except queue.Empty:                                       # the readers may be out of slots: hand the oldest one back
-                ev, slot = pending.pop(0)
-                ev.synchronize()
-                free.put(slot)
-                continue
-            if isinstance(item, BaseException):
-                raise item
-            if item is None:
-                done += 1
-                continue
-            i, slot = item
-            upload(i, slot)
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append((ev, slot))
-    finally:
-        stop.set()
-        for _ in threads:
-            free.put(None)
-        for t in threads:
-            t.join(timeout=60)
-        torch.cuda.synchronize(dev)
-
-
 class ImagePool:
     """Every image pair of a folder (or two), decoded once and resident on the device as ONE packed uint8 buffer.
 
         pool = ImagePool(hr_dir, lr_dir=None, patch=64, device="cuda:0", readers=8, max_bytes=64 << 30)
         pool.buf [total_bytes] uint8, pool.sizes [(h, w)] LR sizes, pool.offsets int64 [n, 2], pool.stems, pool.skipped
 
-    Pairing and order follow cache.build_from_folders: matched by stem, sorted, image index = position in that order (among the
+    Pairing and order are cache.list_pairs', as in cache.build_from_folders: matched by stem, sorted, image index = position in that order (among the
     images kept).  Pass 1 reads the sizes from the headers, leaves out (and counts) images smaller than the patch, lays the pool out
     (pool_layout) and allocates it; more than max_bytes is an error -- there is no second route.  Pass 2: `readers` host threads
     (at most 16) decode into pinned uint8 slots and make no GPU call; the calling thread uploads each image into its place.
@@ -735,23 +630,15 @@ class ImagePool:
             raise _lib.FFError(f"ImagePool: patch and readers must be >= 1, got {patch}, {readers}")
         if self.dev.type != "cuda" or not torch.cuda.is_available():
             raise _lib.FFError("ImagePool needs an MI355X (torch device 'cuda'): the images live on the device")
-        hr_files = cache._image_stems(hr_dir)
-        lr_files = None
-        if lr_dir is not None:
-            lr_files = cache._image_stems(lr_dir)
-            missing = sorted(set(hr_files) ^ set(lr_files))
-            if missing:
-                raise FileNotFoundError(f"ImagePool: {missing[0]} has no partner in {lr_dir if missing[0] in hr_files else hr_dir}")
-        items, sizes = [], []
-        for stem in sorted(hr_files):                                 # pass 1: headers only
-            W, H = Image.open(hr_files[stem]).size
-            if lr_files is None:
+        items, sizes = cache.list_pairs(hr_dir, lr_dir), []
+        for _, hr_path, lr_path in items:                             # pass 1: headers only
+            W, H = Image.open(hr_path).size
+            if lr_path is None:
                 h, w = H // 4, W // 4
             else:
-                w, h = Image.open(lr_files[stem]).size
+                w, h = Image.open(lr_path).size
                 if (H, W) != (4 * h, 4 * w):
-                    raise _lib.FFError(f"{hr_files[stem]}: HR is {H}x{W}, not exactly 4x its LR {lr_files[stem]} ({h}x{w})")
-            items.append((stem, hr_files[stem], None if lr_files is None else lr_files[stem]))
+                    raise _lib.FFError(f"{hr_path}: HR is {H}x{W}, not exactly 4x its LR {lr_path} ({h}x{w})")
             sizes.append((h, w))
         keep, self.skipped = pool_members(sizes, self.patch)
         if not keep:
@@ -763,7 +650,7 @@ class ImagePool:
             raise _lib.FFError(f"ImagePool: {len(keep)} images need {self.total_bytes} bytes on the device, max_bytes allows {int(max_bytes)}")
         with torch.cuda.device(self.dev):
             self.buf = torch.empty(self.total_bytes, dtype=torch.uint8, device=self.dev)
-            self._fill([items[i] for i in keep], lr_files is None, max(1, min(16, int(readers))))
+            self._fill([items[i] for i in keep], lr_dir is None, max(1, min(16, int(readers))))
 
     def _fill(self, items, hr_only: bool, n_readers: int):
         from . import ops
@@ -792,7 +679,11 @@ class ImagePool:
             else:                                                     # LR and HR are adjacent in the slot as they are in the pool
                 self.buf[lo:lo + 51 * h * w].copy_(slot[:51 * h * w], non_blocking=True)
 
-        _fill_from_readers(len(items), n_readers, lambda: torch.empty(slot_bytes, dtype=torch.uint8, pin_memory=True), read, upload, self.dev)
+        with ReadAhead(len(items), read, lambda: torch.empty(slot_bytes, dtype=torch.uint8, pin_memory=True), n_readers, name="ff-pool-reader") as reads:
+            for i, slot, _ in reads:                                  # arrival order: every image has its own place in the pool
+                upload(i, slot)
+                reads.release(slot, cache.recorded_event())
+        torch.cuda.synchronize(self.dev)
 
     def __len__(self) -> int:
         return len(self.sizes)

@@ -611,6 +611,17 @@ def is_parameter_key(k: str) -> bool:
                              "multi_domain_freq.dct.high_mask", "multi_domain_freq.dwt.lo_", "multi_domain_freq.dwt.hi_", "edge_refine.gaussian.kernel"))
 
 
+def load_fusion_weights(path: Optional[str]) -> Dict[str, T]:
+    """--weights of train_cached / train_live: a reference-keyed fusion (+ collaborative) state dict, bare or under `model_state_dict`,
+    `module.` prefixes stripped; without a path the seeded synthetic weights (smoke runs)."""
+    if not path:
+        from .weights import synth_state_dict
+        return synth_state_dict(1234, parts=("fusion", "collab"))
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck.get("model_state_dict", ck) if isinstance(ck, dict) else ck
+    return {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
+
+
 def build_checkpoint(model_sd: Dict[str, T], exp_avg: Dict[str, T], exp_avg_sq: Dict[str, T], ema_shadow: Dict[str, T], step: int, hp: dict,
                      epoch: int, metrics: Optional[dict] = None, lr_now: Optional[float] = None, scheduler_state: Optional[dict] = None,
                      stage: Optional[int] = None) -> dict:

@@ -16,8 +16,6 @@ from __future__ import annotations
 import argparse
 import sys
 
-import torch
-
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m isr2_amd.train_cached", description=__doc__.split("\n\n")[0])
@@ -42,15 +40,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
 
     from . import epoch as E
-    from .train import FusionTrainer
-    from .weights import synth_state_dict
-    if a.weights:
-        ck = torch.load(a.weights, map_location="cpu", weights_only=True)
-        sd = ck.get("model_state_dict", ck) if isinstance(ck, dict) else ck
-        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
-    else:
-        sd = synth_state_dict(1234, parts=("fusion", "collab"))
-    tr = FusionTrainer(sd, a.device, dropout=a.dropout, seed=a.seed, gemm=a.gemm)
+    from .train import FusionTrainer, load_fusion_weights
+    tr = FusionTrainer(load_fusion_weights(a.weights), a.device, dropout=a.dropout, seed=a.seed, gemm=a.gemm)
     start, best = 0, float("-inf")
     if a.resume:
         ck = tr.load_checkpoint(a.resume)

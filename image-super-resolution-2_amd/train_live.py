@@ -29,8 +29,6 @@ import argparse
 import os
 import sys
 
-import torch
-
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m isr2_amd.train_live", description=__doc__.split("\n\n")[0])
@@ -65,17 +63,10 @@ def main(argv=None) -> int:
     from . import ops
     from .build_cache import load_state_dict
     from .model import FreqFusionHIP
-    from .train import FusionTrainer
-    from .weights import synth_state_dict
+    from .train import FusionTrainer, load_fusion_weights
     ops.set_gemm_mode(a.expert_gemm)
     model = FreqFusionHIP(load_state_dict(a.expert_weights), a.device)           # only its three experts run here
-    if a.weights:
-        ck = torch.load(a.weights, map_location="cpu", weights_only=True)
-        fusion_sd = ck.get("model_state_dict", ck) if isinstance(ck, dict) else ck
-        fusion_sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in fusion_sd.items()}
-    else:
-        fusion_sd = synth_state_dict(1234, parts=("fusion", "collab"))
-    tr = FusionTrainer(fusion_sd, a.device, dropout=a.dropout, seed=a.seed, gemm=a.gemm)
+    tr = FusionTrainer(load_fusion_weights(a.weights), a.device, dropout=a.dropout, seed=a.seed, gemm=a.gemm)
     start, best = 0, float("-inf")
     if a.resume:
         ck = tr.load_checkpoint(os.path.join(a.out, "latest.pth"))

@@ -20,9 +20,7 @@ from __future__ import annotations
 
 import glob
 import os
-import queue
 import sys
-import threading
 import time
 import warnings
 from collections import OrderedDict
@@ -37,9 +35,11 @@ if _PROJECT_ROOT not in sys.path:
     sys.path.insert(0, _PROJECT_ROOT)
 
 from isr2_amd import ops  # noqa: E402
+from isr2_amd.cache import pinned_u8, recorded_event  # noqa: E402
 from isr2_amd.lib import FFError  # noqa: E402
 from isr2_amd.model import FreqFusionHIP  # noqa: E402
 from isr2_amd.parallel import shard_list, broadcast_state_dict  # noqa: E402
+from isr2_amd.staging import ReadAhead, WriteBehind  # noqa: E402
 from isr2_amd.weights import synth_state_dict, param_spec, HAT_PREFIX, DAT_PREFIX, NAF_PREFIX  # noqa: E402
 
 # reference io.py:40-58 -- the flags the shipped checkpoint was trained with; this build implements exactly
@@ -266,108 +266,47 @@ def _build_and_load(model_dir: str, device, rank: int = 0, world: int = 1):
 # --------------------------------------------------------------------------------------------------------------------
 # Host image pipeline: decode and encode beside the GPU
 class _HostPipeline:
-    """Reader thread: PNG -> uint8 HWC in a pinned staging slot.  Writer threads: pinned uint8 HWC -> PNG.
-    The calling thread owns every GPU call (H2D copy, kernels, D2H copy); a slot is reused only after the event that marks
-    its last copy has completed.  Exceptions raised on a worker thread are re-raised on the calling thread."""
+    """PNG decode and encode beside the GPU on isr2_amd.staging: a reader thread decodes into growable pinned uint8 slots (_decode),
+    writer threads encode pinned uint8 results at PNG_LEVEL (_encode); the calling thread owns every GPU call (H2D copy, kernels,
+    D2H copy)."""
 
     def __init__(self, paths, out_dir, device, n_slots: int = 5, n_writers: int = 4):
         self.paths, self.out_dir, self.device = list(paths), out_dir, device
-        self.err = None
-        self.in_free, self.in_ready = queue.Queue(), queue.Queue()
-        self.out_free, self.out_ready = queue.Queue(), queue.Queue()
-        for _ in range(n_slots):
-            self.in_free.put({"buf": None, "ev": None})
-            self.out_free.put({"buf": None})
-        self.t_decode = self.t_encode = 0.0
-        self.reader = threading.Thread(target=self._read_loop, name="ff-png-reader", daemon=True)
-        self.writers = [threading.Thread(target=self._write_loop, name=f"ff-png-writer{i}", daemon=True) for i in range(n_writers)]
-        self.reader.start()
-        for t in self.writers:
-            t.start()
+        self.writes = WriteBehind(self._encode, lambda: {"buf": None}, n_writers, n_slots, name="ff-png-writer")
+        self.reads = ReadAhead(len(self.paths), self._decode, lambda: {"buf": None}, n_slots=n_slots, name="ff-png-reader")
 
-    @staticmethod
-    def _pinned(slot, nbytes: int):
-        if slot["buf"] is None or slot["buf"].numel() < nbytes:
-            slot["buf"] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8).pin_memory()
-        return slot["buf"]
+    def _decode(self, i, slot):
+        arr = np.asarray(Image.open(self.paths[i]).convert("RGB"), dtype=np.uint8)
+        h, w, _ = arr.shape
+        pinned_u8(slot, "buf", arr.size)[:arr.size].view(h, w, 3).numpy()[...] = arr
+        return h, w
 
-    def _read_loop(self):
-        try:
-            for p in self.paths:
-                slot = self.in_free.get()
-                if slot is None:
-                    return
-                if slot["ev"] is not None:
-                    slot["ev"].synchronize()                     # the previous H2D copy out of this slot has finished
-                t0 = time.perf_counter()
-                arr = np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8)
-                h, w, _ = arr.shape
-                buf = self._pinned(slot, arr.size)
-                buf[:arr.size].view(h, w, 3).numpy()[...] = arr
-                self.t_decode += time.perf_counter() - t0
-                self.in_ready.put((slot, p, h, w))
-        except BaseException as e:                               # noqa: BLE001 -- handed to the calling thread
-            self.err = e
-        finally:
-            self.in_ready.put(None)
-
-    def _write_loop(self):
-        try:
-            while True:
-                item = self.out_ready.get()
-                if item is None:
-                    return
-                slot, ev, name, h, w = item
-                ev.synchronize()                                 # the D2H copy into this slot has finished
-                t0 = time.perf_counter()
-                arr = slot["buf"][:h * w * 3].view(h, w, 3).numpy()
-                Image.fromarray(arr).save(os.path.join(self.out_dir, name), format="PNG", compress_level=PNG_LEVEL)
-                self.t_encode += time.perf_counter() - t0
-                self.out_free.put(slot)
-        except BaseException as e:                               # noqa: BLE001
-            self.err = e
-            self.out_free.put({"buf": None})                     # keep the producer from blocking forever
-
-    def _check(self):
-        if self.err is not None:
-            raise self.err
+    def _encode(self, slot, job):
+        name, h, w = job
+        Image.fromarray(slot["buf"][:h * w * 3].view(h, w, 3).numpy()).save(os.path.join(self.out_dir, name), format="PNG", compress_level=PNG_LEVEL)
 
     def __iter__(self):
         """Yields (path, lr [1,3,H,W] fp32 on the device) in list order."""
-        while True:
-            item = self.in_ready.get()
-            self._check()
-            if item is None:
-                return
-            slot, p, h, w = item
+        for i, slot, (h, w) in self.reads:
             dev_u8 = slot["buf"][:h * w * 3].view(h, w, 3).to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            slot["ev"] = ev
-            self.in_free.put(slot)
-            yield p, ops.u8_to_f32_image(dev_u8)
+            self.reads.release(slot, recorded_event())
+            yield self.paths[i], ops.u8_to_f32_image(dev_u8)
 
     def save(self, sr: torch.Tensor, name: str):
         """Queue `sr` [1,3,H,W] (device) for PNG encoding: converted to uint8 HWC on the device, copied to a pinned slot."""
-        self._check()
         u8 = ops.f32_to_u8_image(sr)
         h, w, _ = u8.shape
-        slot = self.out_free.get()
-        self._check()
-        self._pinned(slot, u8.numel())[:u8.numel()].view(h, w, 3).copy_(u8, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
+        slot = self.writes.take()
+        pinned_u8(slot, "buf", u8.numel())[:u8.numel()].view(h, w, 3).copy_(u8, non_blocking=True)
+        ev = recorded_event()
         u8.record_stream(torch.cuda.current_stream())
-        self.out_ready.put((slot, ev, name, h, w))
+        self.writes.submit(slot, ev, (name, h, w))
 
     def close(self):
-        for _ in self.writers:
-            self.out_ready.put(None)
-        for t in self.writers:
-            t.join()
-        self.in_free.put(None)
-        self.reader.join(timeout=5)
-        self._check()
+        try:
+            self.writes.close()
+        finally:
+            self.reads.close()
 
 
 # Graph capture costs two extra forwards and pins an activation pool; it pays where the Python launch loop (~1400 launches) is as long

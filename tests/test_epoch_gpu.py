@@ -14,6 +14,7 @@ import math
 import os
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -317,6 +318,63 @@ def test_augmented_micro_batch_carries_one_code_per_sample(tmp_path):
     (lr, hr, outs, feats), = list(plain.batches(0))
     for j, stem in enumerate(plain.stems):
         assert torch.equal(lr[j].cpu(), cache.read_sample(str(tmp_path), stem)["lr"])
+
+
+def _epoch_from_files(data, cdir, epoch):
+    """What `data` must yield for `epoch`: ops.d4_nchw of the files, in epoch_plan's order and with its codes."""
+    from isr2_amd import cache, ops
+    from isr2_amd import epoch as E
+    idx, codes = E.epoch_plan(len(data.stems), data.repeat, data.B, data.seed, epoch, data.augment, data.shuffle)
+    want = []
+    for b in range(len(idx)):
+        rows = [cache.sample_fields(cache.read_sample(cdir, data.stems[int(i) % len(data.stems)])) for i in idx[b]]
+        want.append({k: ops.d4_nchw(torch.stack([r[k] for r in rows]).cuda(), [int(c) for c in codes[b]]) for k in E.FIELDS})
+    return want
+
+
+def _same_batches(got, want):
+    from isr2_amd import cache
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        lr, hr, outs, feats = cache.fields_batch(w)
+        assert torch.equal(g[0], lr) and torch.equal(g[1], hr)
+        for k in EXPERTS:
+            assert torch.equal(g[2][k], outs[k]) and torch.equal(g[3][k], feats[k]), k
+
+
+def test_abandoned_epoch_leaves_the_next_one_whole(tmp_path):
+    """Six samples at 8x8 LR, batch 2, two staging slots: three micro-batches, so a slot is reused inside one epoch.  Epoch 0 is closed
+    after its first micro-batch (a reader at work, a filled slot never uploaded); all of epoch 1 still holds the files' bits."""
+    _need_gpu()
+    from isr2_amd import epoch as E
+    _write_cache(tmp_path, 6, 571, 8, 8)
+    data = E.CachedEpoch(str(tmp_path), batch_size=2, augment=True, seed=3, prefetch=2)
+    assert len(data) == 3 and data.layout["feat_nafnet"][1] == (2, 64, 8, 8) and data.layout["out_dat"][1] == (2, 3, 32, 32)
+    it = data.batches(0)
+    first = next(it)
+    it.close()
+    want0, want1 = _epoch_from_files(data, str(tmp_path), 0), _epoch_from_files(data, str(tmp_path), 1)
+    _same_batches([first], want0[:1])
+    assert not [t.name for t in threading.enumerate() if t.name.startswith("ff-")]
+    _same_batches(list(data.batches(1)), want1)
+    wide = E.CachedEpoch(str(tmp_path), batch_size=2, augment=True, seed=3, prefetch=3)
+    _same_batches(list(wide.batches(1)), want1)
+
+
+def test_bad_sample_reaches_the_stepping_thread(tmp_path):
+    """A sample whose feat_dat has another shape, in the second micro-batch: the FFError naming the file is raised by the iteration,
+    and no reader thread outlives it."""
+    _need_gpu()
+    from isr2_amd import cache
+    from isr2_amd import epoch as E
+    from isr2_amd.lib import FFError
+    _write_cache(tmp_path, 6, 572, 8, 8)
+    lr, hr, outs, feats = cache.fields_batch(cache.sample_fields(cache.read_sample(str(tmp_path), "img002")))
+    cache.write_sample(str(tmp_path), "img002", lr, hr, outs, dict(feats, dat=torch.zeros(180, 4, 8)))
+    data = E.CachedEpoch(str(tmp_path), batch_size=2, augment=False, shuffle=False, prefetch=2)
+    with pytest.raises(FFError, match="img002"):                        # raised while the first micro-batch is handed out or right after it
+        list(data.batches(0))
+    assert not [t.name for t in threading.enumerate() if t.name.startswith("ff-")]
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16x3"])

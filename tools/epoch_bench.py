@@ -78,8 +78,7 @@ def main():
             nb = min(16, a.samples - done)
             d = {k: torch.from_numpy(v) for k, v in make_train_batch(7000 + done, nb, a.size, a.size).items()}
             for j in range(nb):
-                cache.write_sample(tmp, f"s{done + j:05d}", d["lr"][j], d["hr"][j], {k: d["out_" + k][j:j + 1] for k in E.EXPERTS},
-                                   {k: d["feat_" + k][j:j + 1] for k in E.EXPERTS})
+                cache.write_sample(tmp, f"s{done + j:05d}", *cache.fields_batch({k: v[j:j + 1] for k, v in d.items()}))
             done += nb
         t_write = time.perf_counter() - t0
         if a.resident:
@@ -89,7 +88,7 @@ def main():
         warm = make_train_batch(503, a.batch, a.size, a.size)
         w = {k: torch.from_numpy(v).cuda() for k, v in warm.items()}
         for _ in range(2):                                            # allocator, workspaces, code objects
-            tr.step(w["lr"], w["hr"], {k: w["out_" + k] for k in E.EXPERTS}, {k: w["feat_" + k] for k in E.EXPERTS})
+            tr.step(*cache.fields_batch(w))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = E.train_epoch(tr, data, 0, a.accum)
@@ -106,14 +105,14 @@ def resident(a, tmp, t_write):
     """--resident: CachedEpoch and ResidentEpoch on the cache in `tmp`, alternating, with the step-only ceiling and the gather alone."""
     import numpy as np
     from train_inputs import make_train_batch
-    from isr2_amd import ops
+    from isr2_amd import cache, ops
     from isr2_amd import epoch as E
     from isr2_amd.train import FusionTrainer
     from isr2_amd.weights import synth_state_dict
     rounds = max(3, a.rounds)
     tr = FusionTrainer(synth_state_dict(1234, parts=("fusion", "collab")), "cuda:0", gemm=a.mode)
     w = {k: torch.from_numpy(v).cuda() for k, v in make_train_batch(503, a.batch, a.size, a.size).items()}
-    fixed = (w["lr"], w["hr"], {k: w["out_" + k] for k in E.EXPERTS}, {k: w["feat_" + k] for k in E.EXPERTS})
+    fixed = cache.fields_batch(w)
     for _ in range(2):                                                # allocator, workspaces, code objects
         tr.step(*fixed)
     torch.cuda.synchronize()
