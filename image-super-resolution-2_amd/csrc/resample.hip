@@ -299,3 +299,79 @@ extern "C" int ff_resize_aa(const float* in, float* out, int planes, int Hi, int
   FF_LAUNCH_CHECK("ff_resize_aa");
   return FF_OK;
 }
+
+// ---- OpenCV's INTER_CUBIC restated (isr2_amd.epoch.live_val_images: the reference's ValidationDataset, dataset.py:473-506) ------------
+// cv2.resize(..., interpolation=INTER_CUBIC) of planar fp32 [planes][Hi][Wi] -> [planes][Ho][Wo] at any ratio, up or down: four taps per
+// axis whatever the ratio (no antialiasing when shrinking), replicated border, no clamping of values.  Each axis is driven by a host table
+// (ops.cv_cubic_tables): idx [O][4] int32 = the taps s - 1 .. s + 2 clamped to the image, wt [O][4] fp32 = interpolateCubic's weights
+// (A = -0.75) of x = f - s, f = float((d + 0.5) * scale - 0.5), s = floor(f).  Fixed arithmetic, so that a numpy restatement
+// (tests/golden/cv_cubic_ref.py) matches bit for bit: per source row h = ((v0 a0 + v1 a1) + v2 a2) + v3 a3, then
+// out = ((h0 b0 + h1 b1) + h2 b2) + h3 b3, every product and every sum rounded on its own -- contraction is OFF in cvc_dot4 (a fused
+// multiply-add would change the bits; the rest of this file keeps the compiler's default).  A gather that runs once per validation image:
+// direct form, no LDS.  One work item = up to four consecutive output pixels of one row; VEC (Wo % 4 == 0 and a 16-byte aligned output):
+// one 16-byte store, else scalar stores.  Table indices are clamped again here, so a wrong table gives wrong values, never an access
+// outside the buffers.  Offsets are 64-bit.
+__device__ __forceinline__ float cvc_dot4(float v0, float v1, float v2, float v3, float w0, float w1, float w2, float w3) {
+#pragma clang fp contract(off)
+  const float p0 = v0 * w0, p1 = v1 * w1, p2 = v2 * w2, p3 = v3 * w3;
+  return ((p0 + p1) + p2) + p3;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void resize_cv_cubic_kernel(const float* __restrict__ in, float* __restrict__ out, int planes, int Hi, int Wi,
+                                                              int Ho, int Wo, const int* __restrict__ idx_w, const float* __restrict__ wt_w,
+                                                              const int* __restrict__ idx_h, const float* __restrict__ wt_h) {
+  const int q = (Wo + 3) >> 2;                                   // four-pixel groups per output row
+  const long long total = (long long)planes * Ho * q;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int xg = (int)(i % q); long long t = i / q;
+    const int oy = (int)(t % Ho); const long long pl = t / Ho;
+    const float* src = in + pl * Hi * Wi;
+    const float* line[4]; float b[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      line[j] = src + (long long)min(max(idx_h[4ll * oy + j], 0), Hi - 1) * Wi;
+      b[j] = wt_h[4ll * oy + j];
+    }
+    const int x0 = xg * 4, n = VEC ? 4 : min(4, Wo - x0);
+    f32x4 r = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e < n) {
+        const long long tw = 4ll * (x0 + e);
+        int cx[4]; float a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          cx[k] = min(max(idx_w[tw + k], 0), Wi - 1);
+          a[k] = wt_w[tw + k];
+        }
+        float h[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[j] = cvc_dot4(line[j][cx[0]], line[j][cx[1]], line[j][cx[2]], line[j][cx[3]], a[0], a[1], a[2], a[3]);
+        r[e] = cvc_dot4(h[0], h[1], h[2], h[3], b[0], b[1], b[2], b[3]);
+      }
+    }
+    float* dst = out + (pl * Ho + oy) * Wo + x0;
+    if (VEC) *reinterpret_cast<f32x4*>(dst) = r;
+    else
+      for (int e = 0; e < n; ++e) dst[e] = r[e];
+  }
+}
+
+extern "C" int ff_resize_cv_cubic(const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, const int* idx_w, const float* wt_w,
+                                  const int* idx_h, const float* wt_h, void* stream) {
+  FF_CHECK_ARG(in && out && idx_w && wt_w && idx_h && wt_h, "ff_resize_cv_cubic: null pointer");
+  FF_CHECK_ARG(planes >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1, "ff_resize_cv_cubic: bad sizes (planes %d, %d x %d -> %d x %d)", planes,
+               Hi, Wi, Ho, Wo);
+  FF_CHECK_ARG(planes <= (1 << 20) && Hi <= (1 << 20) && Wi <= (1 << 20) && Ho <= (1 << 20) && Wo <= (1 << 20),
+               "ff_resize_cv_cubic: sizes out of range (planes %d, %d x %d -> %d x %d)", planes, Hi, Wi, Ho, Wo);
+  const long long total = (long long)planes * Ho * ((Wo + 3) / 4);
+  long long nb = (total + 255) / 256;                            // grid-stride: the grid is bounded whatever the sizes are
+  if (nb > 16384) nb = 16384;
+  FF_CHECK_ARG(nb >= 1 && nb <= 16384, "ff_resize_cv_cubic: %lld work items give a grid of %lld blocks", total, nb);
+  const bool vec = Wo % 4 == 0 && (((uintptr_t)out) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(resize_cv_cubic_kernel<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, in, out, planes, Hi, Wi, Ho, Wo, idx_w, wt_w, idx_h, wt_h);
+  else hipLaunchKernelGGL(resize_cv_cubic_kernel<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, in, out, planes, Hi, Wi, Ho, Wo, idx_w, wt_w, idx_h, wt_h);
+  FF_LAUNCH_CHECK("ff_resize_cv_cubic");
+  return FF_OK;
+}

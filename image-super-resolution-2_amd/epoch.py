@@ -20,6 +20,7 @@ configuration selects: dataset.train.cache_data false, repeat_factor 6):
 
     src/data/dataset.py:236-296, :562-565; augmentations.py:77-79, :128-135, :169-171   -> live_plan(), ImagePool, LiveEpoch
     train.py:413-523 on centre patches                                                     -> live_val_samples()
+    train.py:413-523 on ValidationDataset's resized whole images (dataset.py:473-506)      -> live_val_images(), val_resized_shape()
 
 The images are decoded once into one device buffer; a micro-batch is one sampler launch (csrc/sample_batch.hip: crop, u8 -> fp32
 and the paired D4 symmetry) and one replay of the captured expert graph, with nothing read from disk.  Its crop and augmentation
@@ -488,10 +489,12 @@ def validate(trainer, samples: Iterable[dict], use_ema: bool = True, crop_border
 
 
 def fit(trainer, train_data, val_samples, out_dir: str, epochs: int, start_epoch: int = 0, accumulation_steps: int = 2, validate_every: int = 1,
-        best_psnr: float = float("-inf"), schedule: Optional[dict] = None, log=print) -> dict:
+        best_psnr: float = float("-inf"), schedule: Optional[dict] = None, log=print, validate_start: int = 0) -> dict:
     """The reference's epoch loop (train.py:1056-1160): per epoch train -> validate with EMA weights (every `validate_every` epochs and
     the last one) -> latest.pth, copied to best.pth on a new best PSNR.  One JSON line per epoch through `log`.
-    val_samples: a callable returning an iterable of samples (called per validation), or a list."""
+    val_samples: a callable returning an iterable of samples (called per validation), or a list.
+    validate_start: no validation in epochs before it (the reference's validation.validate_start, train.py:1116-1119), the last epoch
+    excepted.  The every-N rule here is (epoch + 1) % N == 0; the reference tests epoch % N == 0."""
     os.makedirs(out_dir, exist_ok=True)
     latest, best = os.path.join(out_dir, "latest.pth"), os.path.join(out_dir, "best.pth")
     sched = dict(SCHEDULE, base_lr=trainer.hp["lr"], **(schedule or {}))
@@ -507,7 +510,7 @@ def fit(trainer, train_data, val_samples, out_dir: str, epochs: int, start_epoch
         t1 = time.perf_counter()
         row = dict(epoch=epoch, **tm, train_s=t1 - t0, data_wait_s=getattr(train_data, "wait_s", 0.0))
         metrics_now = {}
-        if (epoch + 1) % max(1, int(validate_every)) == 0 or epoch == int(epochs) - 1:
+        if (epoch >= int(validate_start) and (epoch + 1) % max(1, int(validate_every)) == 0) or epoch == int(epochs) - 1:
             metrics_now = validate(trainer, val_samples() if callable(val_samples) else val_samples, use_ema=True)
             row.update(metrics_now, val_s=time.perf_counter() - t1)
         trainer.save_checkpoint(latest, epoch=epoch, metrics=dict(metrics_now, loss=tm["loss"], best_psnr=max(best_psnr, metrics_now.get("psnr", best_psnr))),
@@ -619,28 +622,35 @@ class ImagePool:
     images kept).  Pass 1 reads the sizes from the headers, leaves out (and counts) images smaller than the patch, lays the pool out
     (pool_layout) and allocates it; more than max_bytes is an error -- there is no second route.  Pass 2: `readers` host threads
     (at most 16) decode into pinned uint8 slots and make no GPU call; the calling thread uploads each image into its place.
-    With lr_dir an HR image that is not exactly 4x its LR partner is an error naming the file.  Without it HR is cropped top-left to
+    With lr_dir an HR image that is not exactly 4x its LR partner is an error naming the file (skip_mismatched: left out and counted in
+    `skipped` instead: live_val_images).  Without it HR is cropped top-left to
     multiples of 4 and LR = f32_to_u8_image(resize_aa(u8_to_f32_image(hr))) on the device, as build_from_folders makes it.
     A reader's exception ends construction and is re-raised."""
 
-    def __init__(self, hr_dir: str, lr_dir: Optional[str] = None, patch: int = 64, device="cuda:0", readers: int = 8, max_bytes: int = 64 << 30):
+    def __init__(self, hr_dir: str, lr_dir: Optional[str] = None, patch: int = 64, device="cuda:0", readers: int = 8, max_bytes: int = 64 << 30,
+                 skip_mismatched: bool = False):
         from PIL import Image
         self.patch, self.dev = int(patch), torch.device(device)
         if self.patch < 1 or int(readers) < 1:
             raise _lib.FFError(f"ImagePool: patch and readers must be >= 1, got {patch}, {readers}")
         if self.dev.type != "cuda" or not torch.cuda.is_available():
             raise _lib.FFError("ImagePool needs an MI355X (torch device 'cuda'): the images live on the device")
-        items, sizes = cache.list_pairs(hr_dir, lr_dir), []
-        for _, hr_path, lr_path in items:                             # pass 1: headers only
+        items, sizes, paired = cache.list_pairs(hr_dir, lr_dir), [], []
+        for stem, hr_path, lr_path in items:                          # pass 1: headers only
             W, H = Image.open(hr_path).size
             if lr_path is None:
                 h, w = H // 4, W // 4
             else:
                 w, h = Image.open(lr_path).size
                 if (H, W) != (4 * h, 4 * w):
+                    if skip_mismatched:
+                        continue
                     raise _lib.FFError(f"{hr_path}: HR is {H}x{W}, not exactly 4x its LR {lr_path} ({h}x{w})")
             sizes.append((h, w))
+            paired.append((stem, hr_path, lr_path))
+        mismatched, items = len(items) - len(paired), paired
         keep, self.skipped = pool_members(sizes, self.patch)
+        self.skipped += mismatched
         if not keep:
             raise _lib.FFError(f"{hr_dir}: no image holds a {self.patch}x{self.patch} LR patch ({self.skipped} skipped)")
         self.stems = [items[i][0] for i in keep]
@@ -835,15 +845,70 @@ class LiveEpoch:
 def live_val_samples(model, hr_dir: str, lr_dir: Optional[str] = None, patch: int = 64) -> List[dict]:
     """The validation set of a live run, computed once (the experts are frozen): per image the centre patch and the three expert
     images, dicts in cache.read_sample's shape {lr [3,p,p], hr [3,4p,4p], expert_imgs, filename} on the host.  No features: the
-    eval path skips the collaborative block (enhanced_fusion.py:331, 359-362).  validate() takes the list as it is."""
+    eval path skips the collaborative block (enhanced_fusion.py:331, 359-362).  validate() takes the list as it is; its `skipped`
+    counts the images smaller than the patch."""
     from . import ops
     with torch.cuda.device(model.dev):
         pool = ImagePool(hr_dir, lr_dir, patch=patch, device=model.dev, readers=4)
-        out = []
+        out = ValSamples()
+        out.skipped = pool.skipped
         for i, stem in enumerate(pool.stems):
             h, w = pool.sizes[i]
             lr_u8, hr_u8 = pool.image(i)
             lr, hr = ops.crop_pairs_u8(lr_u8.clone(), hr_u8.clone(), cache.crop_plan(h, w, patch, 1, 0, i, center=True), patch)
+            outs, _ = model.experts_with_features(lr, streams=True)
+            out.append({"lr": lr[0].cpu(), "hr": hr[0].cpu(), "expert_imgs": {k: outs[k][0].cpu() for k in EXPERTS}, "filename": stem})
+    return out
+
+
+def val_resized_shape(lr_h: int, lr_w: int, max_size: Optional[int] = 512, scale: int = 4) -> Optional[Tuple[int, int]]:
+    """ValidationDataset's size rule (dataset.py:481-490) -> the LR size (h, w) an image pair is resized to, or None when it is kept:
+    resized only when max(lr_h, lr_w) > max_size // scale; the longer side becomes max_size // scale and the other one
+    int(other * new / longer) -- Python float division, then truncation; a square image takes the second (width) branch.  The HR
+    partner goes to `scale` times that.  max_size None: never."""
+    lr_h, lr_w = int(lr_h), int(lr_w)
+    if max_size is None or max(lr_h, lr_w) <= int(max_size) // int(scale):
+        return None
+    if lr_h > lr_w:
+        new_h = int(max_size) // int(scale)
+        new_w = int(lr_w * new_h / lr_h)
+    else:
+        new_w = int(max_size) // int(scale)
+        new_h = int(lr_h * new_w / lr_w)
+    return new_h, new_w
+
+
+class ValSamples(list):
+    """The list live_val_samples / live_val_images return; `skipped` counts the pairs left out (smaller than the patch; HR not 4x the LR)."""
+    skipped = 0
+
+
+@torch.no_grad()
+def live_val_images(model, hr_dir: str, lr_dir: Optional[str] = None, max_size: Optional[int] = 512, scale: int = 4) -> List[dict]:
+    """The reference's validation set (create_dataloaders -> ValidationDataset(hr_dir, lr_dir, scale, max_size=512), dataset.py:473-506,
+    what train.py:642 builds), computed once: WHOLE images, dicts in cache.read_sample's shape {lr [3,h,w], hr [3,4h,4w], expert_imgs,
+    filename} on the host, no features -- validate() takes the list as it is.  Per pair: decoded as ImagePool decodes (without lr_dir
+    the LR is made on the device as the pool makes it; a pair whose HR is not exactly 4x its LR is left out and counted in the
+    result's `skipped`), u8 / 255, then -- only when the LR's longer side exceeds max_size // scale (val_resized_shape) -- LR and HR
+    through ops.resize_cv_cubic (OpenCV's INTER_CUBIC restated, csrc/resample.hip) to (new_h, new_w) and four times that, clamp to
+    [0, 1], and the three experts once on the whole LR.  max_size None: no resize.  The resize is parity unpinned (OpenCV absent)."""
+    from . import ops
+    from . import autograd as ag
+    if int(scale) != 4:
+        raise _lib.FFError(f"live_val_images: the experts are x4 networks, scale {scale} is refused")
+    with torch.cuda.device(model.dev):
+        pool = ImagePool(hr_dir, lr_dir, patch=1, device=model.dev, readers=4, skip_mismatched=True)
+        out = ValSamples()
+        out.skipped = pool.skipped
+        for i, stem in enumerate(pool.stems):
+            h, w = pool.sizes[i]
+            lr_u8, hr_u8 = pool.image(i)
+            lr, hr = ops.u8_to_f32_image(lr_u8.clone()), ops.u8_to_f32_image(hr_u8.clone())
+            new = val_resized_shape(h, w, max_size, scale)
+            if new is not None:
+                lr = ops.resize_cv_cubic(lr, new[0], new[1])
+                hr = ops.resize_cv_cubic(hr, 4 * new[0], 4 * new[1])
+            lr, hr = ag.k_unary("clamp01", lr), ag.k_unary("clamp01", hr)
             outs, _ = model.experts_with_features(lr, streams=True)
             out.append({"lr": lr[0].cpu(), "hr": hr[0].cpu(), "expert_imgs": {k: outs[k][0].cpu() for k in EXPERTS}, "filename": stem})
     return out

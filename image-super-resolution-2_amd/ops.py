@@ -1955,6 +1955,86 @@ def resize_aa(x: T, size: Tuple[int, int]) -> T:
     return out
 
 
+def cv_cubic_tables(n_in: int, n_out: int):
+    """Host tables of one axis of resize_cv_cubic (numpy): idx int32 [n_out, 4], wt float32 [n_out, 4].  OpenCV's INTER_CUBIC restated
+    (resize.cpp, the table its resize builds per axis, and interpolateCubic): scale = double(n_in) / n_out,
+    f = float32((d + 0.5) * scale - 0.5) with the product and the difference in double, s = floor(f), x = f - s in fp32; taps
+    s - 1 .. s + 2, each clamped to [0, n_in - 1] (replicated border); weights in fp32 with A = -0.75f:
+        c0 = ((A (x + 1) - 5 A)(x + 1) + 8 A)(x + 1) - 4 A,  c1 = ((A + 2) x - (A + 3)) x x + 1,
+        c2 = ((A + 2)(1 - x) - (A + 3))(1 - x)(1 - x) + 1,   c3 = 1 - c0 - c1 - c2
+    every operation rounded to fp32.  Any ratio, up or down: four taps, no antialiasing."""
+    import numpy as np
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise _lib.FFError(f"cv_cubic_tables: sizes must be >= 1, got {n_in} -> {n_out}")
+    F = np.float32
+    scale = float(n_in) / float(n_out)
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * scale - 0.5).astype(F)
+    s = np.floor(f)
+    x = (f - s).astype(F)
+    A, one = F(-0.75), F(1)
+    x1, u = x + one, one - x
+    c0 = ((A * x1 - F(5) * A) * x1 + F(8) * A) * x1 - F(4) * A
+    c1 = ((A + F(2)) * x - (A + F(3))) * x * x + one
+    c2 = ((A + F(2)) * u - (A + F(3))) * u * u + one
+    c3 = one - c0 - c1 - c2
+    wt = np.stack([c0, c1, c2, c3], axis=1).astype(F)
+    idx = np.clip(s.astype(np.int64)[:, None] + np.arange(-1, 3)[None, :], 0, n_in - 1).astype(np.int32)
+    return np.ascontiguousarray(idx), np.ascontiguousarray(wt)
+
+
+_CVC_TABLES: Dict[tuple, Tuple[T, T]] = {}
+
+
+def _cvc_tables_dev(n_in: int, n_out: int, device) -> Tuple[T, T]:
+    key = (n_in, n_out, str(device))
+    ent = _CVC_TABLES.get(key)
+    if ent is None:
+        if len(_CVC_TABLES) >= 64:                      # as _aa_tables_dev
+            _CVC_TABLES.clear()
+        idx, wt = cv_cubic_tables(n_in, n_out)
+        ent = _CVC_TABLES[key] = (torch.from_numpy(idx).to(device), torch.from_numpy(wt).to(device))
+    return ent
+
+
+def resize_cv_cubic(x: T, Ho: int, Wo: int, out: Optional[T] = None, tables=None) -> T:
+    """OpenCV's INTER_CUBIC restated, on the device (csrc/resample.hip): x [N,C,Hi,Wi] fp32 -> [N,C,Ho,Wo] = per plane
+    cv2.resize(plane, (Wo, Ho), interpolation=cv2.INTER_CUBIC) as tests/golden/cv_cubic_ref.py restates it, bit for bit -- any ratio,
+    four taps per axis, no antialiasing, replicated border, values not clamped.  Equal sizes give the input's bits.
+    out: a contiguous [N,C,Ho,Wo] fp32 tensor to write (a view at any 4-byte offset).  tables: ((idx_w, wt_w), (idx_h, wt_h)) device
+    tensors in cv_cubic_tables' shapes instead of the cached ones; anything else is refused before the launch.
+    Parity with an OpenCV binary: unpinned (OpenCV absent)."""
+    _chk(x, "resize_cv_cubic.x")
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise _lib.FFError(f"resize_cv_cubic: expected a non-empty contiguous [N,C,H,W] tensor, got {list(x.shape)}")
+    N, C, Hi, Wi = x.shape
+    Ho, Wo = int(Ho), int(Wo)
+    if Ho < 1 or Wo < 1:
+        raise _lib.FFError(f"resize_cv_cubic: the output size must be >= 1 x 1, got {Ho} x {Wo}")
+    if tables is None:
+        tw, th = _cvc_tables_dev(Wi, Wo, x.device), _cvc_tables_dev(Hi, Ho, x.device)
+    else:
+        try:
+            (tw, th) = tables
+            (iw, ww), (ih, wh) = tw, th
+        except (TypeError, ValueError):
+            raise _lib.FFError("resize_cv_cubic: tables must be ((idx_w, wt_w), (idx_h, wt_h))") from None
+        for name, idx, wt, n in (("w", iw, ww, Wo), ("h", ih, wh, Ho)):
+            for t, dt in ((idx, torch.int32), (wt, torch.float32)):
+                if not torch.is_tensor(t) or t.device != x.device or t.dtype != dt or tuple(t.shape) != (n, 4) or not t.is_contiguous():
+                    raise _lib.FFError(f"resize_cv_cubic: the {name} tables must be contiguous int32 / float32 [{n}, 4] tensors on x's device")
+    if out is None:
+        out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "resize_cv_cubic.out")
+        if tuple(out.shape) != (N, C, Ho, Wo) or not out.is_contiguous() or out.device != x.device:
+            raise _lib.FFError(f"resize_cv_cubic: out must be a contiguous [{N},{C},{Ho},{Wo}] tensor on x's device, got {list(out.shape)}")
+    _lib.check(_L().ff_resize_cv_cubic(x.data_ptr(), out.data_ptr(), N * C, Hi, Wi, Ho, Wo, tw[0].data_ptr(), tw[1].data_ptr(),
+                                       th[0].data_ptr(), th[1].data_ptr(), _stream()))
+    _note(0.0, 4.0 * N * C * (Hi * Wi + Ho * Wo))
+    return out
+
+
 for _n in ("conv2d", "cab_fused", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "hab_link", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
            "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
            "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):

@@ -6,12 +6,17 @@ warm-up 5 epochs + cosine restarts, batch 14, accumulation_steps 2, EMA 0.9995, 
                                   [--expert-weights DIR] [--batch 14] [--accum 2] [--repeat 6] [--patch 64] [--validate-every 1]
                                   [--seed 0] [--no-augment] [--dropout 0.1] [--gemm f32] [--expert-gemm bf16x3] [--readers 8]
                                   [--pool-gb 64] [--device cuda:0] [--color-jitter] [--jitter-prob 0.5] [--jitter-range 0.2 0.2 0.2]
+                                  [--val-protocol patch|reference] [--val-max-size 512] [--validate-start 0]
 
 --hr / --lr: folders of images matched by stem, every HR image exactly 4x its LR partner; without --lr the LR images are made on the
 device (antialiased bicubic x1/4 of the HR image cropped to multiples of 4, quantised to uint8).  The training images are decoded once
 into a device-resident pool (isr2_amd.epoch.ImagePool; more than --pool-gb GiB is an error); every epoch cuts fresh random crops with
 paired flips / rotations out of it (epoch.live_plan, one sampler launch per micro-batch) and replays the expert graph on them
-(epoch.LiveEpoch).  The validation set is the centre patch of every --val-hr image, its expert outputs computed once.
+(epoch.LiveEpoch).  The validation set is the centre patch of every --val-hr image, its expert outputs computed once
+(--val-protocol patch, the default: epoch.live_val_samples) or, with --val-protocol reference, what the reference's train.py validates
+on: every whole --val-hr / --val-lr pair, resized with OpenCV's INTER_CUBIC restated on the device when the LR's longer side exceeds
+--val-max-size // 4 (epoch.live_val_images; 0 = no limit; the resize is parity unpinned (OpenCV absent)).  --validate-start N: no
+validation before epoch N, the last epoch excepted.
 Expert weights: --expert-weights DIR (default $FREQFUSION_PRETRAINED, else ./pretrained) with hat/, dat/ and nafnet/ checkpoints as
 the plugin finds them; a missing one is replaced by seeded synthetic weights with a warning (smoke runs).  --weights: a
 reference-keyed fusion (+ collaborative) state dict, bare or under `model_state_dict`; without it the seeded synthetic weights.
@@ -22,7 +27,7 @@ micro-batch between the sampler and the experts, csrc/color_jitter.hip): with pr
 brightness, contrast and saturation factors 1 + uniform(-r, r), r = --jitter-range B C S.  The defaults are the values the reference
 trains with (its class defaults; the YAML's are never read).  Off unless asked for; validation samples are never jittered.  Its
 draws are parity unpinned (RNG stream), its 8-bit HSV step parity unpinned (OpenCV absent).
-Not applied: the reference's OpenCV resize of images smaller than the patch, SyncBatchNorm / several GPUs."""
+Not applied: the reference's OpenCV resize of TRAINING images smaller than the patch (the pool holds uint8), SyncBatchNorm / several GPUs."""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +62,9 @@ def main(argv=None) -> int:
     ap.add_argument("--color-jitter", action="store_true")
     ap.add_argument("--jitter-prob", type=float, default=0.5)
     ap.add_argument("--jitter-range", type=float, nargs=3, default=[0.2, 0.2, 0.2], metavar=("B", "C", "S"))
+    ap.add_argument("--val-protocol", default="patch", choices=("patch", "reference"))
+    ap.add_argument("--val-max-size", type=int, default=512)
+    ap.add_argument("--validate-start", type=int, default=0)
     a = ap.parse_args(argv)
 
     from . import epoch as E
@@ -72,12 +80,16 @@ def main(argv=None) -> int:
         ck = tr.load_checkpoint(os.path.join(a.out, "latest.pth"))
         start = int(ck["epoch"]) + 1
         best = float(ck.get("metrics", {}).get("best_psnr", best))
-    val = E.live_val_samples(model, a.val_hr, a.val_lr, patch=a.patch)
+    if a.val_protocol == "reference":
+        val = E.live_val_images(model, a.val_hr, a.val_lr, max_size=a.val_max_size if a.val_max_size > 0 else None)
+    else:
+        val = E.live_val_samples(model, a.val_hr, a.val_lr, patch=a.patch)
     pool = E.ImagePool(a.hr, a.lr, patch=a.patch, device=a.device, readers=a.readers, max_bytes=int(a.pool_gb * (1 << 30)))
     jitter = dict(prob=a.jitter_prob, brightness=a.jitter_range[0], contrast=a.jitter_range[1], saturation=a.jitter_range[2]) if a.color_jitter else None
     data = E.LiveEpoch(model, pool, a.batch, a.repeat, augment=not a.no_augment, seed=a.seed, color_jitter=jitter)
     try:
-        E.fit(tr, data, val, a.out, a.epochs, start, a.accum, a.validate_every, best, log=lambda line: print(line, flush=True))
+        E.fit(tr, data, val, a.out, a.epochs, start, a.accum, a.validate_every, best, log=lambda line: print(line, flush=True),
+              validate_start=a.validate_start)
     finally:
         data.close()
     return 0

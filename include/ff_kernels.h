@@ -553,6 +553,17 @@ int ff_crop_pairs_u8(const unsigned char* lr_u8, const unsigned char* hr_u8, int
                      float* hr_out, void* stream);
 int ff_resize_aa(const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, const int* span_w, const float* wt_w,
                  const int* span_h, const float* wt_h, void* stream);
+/* OpenCV's INTER_CUBIC restated (cv2.resize in the reference's ValidationDataset, dataset.py:473-506; csrc/resample.hip,
+ * ops.resize_cv_cubic, epoch.live_val_images): planar fp32 [planes][Hi][Wi] -> [planes][Ho][Wo] at any ratio, up or down; four taps per
+ * axis whatever the ratio (no antialiasing), replicated border, no clamping of values.  Per axis a DEVICE table from
+ * ops.cv_cubic_tables: idx [O][4] int32 = taps s - 1 .. s + 2 clamped to [0, n_in - 1], wt [O][4] fp32 = interpolateCubic's weights
+ * (A = -0.75f) of x = f - s, f = float((d + 0.5) * (double(n_in) / n_out) - 0.5), s = floor(f).  Per source row
+ * h = ((v0 a0 + v1 a1) + v2 a2) + v3 a3 with the horizontal weights, then out = ((h0 b0 + h1 b1) + h2 b2) + h3 b3 with the vertical ones,
+ * every product and sum rounded on its own (no fused multiply-add).  The kernel clamps the table indices again, so no table reads outside
+ * the image.  First check, before any launch: null pointers, a size < 1, a size > 2^20, the grid bound.  Added under ABI version 7 (an
+ * additive entry point: no existing prototype changed). */
+int ff_resize_cv_cubic(const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, const int* idx_w, const float* wt_w,
+                       const int* idx_h, const float* wt_h, void* stream);
 
 /* One training micro-batch out of a resident image pool (isr2_amd.epoch.ImagePool / LiveEpoch; csrc/sample_batch.hip): crop, u8 -> fp32
  * and the paired D4 augmentation of B samples, LR and HR, in one launch.  pool: one device byte buffer, every image uint8 HWC packed
