@@ -204,7 +204,7 @@ __device__ __forceinline__ void ff_wave_rows_to_frags(const float* __restrict__ 
 //   win_attn_fused_v2_ln.inc      win_attn_fused_v2_kernel, hab_link_kernel: statistics and step (slower through the statistics helper)
 //   token_projmlp_ln_stats.inc    token_projmlp_kernel, token_projmlp_bf16_kernel, hab_link_kernel: statistics in the ACCUMULATOR
 //                                 layout (a helper spills; the bf16 step after it is token_projmlp_bf16_ln.inc)
-// Callers: token_mlp_kernel (all three helpers), win_attn_fused_kernel (the statistics; its step is frag_ln_opt_step.inc).
+// Callers: token_mlp_kernel (all three helpers), win_attn_fused_kernel (the corrected statistics; its step is frag_ln_opt_step.inc).
 // Where K is a compile-time 16 KS (NAFNet) the k < K masks and the index clamps fold away.
 // Statistics of a row over its K channels: plain sums in st-major order, the lane pair (l, l ^ 32) holds the row's two halves.
 template <int KS>
@@ -226,6 +226,35 @@ __device__ __forceinline__ void ff_frag_ln_stats(const float (&v)[KS][8], int K,
     }
   qv += __shfl_xor(qv, 32);
   rstd = 1.0f / sqrtf(qv / (float)K + eps);
+}
+
+// The same, corrected two-pass (as win_attn_fused_v2_ln.inc): the residuals' own sum repairs the rounding of the first-pass mean.  On a
+// (near-)constant row that rounding is all there is -- 0.1 in every channel came out 8.8e-6 from beta, (x - mean) * rstd with rstd = 316 --
+// and there x - mean is exact, so the corrected mean is the row's value and the output is beta.  win_attn_fused_kernel only, whose
+// normalised rows are held to 2e-6: token_mlp_kernel (held to 6e-5 on its output) goes from 234-238 VGPRs to 36 bytes of scratch with it.
+template <int KS>
+__device__ __forceinline__ void ff_frag_ln_stats_corrected(const float (&v)[KS][8], int K, int hh, float eps, float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int st = 0; st < KS; ++st)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += v[st][j];
+  s += __shfl_xor(s, 32);
+  mean = s / (float)K;
+  float qv = 0.f, sd = 0.f;
+#pragma unroll
+  for (int st = 0; st < KS; ++st)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = (16 * st + 8 * hh + j < K) ? v[st][j] - mean : 0.f;
+      qv += d * d;
+      sd += d;
+    }
+  qv += __shfl_xor(qv, 32);
+  sd += __shfl_xor(sd, 32);
+  const float dm = sd / (float)K;
+  mean += dm;
+  rstd = 1.0f / sqrtf(fmaxf(qv / (float)K - dm * dm, 0.f) + eps);
 }
 
 // One k-step: f[j] = (v[j] - mean) * rstd * gamma[k0 + j] + beta[k0 + j], zero beyond K (k0 = 16 st + 8 hh).  The two float4

@@ -154,7 +154,8 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
     float mean = 0.f, rstd = 1.f;
     if (p.gamma) {
       // ff_frag_ln_stats, inline on purpose: with the helper token_linear_kernel<1, 8, false, false, 1> goes from 165 to 169 VGPRs
-      // and its reported occupancy from 3 to 2 waves per SIMD (reference and __restrict__ forms alike)
+      // and its reported occupancy from 3 to 2 waves per SIMD (reference and __restrict__ forms alike).  With the statistics epilogue
+      // below that form stands at 167 of 168 and <1, 4, true, false, 3> at 128 of 128: the next register costs either a step.
       float s = 0.f;
 #pragma unroll
       for (int st = 0; st < TL_KS; ++st)
@@ -183,7 +184,18 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
   // LayerNorm statistics of a channel range of the (activated) OUTPUT, taken from the accumulators on their way out: the
   // consumer (DAT's SpatialGate: LayerNorm -> depth-wise 3x3, dat_arch.py:117-122) normalises on load, so the separate
   // LayerNorm pass over the 360-channel half (read 94 MB, write 94 MB) disappears
-  float ssum = 0.f, ssq = 0.f;
+  // Two-pass-grade, although the accumulators leave tile by tile and a second pass does not exist (var = ssq / n - mean^2 from running
+  // sums loses rstd digits as (mean / std)^2: 2e-5 relative at 8, 3e-4 at 32).  Every value is first shifted by a pivot, the mean of
+  // the lane's first in-range group: where the row's offset is large against its spread the subtraction is exact, and what is left has
+  // a mean of about one std at most (a single value as the pivot can be an outlier: it cost the MEAN a digit on GELU rows).  A lane's
+  // four activated values of an epilogue group are in registers together, so the group's own mean and centred sum of squares are
+  // two-pass; groups merge with the pairwise update (Chan et al.)
+  //   n = na + nb, d = mb - ma, m = ma + d nb / n, M2 = M2a + M2b + d^2 na nb / n,
+  // which also keeps an outlier pivot harmless.  Two forms that do not do: the pairwise merge without a pivot is first-order in the
+  // rounding of every group mean (6e-7 on rstd at mean / std 64, over the bar); a single value as the pivot can be an outlier and
+  // costs the mean a digit on GELU rows (2.9e-7 at a bias offset of 0, over its floor of 2^-22).  The running count is a register too: as two scalars (it depends on hh alone) it
+  // pushed the non-VEC4 forms past their SGPR budget, and <1, 8, false, false, 1> from 165 to 169 VGPRs.
+  float smean = 0.f, sm2 = 0.f, scnt = 0.f, spiv = 0.f;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // tile 0 (this wave's DMA pieces) landed
   for (int nt = 0; nt < p.NT; ++nt) {
     const int buf = nt & 1;
@@ -254,11 +266,28 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
         for (int e = 0; e < 4; ++e) v4[e] = ff_act_c<ACT, true>(acc[4 * g + e]);
       }
       *reinterpret_cast<f32x4*>(tr + l31 * TL_TR + 8 * g + 4 * hh) = v4;
-      if (p.stats) {
-        const int c0 = nt * 32 + 8 * g + 4 * hh;
+      if (!TL_OUT16 && p.stats && nt * 32 + 8 * g + 8 > p.st_lo && nt * 32 + 8 * g < p.st_hi) {      // wave-uniform: the group meets the range
+        const int cb = nt * 32 + 8 * g + 4 * hh;
+        const float cn = (float)max(0, min(cb + 4, p.st_hi) - max(cb, p.st_lo));
+        float w[4], ts = 0.f, tq2 = 0.f;
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (c0 + e >= p.st_lo && c0 + e < p.st_hi) { ssum += v4[e]; ssq += v4[e] * v4[e]; }
+        for (int e = 0; e < 4; ++e) {
+          w[e] = (cb + e >= p.st_lo && cb + e < p.st_hi) ? v4[e] - spiv : 0.f;
+          ts += w[e];
+        }
+        float tm = ts * __builtin_amdgcn_rcpf(fmaxf(cn, 1.f));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = (cb + e >= p.st_lo && cb + e < p.st_hi) ? w[e] - tm : 0.f;
+          tq2 += d * d;
+        }
+        const bool first = scnt == 0.f;            // the lane's first in-range group: spiv was 0, so tm is the group's plain mean --
+        spiv = first ? tm : spiv;                  // it becomes the pivot, and the group's shifted mean is 0 (no branch: a divergent
+        tm = first ? 0.f : tm;                     // one cost <1, 4, true, false, 3> and <1, 8, false, false, 1> an occupancy step)
+        const float dl = tm - smean, wn = cn * __builtin_amdgcn_rcpf(fmaxf(scnt + cn, 1.f));   // cn = 0: nothing moves
+        smean += dl * wn;
+        sm2 += tq2 + dl * dl * scnt * wn;
+        scnt += cn;
       }
     }
     // One wait per tile, placed BEFORE this tile's stores: it retires the DMA of tile nt+1 (issued a whole tile ago),
@@ -320,12 +349,14 @@ __global__ __launch_bounds__(512) void TL_KERNEL(TokenLinParams p) {
     }
 #endif
   }
-  if (p.stats) {
-    ssum += __shfl_xor(ssum, 32);
-    ssq += __shfl_xor(ssq, 32);
-    const float n = (float)(p.st_hi - p.st_lo);
-    const float mean = ssum / n;
-    const float var = fmaxf(ssq / n - mean * mean, 0.f);
+  if (!TL_OUT16 && p.stats) {                                              // (the rows16 entry point takes no statistics output)
+    // the lane pair (l, l ^ 32) holds the two halves of the token's range: one more pairwise merge, still in the shifted domain (the
+    // pivots' difference is exact where it matters), written by the hh = 0 lane
+    const float na = scnt, nb = __shfl_xor(scnt, 32);
+    const float mo = __shfl_xor(smean, 32), m2o = __shfl_xor(sm2, 32), po = __shfl_xor(spiv, 32);
+    const float n = fmaxf(na + nb, 1.f), dl = (nb > 0.f && na > 0.f) ? (po - spiv) + (mo - smean) : 0.f;
+    const float mean = (na > 0.f ? spiv + (smean + dl * (nb / n)) : po + mo);
+    const float var = (sm2 + m2o + dl * dl * (na * nb / n)) / n;
     if (hh == 0 && tvalid) *reinterpret_cast<float2*>(p.stats + 2 * tok) = make_float2(mean, 1.0f / sqrtf(var + p.st_eps));
   }
 }

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(512) void win_attn_fused_kernel(WinFusedParams p) {
       }
     }
     float mean = 0.f, rstd = 1.f;
-    if (p.gamma) ff_frag_ln_stats<WF_KS>(v, p.K, hh, p.eps, mean, rstd);
+    if (p.gamma) ff_frag_ln_stats_corrected<WF_KS>(v, p.K, hh, p.eps, mean, rstd);
 #define LN_OPT_KS WF_KS
 #define LN_OPT_TOK (long long)mytok
 #include "frag_ln_opt_step.inc"

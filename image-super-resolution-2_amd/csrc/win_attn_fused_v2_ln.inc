@@ -13,16 +13,22 @@
         for (int j = 0; j < 8; ++j) s += v[st][j];
       s += __shfl_xor(s, 32);
       mean = s / (float)p.K;
-      float qv = 0.f;
+      // corrected two-pass: the residuals' own sum repairs the rounding of the first-pass mean.  On a (near-)constant row that rounding
+      // is all there is -- 0.1 in every channel came out 8.8e-6 from beta, (x - mean) * rstd with rstd = 316 -- and x - mean is exact.
+      float qv = 0.f, sd = 0.f;
 #pragma unroll
       for (int st = 0; st < WF_KS; ++st)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float dd = (16 * st + 8 * hh + j < p.K) ? v[st][j] - mean : 0.f;
           qv += dd * dd;
+          sd += dd;
         }
       qv += __shfl_xor(qv, 32);
-      rstd = 1.0f / sqrtf(qv / (float)p.K + p.eps);
+      sd += __shfl_xor(sd, 32);
+      const float dm = sd / (float)p.K;
+      mean += dm;
+      rstd = 1.0f / sqrtf(fmaxf(qv / (float)p.K - dm * dm, 0.f) + p.eps);
     }
 #pragma unroll
     for (int st = 0; st < WF_KS; ++st) {

@@ -2,11 +2,16 @@
 Tolerances: fp32 MFMA is an exact-fp32 fma chain, so contractions agree with torch to ~1e-5 relative of
 the accumulated magnitude; pointwise ops to a few ulp."""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import cond_inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -861,7 +866,10 @@ def test_sgfn_layernorm_on_load(dev, H, W):
     mean_ref = x2.mean(-1).reshape(M)
     rstd_ref = 1.0 / torch.sqrt(x2.var(-1, unbiased=False).reshape(M) + 1e-5)
     close(stats[:, 0], mean_ref, 3e-5, "token mean")
-    assert ((stats[:, 1] - rstd_ref).abs() / rstd_ref).max().item() < 2e-4
+    # rstd by the rule of tests/test_conditioning_gpu.py: fp64 statistics of the kernel's own output, 4 x the two-pass fp32 stand-in's error
+    _, rr, _, rstd_bar = cond_inputs.stats_bars(y[..., Hd // 2:].reshape(M, Hd // 2).cpu())
+    assert ((stats[:, 1].cpu().double() - rr).abs() / rr).max().item() <= rstd_bar
+    assert ((stats[:, 1] - rstd_ref).abs() / rstd_ref).max().item() < 2e-4       # and, as before, against the independent torch chain
     z = ops.dwconv3x3_ln(y[..., Hd // 2:], pack_dw(wd), bd, stats, g2, bb2, mul_in=y[..., :Hd // 2])
     close(z, ref, 1e-4, "SpatialGate with LayerNorm on load")
 
