@@ -3,11 +3,15 @@
 PyTorch is plumbing here: it owns device memory and the stream.  Every function below only validates
 shapes/strides and forwards raw pointers to libff_hip.so; there is no PyTorch compute fallback -- a
 missing library or a CPU tensor raises.
+Every pointer is obtained through the operand helpers (_rows, _nhwc, _dense, _image / _images, _out), and every refusal of a call precedes its
+first library call.
 Tensors are fp32, channel-last.  "rows view": any tensor whose last dim is contiguous and whose
 leading dims collapse to a single row stride (e.g. a channel slice t[..., a:b] of an NHWC buffer).
 """
 from __future__ import annotations
 
+import functools
+import math
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -33,8 +37,7 @@ def _numel(*ts) -> float:
 
 
 def _instrument(fn):
-    import functools
-
+    """Decorator of the wrappers bench.py's per-kernel-class breakdown keys on (by __name__)."""
     @functools.wraps(fn)
     def wrapped(*a, **k):
         if _PROF is None:
@@ -269,6 +272,117 @@ class PreparedWeights:
 PREPARED = PreparedWeights()
 
 
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+# ---- the operand vocabulary ----------------------------------------------------------------------------------------------------------
+# Every wrapper below takes every pointer it hands to the library from one of these helpers, before its first library call.  Each takes
+# the operand, its name "op.operand" and what is expected of it, and raises FFError beginning with that name or returns what the C call
+# needs.  A `shape` may hold None for an extent that is free.
+_F32 = (torch.float32,)
+_BF16 = (torch.bfloat16,)
+_F32_BF16 = (torch.float32, torch.bfloat16)
+_U8 = (torch.uint8,)
+_I32 = (torch.int32,)
+_I64 = (torch.int64,)
+
+
+def _dev(t, name: str, dtype) -> None:
+    """A tensor on the device of one of the dtypes (a tuple; None = any)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or (dtype is not None and t.dtype not in dtype):
+        kinds = "" if dtype is None else " or ".join(str(d).replace("torch.", "") for d in dtype) + " "
+        raise _lib.FFError(f"{name}: expected a CUDA(HIP) {kinds}tensor")
+
+
+def _rows(t, name: str, rows: Optional[int] = None, C: Optional[int] = None, dtype=_F32, optional: bool = False):
+    """Rows operand -> (ptr, ld, rows, C): a tensor whose last dim is contiguous and whose leading dims collapse to rows of stride ld,
+    of `rows` rows and `C` channels where given.  optional: None -> (None, 0)."""
+    if t is None and optional:
+        return None, 0
+    _dev(t, name, dtype)
+    shp = t.shape
+    c = shp[-1]
+    ld = c if len(shp) == 1 else t.stride(-2)               # (a vector is one row)
+    if c and t.is_contiguous():                             # the common case, without the walk over the strides
+        r = t.numel() // c
+    else:
+        if t.stride(-1) != 1 and c != 1:
+            raise _lib.FFError(f"{name}: last dim must be contiguous")
+        r, expect = 1, ld
+        for d in range(len(shp) - 2, -1, -1):
+            if shp[d] != 1 and t.stride(d) != expect:
+                raise _lib.FFError(f"{name}: leading dims do not collapse to a constant row stride {tuple(shp)} {t.stride()}")
+            expect = expect * shp[d]
+            r *= shp[d]
+    if (rows is not None and r != rows) or (C is not None and c != C):
+        raise _lib.FFError(f"{name}: shape mismatch: expected (rows, channels) = ({rows}, {C}) (None = any), got {tuple(shp)}")
+    return t.data_ptr(), ld, r, c
+
+
+def rows_view(t: T, name: str = "tensor") -> Tuple[int, int, int, int]:
+    """-> (ptr, ld, rows, C) for an fp32 tensor whose leading dims collapse to rows of stride ld."""
+    return _rows(t, name)
+
+
+def _nhwc(t, name: str, shape=None, dtype=_F32, optional: bool = False):
+    """NHWC operand -> (ptr, ld, B, H, W, C): a 4-D rows view, of exactly `shape` where given.  optional: None -> (None, 0)."""
+    if t is None and optional:
+        return None, 0
+    p, ld, _, c = _rows(t, name, dtype=dtype)
+    if t.dim() != 4:
+        raise _lib.FFError(f"{name}: expected [B,H,W,C]")
+    if shape is not None and any(e is not None and e != s for s, e in zip(t.shape, shape)):
+        raise _lib.FFError(f"{name}: shape {tuple(t.shape)} != {tuple('*' if e is None else e for e in shape)}")
+    return p, ld, t.shape[0], t.shape[1], t.shape[2], c
+
+
+def _dense(t, name: str, dtype=_F32, n: Optional[int] = None, shape=None, optional: bool = False):
+    """Vector / table / dense-tensor operand -> ptr: on the device, of `dtype`, contiguous, with exactly n elements (any shape, e.g.
+    [1,C,1,1]) or of exactly `shape`.  optional: None -> None."""
+    if t is None and optional:
+        return None
+    _dev(t, name, dtype)
+    if (not t.is_contiguous() or (n is not None and t.numel() != n)
+            or (shape is not None and (t.dim() != len(shape) or any(e is not None and e != s for s, e in zip(t.shape, shape))))):
+        want = f"{n} elements" if shape is None else f"shape {list('*' if e is None else e for e in shape)}"
+        raise _lib.FFError(f"{name}: must be a contiguous tensor" + ("" if n is None and shape is None else " of " + want)
+                           + f", got shape {list(t.shape)} with strides {list(t.stride())}")
+    return t.data_ptr()
+
+
+def _image(t, name: str, optional: bool = False):
+    """Prepared image -> ptr: what prep.py builds (pk[...] entries, PREPARED values) or a wrapper's own workspace: on the device and
+    contiguous, of any dtype."""
+    return _dense(t, name, None, optional=optional)
+
+
+def _images(pk: dict, name: str, *keys):
+    """The pointers of several entries of one prep.py dict."""
+    return tuple(_image(pk[k], f"{name}.{k}") for k in keys)
+
+
+def _out(out, name: str, shape, device, bf16: bool = False, kind: str = "rows"):
+    """Output -> (out, ptr, ld): a fresh buffer of `shape` when out is None (kind "rows" / "nhwc": empty_rows or empty_rows_bf16; "dense":
+    contiguous) -- what this module allocated itself is not validated again -- else the caller's `out` validated: fp32 (bf16: bfloat16)
+    rows of prod(shape[:-1]) rows and shape[-1] channels ("rows"), an NHWC rows view of exactly `shape` ("nhwc"), or a contiguous tensor
+    of exactly `shape` ("dense", ld = shape[-1])."""
+    dtype = _BF16 if bf16 else _F32
+    if out is None:
+        if kind == "dense":
+            out = torch.empty(tuple(shape), device=device, dtype=dtype[0])
+        else:
+            out = empty_rows_bf16(shape, device) if bf16 else empty_rows(shape, device)
+        return out, out.data_ptr(), (out.stride(-2) if out.dim() > 1 else shape[-1])
+    if kind == "dense":
+        return out, _dense(out, name, dtype, shape=shape), shape[-1]
+    if kind == "nhwc":
+        p, ld, *_ = _nhwc(out, name, shape, dtype)
+    else:
+        p, ld, *_ = _rows(out, name, math.prod(shape[:-1]), shape[-1], dtype)
+    return out, p, ld
+
+
 def _split_weight(w: T, dynamic: bool, cin: int):
     """bf16 hi/lo planes [N][Kp] of a packed fp32 weight [N][taps*cin]; cached on the tensor object unless
     `dynamic`.  Per-tap padded (TAP) K layout when cin >= 32 and cin % 4 == 0, flat otherwise."""
@@ -276,6 +390,7 @@ def _split_weight(w: T, dynamic: bool, cin: int):
     cached = None if dynamic else PREPARED.peek(w, "split")
     if cached is not None and cached[4] >= nterms:
         return cached
+    wp = _dense(w, "split_weight.w", shape=(None, None))
     N, K = w.shape
     if cin >= 32 and cin % 4 == 0:
         Cp = (cin + 31) // 32 * 32
@@ -284,54 +399,12 @@ def _split_weight(w: T, dynamic: bool, cin: int):
         Cp, Kp = 0, (K + 31) // 32 * 32
     hi = torch.empty((N, Kp), device=w.device, dtype=torch.bfloat16)
     lo = torch.empty((N, Kp), device=w.device, dtype=torch.bfloat16) if nterms == 3 else None
-    _lib.check(_L().ff_split_bf16(w.data_ptr(), N, K, Kp, cin, Cp, hi.data_ptr(), lo.data_ptr() if lo is not None else None,
+    _lib.check(_L().ff_split_bf16(wp, N, K, Kp, cin, Cp, _image(hi, "split_weight.hi"), _image(lo, "split_weight.lo", optional=True),
                                   _stream()))
     ent = (hi, lo, Kp, Cp, nterms)
     if not dynamic:
         PREPARED.put(w, "split", ent)
     return ent
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _chk(t: T, name: str):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or (t.dtype != torch.float32 and not (t.dtype == torch.bfloat16 and name.endswith("|bf16ok"))):
-        raise _lib.FFError(f"{name.split('|')[0]}: expected a CUDA(HIP) float32 tensor")
-
-
-def _ptr(t: Optional[T]) -> Optional[int]:
-    if t is None:
-        return None
-    _chk(t, "arg")
-    return t.data_ptr()
-
-
-def rows_view(t: T, name: str = "tensor") -> Tuple[int, int, int, int]:
-    """-> (ptr, ld, rows, C) for a tensor whose leading dims collapse to rows of stride ld."""
-    _chk(t, name)
-    if t.dim() == 1:
-        return t.data_ptr(), t.shape[0], 1, t.shape[0]
-    if t.stride(-1) != 1 and t.shape[-1] != 1:
-        raise _lib.FFError(f"{name}: last dim must be contiguous")
-    ld = t.stride(-2)
-    rows = 1
-    expect = ld
-    for d in range(t.dim() - 2, -1, -1):
-        if t.shape[d] != 1 and t.stride(d) != expect:
-            raise _lib.FFError(f"{name}: leading dims do not collapse to a constant row stride {tuple(t.shape)} {t.stride()}")
-        expect = expect * t.shape[d]
-        rows *= t.shape[d]
-    return t.data_ptr(), ld, rows, t.shape[-1]
-
-
-def _nhwc(t: T, name: str):
-    """-> (ptr, ld, B, H, W, C) for a 4-D NHWC rows view."""
-    if t.dim() != 4:
-        raise _lib.FFError(f"{name}: expected [B,H,W,C]")
-    p, ld, rows, c = rows_view(t, name)
-    return p, ld, t.shape[0], t.shape[1], t.shape[2], c
 
 
 class PoolPartials:
@@ -354,6 +427,7 @@ class PoolPartials:
         return pooled
 
 
+@_instrument
 def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1), pad=(0, 0), act=None,
            res: Optional[T] = None, mul: Optional[T] = None, alpha: float = 1.0, shuffle: int = 0,
            out: Optional[T] = None, tile_hint: int = 0, dynamic_w: bool = False, want_pool: bool = False, out_bf16: bool = False,
@@ -365,22 +439,18 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
     per_image (implied by want_pool; matters for B > 1 only): the batch is B independent images and every image must come out with
     the bits of its own B == 1 call -- the LDS-resident kernel goes through ff_conv3x3_halo_images (kernel form and pool partial rows
     of one image's launch), the implicit GEMM gets the tile configuration of one image's row count as its hint."""
-    per_image = bool(per_image or want_pool) and x.dim() == 4 and x.shape[0] > 1
+    xp, ldi, B, H, W, Cin = _nhwc(x, "conv2d.x", dtype=_F32_BF16)
+    per_image = bool(per_image or want_pool) and B > 1
     in_bf16 = x.dtype == torch.bfloat16
-    xp, ldi, B, H, W, Cin = _nhwc(x, "conv2d.x|bf16ok" if in_bf16 else "conv2d.x")
     KH, KW = ksize
+    wp = _dense(w, "conv2d.w", shape=(None, KH * KW * Cin))
     Cout = w.shape[0]
-    if w.dim() != 2 or w.shape[1] != KH * KW * Cin or not w.is_contiguous():
-        raise _lib.FFError(f"conv2d: packed weight must be [Cout, {KH * KW * Cin}], got {tuple(w.shape)}")
     Ho = (H + 2 * pad[0] - KH) // stride[0] + 1
     Wo = (W + 2 * pad[1] - KW) // stride[1] + 1
     oshape = (B, Ho * 2, Wo * 2, Cout // 4) if shuffle == 2 else (B, Ho, Wo, Cout)
-    if out is None:
-        out = empty_rows_bf16(oshape, x.device) if out_bf16 else empty_rows(oshape, x.device)
-    elif tuple(out.shape) != oshape:
-        raise _lib.FFError(f"conv2d: out shape {tuple(out.shape)} != {oshape}")
-    out_bf16 = out.dtype == torch.bfloat16
-    op, ldo, *_ = _nhwc(out, "conv2d.out|bf16ok" if out_bf16 else "conv2d.out")
+    if out is not None:
+        out_bf16 = out.dtype == torch.bfloat16
+    out, op, ldo = _out(out, "conv2d.out", oshape, x.device, bf16=out_bf16, kind="nhwc")
     halo_ok = (_HALO and _GEMM_MODE in ("bf16x3", "bf16") and (KH, KW) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1)
                and not dynamic_w and Cin >= 32 and Cin % 4 == 0 and ldi % 4 == 0 and xp % 16 == 0
                and (Cout <= 64 or Cin >= 128 or 128 < Cout <= 192)   # measured (profiles/r01_conv3x3_halo_vs_igemm.txt); 64 -> 256 ties
@@ -389,11 +459,9 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
     # images keeps its batches below it -- HatHIP.forward sizes its chunks so -- and every other term is one image's.)
     if (in_bf16 or out_bf16) and not (halo_ok and _GEMM_MODE == "bf16" and shuffle == 0 and res is None):
         raise _lib.FFError("conv2d: bf16 input / output rows exist for the LDS-resident 3x3 kernel in plain-bf16 mode only")
-    rp, ldr = None, 0
-    if res is not None:
-        if tuple(res.shape) != oshape:
-            raise _lib.FFError(f"conv2d: res shape {tuple(res.shape)} != {oshape}")
-        rp, ldr, *_ = _nhwc(res, "conv2d.res")
+    rp, ldr, *_ = _nhwc(res, "conv2d.res", oshape, optional=True)
+    bp = _dense(bias, "conv2d.bias", n=Cout, optional=True)
+    mp = _dense(mul, "conv2d.mul", n=Cout, optional=True)
     if (_GEMM_MODE != "f32" and (KH, KW) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1) and Cout <= 16
             and Cin * (1 if Cout == 1 else (4 if Cout <= 4 else 16)) <= 128 and shuffle == 0 and mul is None and not dynamic_w and H * W >= 4096 and xp != op):
         # small-channel tail convolutions: exact fp32 on the VALU from an LDS halo tile (csrc/conv3x3_small.hip).  Measured on
@@ -401,12 +469,11 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
         # 64->3 202 -> 370 and 32->16 187 -> 199 (VALU-bound: Cin * CT FMAs per pixel and tap), hence the Cin * CT <= 128 rule
         from . import prep as _prep
         ws = PREPARED.get(w, "small", lambda: _prep.pack_conv3x3_small(w, Cin))
-        _lib.check(_L().ff_conv3x3_small(xp, ldi, ws.data_ptr(), ws.shape[2], _ptr(bias), rp, ldr, op, ldo, B, H, W, Cin, Cout, ACT[act],
+        _lib.check(_L().ff_conv3x3_small(xp, ldi, _image(ws, "conv2d.w[small]"), ws.shape[2], bp, rp, ldr, op, ldo, B, H, W, Cin, Cout, ACT[act],
                                          float(alpha), _stream()))
     elif _GEMM_MODE == "f32":
-        _lib.check(_L().ff_conv2d(xp, w.data_ptr(), _ptr(bias), _ptr(mul), rp, op, B, H, W, Cin, ldi, Ho, Wo, Cout, ldo, ldr,
-                                  KH, KW, stride[0], stride[1], pad[0], pad[1], ACT[act], float(alpha), shuffle, tile_hint,
-                                  _stream()))
+        _lib.check(_L().ff_conv2d(xp, wp, bp, mp, rp, op, B, H, W, Cin, ldi, Ho, Wo, Cout, ldo, ldr, KH, KW, stride[0], stride[1],
+                                  pad[0], pad[1], ACT[act], float(alpha), shuffle, tile_hint, _stream()))
     elif halo_ok:
         from . import prep as _prep
 
@@ -416,34 +483,35 @@ def conv2d(x: T, w: T, bias: Optional[T] = None, *, ksize=(1, 1), stride=(1, 1),
             bn = _prep.halo_bn(Cout)
             return (_prep.pack_conv3x3_halo(w, Cin, bn, nt_), bn)
         img = PREPARED.get(w, "halo" if nt_ == 3 else "halo1", _mk_halo)
+        imgp = _image(img[0], "conv2d.w[halo]")
         part = None
         halo_fn, rows_fn = ((_L().ff_conv3x3_halo_images, _L().ff_conv3x3_halo_images_pool_rows) if per_image else
                             (_L().ff_conv3x3_halo, _L().ff_conv3x3_halo_pool_rows))
         if want_pool and (B == 1 or per_image) and shuffle == 0 and Cout <= img[1]:
             prow = int(rows_fn(B, H, W, Cout, img[1], nt_))
             part = torch.empty((prow, img[1]), device=x.device, dtype=torch.float32)
-        _lib.check(halo_fn(xp, ldi, img[0].data_ptr(), img[1], _ptr(bias), _ptr(mul), rp, ldr, op, ldo, B, H, W,
-                           Cin, Cout, ACT[act], float(alpha), shuffle, _ptr(part), _nterms(),
-                           (1 if in_bf16 else 0) | (2 if out_bf16 else 0), _stream()))
+        _lib.check(halo_fn(xp, ldi, imgp, img[1], bp, mp, rp, ldr, op, ldo, B, H, W, Cin, Cout, ACT[act], float(alpha), shuffle,
+                           _dense(part, "conv2d.part", optional=True), nt_, (1 if in_bf16 else 0) | (2 if out_bf16 else 0), _stream()))
         if part is not None:
             pp = PoolPartials(part, Cout, 1.0 / float(H * W), images=B)
             _note(2.0 * B * Ho * Wo * Cout * KH * KW * Cin, 4.0 * (_numel(x, w, out, res)))
             return out, (pp if want_pool == "partials" else pp.mean())
     else:
         aligned = (ldi % 4 == 0) and (xp % 16 == 0)
-        hi, lo, Kp, Cp, _ = _split_weight(w, dynamic_w, Cin if aligned else 0)
+        ent = _split_weight(w, dynamic_w, Cin if aligned else 0)
+        hip, lop = _image(ent[0], "conv2d.w[hi]"), _image(ent[1], "conv2d.w[lo]", optional=True)
         if per_image and tile_hint <= 0:                    # the tile configuration one image's launch picks for itself
             tile_hint = int(_L().ff_conv2d_bf16s_tile(Ho * Wo, Cout, KH * KW * Cin, 1 if aligned and Cin % 4 == 0 else 0))
-        _lib.check(_L().ff_conv2d_bf16s(xp, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, _ptr(bias), _ptr(mul),
-                                        rp, op, B, H, W, Cin, ldi, Ho, Wo, Cout, ldo, ldr, KH, KW, stride[0], stride[1],
-                                        pad[0], pad[1], ACT[act], float(alpha), shuffle, GEMM_MODES[_GEMM_MODE], tile_hint,
-                                        None, _stream()))
+        _lib.check(_L().ff_conv2d_bf16s(xp, hip, lop, ent[2], ent[3], bp, mp, rp, op, B, H, W, Cin, ldi, Ho, Wo, Cout, ldo, ldr, KH, KW,
+                                        stride[0], stride[1], pad[0], pad[1], ACT[act], float(alpha), shuffle, GEMM_MODES[_GEMM_MODE],
+                                        tile_hint, None, _stream()))
     _note(2.0 * B * Ho * Wo * Cout * KH * KW * Cin, 4.0 * (_numel(x, w, out, res)))
     if want_pool:
         return out, pool_mean(out)
     return out
 
 
+@_instrument
 def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] = None, mul: Optional[T] = None,
            alpha: float = 1.0, out: Optional[T] = None, dynamic_w: bool = False, kmul: Optional[T] = None,
            gate_pairs: bool = False, out_bf16: bool = False, tile_hint: int = 0, rows_gemm: bool = False,
@@ -473,94 +541,84 @@ def linear(x: T, w: T, bias: Optional[T] = None, *, act=None, res: Optional[T] =
                                  gate_pairs=gate_pairs, out_bf16=out_bf16, tile_hint=tile_hint)
     if out_bf16 or tile_hint:
         raise _lib.FFError("linear: out_bf16 / tile_hint belong to the bf16-rows route (bf16 x, or rows_gemm)")
-    xp, ldi, rows, K = rows_view(x, "linear.x")
+    xp, ldi, rows, K = _rows(x, "linear.x")
+    wp = _dense(w, "linear.w", shape=(None, K))
     N = w.shape[0]
-    if w.dim() != 2 or w.shape[1] != K or not w.is_contiguous():
-        raise _lib.FFError(f"linear: weight must be [N, {K}], got {tuple(w.shape)}")
     if (kmul is not None or gate_pairs) and _GEMM_MODE == "f32":
         raise _lib.FFError("linear: kmul / gate_pairs exist in the split-bf16 kernels only")
     No = N // 2 if gate_pairs else N
-    oshape = tuple(x.shape[:-1]) + (No,)
-    if out is None:
-        out = empty_rows(oshape, x.device)
-    op, ldo, orows, oc = rows_view(out, "linear.out")
-    if orows != rows or oc != No:
-        raise _lib.FFError("linear: out shape mismatch")
-    rp, ldr = None, 0
-    if res is not None:
-        rp, ldr, rrows, rc = rows_view(res, "linear.res")
-        if rrows != rows or rc != N:
-            raise _lib.FFError("linear: res shape mismatch")
+    out, op, ldo = _out(out, "linear.out", tuple(x.shape[:-1]) + (No,), x.device)
+    rp, ldr, *_ = _rows(res, "linear.res", rows, N, optional=True)
     if rows_per_image and rows % rows_per_image:
         raise _lib.FFError(f"linear: {rows} rows are not whole images of rows_per_image = {rows_per_image} rows")
+    bp = _dense(bias, "linear.bias", n=N, optional=True)
+    mp = _dense(mul, "linear.mul", n=N, optional=True)
+    images, kp = _kmul_images(kmul, K, rows)                 # (refusals first: nothing is launched, no weight is split, before them)
     if _GEMM_MODE == "f32":
-        _lib.check(_L().ff_conv2d(xp, w.data_ptr(), _ptr(bias), _ptr(mul), rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr,
-                                  1, 1, 1, 1, 0, 0, ACT[act], float(alpha), 0, 0, _stream()))
+        _lib.check(_L().ff_conv2d(xp, wp, bp, mp, rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
+                                  float(alpha), 0, 0, _stream()))
     else:
         aligned = (ldi % 4 == 0) and (xp % 16 == 0)
-        images = _kmul_images(kmul, K, rows)                 # (refusals first: nothing is launched, no weight is split, before them)
         if images > 1 and (act is not None or alpha != 1.0 or gate_pairs or not aligned or K % 4 or N % 4):
             raise _lib.FFError("linear: kmul [B, K] comes with the (bias, * mul, + res) epilogue on 16-byte aligned rows only")
-        hi, lo, Kp, Cp, _ = _split_weight(w, dynamic_w, K if aligned else 0)
+        ent = _split_weight(w, dynamic_w, K if aligned else 0)
+        hip, lop = _image(ent[0], "linear.w[hi]"), _image(ent[1], "linear.w[lo]", optional=True)
         if images > 1:
-            _lib.check(_L().ff_conv2d_bf16s_kmul_images(xp, ldi, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp,
-                                                        kmul.data_ptr(), images, rows // images, _ptr(bias), _ptr(mul), rp, ldr, op, ldo,
-                                                        rows, K, N, GEMM_MODES[_GEMM_MODE], 0, _stream()))
+            _lib.check(_L().ff_conv2d_bf16s_kmul_images(xp, ldi, hip, lop, ent[2], ent[3], kp, images, rows // images, bp, mp, rp, ldr,
+                                                        op, ldo, rows, K, N, GEMM_MODES[_GEMM_MODE], 0, _stream()))
         else:
             hint = 0                                         # several images: the tile configuration one image's launch picks for itself
             if rows_per_image and rows_per_image != rows:
                 hint = int(_L().ff_conv2d_bf16s_tile(rows_per_image, N, K, 1 if aligned and K % 4 == 0 else 0))
-            _lib.check(_L().ff_conv2d_bf16s(xp, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, _ptr(bias), _ptr(mul),
-                                            rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1, 1, 1, 0, 0, ACT[act],
-                                            float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], hint, _ptr(kmul), _stream()))
+            _lib.check(_L().ff_conv2d_bf16s(xp, hip, lop, ent[2], ent[3], bp, mp, rp, op, 1, 1, rows, K, ldi, 1, rows, N, ldo, ldr, 1, 1,
+                                            1, 1, 0, 0, ACT[act], float(alpha), 1 if gate_pairs else 0, GEMM_MODES[_GEMM_MODE], hint, kp, _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K + N * K + rows * No * (2 if res is not None else 1)))
     return out
 
 
 def _linear_wimages(x: T, w: T, bias, *, act, res, mul, alpha, out, dynamic_w, kmul, gate_pairs, out_bf16, tile_hint, rows_gemm) -> T:
     """linear with one weight matrix per image, w [B, N, K].  Every refusal comes before the weight split and the launch."""
-    _chk(w, "linear.w")
+    _dev(w, "linear.w", _F32)
     B, N, K = w.shape
     if _GEMM_MODE == "f32" or not dynamic_w or not w.is_contiguous():
         raise _lib.FFError("linear: per-image weights [B, N, K] are contiguous dynamic weights (dynamic_w=True) of the split-bf16 modes")
     if (x.dtype != torch.float32 or rows_gemm or kmul is not None or gate_pairs or out_bf16 or tile_hint or act is not None
             or alpha != 1.0):
         raise _lib.FFError("linear: per-image weights come with fp32 rows and the (bias, * mul, + res) epilogue only")
-    xp, ldi, rows, xk = rows_view(x, "linear.x")
+    xp, ldi, rows, xk = _rows(x, "linear.x")
     if xk != K or rows % B or (rows // B) % 256:
         raise _lib.FFError(f"linear: per-image weights {tuple(w.shape)} need [rows, {K}] input with B = {B} equal groups of a multiple of "
                            f"256 rows, got {rows} rows of {xk}")
     if ldi % 4 or xp % 16 or K % 4 or N % 4:
         raise _lib.FFError("linear: per-image weights need 16-byte aligned rows, K % 4 == 0 and N % 4 == 0")
-    oshape = tuple(x.shape[:-1]) + (N,)
-    if out is None:
-        out = empty_rows(oshape, x.device)
-    op, ldo, orows, oc = rows_view(out, "linear.out")
-    if orows != rows or oc != N or ldo % 4 or op % 16:
+    out, op, ldo = _out(out, "linear.out", tuple(x.shape[:-1]) + (N,), x.device)
+    if ldo % 4 or op % 16:
         raise _lib.FFError("linear: out shape mismatch (per-image weights: 16-byte aligned rows)")
-    rp, ldr = None, 0
-    if res is not None:
-        rp, ldr, rrows, rc = rows_view(res, "linear.res")
-        if rrows != rows or rc != N or ldr % 4 or rp % 16:
-            raise _lib.FFError("linear: res shape mismatch (per-image weights: 16-byte aligned rows)")
-    hi, lo, Kp, Cp, _ = _split_weight(w.reshape(B * N, K), True, K)        # rows are split independently: image b's planes at [b * N, (b + 1) * N)
-    _lib.check(_L().ff_conv2d_bf16s_wimages(xp, ldi, hi.data_ptr(), lo.data_ptr() if lo is not None else None, Kp, Cp, B, rows // B,
-                                            _ptr(bias), _ptr(mul), rp, ldr, op, ldo, rows, K, N, GEMM_MODES[_GEMM_MODE], 0, _stream()))
+    rp, ldr, *_ = _rows(res, "linear.res", rows, N, optional=True)
+    if res is not None and (ldr % 4 or rp % 16):
+        raise _lib.FFError("linear: res shape mismatch (per-image weights: 16-byte aligned rows)")
+    bp = _dense(bias, "linear.bias", n=N, optional=True)
+    mp = _dense(mul, "linear.mul", n=N, optional=True)
+    ent = _split_weight(w.reshape(B * N, K), True, K)        # rows are split independently: image b's planes at [b * N, (b + 1) * N)
+    hip, lop = _image(ent[0], "linear.w[hi]"), _image(ent[1], "linear.w[lo]", optional=True)
+    _lib.check(_L().ff_conv2d_bf16s_wimages(xp, ldi, hip, lop, ent[2], ent[3], B, rows // B, bp, mp, rp, ldr, op, ldo, rows, K, N,
+                                            GEMM_MODES[_GEMM_MODE], 0, _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K + B * N * K + rows * N * (2 if res is not None else 1)))
     return out
 
 
-def _kmul_images(kmul: Optional[T], K: int, rows: int) -> int:
-    """linear's kmul: [K] (or [1, K]) -> 1; a contiguous [B, K] matrix with B > 1 dividing the row count -> B; anything else raises."""
+def _kmul_images(kmul: Optional[T], K: int, rows: int):
+    """linear's kmul -> (images, ptr): [K] (or [1, K]) -> 1; a contiguous [B, K] matrix with B > 1 dividing the row count -> B; None ->
+    (1, None); anything else raises."""
     if kmul is None:
-        return 1
-    _chk(kmul, "linear.kmul")
+        return 1, None
+    _dev(kmul, "linear.kmul", _F32)
     if not kmul.is_contiguous() or kmul.numel() % K or (kmul.numel() != K and (kmul.dim() != 2 or kmul.shape[1] != K)):
         raise _lib.FFError(f"linear: kmul must be a contiguous [{K}] vector or [B, {K}] matrix, got {tuple(kmul.shape)}")
     images = kmul.numel() // K
     if images < 1 or rows % images:
         raise _lib.FFError(f"linear: kmul {tuple(kmul.shape)} needs a row count that B = {images} divides, got {rows} rows")
-    return images
+    return images, _dense(kmul, "linear.kmul", n=images * K)
 
 
 def rows_gemm_ok(K: int) -> bool:
@@ -569,59 +627,52 @@ def rows_gemm_ok(K: int) -> bool:
 
 
 def _linear_rows_bf16(x: T, w: T, bias, *, act, res, mul, alpha, out, dynamic_w, kmul, gate_pairs, out_bf16, tile_hint) -> T:
-    xp, lda, rows, K = rows_view(x, "linear.x|bf16ok")
+    xp, lda, rows, K = _rows(x, "linear.x", dtype=_F32_BF16)
     a32 = x.dtype == torch.float32
+    _dense(w, "linear.w", shape=(None, K))
     N = w.shape[0]
-    if w.dim() != 2 or w.shape[1] != K or not w.is_contiguous():
-        raise _lib.FFError(f"linear: weight must be [N, {K}], got {tuple(w.shape)}")
     if _GEMM_MODE != "bf16" or not rows_gemm_ok(K):
         raise _lib.FFError("linear: the bf16-rows GEMM exists in plain-bf16 mode for K % 64 == 0 only")
     if kmul is not None and not a32:
         raise _lib.FFError("linear: kmul scales fp32 input rows only")
-    images = _kmul_images(kmul, K, rows)
+    images, kp = _kmul_images(kmul, K, rows)
     if act is not None or alpha != 1.0 or (a32 and gate_pairs) or (gate_pairs and (res is not None or mul is not None)) or out_bf16 != gate_pairs:
         raise _lib.FFError("linear: the bf16-rows GEMM has three epilogues: bias (* mul + res) -> fp32 rows, or the SimpleGate pair "
                            "product -> bf16 rows")
     No = N // 2 if gate_pairs else N
-    oshape = tuple(x.shape[:-1]) + (No,)
-    if out is None:
-        out = empty_rows_bf16(oshape, x.device) if out_bf16 else empty_rows(oshape, x.device)
-    elif (out.dtype == torch.bfloat16) != out_bf16:
+    if out is not None and (out.dtype == torch.bfloat16) != out_bf16:
         raise _lib.FFError("linear: out dtype does not match out_bf16")
-    op, ldo, orows, oc = rows_view(out, "linear.out|bf16ok" if out_bf16 else "linear.out")
-    if orows != rows or oc != No:
-        raise _lib.FFError("linear: out shape mismatch")
-    rp, ldr = None, 0
-    if res is not None:
-        rp, ldr, rrows, rc = rows_view(res, "linear.res")
-        if rrows != rows or rc != N:
-            raise _lib.FFError("linear: res shape mismatch")
-    hi, _, Kp, _, _ = _split_weight(w, dynamic_w, K)
+    out, op, ldo = _out(out, "linear.out", tuple(x.shape[:-1]) + (No,), x.device, bf16=out_bf16)
+    rp, ldr, *_ = _rows(res, "linear.res", rows, N, optional=True)
+    bp = _dense(bias, "linear.bias", n=N, optional=True)
+    mp = _dense(mul, "linear.mul", n=N, optional=True)
+    ent = _split_weight(w, dynamic_w, K)
+    hip = _image(ent[0], "linear.w[hi]")
     if images > 1:
-        _lib.check(_L().ff_gemm_rows_bf16_kmul_images(xp, lda, hi.data_ptr(), Kp, kmul.data_ptr(), images, rows // images, _ptr(bias), _ptr(mul),
+        _lib.check(_L().ff_gemm_rows_bf16_kmul_images(xp, lda, hip, ent[2], kp, images, rows // images, bp, mp,
                                                       rp, ldr, op, ldo, rows, N, K, int(tile_hint), _stream()))
     else:
-        _lib.check(_L().ff_gemm_rows_bf16(xp, 1 if a32 else 0, lda, hi.data_ptr(), Kp, _ptr(kmul), _ptr(bias), _ptr(mul), rp, ldr, op, ldo, rows,
+        _lib.check(_L().ff_gemm_rows_bf16(xp, 1 if a32 else 0, lda, hip, ent[2], kp, bp, mp, rp, ldr, op, ldo, rows,
                                           N, K, 1 if gate_pairs else 0, int(tile_hint), _stream()))
     _note(2.0 * rows * N * K, (4.0 if a32 else 2.0) * rows * K + 2.0 * N * K + (2.0 if out_bf16 else 4.0) * rows * No + (4.0 * rows * No if res is not None else 0.0))
     return out
 
 
+@_instrument
 def window_attn(qkv: T, out: T, biasT: T, *, q_off: int, k_off: int, v_off: int, o_off: int, H: int, W: int, Hp: int,
                 Wp: int, win: Tuple[int, int], kwin: Tuple[int, int], shift: Tuple[int, int], use_mask: bool, heads: int,
                 d: int, scale: float, rel_table: Optional[T] = None) -> T:
     qp, ldq, B, h_, w_, _ = _nhwc(qkv, "window_attn.qkv")
-    op, ldo, *_ = _nhwc(out, "window_attn.out")
-    if (h_, w_) != (H, W) or tuple(out.shape[:3]) != (B, H, W):
+    if (h_, w_) != (H, W):
         raise _lib.FFError("window_attn: qkv/out spatial dims mismatch")
+    op, ldo, *_ = _nhwc(out, "window_attn.out", (B, H, W, None))
     nk = kwin[0] * kwin[1]
-    if tuple(biasT.shape) != (heads, nk, 256) or not biasT.is_contiguous():
-        raise _lib.FFError(f"window_attn: biasT must be [{heads},{nk},256]")
+    bp = _dense(biasT, "window_attn.biasT", shape=(heads, nk, 256))
     if q_off + heads * d > qkv.shape[-1] or k_off + heads * d > qkv.shape[-1] or v_off + heads * d > qkv.shape[-1] \
             or o_off + heads * d > out.shape[-1]:
         raise _lib.FFError("window_attn: channel offsets out of range")
     if _GEMM_MODE == "f32":
-        _lib.check(_L().ff_window_attn(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, biasT.data_ptr(), B, H, W, Hp, Wp, win[0],
+        _lib.check(_L().ff_window_attn(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, bp, B, H, W, Hp, Wp, win[0],
                                        win[1], kwin[0], kwin[1], shift[0], shift[1], int(use_mask), heads, d, float(scale),
                                        _stream()))
     else:
@@ -629,16 +680,14 @@ def window_attn(qkv: T, out: T, biasT: T, *, q_off: int, k_off: int, v_off: int,
         if rel_table is not None and tuple(kwin) != tuple(win):
             # overlapping keys: the rotated table of prep.pack_rel_overlap, gathered in the kernel through a per-key offset table
             n = (win[0] + kwin[0] - 1) * (win[1] + kwin[1] - 1)
-            if tuple(rel_table.shape) != (heads, n) or not rel_table.is_contiguous() or kwin[1] % 8 or tuple(shift) != (0, 0):
+            if kwin[1] % 8 or tuple(shift) != (0, 0):
                 raise _lib.FFError(f"window_attn: overlapping-window rel_table must be [heads, {n}] (prep.pack_rel_overlap), kw % 8 == 0, no shift")
-            relp = rel_table.data_ptr()
+            relp = _dense(rel_table, "window_attn.rel_table", shape=(heads, n))
         elif rel_table is not None and tuple(kwin) == tuple(win) and win[1] & (win[1] - 1) == 0 and win[1] >= 8:
-            if tuple(rel_table.shape) != (heads, (2 * win[0] - 1) * (2 * win[1] - 1)) or not rel_table.is_contiguous():
-                raise _lib.FFError("window_attn: rel_table must be [heads, (2wh-1)*(2ww-1)]")
-            relp = rel_table.data_ptr()
+            relp = _dense(rel_table, "window_attn.rel_table", shape=(heads, (2 * win[0] - 1) * (2 * win[1] - 1)))
         from . import prep as _prep
         bq = PREPARED.get(biasT, "quad", lambda: _prep.quad_bias(biasT))          # load-time relayout, once per table
-        _lib.check(_L().ff_window_attn_bf16s(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, bq.data_ptr(), B, H, W, Hp, Wp,
+        _lib.check(_L().ff_window_attn_bf16s(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, _image(bq, "window_attn.biasT[quad]"), B, H, W, Hp, Wp,
                                              win[0], win[1], kwin[0], kwin[1], shift[0], shift[1], int(use_mask), heads, d,
                                              float(scale), 1 if _GEMM_MODE == "bf16" else 3, relp, _stream()))
     nwin = B * (Hp // win[0]) * (Wp // win[1])
@@ -646,46 +695,45 @@ def window_attn(qkv: T, out: T, biasT: T, *, q_off: int, k_off: int, v_off: int,
     return out
 
 
+@_instrument
 def ocab_attn(qkv: T, out: T, rel_rotated: T, *, q_off: int, k_off: int, v_off: int, o_off: int = 0, H: int, W: int, heads: int, d: int,
               ws: int, ows: int, scale: float) -> T:
     """HAT OCAB attention stage in one persistent-workgroup launch (plain bf16; csrc/ocab_attn.hip): 16x16 query windows against
     24x24 zero-padded key windows, bias from the rotated compact table of prep.pack_rel_overlap [heads, 39*39]."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError("ocab_attn exists for the plain-bf16 contraction mode only")
-    qp, ldq, B, h_, w_, _ = _nhwc(qkv, "ocab_attn.qkv")
+    qp, ldq, B, *_ = _nhwc(qkv, "ocab_attn.qkv", (None, H, W, None))
+    op, ldo, *_ = _nhwc(out, "ocab_attn.out", (B, H, W, None), _F32_BF16)
     out_bf16 = out.dtype == torch.bfloat16
-    op, ldo, *_ = _nhwc(out, "ocab_attn.out|bf16ok" if out_bf16 else "ocab_attn.out")
-    if (h_, w_) != (H, W) or tuple(out.shape[:3]) != (B, H, W) or tuple(rel_rotated.shape) != (heads, (ws + ows - 1) ** 2) or not rel_rotated.is_contiguous():
-        raise _lib.FFError("ocab_attn: shape mismatch")
-    _lib.check(_L().ff_ocab_attn(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, rel_rotated.data_ptr(), B, H, W, heads, d, ws, ows,
+    relp = _dense(rel_rotated, "ocab_attn.rel_rotated", shape=(heads, (ws + ows - 1) ** 2))
+    _lib.check(_L().ff_ocab_attn(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, relp, B, H, W, heads, d, ws, ows,
                                  float(scale), int(out_bf16), _stream()))
     nwin = B * (H // ws) * (W // ws)
     _note(4.0 * nwin * heads * ws * ws * ows * ows * d, 4.0 * B * H * W * heads * d * 4)
     return out
 
 
+@_instrument
 def ocab_attn_rows16(qkv16: T, out: T, rel_rotated: T, *, q_off: int, k_off: int, v_off: int, o_off: int = 0, H: int, W: int, heads: int,
                      d: int, ws: int, ows: int) -> T:
     """ocab_attn on the head-padded bf16 rows of token_linear_rows16 (csrc/ocab_attn.hip, ROWS16): head h of q / k / v at
     q_off / k_off / v_off + 32 h, q already scaled."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError("ocab_attn_rows16 exists for the plain-bf16 contraction mode only")
-    if qkv16.dtype != torch.bfloat16:
-        raise _lib.FFError("ocab_attn_rows16: qkv must be bf16 rows")
-    qp, ldq, B, h_, w_, _ = _nhwc(qkv16, "ocab_attn_rows16.qkv|bf16ok")
+    qp, ldq, B, *_ = _nhwc(qkv16, "ocab_attn_rows16.qkv", (None, H, W, None), _BF16)
+    op, ldo, *_ = _nhwc(out, "ocab_attn_rows16.out", (B, H, W, None), _F32_BF16)
     out_bf16 = out.dtype == torch.bfloat16
-    op, ldo, *_ = _nhwc(out, "ocab_attn_rows16.out|bf16ok" if out_bf16 else "ocab_attn_rows16.out")
-    if (h_, w_) != (H, W) or tuple(out.shape[:3]) != (B, H, W) or tuple(rel_rotated.shape) != (heads, (ws + ows - 1) ** 2) or not rel_rotated.is_contiguous():
-        raise _lib.FFError("ocab_attn_rows16: shape mismatch")
+    relp = _dense(rel_rotated, "ocab_attn_rows16.rel_rotated", shape=(heads, (ws + ows - 1) ** 2))
     if max(q_off, k_off, v_off) + heads * 32 > qkv16.shape[-1]:
         raise _lib.FFError("ocab_attn_rows16: channel offsets out of range")
-    _lib.check(_L().ff_ocab_attn_rows16(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, rel_rotated.data_ptr(), B, H, W, heads, d, ws, ows,
+    _lib.check(_L().ff_ocab_attn_rows16(qp, ldq, q_off, k_off, v_off, op, ldo, o_off, relp, B, H, W, heads, d, ws, ows,
                                         int(out_bf16), _stream()))
     nwin = B * (H // ws) * (W // ws)
     _note(4.0 * nwin * heads * ws * ws * ows * ows * d, B * H * W * heads * (2.0 * 3 * 32 + (2.0 if out_bf16 else 4.0) * d))
     return out
 
 
+@_instrument
 def win_attn_fused(x: T, out: T, pk: dict, rel_padded: T, *, gamma: Optional[T], beta: Optional[T], eps: float = 1e-5,
                    H: int, W: int, Hp: int, Wp: int, win: Tuple[int, int], shift: Tuple[int, int], use_mask: bool,
                    head0: int = 0, nheads: Optional[int] = None, o_off: int = 0, zero_pad: bool = False,
@@ -693,31 +741,25 @@ def win_attn_fused(x: T, out: T, pk: dict, rel_padded: T, *, gamma: Optional[T],
     """LayerNorm + qkv projection + window attention of `nheads` heads in one launch (csrc/win_attn_fused.hip); pk from
     prep.pack_win_attn, rel_padded from prep.pack_win_rel.  x [B,H,W,K] rows view; out [B,H,W,>= o_off + heads*d].
     want_xn: also return the normalised rows; v_out: receives v of the processed heads at channel v_off + g*d."""
-    xp, ldx, B, h_, w_, K = _nhwc(x, "win_attn_fused.x")
+    xp, ldx, B, _, _, K = _nhwc(x, "win_attn_fused.x", (None, H, W, pk["K"]))
+    op, ldo, *_ = _nhwc(out, "win_attn_fused.out", (B, H, W, None), _F32_BF16)
     out_bf16 = out.dtype == torch.bfloat16
-    op, ldo, *_ = _nhwc(out, "win_attn_fused.out|bf16ok" if out_bf16 else "win_attn_fused.out")
     xn_bf16 = want_xn == "bf16"
     if (out_bf16 or xn_bf16) and _GEMM_MODE != "bf16":
         raise _lib.FFError("win_attn_fused: bf16 outputs exist for the plain-bf16 contraction mode only")
-    if (h_, w_) != (H, W) or tuple(out.shape[:3]) != (B, H, W) or K != pk["K"]:
-        raise _lib.FFError("win_attn_fused: x/out dims mismatch")
     nheads = pk["heads"] - head0 if nheads is None else nheads
-    if tuple(rel_padded.shape[:2]) != (pk["heads"], 2 * win[0] - 1) or not rel_padded.is_contiguous():
-        raise _lib.FFError("win_attn_fused: rel_padded must be [heads][2wh-1][stride]")
+    relp = _dense(rel_padded, "win_attn_fused.rel_padded", shape=(pk["heads"], 2 * win[0] - 1, None))
     if _GEMM_MODE not in ("bf16x3", "bf16"):
         raise _lib.FFError("win_attn_fused exists for the bf16 contraction modes only")
+    gp = _dense(gamma, "win_attn_fused.gamma", n=K, optional=True)
+    bp = _dense(beta, "win_attn_fused.beta", n=K, optional=True)
+    wp, wbp = _image(pk["w"], "win_attn_fused.pk.w"), _image(pk["b"], "win_attn_fused.pk.b")
+    vp, ldv, *_ = _nhwc(v_out, "win_attn_fused.v_out", (B, H, W, None), optional=True)
     xn, xnp, ldxn = None, None, 0
     if want_xn:
-        xn = empty_rows_bf16(tuple(x.shape), x.device) if xn_bf16 else empty_like_rows(x)
-        xnp, ldxn, _, _ = rows_view(xn, "win_attn_fused.xn|bf16ok" if xn_bf16 else "win_attn_fused.xn")
-    vp, ldv = None, 0
-    if v_out is not None:
-        vp, ldv, vb, vh, vw, _ = _nhwc(v_out, "win_attn_fused.v_out")
-        if (vb, vh, vw) != (B, H, W):
-            raise _lib.FFError("win_attn_fused: v_out dims mismatch")
-    _lib.check(_L().ff_win_attn_fused(xp, ldx, op, ldo, o_off, _ptr(gamma), _ptr(beta), float(eps), pk["w"].data_ptr(),
-                                      pk["b"].data_ptr(), rel_padded.data_ptr(), rel_padded.shape[1], rel_padded.shape[2], B, H, W,
-                                      Hp, Wp, win[0], win[1], shift[0], shift[1], int(use_mask), head0, nheads, pk["d"], K,
+        xn, xnp, ldxn = _out(None, "win_attn_fused.xn", tuple(x.shape), x.device, bf16=xn_bf16)
+    _lib.check(_L().ff_win_attn_fused(xp, ldx, op, ldo, o_off, gp, bp, float(eps), wp, wbp, relp, rel_padded.shape[1], rel_padded.shape[2],
+                                      B, H, W, Hp, Wp, win[0], win[1], shift[0], shift[1], int(use_mask), head0, nheads, pk["d"], K,
                                       int(zero_pad), xnp, ldxn, vp, ldv, v_off, 1 if _GEMM_MODE == "bf16" else 3, int(out_bf16), int(xn_bf16),
                                       _stream()))
     nwin = B * (Hp // win[0]) * (Wp // win[1])
@@ -726,60 +768,61 @@ def win_attn_fused(x: T, out: T, pk: dict, rel_padded: T, *, gamma: Optional[T],
     return (out, xn) if want_xn else out
 
 
+@_instrument
 def token_mlp(x: T, gamma: T, beta: T, pk: dict, eps: float = 1e-5) -> T:
     """x + fc2(GELU(fc1(LayerNorm(x)))) in one launch (bf16x3 only); pk from prep.pack_token_mlp."""
-    xp, ldx, rows, K = rows_view(x, "token_mlp.x")
-    if K != pk["K"] or pk["N"] != K:
+    xp, ldx, rows, K = _rows(x, "token_mlp.x", C=pk["K"])
+    if pk["N"] != K:
         raise _lib.FFError("token_mlp: shape mismatch")
-    out = empty_like_rows(x)
-    op_, ldo_, _, _ = rows_view(out, "token_mlp.out")
-    _lib.check(_L().ff_token_mlp(xp, ldx, op_, ldo_, rows, K, pk["ht"], pk["N"], gamma.data_ptr(), beta.data_ptr(),
-                                 float(eps), pk["w"].data_ptr(), pk["b1"].data_ptr(), pk["b2"].data_ptr(), _nterms(), _stream()))
+    gp, bp = _dense(gamma, "token_mlp.gamma", n=K), _dense(beta, "token_mlp.beta", n=K)
+    wp, b1p, b2p = _images(pk, "token_mlp.pk", "w", "b1", "b2")
+    nt = _nterms()
+    out, op_, ldo_ = _out(None, "token_mlp.out", tuple(x.shape), x.device)
+    _lib.check(_L().ff_token_mlp(xp, ldx, op_, ldo_, rows, K, pk["ht"], pk["N"], gp, bp, float(eps), wp, b1p, b2p, nt, _stream()))
     _note(4.0 * rows * K * pk["ht"] * 32, 8.0 * rows * K)
     return out
 
 
+@_instrument
 def token_projmlp(att: T, x: T, pk: dict, gamma: T, beta: T, *, c2: Optional[T] = None, c2_scale: Optional[T] = None,
                   eps: float = 1e-5) -> T:
     """x1 = x + proj(att) + c2 * c2_scale; return x1 + fc2(GELU(fc1(LayerNorm(x1)))) in one launch (bf16x3); pk from
     prep.pack_token_projmlp.  c2_scale [K] (or [1,K]): one gate for every row.  c2_scale [B,K] with B = x.shape[0] > 1: one gate per image
     (ff_token_projmlp_images; every image must be a multiple of 256 rows), bit-equal to B calls on the row slices."""
-    att_bf16 = att.dtype == torch.bfloat16
+    att_bf16 = isinstance(att, torch.Tensor) and att.dtype == torch.bfloat16
     c2_bf16 = c2 is not None and c2.dtype == torch.bfloat16
     if (att_bf16 or c2_bf16) and _GEMM_MODE != "bf16":
         raise _lib.FFError("token_projmlp: bf16 att / c2 rows exist for the plain-bf16 contraction mode only")
-    ap, lda, rows, K = rows_view(att, "token_projmlp.att|bf16ok" if att_bf16 else "token_projmlp.att")
-    xp, ldx, xr, xk = rows_view(x, "token_projmlp.x")
-    if xr != rows or xk != K or K != pk["mlp"]["K"]:
-        raise _lib.FFError("token_projmlp: shape mismatch")
-    cp, ldc = None, 0
-    if c2 is not None:
-        cp, ldc, cr, ck = rows_view(c2, "token_projmlp.c2|bf16ok" if c2_bf16 else "token_projmlp.c2")
-        if cr != rows or ck != K or c2_scale is None:
-            raise _lib.FFError("token_projmlp: c2 shape mismatch")
+    ap, lda, rows, K = _rows(att, "token_projmlp.att", C=pk["mlp"]["K"], dtype=_F32_BF16)
+    xp, ldx, *_ = _rows(x, "token_projmlp.x", rows, K)
+    cp, ldc, *_ = _rows(c2, "token_projmlp.c2", rows, K, _F32_BF16, optional=True)
+    if c2 is not None and c2_scale is None:
+        raise _lib.FFError("token_projmlp: c2 shape mismatch")
     nimg = 1
     if c2 is not None and c2_scale.numel() != K:
         nimg = int(x.shape[0])
         if c2_scale.dim() != 2 or tuple(c2_scale.shape) != (nimg, K) or not c2_scale.is_contiguous() or rows % nimg:
-            raise _lib.FFError(f"token_projmlp: c2_scale must be [{K}] or one row per image [{nimg},{K}], got {tuple(c2_scale.shape)}")
+            raise _lib.FFError(f"token_projmlp.c2_scale: must be [{K}] or one row per image [{nimg},{K}], got {tuple(c2_scale.shape)}")
         if (rows // nimg) % 256:
             raise _lib.FFError(f"token_projmlp: a per-image gate needs images of a multiple of 256 rows, got {rows // nimg}")
-    out = empty_like_rows(x)
-    op_, ldo_, _, _ = rows_view(out, "token_projmlp.out")
+    sp = _dense(c2_scale, "token_projmlp.c2_scale", n=nimg * K, optional=True)
+    gp, bp = _dense(gamma, "token_projmlp.gamma", n=K), _dense(beta, "token_projmlp.beta", n=K)
     m = pk["mlp"]
+    (pwp, pbp), (wp, b1p, b2p) = _images(pk["proj"], "token_projmlp.pk.proj", "w", "b"), _images(m, "token_projmlp.pk.mlp", "w", "b1", "b2")
+    nt = _nterms()
+    out, op_, ldo_ = _out(None, "token_projmlp.out", tuple(x.shape), x.device)
+    rows16 = (1 if att_bf16 else 0) | (2 if c2_bf16 else 0)
     if nimg > 1:
-        _lib.check(_L().ff_token_projmlp_images(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), K, nimg, rows // nimg, op_, ldo_, rows, K, m["ht"],
-                                                pk["proj"]["w"].data_ptr(), pk["proj"]["b"].data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                float(eps), m["w"].data_ptr(), m["b1"].data_ptr(), m["b2"].data_ptr(), _nterms(),
-                                                (1 if att_bf16 else 0) | (2 if c2_bf16 else 0), _stream()))
+        _lib.check(_L().ff_token_projmlp_images(ap, lda, xp, ldx, cp, ldc, sp, K, nimg, rows // nimg, op_, ldo_, rows, K, m["ht"], pwp, pbp,
+                                                gp, bp, float(eps), wp, b1p, b2p, nt, rows16, _stream()))
     else:
-        _lib.check(_L().ff_token_projmlp(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), op_, ldo_, rows, K, m["ht"], pk["proj"]["w"].data_ptr(),
-                                         pk["proj"]["b"].data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), m["w"].data_ptr(),
-                                         m["b1"].data_ptr(), m["b2"].data_ptr(), _nterms(), (1 if att_bf16 else 0) | (2 if c2_bf16 else 0), _stream()))
+        _lib.check(_L().ff_token_projmlp(ap, lda, xp, ldx, cp, ldc, sp, op_, ldo_, rows, K, m["ht"], pwp, pbp, gp, bp, float(eps), wp, b1p,
+                                         b2p, nt, rows16, _stream()))
     _note(2.0 * rows * K * K + 4.0 * rows * K * m["ht"] * 32, 4.0 * rows * K * (2 + (0.5 if att_bf16 else 1.0) + (0 if c2 is None else (0.5 if c2_bf16 else 1.0))))
     return out
 
 
+@_instrument
 def hab_link(att: T, x: T, pk: dict, gamma2: T, beta2: T, *, c2: T, c2_scale: T, wf: dict, rel_padded: T, gamma1: T, beta1: T,
              shift: Tuple[int, int], use_mask: bool, eps2: float = 1e-5, eps1: float = 1e-5) -> Tuple[T, T, T]:
     """One HAB's token_projmlp and the next HAB's win_attn_fused in one launch (csrc/hab_link.hip; plain bf16, 16x16 windows, six
@@ -789,30 +832,29 @@ def hab_link(att: T, x: T, pk: dict, gamma2: T, beta2: T, *, c2: T, c2_scale: T,
     -> (x_out fp32, xn bf16, att_out bf16), each bit-equal to the two launches."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError("hab_link exists for the plain-bf16 contraction mode only")
-    if att.dtype != torch.bfloat16 or c2 is None or c2.dtype != torch.bfloat16 or c2_scale is None:
+    if c2 is None or c2_scale is None:
         raise _lib.FFError("hab_link: att and c2 must be bf16 rows, and the gate is required")
-    ap, lda, B, H, W, K = _nhwc(att, "hab_link.att|bf16ok")
-    xp, ldx, xb, xh_, xw, xk = _nhwc(x, "hab_link.x")
-    cp, ldc, cb, ch, cw, ck = _nhwc(c2, "hab_link.c2|bf16ok")
-    if (xb, xh_, xw, xk) != (B, H, W, K) or (cb, ch, cw, ck) != (B, H, W, K) or K != pk["mlp"]["K"] or K != wf["K"]:
+    ap, lda, B, H, W, K = _nhwc(att, "hab_link.att", dtype=_BF16)
+    xp, ldx, *_ = _nhwc(x, "hab_link.x", (B, H, W, K))
+    cp, ldc, *_ = _nhwc(c2, "hab_link.c2", (B, H, W, K), _BF16)
+    if K != pk["mlp"]["K"] or K != wf["K"]:
         raise _lib.FFError("hab_link: shape mismatch")
-    if tuple(c2_scale.shape) not in (((K,), (1, K)) if B == 1 else ((B, K),)) or not c2_scale.is_contiguous():
+    sp = _dense(c2_scale, "hab_link.c2_scale", n=B * K)
+    if tuple(c2_scale.shape) not in (((K,), (1, K)) if B == 1 else ((B, K),)):
         raise _lib.FFError(f"hab_link: c2_scale must be [{K}] for one image or one row per image [{B},{K}], got {tuple(c2_scale.shape)}")
-    if tuple(rel_padded.shape[:2]) != (wf["heads"], 31) or not rel_padded.is_contiguous():
-        raise _lib.FFError("hab_link: rel_padded must be [heads][31][stride]")
-    out = empty_like_rows(x)
-    op_, ldo_, *_ = _nhwc(out, "hab_link.out")
-    xn = empty_rows_bf16(tuple(x.shape), x.device)
-    xnp, ldxn, *_ = _nhwc(xn, "hab_link.xn|bf16ok")
-    ao = empty_rows_bf16(tuple(x.shape), x.device)
-    aop, ldao, *_ = _nhwc(ao, "hab_link.att_out|bf16ok")
+    relp = _dense(rel_padded, "hab_link.rel_padded", shape=(wf["heads"], 31, None))
+    g2p, b2p_ = _dense(gamma2, "hab_link.gamma2", n=K), _dense(beta2, "hab_link.beta2", n=K)
+    g1p, b1p_ = _dense(gamma1, "hab_link.gamma1", n=K), _dense(beta1, "hab_link.beta1", n=K)
     m = pk["mlp"]
-    _lib.check(_L().ff_hab_link(ap, lda, xp, ldx, cp, ldc, _ptr(c2_scale), K, B, H * W, op_, ldo_, B * H * W, K, m["ht"],
-                                pk["proj"]["w"].data_ptr(), pk["proj"]["b"].data_ptr(), gamma2.data_ptr(), beta2.data_ptr(), float(eps2),
-                                m["w"].data_ptr(), m["b1"].data_ptr(), m["b2"].data_ptr(), 1, 3,
-                                aop, ldao, 0, gamma1.data_ptr(), beta1.data_ptr(), float(eps1), wf["w"].data_ptr(), wf["b"].data_ptr(),
-                                rel_padded.data_ptr(), rel_padded.shape[1], rel_padded.shape[2], H, W, 16, 16, shift[0], shift[1],
-                                int(use_mask), wf["heads"], wf["d"], xnp, ldxn, 1, 1, _stream()))
+    (pwp, pbp), (wp, b1p, b2p) = _images(pk["proj"], "hab_link.pk.proj", "w", "b"), _images(m, "hab_link.pk.mlp", "w", "b1", "b2")
+    wfw, wfb = _images(wf, "hab_link.wf", "w", "b")
+    out, op_, ldo_ = _out(None, "hab_link.out", tuple(x.shape), x.device, kind="nhwc")
+    xn, xnp, ldxn = _out(None, "hab_link.xn", tuple(x.shape), x.device, bf16=True, kind="nhwc")
+    ao, aop, ldao = _out(None, "hab_link.att_out", tuple(x.shape), x.device, bf16=True, kind="nhwc")
+    _lib.check(_L().ff_hab_link(ap, lda, xp, ldx, cp, ldc, sp, K, B, H * W, op_, ldo_, B * H * W, K, m["ht"], pwp, pbp, g2p, b2p_, float(eps2),
+                                wp, b1p, b2p, 1, 3, aop, ldao, 0, g1p, b1p_, float(eps1), wfw, wfb, relp, rel_padded.shape[1],
+                                rel_padded.shape[2], H, W, 16, 16, shift[0], shift[1], int(use_mask), wf["heads"], wf["d"], xnp, ldxn, 1, 1,
+                                _stream()))
     rows, nwin, nh, d = B * H * W, B * (H // 16) * (W // 16), wf["heads"], wf["d"]
     # the parents' sums (token_projmlp with bf16 att / c2, win_attn_fused with bf16 xn / out) minus the attention's read of x
     _note(2.0 * rows * K * K + 4.0 * rows * K * m["ht"] * 32 + 2.0 * nwin * 256 * K * 3 * nh * d + 4.0 * nwin * nh * 256 * 256 * d,
@@ -829,11 +871,14 @@ def cab_fused_ok(x: T) -> bool:
     B, H, W, C = x.shape
     if not (_HALO and _GEMM_MODE == "bf16" and C == 180 and H * W >= 1024 and H % 16 == 0 and W % 16 == 0):
         return False
-    ld = x.stride(2)
-    rows_ok = x.stride(3) == 1 and x.stride(1) == W * ld and (B == 1 or x.stride(0) == H * W * ld)
-    return rows_ok and ld % 8 == 0 and ld >= C and x.data_ptr() % 16 == 0 and B * H * W * max(ld, 192) < 2 ** 31
+    try:
+        xp, ld, *_ = _nhwc(x, "cab_fused.xn", dtype=_BF16)
+    except _lib.FFError:                                    # no constant row pitch
+        return False
+    return ld % 8 == 0 and ld >= C and xp % 16 == 0 and B * H * W * max(ld, 192) < 2 ** 31
 
 
+@_instrument
 def cab_fused(xn: T, cab0: Tuple[T, T], cab2: Tuple[T, T], out: Optional[T] = None):
     """HAT's CAB without its gate in one launch (csrc/cab_fused.hip; plain bf16): c2 = conv3x3(gelu(conv3x3(xn) + b0)) + b2 with c1 kept in
     LDS.  xn [B,H,W,180] bf16 rows; cab0 = (packed weight [60, 9*180], bias), cab2 = (packed weight [180, 9*60], bias), the pairs conv2d
@@ -842,170 +887,164 @@ def cab_fused(xn: T, cab0: Tuple[T, T], cab2: Tuple[T, T], out: Optional[T] = No
     same MFMA order, and image b's partial rows are those of its own B == 1 call."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError("cab_fused exists for the plain-bf16 contraction mode only")
-    if xn.dtype != torch.bfloat16:
-        raise _lib.FFError("cab_fused: xn must be bf16 rows")
     from . import prep as _prep
-    xp, ldi, B, H, W, Cin = _nhwc(xn, "cab_fused.xn|bf16ok")
+    xp, ldi, B, H, W, Cin = _nhwc(xn, "cab_fused.xn", dtype=_BF16)
     (w0, b0), (w2, b2) = cab0, cab2
-    Cmid, Cout = w0.shape[0], w2.shape[0]
-    if w0.dim() != 2 or w0.shape[1] != 9 * Cin or w2.dim() != 2 or w2.shape[1] != 9 * Cmid or b0 is None or b2 is None:
-        raise _lib.FFError(f"cab_fused: packed weights must be [Cmid, {9 * Cin}] and [Cout, 9 * Cmid], both with a bias")
+    _dense(w0, "cab_fused.w0", shape=(None, 9 * Cin))
+    Cmid = w0.shape[0]
+    _dense(w2, "cab_fused.w2", shape=(None, 9 * Cmid))
+    Cout = w2.shape[0]
+    b0p, b2p = _dense(b0, "cab_fused.b0", n=Cmid), _dense(b2, "cab_fused.b2", n=Cout)
+    oshape = (B, H, W, Cout)
+    if out is not None:                                     # (the caller's buffer is refused before a weight image is built)
+        out, op, ldo = _out(out, "cab_fused.out", oshape, xn.device, bf16=True, kind="nhwc")
     img0 = PREPARED.get(w0, "halo1", lambda: (_prep.pack_conv3x3_halo(w0, Cin, _prep.halo_bn(Cmid), 1), _prep.halo_bn(Cmid)))
     img2 = PREPARED.get(w2, "halo1", lambda: (_prep.pack_conv3x3_halo(w2, Cmid, _prep.halo_bn(Cout), 1), _prep.halo_bn(Cout)))
     if (img0[1], img2[1]) != (64, 192):
         raise _lib.FFError(f"cab_fused: weight images of tile widths {img0[1]} / {img2[1]}, built for 64 / 192")
-    oshape = (B, H, W, Cout)
+    i0p, i2p = _image(img0[0], "cab_fused.w0[halo1]"), _image(img2[0], "cab_fused.w2[halo1]")
     if out is None:
-        out = empty_rows_bf16(oshape, xn.device)
-    elif tuple(out.shape) != oshape or out.dtype != torch.bfloat16:
-        raise _lib.FFError(f"cab_fused: out must be bf16 rows {oshape}")
-    op, ldo, *_ = _nhwc(out, "cab_fused.out|bf16ok")
+        out, op, ldo = _out(None, "cab_fused.out", oshape, xn.device, bf16=True, kind="nhwc")
     prow = int(_L().ff_conv3x3_halo_images_pool_rows(B, H, W, Cout, 192, 1))
     if prow < 0:
         raise _lib.FFError("cab_fused: bad shape")
     part = torch.empty((prow, 192), device=xn.device, dtype=torch.float32)
-    _lib.check(_L().ff_cab_fused(xp, ldi, img0[0].data_ptr(), img0[0].numel() * img0[0].element_size(), _ptr(b0),
-                                 img2[0].data_ptr(), img2[0].numel() * img2[0].element_size(), _ptr(b2), op, ldo, part.data_ptr(),
-                                 B, H, W, Cin, Cmid, Cout, 1, 3, _stream()))
+    _lib.check(_L().ff_cab_fused(xp, ldi, i0p, img0[0].numel() * img0[0].element_size(), b0p, i2p, img2[0].numel() * img2[0].element_size(),
+                                 b2p, op, ldo, _dense(part, "cab_fused.part"), B, H, W, Cin, Cmid, Cout, 1, 3, _stream()))
     _note(2.0 * B * H * W * 9 * (Cin * Cmid + Cmid * Cout), 2.0 * _numel(xn, out) + 2.0 * _numel(w0, w2))
     return out, PoolPartials(part, Cout, 1.0 / float(H * W), images=B)
 
 
+@_instrument
 def token_linear(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T] = None, eps: float = 1e-5, act=None,
                  res: Optional[T] = None, res2: Optional[T] = None, res2_scale: Optional[T] = None, want_xn: bool = False,
                  stats_range: Optional[Tuple[int, int]] = None, stats_eps: float = 1e-5):
     """res + res2*scale + act(LayerNorm?(x) @ W^T + b) for K <= 192 in one launch (bf16x3); pk from prep.pack_token_linear.
     want_xn: also return LayerNorm(x) (written by the same launch) -> (out, xn).
     stats_range=(lo, hi): also return [rows, 2] (mean, rstd) of the activated output channels [lo, hi) -> (out, stats)."""
-    xp, ldx, rows, K = rows_view(x, "token_linear.x")
+    xp, ldx, rows, K = _rows(x, "token_linear.x")
     if K != pk["K"]:
         raise _lib.FFError("token_linear: K mismatch")
     N = pk["N"]
+    rp, ldr, *_ = _rows(res, "token_linear.res", rows, N, optional=True)
+    r2p, ldr2, *_ = _rows(res2, "token_linear.res2", rows, N, optional=True)
+    if res2 is not None and res2_scale is None:
+        raise _lib.FFError("token_linear: res2 shape mismatch")
+    s2p = _dense(res2_scale, "token_linear.res2_scale", n=N, optional=True)
+    if want_xn and gamma is None:
+        raise _lib.FFError("token_linear: want_xn needs LayerNorm parameters")
+    gp = _dense(gamma, "token_linear.gamma", n=K, optional=True)
+    bp = _dense(beta, "token_linear.beta", n=K, optional=True)
+    wp, wbp = _image(pk["w"], "token_linear.pk.w"), _image(pk["b"], "token_linear.pk.b", optional=True)
+    nt = _nterms()
     # the padded row pitch of empty_rows makes every 32-column store segment of the kernel one whole 128-byte line (no
     # partial-line writes); consumers take the pitch as their ld argument
-    out = empty_rows(tuple(x.shape[:-1]) + (N,), x.device)
-    op, ldo, _, _ = rows_view(out, "token_linear.out")
-    rp, ldr, r2p, ldr2 = None, 0, None, 0
-    if res is not None:
-        rp, ldr, rr, rc = rows_view(res, "token_linear.res")
-        if rr != rows or rc != N:
-            raise _lib.FFError("token_linear: res shape mismatch")
-    if res2 is not None:
-        r2p, ldr2, rr, rc = rows_view(res2, "token_linear.res2")
-        if rr != rows or rc != N or res2_scale is None or res2_scale.numel() != N:
-            raise _lib.FFError("token_linear: res2 shape mismatch")
+    out, op, ldo = _out(None, "token_linear.out", tuple(x.shape[:-1]) + (N,), x.device)
     xn, xnp, ldxn = None, None, 0
     if want_xn:
-        if gamma is None:
-            raise _lib.FFError("token_linear: want_xn needs LayerNorm parameters")
-        xn = empty_like_rows(x)
-        xnp, ldxn, _, _ = rows_view(xn, "token_linear.xn")
+        xn, xnp, ldxn = _out(None, "token_linear.xn", tuple(x.shape), x.device)
     stats, sp, slo, shi = None, None, 0, 0
     if stats_range is not None:
         slo, shi = stats_range
-        stats = torch.empty((rows, 2), device=x.device, dtype=torch.float32)
-        sp = stats.data_ptr()
-    _lib.check(_L().ff_token_linear(xp, ldx, op, ldo, rows, K, pk["kpad"], N, pk["nt"], _ptr(gamma), _ptr(beta), float(eps),
-                                    pk["w"].data_ptr(), _ptr(pk["b"]), ACT[act], rp, ldr, r2p, ldr2, _ptr(res2_scale), xnp, ldxn,
-                                    sp, slo, shi, float(stats_eps), _nterms(), _stream()))
+        stats, sp, _ = _out(None, "token_linear.stats", (rows, 2), x.device, kind="dense")
+    _lib.check(_L().ff_token_linear(xp, ldx, op, ldo, rows, K, pk["kpad"], N, pk["nt"], gp, bp, float(eps), wp, wbp, ACT[act], rp, ldr,
+                                    r2p, ldr2, s2p, xnp, ldxn, sp, slo, shi, float(stats_eps), nt, _stream()))
     _note(2.0 * rows * N * K, 4.0 * (rows * K * (2 if want_xn else 1) + rows * N * (1 + (res is not None) + (res2 is not None))))
     if stats is not None:
         return out, stats
     return (out, xn) if want_xn else out
 
 
+@_instrument
 def token_linear_rows16(x: T, pk: dict, *, gamma: Optional[T] = None, beta: Optional[T] = None, eps: float = 1e-5,
                         out: Optional[T] = None) -> T:
     """bf16( (LayerNorm?(x) @ W^T + b) * pk["scale"] ) as bf16 rows in one launch (plain bf16 only; csrc/token_linear.hip); pk from
     prep.pack_ocab_qkv.  out (optional): a bf16 rows view [..., N] to write into."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError("token_linear_rows16 exists for the plain-bf16 contraction mode only")
-    xp, ldx, rows, K = rows_view(x, "token_linear_rows16.x")
+    xp, ldx, rows, K = _rows(x, "token_linear_rows16.x")
     if K != pk["K"]:
         raise _lib.FFError("token_linear_rows16: K mismatch")
     N = pk["N"]
-    if out is None:
-        out = empty_rows_bf16(tuple(x.shape[:-1]) + (N,), x.device)
-    op, ldo, orows, oc = rows_view(out, "token_linear_rows16.out|bf16ok")
-    if out.dtype != torch.bfloat16 or orows != rows or oc != N:
-        raise _lib.FFError("token_linear_rows16: out must be bf16 rows [rows, N]")
-    _lib.check(_L().ff_token_linear_rows16(xp, ldx, op, ldo, rows, K, pk["kpad"], N, pk["nt"], _ptr(gamma), _ptr(beta), float(eps),
-                                           pk["w"].data_ptr(), _ptr(pk["b"]), pk["scale"].data_ptr(), ACT[None], None, 0, None, 0, None,
-                                           None, 0, None, 0, 0, 0.0, 1, _stream()))
+    gp = _dense(gamma, "token_linear_rows16.gamma", n=K, optional=True)
+    bp = _dense(beta, "token_linear_rows16.beta", n=K, optional=True)
+    wp, wbp = _image(pk["w"], "token_linear_rows16.pk.w"), _image(pk["b"], "token_linear_rows16.pk.b", optional=True)
+    scp = _image(pk["scale"], "token_linear_rows16.pk.scale")
+    out, op, ldo = _out(out, "token_linear_rows16.out", tuple(x.shape[:-1]) + (N,), x.device, bf16=True)
+    _lib.check(_L().ff_token_linear_rows16(xp, ldx, op, ldo, rows, K, pk["kpad"], N, pk["nt"], gp, bp, float(eps), wp, wbp, scp, ACT[None],
+                                           None, 0, None, 0, None, None, 0, None, 0, 0, 0.0, 1, _stream()))
     _note(2.0 * rows * N * K, 4.0 * rows * K + 2.0 * rows * N)
     return out
 
 
+@_instrument
 def dwconv3_gate_pool(t: T, w_tap: T, bias: T):
     """t [B,H,W,2C] -> (dw3x3(t)[..., :C] * dw3x3(t)[..., C:], its per-channel mean [B,C]) in one pass.  B > 1: one launch for the
     batch (ff_dwconv3_gate_pool_images), every image with the bits of its own B == 1 call."""
     tp, ldi, B, H, W, C2 = _nhwc(t, "dwconv3_gate_pool.t")
-    if B < 1 or C2 % 2 or tuple(w_tap.shape) != (9, C2):
+    if B < 1 or C2 % 2:
         raise _lib.FFError("dwconv3_gate_pool: expects [B,H,W,2C] with B >= 1, [9, 2C] tap-major weights")
+    wp = _dense(w_tap, "dwconv3_gate_pool.w_tap", shape=(9, C2))
+    bp = _dense(bias, "dwconv3_gate_pool.bias", n=C2)
     C = C2 // 2
-    out = torch.empty((B, H, W, C), device=t.device, dtype=torch.float32)
-    pooled = torch.empty((B, C), device=t.device, dtype=torch.float32)
+    out, op, _ = _out(None, "dwconv3_gate_pool.out", (B, H, W, C), t.device, kind="dense")
+    pooled, pp, _ = _out(None, "dwconv3_gate_pool.pooled", (B, C), t.device, kind="dense")
+    nwork = int(_L().ff_dwconv3_gate_pool_workspace(C) if B == 1 else _L().ff_dwconv3_gate_pool_images_workspace(B, C))
+    work = torch.empty(nwork, device=t.device, dtype=torch.float32)
+    workp = _image(work, "dwconv3_gate_pool.work")
     if B == 1:
-        nwork = int(_L().ff_dwconv3_gate_pool_workspace(C))
-        work = torch.empty(nwork, device=t.device, dtype=torch.float32)
-        _lib.check(_L().ff_dwconv3_gate_pool(tp, ldi, out.data_ptr(), C, H, W, C, w_tap.data_ptr(), bias.data_ptr(), pooled.data_ptr(),
-                                             work.data_ptr(), nwork, _stream()))
+        _lib.check(_L().ff_dwconv3_gate_pool(tp, ldi, op, C, H, W, C, wp, bp, pp, workp, nwork, _stream()))
     else:
-        nwork = int(_L().ff_dwconv3_gate_pool_images_workspace(B, C))
-        work = torch.empty(nwork, device=t.device, dtype=torch.float32)
-        _lib.check(_L().ff_dwconv3_gate_pool_images(tp, ldi, out.data_ptr(), C, B, H, W, C, w_tap.data_ptr(), bias.data_ptr(),
-                                                    pooled.data_ptr(), work.data_ptr(), nwork, _stream()))
+        _lib.check(_L().ff_dwconv3_gate_pool_images(tp, ldi, op, C, B, H, W, C, wp, bp, pp, workp, nwork, _stream()))
     _note(2.0 * B * H * W * C2 * 9, 4.0 * B * H * W * (C2 + C))
     return out, pooled
 
 
+@_instrument
 def naf_front(x: T, pk: dict, ln_g: T, ln_b: T, w_tap: T, dw_bias: T, eps: float = 1e-6):
     """x [B,H,W,C] (C = 64 / 128) -> (SimpleGate(dw3x3(conv1(LayerNorm2d(x)))) [B,H,W,C], its per-channel mean [B,C]) in one launch;
     pk = prep.pack_token_linear(conv1 weight [2C, C], bias), w_tap [9, 2C] tap-major depth-wise weights.  B > 1: one launch for
     the batch (ff_naf_front_images), every image with the bits of its own B == 1 call."""
     xp, ldx, B, H, W, C = _nhwc(x, "naf_front.x")
-    if B < 1 or C not in (64, 128) or pk["N"] != 2 * C or pk["K"] != C or pk["kpad"] != C or tuple(w_tap.shape) != (9, 2 * C):
+    if B < 1 or C not in (64, 128) or pk["N"] != 2 * C or pk["K"] != C or pk["kpad"] != C:
         raise _lib.FFError("naf_front: expects [B,H,W,C] with B >= 1, C in (64, 128), conv1 packed as [2C, C], [9, 2C] tap-major weights")
-    out = torch.empty((B, H, W, C), device=x.device, dtype=torch.float32)
-    pooled = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    gp, bp = _dense(ln_g, "naf_front.ln_g", n=C), _dense(ln_b, "naf_front.ln_b", n=C)
+    tapp = _dense(w_tap, "naf_front.w_tap", shape=(9, 2 * C))
+    dbp = _dense(dw_bias, "naf_front.dw_bias", n=2 * C)
+    wp, wbp = _image(pk["w"], "naf_front.pk.w"), _image(pk["b"], "naf_front.pk.b")
+    nt = _nterms()
+    out, op, _ = _out(None, "naf_front.out", (B, H, W, C), x.device, kind="dense")
+    pooled, pp, _ = _out(None, "naf_front.pooled", (B, C), x.device, kind="dense")
+    nwork = int(_L().ff_naf_front_workspace(H, W, C) if B == 1 else _L().ff_naf_front_images_workspace(B, H, W, C))
+    work = torch.empty(nwork, device=x.device, dtype=torch.float32)
+    workp = _image(work, "naf_front.work")
     if B == 1:
-        nwork = int(_L().ff_naf_front_workspace(H, W, C))
-        work = torch.empty(nwork, device=x.device, dtype=torch.float32)
-        _lib.check(_L().ff_naf_front(xp, ldx, H, W, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b"].data_ptr(),
-                                     w_tap.data_ptr(), dw_bias.data_ptr(), out.data_ptr(), C, pooled.data_ptr(), work.data_ptr(), nwork,
-                                     _nterms(), _stream()))
+        _lib.check(_L().ff_naf_front(xp, ldx, H, W, C, gp, bp, float(eps), wp, wbp, tapp, dbp, op, C, pp, workp, nwork, nt, _stream()))
     else:
-        nwork = int(_L().ff_naf_front_images_workspace(B, H, W, C))
-        work = torch.empty(nwork, device=x.device, dtype=torch.float32)
-        _lib.check(_L().ff_naf_front_images(xp, ldx, B, H, W, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(),
-                                            pk["b"].data_ptr(), w_tap.data_ptr(), dw_bias.data_ptr(), out.data_ptr(), C, pooled.data_ptr(),
-                                            work.data_ptr(), nwork, _nterms(), _stream()))
+        _lib.check(_L().ff_naf_front_images(xp, ldx, B, H, W, C, gp, bp, float(eps), wp, wbp, tapp, dbp, op, C, pp, workp, nwork, nt,
+                                            _stream()))
     _note(2.0 * B * H * W * 2 * C * (C + 9), 4.0 * B * H * W * 2 * C)
     return out, pooled
 
 
-def _dense_out(out: Optional[T], like: T, name: str) -> T:
-    """A fresh dense fp32 tensor of like's shape, or the caller's `out` when it is one (e.g. a leading slice of a batch's buffer)."""
-    if out is None:
-        return torch.empty(tuple(like.shape), device=like.device, dtype=torch.float32)
-    _chk(out, name + ".out")
-    if tuple(out.shape) != tuple(like.shape) or not out.is_contiguous():
-        raise _lib.FFError(f"{name}: out must be a contiguous float32 tensor of shape {tuple(like.shape)}")
-    return out
-
-
+@_instrument
 def naf_ffn(y: T, pk: dict, ln_g: T, ln_b: T, out_scale: T, eps: float = 1e-6, out: Optional[T] = None) -> T:
     """y + out_scale * conv5(SimpleGate(conv4(LayerNorm(y)))) in one launch (C = 64 / 128, bf16x3)."""
-    yp, ldy, rows, C = rows_view(y, "naf_ffn.y")
+    yp, ldy, rows, C = _rows(y, "naf_ffn.y")
     if C != pk["C"]:
         raise _lib.FFError("naf_ffn: channel mismatch")
-    out = _dense_out(out, y, "naf_ffn")
-    _lib.check(_L().ff_naf_ffn(yp, ldy, out.data_ptr(), C, rows, C, ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(),
-                               pk["b4"].data_ptr(), pk["b5"].data_ptr(), out_scale.data_ptr(), _nterms(), _stream()))
+    gp, bp = _dense(ln_g, "naf_ffn.ln_g", n=C), _dense(ln_b, "naf_ffn.ln_b", n=C)
+    sp = _dense(out_scale, "naf_ffn.out_scale", n=C)
+    wp, b4p, b5p = _images(pk, "naf_ffn.pk", "w", "b4", "b5")
+    nt = _nterms()
+    # a fresh dense tensor of y's shape, or the caller's `out` when it is one (e.g. a leading slice of a batch's buffer)
+    out, op, _ = _out(out, "naf_ffn.out", tuple(y.shape), y.device, kind="dense")
+    _lib.check(_L().ff_naf_ffn(yp, ldy, op, C, rows, C, gp, bp, float(eps), wp, b4p, b5p, sp, nt, _stream()))
     _note(2.0 * rows * C * 3 * C, 8.0 * rows * C)
     return out
 
 
+@_instrument
 def naf_tail(g: T, x: T, pk: dict, sca: T, beta: T, ln_g: T, ln_b: T, gamma: T, eps: float = 1e-6, out: Optional[T] = None) -> T:
     """The NAFBlock tail in one launch (C = 64 / 128, plain bf16 only): y = x + beta * conv3(g * sca), then
     y + gamma * conv5(SimpleGate(conv4(LayerNorm(y)))); bit-equal to linear(g, W3, b3, res=x, mul=beta, kmul=sca) followed by
@@ -1013,44 +1052,37 @@ def naf_tail(g: T, x: T, pk: dict, sca: T, beta: T, ln_g: T, ln_b: T, gamma: T, 
     scaled by sca[b], in one launch (ff_naf_tail_images; every image with the bits of its own call)."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError(f"naf_tail exists for the plain-bf16 contraction mode only, not {_GEMM_MODE!r}")
-    gp, ldg, rows, C = rows_view(g, "naf_tail.g")
-    xp, ldx, xr, xc = rows_view(x, "naf_tail.x")
-    if C != pk["C"] or xr != rows or xc != C or tuple(x.shape) != tuple(g.shape):
+    gp, ldg, rows, C = _rows(g, "naf_tail.g", C=pk["C"])
+    xp, ldx, *_ = _rows(x, "naf_tail.x", rows, C)
+    if tuple(x.shape) != tuple(g.shape):
         raise _lib.FFError("naf_tail: shape mismatch")
     images = sca.shape[0] if isinstance(sca, torch.Tensor) and sca.dim() == 2 and sca.shape[0] > 1 else 1
+    if images > 1 and (g.dim() < 2 or g.shape[0] != images):
+        raise _lib.FFError(f"naf_tail: sca {tuple(sca.shape)} must be a contiguous [B, {C}] matrix with B the leading dimension of g {tuple(g.shape)}")
+    scap = _dense(sca, "naf_tail.sca", shape=(images, C)) if images > 1 else _dense(sca, "naf_tail.sca", n=C)
+    bep, gap = _dense(beta, "naf_tail.beta", n=C), _dense(gamma, "naf_tail.gamma", n=C)
+    lgp, lbp = _dense(ln_g, "naf_tail.ln_g", n=C), _dense(ln_b, "naf_tail.ln_b", n=C)
+    wp, b3p, b4p, b5p = _images(pk, "naf_tail.pk", "w", "b3", "b4", "b5")
+    out, op, _ = _out(out, "naf_tail.out", tuple(x.shape), x.device, kind="dense")
     if images > 1:
-        _chk(sca, "naf_tail.sca")
-        if g.dim() < 2 or g.shape[0] != images or tuple(sca.shape) != (images, C) or not sca.is_contiguous():
-            raise _lib.FFError(f"naf_tail: sca {tuple(sca.shape)} must be a contiguous [B, {C}] matrix with B the leading dimension of g {tuple(g.shape)}")
-    for t_, n_ in ((beta, "beta"), (ln_g, "ln_g"), (ln_b, "ln_b"), (gamma, "gamma")) + (() if images > 1 else ((sca, "sca"),)):
-        _chk(t_, "naf_tail." + n_)
-        if t_.numel() != C or not t_.is_contiguous():
-            raise _lib.FFError(f"naf_tail: {n_} must be a contiguous [{C}] vector")
-    out = _dense_out(out, x, "naf_tail")
-    if images > 1:
-        _lib.check(_L().ff_naf_tail_images(gp, ldg, xp, ldx, out.data_ptr(), C, rows, C, sca.data_ptr(), images, rows // images,
-                                           pk["b3"].data_ptr(), beta.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), float(eps),
-                                           pk["w"].data_ptr(), pk["b4"].data_ptr(), pk["b5"].data_ptr(), gamma.data_ptr(), _stream()))
+        _lib.check(_L().ff_naf_tail_images(gp, ldg, xp, ldx, op, C, rows, C, scap, images, rows // images, b3p, bep, lgp, lbp, float(eps),
+                                           wp, b4p, b5p, gap, _stream()))
     else:
-        _lib.check(_L().ff_naf_tail(gp, ldg, xp, ldx, out.data_ptr(), C, rows, C, sca.data_ptr(), pk["b3"].data_ptr(), beta.data_ptr(),
-                                    ln_g.data_ptr(), ln_b.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b4"].data_ptr(),
-                                    pk["b5"].data_ptr(), gamma.data_ptr(), _stream()))
+        _lib.check(_L().ff_naf_tail(gp, ldg, xp, ldx, op, C, rows, C, scap, b3p, bep, lgp, lbp, float(eps), wp, b4p, b5p, gap, _stream()))
     _note(2.0 * rows * C * 4 * C, 12.0 * rows * C)
     return out
 
 
+@_instrument
 def layernorm(x: T, gamma: T, beta: T, eps: float = 1e-5, out: Optional[T] = None, out_bf16: bool = False) -> T:
     """out_bf16: bf16 output rows, (bf16) of the fp32 result, for a consumer that rounds them to bf16 anyway."""
-    xp, ldi, rows, C = rows_view(x, "layernorm.x")
-    if out is None:
-        out = empty_rows_bf16(tuple(x.shape), x.device) if out_bf16 else empty_like_rows(x)
-    elif (out.dtype == torch.bfloat16) != out_bf16:
+    xp, ldi, rows, C = _rows(x, "layernorm.x")
+    if out is not None and (out.dtype == torch.bfloat16) != out_bf16:
         raise _lib.FFError("layernorm: out dtype does not match out_bf16")
-    op, ldo, orows, oc = rows_view(out, "layernorm.out|bf16ok" if out_bf16 else "layernorm.out")
-    if orows != rows or oc != C or gamma.numel() != C or beta.numel() != C:
-        raise _lib.FFError("layernorm: shape mismatch")
+    gp, bp = _dense(gamma, "layernorm.gamma", n=C), _dense(beta, "layernorm.beta", n=C)
+    out, op, ldo = _out(out, "layernorm.out", tuple(x.shape), x.device, bf16=out_bf16)
     fn = _L().ff_layernorm_bf16out if out_bf16 else _L().ff_layernorm
-    _lib.check(fn(xp, ldi, op, ldo, rows, C, gamma.data_ptr(), beta.data_ptr(), float(eps), _stream()))
+    _lib.check(fn(xp, ldi, op, ldo, rows, C, gp, bp, float(eps), _stream()))
     _note(0.0, (6.0 if out_bf16 else 8.0) * rows * C)
     return out
 
@@ -1061,106 +1093,113 @@ def pool_partials(x: T):
     B == 1 call writes them."""
     xp, ld, B, H, W, C = _nhwc(x, "pool_partials.x")
     P = H * W
-    if B != 1:
-        if B < 1 or P % 256:
-            raise _lib.FFError(f"pool_partials: a batch needs images of a multiple of 256 pixels, got {tuple(x.shape)}")
-        rows = int(_L().ff_pool_partials_images_rows(B, P))
-        part = torch.empty((rows, C), device=x.device, dtype=torch.float32)
-        _lib.check(_L().ff_pool_partials_images(xp, ld, B, P, C, part.data_ptr(), part.numel(), _stream()))
-        return PoolPartials(part, C, 1.0 / float(P), images=B)
-    rows = int(_L().ff_pool_partial_rows(P))
-    part = torch.empty((rows, C), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_pool_partials(xp, ld, P, C, part.data_ptr(), part.numel(), _stream()))
-    return PoolPartials(part, C, 1.0 / float(P))
+    if B != 1 and (B < 1 or P % 256):
+        raise _lib.FFError(f"pool_partials: a batch needs images of a multiple of 256 pixels, got {tuple(x.shape)}")
+    rows = int(_L().ff_pool_partial_rows(P) if B == 1 else _L().ff_pool_partials_images_rows(B, P))
+    part, pp, _ = _out(None, "pool_partials.part", (rows, C), x.device, kind="dense")
+    if B == 1:
+        _lib.check(_L().ff_pool_partials(xp, ld, P, C, pp, part.numel(), _stream()))
+    else:
+        _lib.check(_L().ff_pool_partials_images(xp, ld, B, P, C, pp, part.numel(), _stream()))
+    return PoolPartials(part, C, 1.0 / float(P), images=B)
 
 
+@_instrument
 def pool_mean(x: T) -> T:
     """[B,H,W,C] rows view -> [B,C]."""
     xp, ld, B, H, W, C = _nhwc(x, "pool_mean.x")
     P = H * W
     nwork = int(_L().ff_pool_mean_workspace(B, P, C))
     work = torch.empty(nwork, device=x.device, dtype=torch.float32)
-    out = torch.empty((B, C), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_pool_mean(xp, ld, B, P, C, out.data_ptr(), work.data_ptr(), nwork, _stream()))
+    out, op, _ = _out(None, "pool_mean.out", (B, C), x.device, kind="dense")
+    _lib.check(_L().ff_pool_mean(xp, ld, B, P, C, op, _image(work, "pool_mean.work"), nwork, _stream()))
     _note(0.0, 4.0 * B * P * C)
     return out
 
 
+@_instrument
 def vec_mlp(v, W1: T, b1: Optional[T], act1, W2: Optional[T] = None, b2: Optional[T] = None, act2=None,
             post: float = 1.0) -> T:
     """act2(W2 . act1(W1 . v + b1) + b2) * post per row of v [B, Cin] (W2 None: one layer).  v may be a PoolPartials: the pool is
     then finished inside the same launch (two-layer form with a hidden width <= 64), otherwise finished first."""
-    if isinstance(v, PoolPartials):
-        if W2 is not None and W1.shape[0] <= 64 and v.C <= 512:
-            if W1.shape[1] != v.C or W2.shape[1] != W1.shape[0]:
-                raise _lib.FFError("vec_mlp: weight shape mismatch")
-            out = torch.empty((v.images, W2.shape[0]), device=v.part.device, dtype=torch.float32)
-            if v.images > 1:                                 # one workgroup per image, each in the single-image summation order
-                _lib.check(_L().ff_pool_vec_mlp_images(v.part.data_ptr(), v.images, v.rows_per_image, v.part.shape[1], v.inv_count, v.C,
-                                                       W1.data_ptr(), _ptr(b1), W1.shape[0], ACT[act1], W2.data_ptr(), _ptr(b2), W2.shape[0],
-                                                       ACT[act2], float(post), out.data_ptr(), None, _stream()))
-                return out
-            _lib.check(_L().ff_pool_vec_mlp(v.part.data_ptr(), v.part.shape[0], v.part.shape[1], v.inv_count, v.C, W1.data_ptr(), _ptr(b1),
-                                            W1.shape[0], ACT[act1], W2.data_ptr(), _ptr(b2), W2.shape[0], ACT[act2], float(post),
-                                            out.data_ptr(), None, _stream()))
-            return out
-        v = v.mean()
-    B, Cin = v.shape
+    vp = None if isinstance(v, PoolPartials) else _dense(v, "vec_mlp.v", shape=(None, None))
+    for t_, n_ in ((W1, "W1"),) + (() if W2 is None else ((W2, "W2"),)):
+        _dev(t_, "vec_mlp." + n_, _F32)
+        if t_.dim() < 2:
+            raise _lib.FFError(f"vec_mlp.{n_}: expected a [out, in] matrix, got {tuple(t_.shape)}")
     Ch = W1.shape[0]
+    fused = vp is None and W2 is not None and Ch <= 64 and v.C <= 512
+    Cin = v.C if vp is None else v.shape[1]
     Cout = W2.shape[0] if W2 is not None else Ch
     if W1.shape[1] != Cin or (W2 is not None and W2.shape[1] != Ch):
         raise _lib.FFError("vec_mlp: weight shape mismatch")
-    out = torch.empty((B, Cout), device=v.device, dtype=torch.float32)
-    _lib.check(_L().ff_vec_mlp(v.data_ptr(), B, Cin, W1.data_ptr(), _ptr(b1), Ch, ACT[act1], _ptr(W2), _ptr(b2), Cout,
-                               ACT[act2], float(post), out.data_ptr(), _stream()))
+    w1p, b1p = _dense(W1, "vec_mlp.W1", n=Ch * Cin), _dense(b1, "vec_mlp.b1", n=Ch, optional=True)
+    w2p, b2p = _dense(W2, "vec_mlp.W2", n=Cout * Ch, optional=True), _dense(b2, "vec_mlp.b2", n=Cout, optional=True)
+    if fused:
+        vp = _dense(v.part, "vec_mlp.v.part", shape=(v.images * v.rows_per_image, None))
+        out, op, _ = _out(None, "vec_mlp.out", (v.images, Cout), v.part.device, kind="dense")
+        if v.images > 1:                                 # one workgroup per image, each in the single-image summation order
+            _lib.check(_L().ff_pool_vec_mlp_images(vp, v.images, v.rows_per_image, v.part.shape[1], v.inv_count, v.C, w1p, b1p, Ch,
+                                                   ACT[act1], w2p, b2p, Cout, ACT[act2], float(post), op, None, _stream()))
+        else:
+            _lib.check(_L().ff_pool_vec_mlp(vp, v.part.shape[0], v.part.shape[1], v.inv_count, v.C, w1p, b1p, Ch, ACT[act1], w2p, b2p,
+                                            Cout, ACT[act2], float(post), op, None, _stream()))
+        return out
+    if vp is None:
+        v = v.mean()
+        vp = _dense(v, "vec_mlp.v", shape=(None, Cin))
+    B = v.shape[0]
+    out, op, _ = _out(None, "vec_mlp.out", (B, Cout), v.device, kind="dense")
+    _lib.check(_L().ff_vec_mlp(vp, B, Cin, w1p, b1p, Ch, ACT[act1], w2p, b2p, Cout, ACT[act2], float(post), op, _stream()))
     return out
 
 
+@_instrument
 def pixel_mlp(x: T, W1: T, b1: Optional[T], act1, w2: T, b2: float, act2) -> T:
     """[..., C] rows -> [..., 1]: act2(w2 . act1(W1 x + b1) + b2) per row, hidden width <= 16 (fp32, one launch)."""
-    xp, ldi, rows, C = rows_view(x, "pixel_mlp.x")
+    xp, ldi, rows, C = _rows(x, "pixel_mlp.x")
+    w1p = _dense(W1, "pixel_mlp.W1", shape=(None, C))
     Hd = W1.shape[0]
-    if tuple(W1.shape) != (Hd, C) or w2.numel() != Hd or not W1.is_contiguous():
-        raise _lib.FFError("pixel_mlp: weight shape mismatch")
-    out = torch.empty(tuple(x.shape[:-1]) + (1,), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_pixel_mlp(xp, ldi, rows, C, Hd, W1.data_ptr(), _ptr(b1), ACT[act1], w2.reshape(-1).data_ptr(), float(b2), ACT[act2],
-                                 out.data_ptr(), _stream()))
+    b1p = _dense(b1, "pixel_mlp.b1", n=Hd, optional=True)
+    _dev(w2, "pixel_mlp.w2", _F32)
+    w2p = _dense(w2.reshape(-1), "pixel_mlp.w2", n=Hd)
+    out, op, _ = _out(None, "pixel_mlp.out", tuple(x.shape[:-1]) + (1,), x.device, kind="dense")
+    _lib.check(_L().ff_pixel_mlp(xp, ldi, rows, C, Hd, w1p, b1p, ACT[act1], w2p, float(b2), ACT[act2], op, _stream()))
     _note(2.0 * rows * C * Hd, 4.0 * rows * (C + 1))
     return out
 
 
+@_instrument
 def dwconv2d(x: T, w_tap: T, bias: Optional[T] = None, *, ksize=(3, 3), stride=(1, 1), pad=(1, 1),
              post_scale: Optional[T] = None, post_shift: Optional[T] = None, act=None, out: Optional[T] = None,
              mul_in: Optional[T] = None) -> T:
     xp, ldi, B, H, W, C = _nhwc(x, "dwconv2d.x")
     KH, KW = ksize
-    if tuple(w_tap.shape) != (KH * KW, C) or not w_tap.is_contiguous():
-        raise _lib.FFError(f"dwconv2d: tap-major weight must be [{KH * KW},{C}]")
+    wp = _dense(w_tap, "dwconv2d.w_tap", shape=(KH * KW, C))
     Ho = (H + 2 * pad[0] - KH) // stride[0] + 1
     Wo = (W + 2 * pad[1] - KW) // stride[1] + 1
+    bp = _dense(bias, "dwconv2d.bias", n=C, optional=True)
+    psp = _dense(post_scale, "dwconv2d.post_scale", n=C, optional=True)
+    php = _dense(post_shift, "dwconv2d.post_shift", n=C, optional=True)
     if out is None:
-        out = empty_rows((B, Ho, Wo, C), x.device)
-    op, ldo, *_ = _nhwc(out, "dwconv2d.out")
-    mp, ldm = None, 0
-    if mul_in is not None:
-        mp, ldm, mb, mh, mw, mc = _nhwc(mul_in, "dwconv2d.mul_in")
-        if (mb, mh, mw, mc) != (B, Ho, Wo, C):
-            raise _lib.FFError("dwconv2d: mul_in shape mismatch")
-    _lib.check(_L().ff_dwconv2d(xp, ldi, op, ldo, B, H, W, C, Ho, Wo, w_tap.data_ptr(), _ptr(bias), KH, KW, stride[0],
-                                stride[1], pad[0], pad[1], _ptr(post_scale), _ptr(post_shift), ACT[act], mp, ldm, _stream()))
+        out, op, ldo = _out(None, "dwconv2d.out", (B, Ho, Wo, C), x.device, kind="nhwc")
+    else:                                                    # the caller's buffer: any NHWC rows view, as before
+        op, ldo, *_ = _nhwc(out, "dwconv2d.out")
+    mp, ldm, *_ = _nhwc(mul_in, "dwconv2d.mul_in", (B, Ho, Wo, C), optional=True)
+    _lib.check(_L().ff_dwconv2d(xp, ldi, op, ldo, B, H, W, C, Ho, Wo, wp, bp, KH, KW, stride[0], stride[1], pad[0], pad[1], psp, php,
+                                ACT[act], mp, ldm, _stream()))
     _note(2.0 * B * Ho * Wo * C * KH * KW, 4.0 * (B * H * W * C + B * Ho * Wo * C))
     return out
 
 
+@_instrument
 def token_linear_gated(x: T, x2: T, pk: dict, cm: T, gb2: float, *, res: Optional[T] = None) -> T:
     """res + W (x * cm[channel] + x2 * sm[token]) + b with sm = sigmoid(gw2 . gelu(GW1 x + gb1) + gb2) in one launch (bf16x3);
     pk from prep.pack_token_linear_gated.  cm [K] (or [1,K]): one channel gate for every row.  cm [B,K] with B > 1: the rows are B images of
     a multiple of 256 rows each, image b gated by cm[b], in one launch (ff_token_linear_gated_images) -- bit-equal to B calls."""
-    xp, ldx, rows, K = rows_view(x, "token_linear_gated.x")
-    x2p, ldx2, r2, k2 = rows_view(x2, "token_linear_gated.x2")
-    _chk(cm, "token_linear_gated.cm")
-    if r2 != rows or k2 != K or K != pk["K"]:
-        raise _lib.FFError("token_linear_gated: shape mismatch")
+    xp, ldx, rows, K = _rows(x, "token_linear_gated.x", C=pk["K"])
+    x2p, ldx2, *_ = _rows(x2, "token_linear_gated.x2", rows, K)
+    _dev(cm, "token_linear_gated.cm", _F32)
     images = 1
     if cm.numel() != K:                                      # (refusals first: nothing is launched before them)
         if cm.dim() != 2 or cm.shape[1] != K or cm.shape[0] < 1 or not cm.is_contiguous():
@@ -1168,161 +1207,126 @@ def token_linear_gated(x: T, x2: T, pk: dict, cm: T, gb2: float, *, res: Optiona
         images = int(cm.shape[0])
         if rows % images or (rows // images) % 256:
             raise _lib.FFError(f"token_linear_gated: a per-image gate needs B = {images} images of a multiple of 256 rows, got {rows} rows")
+    cmp_ = _dense(cm, "token_linear_gated.cm", n=images * K)
     N = pk["N"]
-    out = empty_rows(tuple(x.shape[:-1]) + (N,), x.device)
-    op, ldo, _, _ = rows_view(out, "token_linear_gated.out")
-    rp, ldr = None, 0
-    if res is not None:
-        rp, ldr, rr, rc = rows_view(res, "token_linear_gated.res")
-        if rr != rows or rc != N:
-            raise _lib.FFError("token_linear_gated: res shape mismatch")
+    rp, ldr, *_ = _rows(res, "token_linear_gated.res", rows, N, optional=True)
+    gb1p, gw2p, wp, wbp = _images(pk, "token_linear_gated.pk", "gb1", "gw2", "w", "b")
+    nt = _nterms()
+    out, op, ldo = _out(None, "token_linear_gated.out", tuple(x.shape[:-1]) + (N,), x.device)
     if images > 1:
-        _lib.check(_L().ff_token_linear_gated_images(xp, ldx, x2p, ldx2, cm.data_ptr(), images, rows // images, pk["gb1"].data_ptr(),
-                                                     pk["gw2"].data_ptr(), float(gb2), op, ldo, rows, K, N, pk["nt"], pk["w"].data_ptr(),
-                                                     pk["b"].data_ptr(), rp, ldr, _nterms(), _stream()))
+        _lib.check(_L().ff_token_linear_gated_images(xp, ldx, x2p, ldx2, cmp_, images, rows // images, gb1p, gw2p, float(gb2), op, ldo,
+                                                     rows, K, N, pk["nt"], wp, wbp, rp, ldr, nt, _stream()))
     else:
-        _lib.check(_L().ff_token_linear_gated(xp, ldx, x2p, ldx2, cm.data_ptr(), None, pk["gb1"].data_ptr(), pk["gw2"].data_ptr(), float(gb2),
-                                              op, ldo, rows, K, N, pk["nt"], pk["w"].data_ptr(), pk["b"].data_ptr(), rp, ldr, _nterms(), _stream()))
+        _lib.check(_L().ff_token_linear_gated(xp, ldx, x2p, ldx2, cmp_, None, gb1p, gw2p, float(gb2), op, ldo, rows, K, N, pk["nt"], wp,
+                                              wbp, rp, ldr, nt, _stream()))
     _note(2.0 * rows * N * K + 2.0 * rows * 32 * K, 4.0 * rows * (2 * K + N * (2 if res is not None else 1)))
     return out
 
 
+@_instrument
 def dwconv3x3_ln(x: T, w_tap: T, bias: Optional[T], stats: T, gamma: T, beta: T, mul_in: Optional[T] = None) -> T:
     """(dw3x3(LayerNorm(x)) + bias) * mul_in with the LayerNorm applied on load from per-token (mean, rstd) `stats`."""
     xp, ldi, B, H, W, C = _nhwc(x, "dwconv3x3_ln.x")
-    if tuple(w_tap.shape) != (9, C) or tuple(stats.shape) != (B * H * W, 2) or gamma.numel() != C or beta.numel() != C:
-        raise _lib.FFError("dwconv3x3_ln: shape mismatch")
-    out = empty_rows((B, H, W, C), x.device)
-    op, ldo, *_ = _nhwc(out, "dwconv3x3_ln.out")
-    mp, ldm = None, 0
-    if mul_in is not None:
-        mp, ldm, mb, mh, mw, mc = _nhwc(mul_in, "dwconv3x3_ln.mul_in")
-        if (mb, mh, mw, mc) != (B, H, W, C):
-            raise _lib.FFError("dwconv3x3_ln: mul_in shape mismatch")
-    _lib.check(_L().ff_dwconv3x3_ln(xp, ldi, op, ldo, B, H, W, C, w_tap.data_ptr(), _ptr(bias), stats.data_ptr(), gamma.data_ptr(),
-                                    beta.data_ptr(), mp, ldm, _stream()))
+    wp = _dense(w_tap, "dwconv3x3_ln.w_tap", shape=(9, C))
+    bp = _dense(bias, "dwconv3x3_ln.bias", n=C, optional=True)
+    sp = _dense(stats, "dwconv3x3_ln.stats", shape=(B * H * W, 2))
+    gp, bep = _dense(gamma, "dwconv3x3_ln.gamma", n=C), _dense(beta, "dwconv3x3_ln.beta", n=C)
+    out, op, ldo = _out(None, "dwconv3x3_ln.out", (B, H, W, C), x.device, kind="nhwc")
+    mp, ldm, *_ = _nhwc(mul_in, "dwconv3x3_ln.mul_in", (B, H, W, C), optional=True)
+    _lib.check(_L().ff_dwconv3x3_ln(xp, ldi, op, ldo, B, H, W, C, wp, bp, sp, gp, bep, mp, ldm, _stream()))
     _note(2.0 * B * H * W * C * 9, 4.0 * B * H * W * C * (3 if mul_in is not None else 2))
     return out
 
 
+@_instrument
 def sgfn_tail(y: T, c2: int, w_tap: T, dw_bias: Optional[T], stats: T, gamma: T, beta: T, w2: T, b2: Optional[T], res: Optional[T] = None) -> T:
     """res + fc2(y[..., :c2] * (dw3x3(LayerNorm(y[..., c2:2 c2])) + dw_bias)) + b2 in one launch (plain bf16; csrc/sgfn_tail.hip).
     y [B,H,W,>= 2 c2] rows view (fc1's output), stats [B*H*W, 2] = (mean, rstd) of y[..., c2:], w_tap [9, c2], w2 [N, c2]."""
     if _GEMM_MODE != "bf16":
         raise _lib.FFError("sgfn_tail exists for the plain-bf16 contraction mode only")
     yp, ldh, B, H, W, Cy = _nhwc(y, "sgfn_tail.y")
+    _dev(w2, "sgfn_tail.w2", _F32)
+    if w2.dim() != 2 or w2.shape[1] != c2:
+        raise _lib.FFError(f"sgfn_tail.w2: expected [N, {c2}], got {tuple(w2.shape)}")
     N = w2.shape[0]
-    if Cy < 2 * c2 or tuple(w_tap.shape) != (9, c2) or tuple(stats.shape) != (B * H * W, 2) or gamma.numel() != c2 or beta.numel() != c2 \
-            or w2.shape[1] != c2:
+    if Cy < 2 * c2:
         raise _lib.FFError("sgfn_tail: shape mismatch")
+    tapp = _dense(w_tap, "sgfn_tail.w_tap", shape=(9, c2))
+    dbp = _dense(dw_bias, "sgfn_tail.dw_bias", n=c2, optional=True)
+    sp = _dense(stats, "sgfn_tail.stats", shape=(B * H * W, 2))
+    gp, bep = _dense(gamma, "sgfn_tail.gamma", n=c2), _dense(beta, "sgfn_tail.beta", n=c2)
+    b2p = _dense(b2, "sgfn_tail.b2", n=N, optional=True)
+    rp, ldr, *_ = _nhwc(res, "sgfn_tail.res", (B, H, W, N), optional=True)
     from . import prep as _prep
     tiles = PREPARED.get(w2, "sgfn", lambda: _prep.pack_sgfn_fc2(w2))
-    out = empty_rows((B, H, W, N), y.device)
-    op, ldo, *_ = _nhwc(out, "sgfn_tail.out")
-    rp, ldr = None, 0
-    if res is not None:
-        if tuple(res.shape) != (B, H, W, N):
-            raise _lib.FFError("sgfn_tail: res shape mismatch")
-        rp, ldr, *_ = _nhwc(res, "sgfn_tail.res")
-    _lib.check(_L().ff_sgfn_tail(yp, ldh, c2, stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w_tap.data_ptr(), _ptr(dw_bias),
-                                 tiles.data_ptr(), tiles.shape[0], _ptr(b2), rp, ldr, op, ldo, B, H, W, N, _stream()))
+    out, op, ldo = _out(None, "sgfn_tail.out", (B, H, W, N), y.device, kind="nhwc")
+    _lib.check(_L().ff_sgfn_tail(yp, ldh, c2, sp, gp, bep, tapp, dbp, _image(tiles, "sgfn_tail.w2[sgfn]"), tiles.shape[0], b2p, rp, ldr,
+                                 op, ldo, B, H, W, N, _stream()))
     _note(2.0 * B * H * W * c2 * (9 + N), 4.0 * B * H * W * (2 * c2 + 2 * N))
     return out
 
 
+@_instrument
 def mix2(a: T, b: Optional[T] = None, *, ka: float = 1.0, kb: float = 1.0, ca: Optional[T] = None,
          cb: Optional[T] = None, pa: Optional[T] = None, pb: Optional[T] = None, clamp01: bool = False,
          out: Optional[T] = None) -> T:
     """out = ka*a*ca[c]*pa[p] + kb*b*cb[c]*pb[p].  ca [B, C] with B > 1: the rows are B equal groups (one image each) and group b is scaled
     by ca[b], in one launch (ff_mix2_images) -- every image with the bits of its own call with ca[b]."""
-    ap, lda, rows, C = rows_view(a, "mix2.a")
-    bp, ldb = None, 0
-    if b is not None:
-        bp, ldb, brows, bc = rows_view(b, "mix2.b")
-        if brows != rows or bc != C:
-            raise _lib.FFError("mix2: a/b shape mismatch")
-    if out is None:
-        out = empty_like_rows(a)
-    op, ldo, orows, oc = rows_view(out, "mix2.out")
-    if orows != rows or oc != C:
-        raise _lib.FFError("mix2: out shape mismatch")
-
-    def pvec(p, nm):
-        if p is None:
-            return None, 0
-        pp, ldp, prows, pc = rows_view(p, nm)
-        if prows != rows or pc != 1:
-            raise _lib.FFError(f"{nm}: per-row vector must be [rows,1]")
-        return pp, ldp
-
-    pap, ldpa = pvec(pa, "mix2.pa")
-    pbp, ldpb = pvec(pb, "mix2.pb")
+    ap, lda, rows, C = _rows(a, "mix2.a")
+    bp, ldb, *_ = _rows(b, "mix2.b", rows, C, optional=True)
+    out, op, ldo = _out(out, "mix2.out", tuple(a.shape), a.device)
+    pap, ldpa, *_ = _rows(pa, "mix2.pa", rows, 1, optional=True)     # per-row vectors [rows, 1]
+    pbp, ldpb, *_ = _rows(pb, "mix2.pb", rows, 1, optional=True)
     images = 1
-    if ca is not None and ca.dim() == 2 and ca.shape[0] > 1:
+    if isinstance(ca, torch.Tensor) and ca.dim() == 2 and ca.shape[0] > 1:
         images = int(ca.shape[0])
-        _chk(ca, "mix2.ca")
-        if ca.shape[1] != C or not ca.is_contiguous() or rows % images:
+        if ca.shape[1] != C or rows % images:
             raise _lib.FFError(f"mix2: ca {tuple(ca.shape)} must be a contiguous [B, {C}] matrix with B dividing the {rows} rows")
-    for v_, nm in ((ca, "ca"), (cb, "cb")):
-        if v_ is not None and v_.numel() != C * (images if nm == "ca" else 1):
-            raise _lib.FFError(f"mix2: {nm} must have {C} elements")
+    cap = _dense(ca, "mix2.ca", n=C * images, optional=True)
+    cbp = _dense(cb, "mix2.cb", n=C, optional=True)
     if images > 1:
-        _lib.check(_L().ff_mix2_images(op, ldo, ap, lda, bp, ldb, rows, C, float(ka), float(kb), ca.data_ptr(), images, rows // images,
-                                       _ptr(cb), pap, ldpa, pbp, ldpb, int(clamp01), _stream()))
-        _note(0.0, 4.0 * rows * C * (3 if b is not None else 2))
-        return out
-    _lib.check(_L().ff_mix2(op, ldo, ap, lda, bp, ldb, rows, C, float(ka), float(kb), _ptr(ca), _ptr(cb), pap, ldpa, pbp,
-                            ldpb, int(clamp01), _stream()))
+        _lib.check(_L().ff_mix2_images(op, ldo, ap, lda, bp, ldb, rows, C, float(ka), float(kb), cap, images, rows // images,
+                                       cbp, pap, ldpa, pbp, ldpb, int(clamp01), _stream()))
+    else:
+        _lib.check(_L().ff_mix2(op, ldo, ap, lda, bp, ldb, rows, C, float(ka), float(kb), cap, cbp, pap, ldpa, pbp, ldpb, int(clamp01),
+                                _stream()))
     _note(0.0, 4.0 * rows * C * (3 if b is not None else 2))
     return out
 
 
+@_instrument
 def fma3(a: Optional[T], b: T, c: T, alpha: float = 1.0, out: Optional[T] = None) -> T:
-    bp, ldb, rows, C = rows_view(b, "fma3.b")
-    cp, ldc, crows, cc = rows_view(c, "fma3.c")
-    if crows != rows or cc != C:
-        raise _lib.FFError("fma3: b/c shape mismatch")
-    ap, lda = None, 0
-    if a is not None:
-        ap, lda, arows, ac = rows_view(a, "fma3.a")
-        if arows != rows or ac != C:
-            raise _lib.FFError("fma3: a shape mismatch")
-    if out is None:
-        out = empty_like_rows(b)
-    op, ldo, orows, oc = rows_view(out, "fma3.out")
-    if orows != rows or oc != C:
-        raise _lib.FFError("fma3: out shape mismatch")
+    bp, ldb, rows, C = _rows(b, "fma3.b")
+    cp, ldc, *_ = _rows(c, "fma3.c", rows, C)
+    ap, lda, *_ = _rows(a, "fma3.a", rows, C, optional=True)
+    out, op, ldo = _out(out, "fma3.out", tuple(b.shape), b.device)
     _lib.check(_L().ff_fma3(op, ldo, ap, lda, bp, ldb, cp, ldc, rows, C, float(alpha), _stream()))
     _note(0.0, 4.0 * rows * C * (4 if a is not None else 3))
     return out
 
 
+@_instrument
 def affine(x: T, scale: T, shift: T, act=None, out: Optional[T] = None) -> T:
-    xp, ldi, rows, C = rows_view(x, "affine.x")
-    if out is None:
-        out = empty_like_rows(x)
-    op, ldo, orows, oc = rows_view(out, "affine.out")
-    if orows != rows or oc != C or scale.numel() != C or shift.numel() != C:
-        raise _lib.FFError("affine: shape mismatch")
-    _lib.check(_L().ff_affine(op, ldo, xp, ldi, rows, C, scale.data_ptr(), shift.data_ptr(), ACT[act], _stream()))
+    xp, ldi, rows, C = _rows(x, "affine.x")
+    scp, shp = _dense(scale, "affine.scale", n=C), _dense(shift, "affine.shift", n=C)
+    out, op, ldo = _out(out, "affine.out", tuple(x.shape), x.device)
+    _lib.check(_L().ff_affine(op, ldo, xp, ldi, rows, C, scp, shp, ACT[act], _stream()))
     _note(0.0, 8.0 * rows * C)
     return out
 
 
 def u8_to_f32_image(img_u8: T) -> T:
     """uint8 HWC [H,W,3] on the device -> fp32 [1,3,H,W] in [0,1] (reference io.py:64-68)."""
-    if not (isinstance(img_u8, torch.Tensor) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3
-            and img_u8.shape[2] == 3 and img_u8.is_contiguous()):
-        raise _lib.FFError("u8_to_f32_image: expected a contiguous CUDA(HIP) uint8 [H,W,3] tensor")
+    ip = _dense(img_u8, "u8_to_f32_image.img_u8", _U8, shape=(None, None, 3))
     H, W, _ = img_u8.shape
-    out = torch.empty((1, 3, H, W), device=img_u8.device, dtype=torch.float32)
-    _lib.check(_L().ff_u8hwc_to_f32nchw(img_u8.data_ptr(), out.data_ptr(), H, W, _stream()))
+    out, op, _ = _out(None, "u8_to_f32_image.out", (1, 3, H, W), img_u8.device, kind="dense")
+    _lib.check(_L().ff_u8hwc_to_f32nchw(ip, op, H, W, _stream()))
     return out
 
 
 def f32_to_u8_image(x: T) -> T:
     """fp32 [1,3,H,W] (or [3,H,W]) -> uint8 HWC [H,W,3]: clamp, *255, round half to even (reference io.py:71-76)."""
-    _chk(x, "f32_to_u8_image.x")
+    _dev(x, "f32_to_u8_image.x", _F32)
     if x.dim() == 4:
         if x.shape[0] != 1:
             raise _lib.FFError("f32_to_u8_image: batch must be 1")
@@ -1332,35 +1336,35 @@ def f32_to_u8_image(x: T) -> T:
     x = x.contiguous()
     _, H, W = x.shape
     out = torch.empty((H, W, 3), device=x.device, dtype=torch.uint8)
-    _lib.check(_L().ff_f32nchw_to_u8hwc(x.data_ptr(), out.data_ptr(), H, W, _stream()))
+    _lib.check(_L().ff_f32nchw_to_u8hwc(_dense(x, "f32_to_u8_image.x"), _dense(out, "f32_to_u8_image.out", _U8), H, W, _stream()))
     return out
 
 
+@_instrument
 def nchw_to_nhwc(x: T, Hp: Optional[int] = None, Wp: Optional[int] = None, add: Optional[T] = None,
                  pad_mode: str = "zero", out: Optional[T] = None) -> T:
-    _chk(x, "nchw_to_nhwc.x")
+    _dev(x, "nchw_to_nhwc.x", _F32)
     x = x.contiguous()
+    xp = _dense(x, "nchw_to_nhwc.x", shape=(None, None, None, None))
     B, C, H, W = x.shape
     Hp, Wp = Hp or H, Wp or W
+    addp = _dense(add, "nchw_to_nhwc.add", n=C, optional=True)
     if out is None:
         out = empty_rows((B, Hp, Wp, C), x.device)
-    op, ldo, *_ = _nhwc(out, "nchw_to_nhwc.out")
-    _lib.check(_L().ff_nchw_to_nhwc(x.data_ptr(), op, B, C, H, W, Hp, Wp, ldo, _ptr(add), 1 if pad_mode == "reflect" else 0,
+    op, ldo, *_ = _nhwc(out, "nchw_to_nhwc.out")             # the caller's buffer: any NHWC rows view, as before
+    _lib.check(_L().ff_nchw_to_nhwc(xp, op, B, C, H, W, Hp, Wp, ldo, addp, 1 if pad_mode == "reflect" else 0,
                                     _stream()))
     return out
 
 
+@_instrument
 def nhwc_to_nchw(x: T, H: Optional[int] = None, W: Optional[int] = None, add: Optional[T] = None, clamp01: bool = False,
                  out: Optional[T] = None) -> T:
     xp, ldi, B, Hs, Ws, C = _nhwc(x, "nhwc_to_nchw.x")
     H, W = H or Hs, W or Ws
-    if out is None:
-        out = torch.empty((B, C, H, W), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "nhwc_to_nchw.out")
-        if tuple(out.shape) != (B, C, H, W) or not out.is_contiguous():
-            raise _lib.FFError(f"nhwc_to_nchw: out must be a contiguous [{B},{C},{H},{W}] tensor")
-    _lib.check(_L().ff_nhwc_to_nchw(xp, out.data_ptr(), B, C, H, W, Hs, Ws, ldi, _ptr(add), int(clamp01), _stream()))
+    addp = _dense(add, "nhwc_to_nchw.add", n=C, optional=True)
+    out, op, _ = _out(out, "nhwc_to_nchw.out", (B, C, H, W), x.device, kind="dense")
+    _lib.check(_L().ff_nhwc_to_nchw(xp, op, B, C, H, W, Hs, Ws, ldi, addp, int(clamp01), _stream()))
     return out
 
 
@@ -1372,6 +1376,7 @@ def _aten_scale(n_in: int, n_out: int, scale_factor: Optional[float]) -> float:
     return float(np.float32(n_in) / np.float32(n_out))
 
 
+@_instrument
 def resize(x: T, size: Tuple[int, int], *, mode: str = "bilinear", scale_factor: Optional[float] = None,
            layout: str = "nhwc", out: Optional[T] = None, mul: float = 1.0) -> T:
     """x NHWC rows view [B,H,W,C] or planar [B,C,H,W] (layout='nchw'); out is always NHWC (may be a channel slice)."""
@@ -1380,15 +1385,15 @@ def resize(x: T, size: Tuple[int, int], *, mode: str = "bilinear", scale_factor:
         xp, ld, B, Hi, Wi, C = _nhwc(x, "resize.x")
         isb, isc, isy, isx = Hi * Wi * ld, 1, Wi * ld, ld
     else:
-        _chk(x, "resize.x")
+        _dev(x, "resize.x", _F32)
         x = x.contiguous()
+        xp = _dense(x, "resize.x", shape=(None, None, None, None))
         B, C, Hi, Wi = x.shape
-        xp = x.data_ptr()
         isb, isc, isy, isx = C * Hi * Wi, Hi * Wi, Wi, 1
     if out is None:
         out = torch.empty((B, Ho, Wo, C), device=x.device, dtype=torch.float32)
-    op, ldo, ob, oh, ow, oc = _nhwc(out, "resize.out")      # out may be larger than (Ho, Wo): the top-left region is written
-    if ob != B or oc != C or oh < Ho or ow < Wo:
+    op, ldo, _, oh, ow, _ = _nhwc(out, "resize.out", (B, None, None, C))   # out may be larger than (Ho, Wo): the top-left region is written
+    if oh < Ho or ow < Wo:
         raise _lib.FFError("resize: out shape mismatch")
     sh = _aten_scale(Hi, Ho, scale_factor)
     sw = _aten_scale(Wi, Wo, scale_factor)
@@ -1398,189 +1403,216 @@ def resize(x: T, size: Tuple[int, int], *, mode: str = "bilinear", scale_factor:
     return out
 
 
+@_instrument
 def avgpool2(x: T) -> T:
     xp, ldi, B, H, W, C = _nhwc(x, "avgpool2.x")
-    out = torch.empty((B, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_avgpool2(xp, ldi, out.data_ptr(), C, B, H, W, C, _stream()))
+    out, op, _ = _out(None, "avgpool2.out", (B, H // 2, W // 2, C), x.device, kind="dense")
+    _lib.check(_L().ff_avgpool2(xp, ldi, op, C, B, H, W, C, _stream()))
     return out
 
 
 def _planar_images(x: T, out: T, name: str):
-    """Planar image(s) [3,H,W] or contiguous [B,3,H,W] and their NHWC output [B,H,W,>=..] -> (B, H, W, out pointer, ldo)."""
-    _chk(x, name + ".x")
+    """Planar image(s) [3,H,W] or contiguous [B,3,H,W] and their NHWC output [B,H,W,>=..] -> (x pointer, B, C, H, W, out pointer, ldo)."""
+    xp = _dense(x, name + ".x")
     B = int(x.shape[0]) if x.dim() == 4 else 1
     C, H, W = x.shape[-3:]
     op, ldo, ob, oh, ow, _ = _nhwc(out, name + ".out")
-    if B > 1 and (not x.is_contiguous() or C != 3 or (ob, oh, ow) != (B, H, W)):
+    if B > 1 and (C != 3 or (ob, oh, ow) != (B, H, W)):
         raise _lib.FFError(f"{name}: expected contiguous planar images [B,3,H,W] and out [B,H,W,.], got {tuple(x.shape)} and {tuple(out.shape)}")
     if B > 1 and out.stride(0) != H * W * ldo:
         raise _lib.FFError(f"{name}: the images of out must follow each other ([B,H,W,ld] rows)")
-    return B, C, H, W, op, ldo
+    return xp, B, C, H, W, op, ldo
 
 
+@_instrument
 def dct8_bands(x_planar: T, dct_mat: T, masks3: T, band_scale: T, out: T, ch_off: int):
     """x_planar [3,H,W] (or [1,3,H,W]); [B,3,H,W] with B > 1: the batch in one launch (ff_dct8_bands_images)."""
-    B, C, H, W, op, ldo = _planar_images(x_planar, out, "dct8_bands")
+    xp, B, C, H, W, op, ldo = _planar_images(x_planar, out, "dct8_bands")
+    dp, mp = _dense(dct_mat, "dct8_bands.dct_mat", n=64), _dense(masks3, "dct8_bands.masks3", n=3 * 64)
+    sp = _dense(band_scale, "dct8_bands.band_scale", n=3)
     if B > 1:
-        _lib.check(_L().ff_dct8_bands_images(x_planar.data_ptr(), B, H, W, dct_mat.data_ptr(), masks3.data_ptr(), band_scale.data_ptr(),
-                                             op, ldo, ch_off, _stream()))
-        return
-    _lib.check(_L().ff_dct8_bands(x_planar.data_ptr(), C, H, W, dct_mat.data_ptr(), masks3.data_ptr(), band_scale.data_ptr(),
-                                  op, ldo, ch_off, _stream()))
+        _lib.check(_L().ff_dct8_bands_images(xp, B, H, W, dp, mp, sp, op, ldo, ch_off, _stream()))
+    else:
+        _lib.check(_L().ff_dct8_bands(xp, C, H, W, dp, mp, sp, op, ldo, ch_off, _stream()))
 
 
+@_instrument
 def dwt_pass(x_planar: T, axis: int, lo8: T, hi8: T) -> Tuple[T, T]:
-    _chk(x_planar, "dwt_pass.x")
+    xp = _dense(x_planar, "dwt_pass.x", shape=(None, None, None))
     C, H, W = x_planar.shape
+    lp, hp = _dense(lo8, "dwt_pass.lo8", n=8), _dense(hi8, "dwt_pass.hi8", n=8)
     Ho = (H + 6) // 2 + 1 if axis == 0 else H
     Wo = (W + 6) // 2 + 1 if axis == 1 else W
     lo = torch.empty((C, Ho, Wo), device=x_planar.device, dtype=torch.float32)
     hi = torch.empty_like(lo)
-    _lib.check(_L().ff_dwt_pass(x_planar.data_ptr(), C, H, W, axis, lo8.data_ptr(), hi8.data_ptr(), lo.data_ptr(),
-                                hi.data_ptr(), _stream()))
+    _lib.check(_L().ff_dwt_pass(xp, C, H, W, axis, lp, hp, _dense(lo, "dwt_pass.lo"), _dense(hi, "dwt_pass.hi"), _stream()))
     return lo, hi
 
 
+@_instrument
 def fft_bands(x_planar: T, twW: Tuple[T, T], twH: Tuple[T, T], mask_logits: T, temp: float, band_scale2: T, out: T,
               ch_lo: int, ch_hi: int):
-    B, C, H, W, op, ldo = _planar_images(x_planar, out, "fft_bands")
+    xp, B, C, H, W, op, ldo = _planar_images(x_planar, out, "fft_bands")
+    _dev(mask_logits, "fft_bands.mask_logits", _F32)
     msz = mask_logits.shape[-1]
+    tw = (_dense(twW[0], "fft_bands.twW[0]", n=W), _dense(twW[1], "fft_bands.twW[1]", n=W),
+          _dense(twH[0], "fft_bands.twH[0]", n=H), _dense(twH[1], "fft_bands.twH[1]", n=H))
+    mp = _dense(mask_logits, "fft_bands.mask_logits", n=msz * msz)
+    sp = _dense(band_scale2, "fft_bands.band_scale2", n=2)
     if B > 1:                                                # the batch through one run of the four kernels (ff_fft_bands_images)
         nwork = int(_L().ff_fft_bands_images_workspace(B, H, W))
         if nwork < 0:
             raise _lib.FFError(f"fft_bands: no batched form for {tuple(x_planar.shape)}")
-        work = torch.empty(nwork, device=x_planar.device, dtype=torch.float32)
-        _lib.check(_L().ff_fft_bands_images(x_planar.data_ptr(), B, H, W, twW[0].data_ptr(), twW[1].data_ptr(), twH[0].data_ptr(),
-                                            twH[1].data_ptr(), mask_logits.data_ptr(), msz, float(temp), band_scale2.data_ptr(),
-                                            work.data_ptr(), nwork, op, ldo, ch_lo, ch_hi, _stream()))
-        return
-    nwork = 4 * C * H * (W // 2 + 1)
+    else:
+        nwork = 4 * C * H * (W // 2 + 1)
     work = torch.empty(nwork, device=x_planar.device, dtype=torch.float32)
-    _lib.check(_L().ff_fft_bands(x_planar.data_ptr(), C, H, W, twW[0].data_ptr(), twW[1].data_ptr(), twH[0].data_ptr(),
-                                 twH[1].data_ptr(), mask_logits.data_ptr(), msz, float(temp), band_scale2.data_ptr(),
-                                 work.data_ptr(), nwork, op, ldo, ch_lo, ch_hi, _stream()))
+    workp = _image(work, "fft_bands.work")
+    if B > 1:
+        _lib.check(_L().ff_fft_bands_images(xp, B, H, W, *tw, mp, msz, float(temp), sp, workp, nwork, op, ldo, ch_lo, ch_hi, _stream()))
+    else:
+        _lib.check(_L().ff_fft_bands(xp, C, H, W, *tw, mp, msz, float(temp), sp, workp, nwork, op, ldo, ch_lo, ch_hi, _stream()))
 
 
+@_instrument
 def chan_attn_weights(qkv: T, q_off: int, k_off: int, temperature: T) -> T:
-    qp, ld, rows, C = rows_view(qkv, "chan_attn_weights.qkv")
+    qp, ld, rows, C = _rows(qkv, "chan_attn_weights.qkv")
+    tp = _dense(temperature, "chan_attn_weights.temperature", n=6)      # one per head: six heads of 30 channels
     nwork = int(_L().ff_chan_attn_workspace(rows))
     work = torch.empty(nwork, device=qkv.device, dtype=torch.float32)
-    wbd = torch.empty((180, 180), device=qkv.device, dtype=torch.float32)
-    _lib.check(_L().ff_chan_attn_weights(qp, ld, q_off, k_off, rows, temperature.data_ptr(), wbd.data_ptr(), work.data_ptr(),
-                                         nwork, _stream()))
+    wbd, wbdp, _ = _out(None, "chan_attn_weights.wbd", (180, 180), qkv.device, kind="dense")
+    _lib.check(_L().ff_chan_attn_weights(qp, ld, q_off, k_off, rows, tp, wbdp, _image(work, "chan_attn_weights.work"), nwork, _stream()))
     return wbd
 
 
+@_instrument
 def chan_qkv_attn(x: T, pk: dict, gamma: T, beta: T, temperature: T, eps: float = 1e-5):
     """DAT channel attention front end in two launches (ff_chan_qkv + ff_chan_attn_finish): x [..., 180] ->
     (v [..., 180], block-diagonal attention matrix [180, 180]); q and k never reach memory.
     x [B,H,W,180] with B > 1 (H * W a multiple of 256): still two launches -- ff_chan_qkv's partials are per 256-token workgroup, so one call
     covers the batch, and ff_chan_attn_finish_images reduces every image's own blocks in the single-image order -> wbd [B,180,180], every
     image's matrix (and v) with the bits of its own call."""
-    xp, ldx, rows, K = rows_view(x, "chan_qkv_attn.x")
+    xp, ldx, rows, K = _rows(x, "chan_qkv_attn.x")
     if K != pk["K"]:
         raise _lib.FFError("chan_qkv_attn: K mismatch")
     images = int(x.shape[0]) if x.dim() == 4 and x.shape[0] > 1 else 1
-    if images > 1:
-        if (rows // images) % 256:
-            raise _lib.FFError(f"chan_qkv_attn: a batch needs images of a multiple of 256 tokens, got {tuple(x.shape)}")
-        v = empty_like_rows(x)
-        vp, ldv, _, _ = rows_view(v, "chan_qkv_attn.v")
-        nwork = int(_L().ff_chan_qkv_images_workspace(images, rows // images))
-        work = torch.empty(nwork, device=x.device, dtype=torch.float32)
-        wbd = torch.empty((images, 180, 180), device=x.device, dtype=torch.float32)
-        _lib.check(_L().ff_chan_qkv(xp, ldx, rows, K, gamma.data_ptr(), beta.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b"].data_ptr(),
-                                    vp, ldv, work.data_ptr(), nwork, _nterms(), _stream()))
-        _lib.check(_L().ff_chan_attn_finish_images(work.data_ptr(), nwork, images, rows // images, temperature.data_ptr(), wbd.data_ptr(),
-                                                   _stream()))
-        _note(2.0 * rows * 576 * K + 2.0 * rows * 6 * 32 * 32, 8.0 * rows * K)
-        return v, wbd
-    v = empty_like_rows(x)
-    vp, ldv, _, _ = rows_view(v, "chan_qkv_attn.v")
-    nwork = int(_L().ff_chan_qkv_workspace(rows))
+    if images > 1 and (rows // images) % 256:
+        raise _lib.FFError(f"chan_qkv_attn: a batch needs images of a multiple of 256 tokens, got {tuple(x.shape)}")
+    gp, bp = _dense(gamma, "chan_qkv_attn.gamma", n=K), _dense(beta, "chan_qkv_attn.beta", n=K)
+    tp = _dense(temperature, "chan_qkv_attn.temperature", n=6)          # one per head: six heads of 30 channels
+    wp, wbp = _image(pk["w"], "chan_qkv_attn.pk.w"), _image(pk["b"], "chan_qkv_attn.pk.b")
+    nt = _nterms()
+    v, vp, ldv = _out(None, "chan_qkv_attn.v", tuple(x.shape), x.device)
+    nwork = int(_L().ff_chan_qkv_images_workspace(images, rows // images)) if images > 1 else int(_L().ff_chan_qkv_workspace(rows))
     work = torch.empty(nwork, device=x.device, dtype=torch.float32)
-    wbd = torch.empty((180, 180), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_chan_qkv(xp, ldx, rows, K, gamma.data_ptr(), beta.data_ptr(), float(eps), pk["w"].data_ptr(), pk["b"].data_ptr(),
-                                vp, ldv, work.data_ptr(), nwork, _nterms(), _stream()))
-    _lib.check(_L().ff_chan_attn_finish(work.data_ptr(), nwork, (rows + 255) // 256, temperature.data_ptr(), wbd.data_ptr(), _stream()))
+    workp = _image(work, "chan_qkv_attn.work")
+    wbd, wbdp, _ = _out(None, "chan_qkv_attn.wbd", (images, 180, 180) if images > 1 else (180, 180), x.device, kind="dense")
+    _lib.check(_L().ff_chan_qkv(xp, ldx, rows, K, gp, bp, float(eps), wp, wbp, vp, ldv, workp, nwork, nt, _stream()))
+    if images > 1:
+        _lib.check(_L().ff_chan_attn_finish_images(workp, nwork, images, rows // images, tp, wbdp, _stream()))
+    else:
+        _lib.check(_L().ff_chan_attn_finish(workp, nwork, (rows + 255) // 256, tp, wbdp, _stream()))
     _note(2.0 * rows * 576 * K + 2.0 * rows * 6 * 32 * 32, 8.0 * rows * K)
     return v, wbd
 
 
+@_instrument
 def band_mha_core(qkv: T, P: int, nbands: int, heads: int) -> T:
-    _chk(qkv, "band_mha_core.qkv")
+    _dev(qkv, "band_mha_core.qkv", _F32)
     E = qkv.shape[-1] // 3
-    out = torch.empty((P * nbands, E), device=qkv.device, dtype=torch.float32)
-    _lib.check(_L().ff_band_mha_core(qkv.data_ptr(), out.data_ptr(), P, nbands, heads, _stream()))
+    qp = _dense(qkv, "band_mha_core.qkv", n=P * nbands * 3 * E)
+    out, op, _ = _out(None, "band_mha_core.out", (P * nbands, E), qkv.device, kind="dense")
+    _lib.check(_L().ff_band_mha_core(qp, op, P, nbands, heads, _stream()))
     return out
 
 
+@_instrument
 def band_weight(x: T, att: T, imp: T) -> T:
-    out = torch.empty_like(x)
+    xp = _dense(x, "band_weight.x")
+    nb = x.shape[-1] // 3
     P = x.numel() // x.shape[-1]
-    _lib.check(_L().ff_band_weight(x.data_ptr(), att.data_ptr(), imp.data_ptr(), out.data_ptr(), P, x.shape[-1] // 3, _stream()))
+    ap, ip = _dense(att, "band_weight.att", n=P * nb), _dense(imp, "band_weight.imp", n=nb)
+    out = torch.empty_like(x)
+    _lib.check(_L().ff_band_weight(xp, ap, ip, _dense(out, "band_weight.out"), P, nb, _stream()))
     return out
 
 
+@_instrument
 def freq_guidance(b3: T) -> T:
+    bp = _dense(b3, "freq_guidance.b3")
     P = b3.numel() // 9
-    out = torch.empty(tuple(b3.shape[:-1]) + (3,), device=b3.device, dtype=torch.float32)
-    _lib.check(_L().ff_freq_guidance(b3.data_ptr(), out.data_ptr(), P, _stream()))
+    out, op, _ = _out(None, "freq_guidance.out", tuple(b3.shape[:-1]) + (3,), b3.device, kind="dense")
+    _lib.check(_L().ff_freq_guidance(bp, op, P, _stream()))
     return out
 
 
+@_instrument
 def dynamic_gates(graw: T, dif: T) -> T:
+    gp = _dense(graw, "dynamic_gates.graw")
     P = graw.numel() // 3
+    dp = _dense(dif, "dynamic_gates.dif", n=P)
     out = torch.empty_like(graw)
-    _lib.check(_L().ff_dynamic_gates(graw.data_ptr(), dif.data_ptr(), out.data_ptr(), P, _stream()))
+    _lib.check(_L().ff_dynamic_gates(gp, dp, _dense(out, "dynamic_gates.out"), P, _stream()))
     return out
 
 
+@_instrument
 def fuse_blend(experts9: T, hier3: T, guide3: T, gates3: T, dif1: T) -> T:
     """experts9 [B,Hh,Wh,9], hier3 [B,Hh,Wh,3], guide3 / gates3 [B,Hl,Wl,3], dif1 [B,Hl,Wl,1], all contiguous -> [B,Hh,Wh,3]; B > 1 in one
     launch (ff_fuse_blend_images)."""
+    ep = _dense(experts9, "fuse_blend.experts9", shape=(None, None, None, 9))
     B, Hh, Wh, _ = experts9.shape
+    gp = _dense(guide3, "fuse_blend.guide3", shape=(B, None, None, 3))
     _, Hl, Wl, _ = guide3.shape
-    out = torch.empty((B, Hh, Wh, 3), device=experts9.device, dtype=torch.float32)
+    hp, tp = _dense(hier3, "fuse_blend.hier3", shape=(B, Hh, Wh, 3)), _dense(gates3, "fuse_blend.gates3", shape=(B, Hl, Wl, 3))
+    dp = _dense(dif1, "fuse_blend.dif1", n=B * Hl * Wl)
+    out, op, _ = _out(None, "fuse_blend.out", (B, Hh, Wh, 3), experts9.device, kind="dense")
     if B > 1:
-        for t, c, hw in ((experts9, 9, (Hh, Wh)), (hier3, 3, (Hh, Wh)), (guide3, 3, (Hl, Wl)), (gates3, 3, (Hl, Wl)), (dif1, 1, (Hl, Wl))):
-            _chk(t, "fuse_blend")
-            if tuple(t.shape) != (B, *hw, c) or not t.is_contiguous():
-                raise _lib.FFError(f"fuse_blend: a batch needs contiguous [{B},{hw[0]},{hw[1]},{c}] tensors, got {tuple(t.shape)}")
-        _lib.check(_L().ff_fuse_blend_images(experts9.data_ptr(), hier3.data_ptr(), guide3.data_ptr(), gates3.data_ptr(), dif1.data_ptr(),
-                                             out.data_ptr(), B, Hh, Wh, Hl, Wl, _stream()))
-        return out
-    _lib.check(_L().ff_fuse_blend(experts9.data_ptr(), hier3.data_ptr(), guide3.data_ptr(), gates3.data_ptr(), dif1.data_ptr(),
-                                  out.data_ptr(), Hh, Wh, Hl, Wl, _stream()))
+        if tuple(dif1.shape) != (B, Hl, Wl, 1):
+            raise _lib.FFError(f"fuse_blend: a batch needs contiguous [{B},{Hl},{Wl},1] tensors, got {tuple(dif1.shape)}")
+        _lib.check(_L().ff_fuse_blend_images(ep, hp, gp, tp, dp, op, B, Hh, Wh, Hl, Wl, _stream()))
+    else:
+        _lib.check(_L().ff_fuse_blend(ep, hp, gp, tp, dp, op, Hh, Wh, Hl, Wl, _stream()))
     return out
 
 
+@_instrument
 def tile_accum(tile: T, wy: T, wx: T, acc: T, wsum: T, sy: int, sx: int):
     """acc [1,C,H,W] += tile [1,C,th,tw] * (wy x wx) at (sy, sx); wsum [1,1,H,W] += wy x wx."""
-    for t_, n_ in ((tile, "tile"), (wy, "wy"), (wx, "wx"), (acc, "acc"), (wsum, "wsum")):
-        _chk(t_, "tile_accum." + n_)
+    _dev(tile, "tile_accum.tile", _F32)
+    if tile.dim() != 4:
+        raise _lib.FFError(f"tile_accum.tile: expected [1,C,th,tw], got {tuple(tile.shape)}")
     _, C, th, tw = tile.shape
+    ap = _dense(acc, "tile_accum.acc", shape=(None, C, None, None))
     _, _, H, W = acc.shape
-    _lib.check(_L().ff_tile_accum(tile.contiguous().data_ptr(), C, th, tw, wy.data_ptr(), wx.data_ptr(), acc.data_ptr(),
-                                  wsum.data_ptr(), H, W, sy, sx, _stream()))
+    tp = _dense(tile.contiguous(), "tile_accum.tile")
+    wyp, wxp = _dense(wy, "tile_accum.wy", n=th), _dense(wx, "tile_accum.wx", n=tw)
+    wsp = _dense(wsum, "tile_accum.wsum", n=H * W)
+    _lib.check(_L().ff_tile_accum(tp, C, th, tw, wyp, wxp, ap, wsp, H, W, sy, sx, _stream()))
 
 
+@_instrument
 def tile_normalize(acc: T, wsum: T):
+    ap = _dense(acc, "tile_normalize.acc", shape=(None, None, None, None))
     _, C, H, W = acc.shape
-    _lib.check(_L().ff_tile_normalize(acc.data_ptr(), wsum.data_ptr(), C, H, W, _stream()))
-
+    wp = _dense(wsum, "tile_normalize.wsum", n=H * W)
+    _lib.check(_L().ff_tile_normalize(ap, wp, C, H, W, _stream()))
 
 
 D4_CODES = 16
 
 
+def _d4_code(code) -> int:
+    c = int(code)
+    if not 0 <= c < D4_CODES:
+        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    return c
+
+
 def d4_check_codes(codes, H: int, W: int):
     """Host-side validation of augmentation codes (bit 0 hflip, bit 1 vflip, bits 2-3 k of rot90) for planes of H x W -> list of ints.
     Odd k swaps H and W: a batch must come out with one shape, so it needs square planes."""
-    cl = [int(c) for c in codes]
+    cl = [_d4_code(c) for c in codes]
     for c in cl:
-        if not 0 <= c < D4_CODES:
-            raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
         if (c >> 2) & 1 and H != W:
             raise _lib.FFError(f"d4 code {c} rotates by an odd quarter turn, which needs square planes, got {H}x{W}")
     return cl
@@ -1591,24 +1623,18 @@ def d4_nchw(x: T, codes, out: Optional[T] = None, codes_dev: Optional[T] = None)
     codes[b] = hflip | vflip << 1 | k << 2, applied as flip(-1), flip(-2), rot90(k, (-2, -1)).  `codes` is a host sequence (checked
     here, before any launch); codes_dev, when given, is the same list already on the device (int32 [B]) so that the eight tensors
     of a micro-batch share one upload."""
-    _chk(x, "d4_nchw.x")
-    if x.dim() != 4 or not x.is_contiguous():
-        raise _lib.FFError("d4_nchw: expected a contiguous [B,C,H,W] tensor")
+    xp = _dense(x, "d4_nchw.x", shape=(None, None, None, None))
     B, C, H, W = x.shape
     cl = d4_check_codes(codes, H, W)
     if len(cl) != B:
         raise _lib.FFError(f"d4_nchw: {len(cl)} codes for a batch of {B}")
     if codes_dev is None:
         codes_dev = torch.tensor(cl, dtype=torch.int32).to(x.device)
-    elif codes_dev.dtype != torch.int32 or not codes_dev.is_cuda or codes_dev.numel() != B or not codes_dev.is_contiguous():
-        raise _lib.FFError("d4_nchw: codes_dev must be a contiguous int32 device tensor of B elements")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _chk(out, "d4_nchw.out")
-        if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
-            raise _lib.FFError("d4_nchw: out must be a distinct contiguous tensor of x's shape")
-    _lib.check(_L().ff_d4_nchw(x.data_ptr(), out.data_ptr(), B, C, H, W, codes_dev.data_ptr(), _stream()))
+    cp = _dense(codes_dev, "d4_nchw.codes_dev", _I32, n=B)
+    out, op, _ = _out(out, "d4_nchw.out", tuple(x.shape), x.device, kind="dense")
+    if op == xp:
+        raise _lib.FFError("d4_nchw: out must be a distinct contiguous tensor of x's shape")
+    _lib.check(_L().ff_d4_nchw(xp, op, B, C, H, W, cp, _stream()))
     return out
 
 
@@ -1621,9 +1647,7 @@ def d4_inverse_code(code: int) -> int:
     """The d4 code whose transform undoes `code` (both read as flip(-1), flip(-2), rot90(k), in that order).  rot^k after exactly one
     flip is a reflection of the square, hence its own inverse; with none or both flips set (both = a half turn) the transform is a
     rotation, and its inverse keeps the flips and turns back: k' = (4 - k) % 4."""
-    c = int(code)
-    if not 0 <= c < D4_CODES:
-        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    c = _d4_code(code)
     if (c & 1) != ((c >> 1) & 1):
         return c
     return (c & 3) | (((4 - (c >> 2)) % 4) << 2)
@@ -1632,9 +1656,7 @@ def d4_inverse_code(code: int) -> int:
 def d4_canonical_code(code: int) -> int:
     """The code in 0..7 (D4_ENSEMBLE) that names the same symmetry as `code`: a half turn is both flips, so k >= 2 toggles both flip
     bits and keeps k - 2."""
-    c = int(code)
-    if not 0 <= c < D4_CODES:
-        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    c = _d4_code(code)
     return c if c < 8 else ((c & 3) ^ 3) | ((c >> 2) - 2) << 2
 
 
@@ -1642,26 +1664,21 @@ def d4_rect(x: T, code: int, out: Optional[T] = None, accum: bool = False, scale
     """ONE symmetry (`code` as in d4_nchw: flip(-1), flip(-2), rot90(k, (-2, -1))) of a planar [B,C,H,W] tensor of any H, W: the result
     is [B,C,H,W] for even k and [B,C,W,H] for odd k.  accum=False: out = t * scale; accum=True: out = (out + t) * scale, the add
     rounded before the multiply.  Everything is checked here, before the launch; `out` must not overlap x."""
-    _chk(x, "d4_rect.x")
-    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+    xp = _dense(x, "d4_rect.x", shape=(None, None, None, None))
+    if x.numel() == 0:
         raise _lib.FFError("d4_rect: expected a non-empty contiguous [B,C,H,W] tensor")
-    c = int(code)
-    if not 0 <= c < D4_CODES:
-        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    c = _d4_code(code)
     B, C, H, W = x.shape
     oshape = (B, C, W, H) if (c >> 2) & 1 else (B, C, H, W)
-    if out is None:
-        if accum:
-            raise _lib.FFError("d4_rect: accum=True needs the tensor to accumulate into (out)")
-        out = torch.empty(oshape, device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "d4_rect.out")
-        if tuple(out.shape) != oshape or not out.is_contiguous() or out.device != x.device:
-            raise _lib.FFError(f"d4_rect: out must be a contiguous {list(oshape)} tensor on x's device, got {list(out.shape)}")
-        nb = 4 * x.numel()
-        if out.data_ptr() < x.data_ptr() + nb and x.data_ptr() < out.data_ptr() + nb:
-            raise _lib.FFError("d4_rect: out overlaps x (the permutation is not in place)")
-    _lib.check(_L().ff_d4_rect_nchw(x.data_ptr(), out.data_ptr(), B, C, H, W, c, 1 if accum else 0, float(scale), _stream()))
+    if out is None and accum:
+        raise _lib.FFError("d4_rect: accum=True needs the tensor to accumulate into (out)")
+    if out is not None and isinstance(out, torch.Tensor) and out.device != x.device:
+        raise _lib.FFError(f"d4_rect: out must be a contiguous {list(oshape)} tensor on x's device, got {list(out.shape)}")
+    out, op, _ = _out(out, "d4_rect.out", oshape, x.device, kind="dense")
+    nb = 4 * x.numel()
+    if op < xp + nb and xp < op + nb:
+        raise _lib.FFError("d4_rect: out overlaps x (the permutation is not in place)")
+    _lib.check(_L().ff_d4_rect_nchw(xp, op, B, C, H, W, c, 1 if accum else 0, float(scale), _stream()))
     return out
 
 
@@ -1669,23 +1686,20 @@ def tile_cut_u8_d4(img_u8: T, code: int, y: int, x: int, th: int, tw: int, out: 
     """The th x tw tile at (y, x) of the TRANSFORMED image d4_rect(u8_to_f32_image(img_u8), code), which is never built: uint8 HWC
     [H,W,3] on the device -> fp32 [1,3,th,tw].  The transformed image is H x W for even k = code >> 2 and W x H for odd k; the tile
     must lie inside it.  Everything is checked here, before the launch."""
-    if not (isinstance(img_u8, torch.Tensor) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3
-            and img_u8.shape[2] == 3 and img_u8.is_contiguous() and img_u8.numel() > 0):
+    ip = _dense(img_u8, "tile_cut_u8_d4.img_u8", _U8, shape=(None, None, 3))
+    if img_u8.numel() == 0:
         raise _lib.FFError("tile_cut_u8_d4: expected a non-empty contiguous CUDA(HIP) uint8 [H,W,3] tensor")
-    c, y, x, th, tw = int(code), int(y), int(x), int(th), int(tw)
-    if not 0 <= c < D4_CODES:
-        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    c, y, x, th, tw = _d4_code(code), int(y), int(x), int(th), int(tw)
     H, W, _ = img_u8.shape
     Ht, Wt = (W, H) if (c >> 2) & 1 else (H, W)
     if th < 1 or tw < 1 or y < 0 or x < 0 or y + th > Ht or x + tw > Wt:
         raise _lib.FFError(f"tile_cut_u8_d4: the {th}x{tw} tile at ({y},{x}) leaves the {Ht}x{Wt} transformed image (code {c} of a {H}x{W} image)")
     if out is None:
         out = torch.empty((1, 3, th, tw), device=img_u8.device, dtype=torch.float32)
-    else:
-        _chk(out, "tile_cut_u8_d4.out")
-        if out.numel() != 3 * th * tw or not out.is_contiguous() or out.device != img_u8.device:
-            raise _lib.FFError(f"tile_cut_u8_d4: out must be a contiguous float32 tensor of 3x{th}x{tw} elements on the image's device")
-    _lib.check(_L().ff_tile_cut_u8_d4(img_u8.data_ptr(), H, W, c, y, x, th, tw, out.data_ptr(), _stream()))
+    op = _dense(out, "tile_cut_u8_d4.out", n=3 * th * tw)
+    if out.device != img_u8.device:
+        raise _lib.FFError(f"tile_cut_u8_d4: out must be a contiguous float32 tensor of 3x{th}x{tw} elements on the image's device")
+    _lib.check(_L().ff_tile_cut_u8_d4(ip, H, W, c, y, x, th, tw, op, _stream()))
     return out
 
 
@@ -1694,30 +1708,25 @@ def tile_fold_d4(acc: T, wsum: T, code: int, ens: Optional[T] = None, accum: boo
     (tile_normalize's arithmetic) and t = d4_rect(v, code):  accum=False: ens = t * scale;  accum=True: ens = (ens + t) * scale, the
     add rounded before the multiply.  acc [1,3,Hc,Wc] and wsum [1,1,Hc,Wc] are only read; ens is [1,3,Hc,Wc] for even k = code >> 2 and
     [1,3,Wc,Hc] for odd k, and must overlap neither.  Everything is checked here, before the launch."""
-    _chk(acc, "tile_fold_d4.acc")
-    _chk(wsum, "tile_fold_d4.wsum")
-    if acc.dim() != 4 or acc.shape[0] != 1 or acc.shape[1] != 3 or not acc.is_contiguous() or acc.numel() == 0:
+    ap = _dense(acc, "tile_fold_d4.acc", shape=(1, 3, None, None))
+    if acc.numel() == 0:
         raise _lib.FFError("tile_fold_d4: acc must be a non-empty contiguous [1,3,Hc,Wc] tensor")
     _, _, Hc, Wc = acc.shape
-    if wsum.numel() != Hc * Wc or tuple(wsum.shape[-2:]) != (Hc, Wc) or not wsum.is_contiguous() or wsum.device != acc.device:
+    wp = _dense(wsum, "tile_fold_d4.wsum", n=Hc * Wc)
+    if tuple(wsum.shape[-2:]) != (Hc, Wc) or wsum.device != acc.device:
         raise _lib.FFError(f"tile_fold_d4: wsum must be a contiguous [1,1,{Hc},{Wc}] tensor on acc's device, got {list(wsum.shape)}")
-    c = int(code)
-    if not 0 <= c < D4_CODES:
-        raise _lib.FFError(f"d4 code {c}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
+    c = _d4_code(code)
     oshape = (1, 3, Wc, Hc) if (c >> 2) & 1 else (1, 3, Hc, Wc)
-    if ens is None:
-        if accum:
-            raise _lib.FFError("tile_fold_d4: accum=True needs the tensor to accumulate into (ens)")
-        ens = torch.empty(oshape, device=acc.device, dtype=torch.float32)
-    else:
-        _chk(ens, "tile_fold_d4.ens")
-        if tuple(ens.shape) != oshape or not ens.is_contiguous() or ens.device != acc.device:
-            raise _lib.FFError(f"tile_fold_d4: ens must be a contiguous {list(oshape)} tensor on acc's device, got {list(ens.shape)}")
-        e0, e1 = ens.data_ptr(), ens.data_ptr() + 4 * ens.numel()
-        for t_, n_ in ((acc, "acc"), (wsum, "wsum")):
-            if e0 < t_.data_ptr() + 4 * t_.numel() and t_.data_ptr() < e1:
-                raise _lib.FFError(f"tile_fold_d4: ens overlaps {n_} (the fold is not in place)")
-    _lib.check(_L().ff_tile_fold_d4(acc.data_ptr(), wsum.data_ptr(), Hc, Wc, c, ens.data_ptr(), 1 if accum else 0, float(scale), _stream()))
+    if ens is None and accum:
+        raise _lib.FFError("tile_fold_d4: accum=True needs the tensor to accumulate into (ens)")
+    if ens is not None and isinstance(ens, torch.Tensor) and ens.device != acc.device:
+        raise _lib.FFError(f"tile_fold_d4: ens must be a contiguous {list(oshape)} tensor on acc's device, got {list(ens.shape)}")
+    ens, ep, _ = _out(ens, "tile_fold_d4.ens", oshape, acc.device, kind="dense")
+    e1 = ep + 4 * ens.numel()
+    for p_, t_, n_ in ((ap, acc, "acc"), (wp, wsum, "wsum")):
+        if ep < p_ + 4 * t_.numel() and p_ < e1:
+            raise _lib.FFError(f"tile_fold_d4: ens overlaps {n_} (the fold is not in place)")
+    _lib.check(_L().ff_tile_fold_d4(ap, wp, Hc, Wc, c, ep, 1 if accum else 0, float(scale), _stream()))
     return ens
 
 
@@ -1726,9 +1735,10 @@ def crop_pairs_u8(lr_u8: T, hr_u8: T, positions, patch: int) -> Tuple[T, T]:
     """K aligned patch pairs out of one uploaded image pair, one launch: lr_u8 [h,w,3], hr_u8 [4h,4w,3] uint8 HWC on the device,
     positions = host sequence of LR (top, left) -> (lr [K,3,p,p], hr [K,3,4p,4p]) fp32 = u8 / 255, HR patch k at (4 top, 4 left).
     Everything, the positions included, is checked here before the launch."""
+    lp = _dense(lr_u8, "crop_pairs_u8.lr_u8", _U8, shape=(None, None, 3))
+    hp = _dense(hr_u8, "crop_pairs_u8.hr_u8", _U8, shape=(None, None, 3))
     for t, name in ((lr_u8, "lr_u8"), (hr_u8, "hr_u8")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
-                and t.is_contiguous() and t.numel() > 0):
+        if t.numel() == 0:
             raise _lib.FFError(f"crop_pairs_u8: {name} must be a non-empty contiguous CUDA(HIP) uint8 [H,W,3] tensor")
     if lr_u8.device != hr_u8.device:
         raise _lib.FFError("crop_pairs_u8: lr_u8 and hr_u8 are on different devices")
@@ -1746,9 +1756,9 @@ def crop_pairs_u8(lr_u8: T, hr_u8: T, positions, patch: int) -> Tuple[T, T]:
             raise _lib.FFError(f"crop_pairs_u8: position ({t_}, {l_}) puts a {p}x{p} patch outside the {h}x{w} LR image")
     K = len(pl)
     pos = torch.tensor(pl, dtype=torch.int32).to(lr_u8.device)
-    lr = torch.empty((K, 3, p, p), device=lr_u8.device, dtype=torch.float32)
-    hr = torch.empty((K, 3, 4 * p, 4 * p), device=lr_u8.device, dtype=torch.float32)
-    _lib.check(_L().ff_crop_pairs_u8(lr_u8.data_ptr(), hr_u8.data_ptr(), h, w, pos.data_ptr(), K, p, lr.data_ptr(), hr.data_ptr(), _stream()))
+    lr, lrp, _ = _out(None, "crop_pairs_u8.lr", (K, 3, p, p), lr_u8.device, kind="dense")
+    hr, hrp, _ = _out(None, "crop_pairs_u8.hr", (K, 3, 4 * p, 4 * p), lr_u8.device, kind="dense")
+    _lib.check(_L().ff_crop_pairs_u8(lp, hp, h, w, _dense(pos, "crop_pairs_u8.pos", _I32, shape=(K, 2)), K, p, lrp, hrp, _stream()))
     _note(0.0, 17.0 * K * 3 * p * p * 5.0)
     return lr, hr
 
@@ -1761,8 +1771,8 @@ def sample_pairs_u8(pool: T, desc_host, patch: int, desc_dev: Optional[T] = None
     d4_nchw(crop_pairs_u8(...), codes).  Every row is checked here before the launch.  desc_dev: the same table already on the device
     (int64 [B,8]); out: (lr, hr) tensors to fill."""
     import numpy as np
-    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
-            and pool.numel() > 0):
+    pp = _dense(pool, "sample_pairs_u8.pool", _U8, shape=(None,))
+    if pool.numel() == 0:
         raise _lib.FFError("sample_pairs_u8: pool must be a non-empty contiguous 1-D CUDA(HIP) uint8 tensor")
     p = int(patch)
     d = np.ascontiguousarray(np.asarray(desc_host, dtype=np.int64))
@@ -1779,19 +1789,16 @@ def sample_pairs_u8(pool: T, desc_host, patch: int, desc_dev: Optional[T] = None
             raise _lib.FFError(f"sample_pairs_u8: sample {b}: d4 code {code}: expected 0..15 (bit 0 hflip, bit 1 vflip, bits 2-3 rot90 k)")
     if desc_dev is None:
         desc_dev = torch.from_numpy(d).to(pool.device)
-    elif not (desc_dev.is_cuda and desc_dev.dtype == torch.int64 and desc_dev.is_contiguous() and tuple(desc_dev.shape) == (B, 8)
-              and desc_dev.device == pool.device):
+    dp = _dense(desc_dev, "sample_pairs_u8.desc_dev", _I64, shape=(B, 8))
+    if desc_dev.device != pool.device:
         raise _lib.FFError(f"sample_pairs_u8: desc_dev must be a contiguous int64 [{B}, 8] tensor on the pool's device")
-    shapes = ((B, 3, p, p), (B, 3, 4 * p, 4 * p))
-    if out is None:
-        lr, hr = (torch.empty(s, device=pool.device, dtype=torch.float32) for s in shapes)
-    else:
-        lr, hr = out
-        for t, s in zip((lr, hr), shapes):
-            _chk(t, "sample_pairs_u8.out")
-            if tuple(t.shape) != s or not t.is_contiguous() or t.device != pool.device:
-                raise _lib.FFError(f"sample_pairs_u8: out must be contiguous {list(shapes[0])} and {list(shapes[1])} tensors on the pool's device")
-    _lib.check(_L().ff_sample_pairs_u8(pool.data_ptr(), desc_dev.data_ptr(), B, p, lr.data_ptr(), hr.data_ptr(), _stream()))
+    lr, hr = (None, None) if out is None else out
+    for t in (lr, hr):
+        if t is not None and isinstance(t, torch.Tensor) and t.device != pool.device:
+            raise _lib.FFError(f"sample_pairs_u8: out must be contiguous {[B, 3, p, p]} and {[B, 3, 4 * p, 4 * p]} tensors on the pool's device")
+    lr, lrp, _ = _out(lr, "sample_pairs_u8.out[0]", (B, 3, p, p), pool.device, kind="dense")
+    hr, hrp, _ = _out(hr, "sample_pairs_u8.out[1]", (B, 3, 4 * p, 4 * p), pool.device, kind="dense")
+    _lib.check(_L().ff_sample_pairs_u8(pp, dp, B, p, lrp, hrp, _stream()))
     _note(0.0, 17.0 * B * 3 * p * p * 5.0)
     return lr, hr
 
@@ -1809,9 +1816,10 @@ def gather_d4_fields(pool: T, n_samples: int, fields, desc_dev: T, out: T, desc_
     same table on the host, is checked too when given: indices in [0, n_samples), codes in 0..15, odd quarter turns only when every field
     is square.  (Without it the kernel's own guards hold: it clamps the index and drops the odd turn of a non-square field.)"""
     import numpy as np
+    pp = _dense(pool, "gather_d4_fields.pool", shape=(None,))
+    op = _dense(out, "gather_d4_fields.out", shape=(None,))
     for t, name in ((pool, "pool"), (out, "out")):
-        _chk(t, "gather_d4_fields." + name)
-        if t.dim() != 1 or not t.is_contiguous() or t.numel() < 1:
+        if t.numel() < 1:
             raise _lib.FFError(f"gather_d4_fields: {name} must be a non-empty contiguous 1-D fp32 tensor")
     if out.device != pool.device:
         raise _lib.FFError("gather_d4_fields: out must be on the pool's device")
@@ -1819,8 +1827,8 @@ def gather_d4_fields(pool: T, n_samples: int, fields, desc_dev: T, out: T, desc_
     fl = np.ascontiguousarray(np.asarray(fields, dtype=np.int64))
     if fl.ndim != 2 or fl.shape[1] != 5 or not 1 <= fl.shape[0] <= GATHER_MAX_FIELDS or n < 1:
         raise _lib.FFError(f"gather_d4_fields: need 1..{GATHER_MAX_FIELDS} rows of 5 fields and n_samples >= 1, got a table of shape {fl.shape} and {n}")
-    if not (isinstance(desc_dev, torch.Tensor) and desc_dev.is_cuda and desc_dev.dtype == torch.int32 and desc_dev.dim() == 2
-            and desc_dev.shape[1] == 2 and desc_dev.shape[0] >= 1 and desc_dev.is_contiguous() and desc_dev.device == pool.device):
+    dp = _dense(desc_dev, "gather_d4_fields.desc_dev", _I32, shape=(None, 2))
+    if desc_dev.shape[0] < 1 or desc_dev.device != pool.device:
         raise _lib.FFError("gather_d4_fields: desc_dev must be a contiguous int32 [B, 2] tensor (B >= 1) on the pool's device")
     B = int(desc_dev.shape[0])
     spans = []
@@ -1842,7 +1850,7 @@ def gather_d4_fields(pool: T, n_samples: int, fields, desc_dev: T, out: T, desc_
             raise _lib.FFError(f"gather_d4_fields: sample index {int(d[:, 0].min())}..{int(d[:, 0].max())} outside the pool's 0..{n - 1}")
         for f in range(fl.shape[0]):                                  # odd quarter turns need square planes, in every field
             d4_check_codes(d[:, 1], int(fl[f, 3]), int(fl[f, 4]))
-    _lib.check(_L().ff_gather_d4_fields(pool.data_ptr(), n, fl.ctypes.data, int(fl.shape[0]), desc_dev.data_ptr(), B, out.data_ptr(), _stream()))
+    _lib.check(_L().ff_gather_d4_fields(pp, n, fl.ctypes.data, int(fl.shape[0]), dp, B, op, _stream()))
     _note(0.0, 8.0 * B * float((fl[:, 2] * fl[:, 3] * fl[:, 4]).sum()))
     return [out[oo:oo + B * C * H * W].view(B, C, H, W) for _, oo, C, H, W in fl.tolist()]
 
@@ -1854,10 +1862,8 @@ def color_jitter_pairs(lr: T, hr: T, table_host, table_dev: Optional[T] = None) 
     mean, saturation sf through the 8-bit HSV conversion (none when sf == 1).  Every row is checked here before the launch: apply in
     {0, 1}, factors finite and in (0, 2).  table_dev: the same table already on the device (fp32 [B,4]).  -> (lr, hr)."""
     import numpy as np
-    for t, name in ((lr, "lr"), (hr, "hr")):
-        _chk(t, "color_jitter_pairs." + name)
-        if t.dim() != 4 or not t.is_contiguous():
-            raise _lib.FFError(f"color_jitter_pairs: {name} must be a contiguous 4-D tensor, got {list(t.shape)}")
+    lrp = _dense(lr, "color_jitter_pairs.lr", shape=(None, None, None, None))
+    hrp = _dense(hr, "color_jitter_pairs.hr", shape=(None, None, None, None))
     B, p = int(lr.shape[0]), int(lr.shape[2])
     if B < 1 or p < 1 or tuple(lr.shape) != (B, 3, p, p) or tuple(hr.shape) != (B, 3, 4 * p, 4 * p) or hr.device != lr.device:
         raise _lib.FFError(f"color_jitter_pairs: need lr [B,3,p,p] and hr [B,3,4p,4p] on one device, got {list(lr.shape)} and {list(hr.shape)}")
@@ -1872,12 +1878,12 @@ def color_jitter_pairs(lr: T, hr: T, table_host, table_dev: Optional[T] = None) 
             raise _lib.FFError(f"color_jitter_pairs: sample {b}: factors ({bf}, {cf}, {sf}) must be finite and inside (0, 2)")
     if table_dev is None:
         table_dev = torch.from_numpy(tb).to(lr.device)
-    elif not (isinstance(table_dev, torch.Tensor) and table_dev.is_cuda and table_dev.dtype == torch.float32 and table_dev.is_contiguous()
-              and tuple(table_dev.shape) == (B, 4) and table_dev.device == lr.device):
+    tp = _dense(table_dev, "color_jitter_pairs.table_dev", shape=(B, 4))
+    if table_dev.device != lr.device:
         raise _lib.FFError(f"color_jitter_pairs: table_dev must be a contiguous float32 [{B}, 4] tensor on lr's device")
     nbytes = int(_L().ff_color_jitter_workspace(B))
     work = torch.empty(nbytes // 8, device=lr.device, dtype=torch.int64)
-    _lib.check(_L().ff_color_jitter_pairs(lr.data_ptr(), hr.data_ptr(), table_dev.data_ptr(), B, p, work.data_ptr(), nbytes, _stream()))
+    _lib.check(_L().ff_color_jitter_pairs(lrp, hrp, tp, B, p, _image(work, "color_jitter_pairs.work"), nbytes, _stream()))
     _note(0.0, 17.0 * float(tb[:, 0].sum()) * 3 * p * p * 4.0 * 3.0)  # applied samples: read for the sums, read and written by the pixel pass
     return lr, hr
 
@@ -1939,8 +1945,8 @@ def resize_aa(x: T, size: Tuple[int, int]) -> T:
     """Antialiased bicubic x1/4 of a planar image batch: x [B,3,H,W] -> [B,3,H/4,W/4] = F.interpolate(x, size, mode='bicubic',
     antialias=True, align_corners=False) -- the degradation the x4 track is defined on (ops.resize's bicubic is ATen's plain
     A = -0.75 kernel without antialiasing: an up-sampler).  `size` must be exactly (H/4, W/4); any other ratio raises."""
-    _chk(x, "resize_aa.x")
-    if x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous() or x.numel() == 0:
+    xp = _dense(x, "resize_aa.x", shape=(None, 3, None, None))
+    if x.numel() == 0:
         raise _lib.FFError("resize_aa: expected a non-empty contiguous [B,3,H,W] tensor")
     B, C, Hi, Wi = x.shape
     Ho, Wo = (int(v) for v in size)
@@ -1948,9 +1954,10 @@ def resize_aa(x: T, size: Tuple[int, int]) -> T:
         raise _lib.FFError(f"resize_aa: only the x1/4 ratio is built: {Hi}x{Wi} -> {Ho}x{Wo} is refused")
     span_w, wt_w = _aa_tables_dev(Wi, Wo, x.device)
     span_h, wt_h = _aa_tables_dev(Hi, Ho, x.device)
-    out = torch.empty((B, C, Ho, Wo), device=x.device, dtype=torch.float32)
-    _lib.check(_L().ff_resize_aa(x.data_ptr(), out.data_ptr(), B * C, Hi, Wi, Ho, Wo, span_w.data_ptr(), wt_w.data_ptr(),
-                                 span_h.data_ptr(), wt_h.data_ptr(), _stream()))
+    tabs = (_dense(span_w, "resize_aa.span_w", _I32, shape=(Wo, 2)), _dense(wt_w, "resize_aa.wt_w", shape=(Wo, AA_TAPS)),
+            _dense(span_h, "resize_aa.span_h", _I32, shape=(Ho, 2)), _dense(wt_h, "resize_aa.wt_h", shape=(Ho, AA_TAPS)))
+    out, op, _ = _out(None, "resize_aa.out", (B, C, Ho, Wo), x.device, kind="dense")
+    _lib.check(_L().ff_resize_aa(xp, op, B * C, Hi, Wi, Ho, Wo, *tabs, _stream()))
     _note(0.0, 4.0 * B * C * (Hi * Wi + Ho * Wo))
     return out
 
@@ -2004,8 +2011,8 @@ def resize_cv_cubic(x: T, Ho: int, Wo: int, out: Optional[T] = None, tables=None
     out: a contiguous [N,C,Ho,Wo] fp32 tensor to write (a view at any 4-byte offset).  tables: ((idx_w, wt_w), (idx_h, wt_h)) device
     tensors in cv_cubic_tables' shapes instead of the cached ones; anything else is refused before the launch.
     Parity with an OpenCV binary: unpinned (OpenCV absent)."""
-    _chk(x, "resize_cv_cubic.x")
-    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+    xp = _dense(x, "resize_cv_cubic.x", shape=(None, None, None, None))
+    if x.numel() == 0:
         raise _lib.FFError(f"resize_cv_cubic: expected a non-empty contiguous [N,C,H,W] tensor, got {list(x.shape)}")
     N, C, Hi, Wi = x.shape
     Ho, Wo = int(Ho), int(Wo)
@@ -2019,23 +2026,14 @@ def resize_cv_cubic(x: T, Ho: int, Wo: int, out: Optional[T] = None, tables=None
             (iw, ww), (ih, wh) = tw, th
         except (TypeError, ValueError):
             raise _lib.FFError("resize_cv_cubic: tables must be ((idx_w, wt_w), (idx_h, wt_h))") from None
-        for name, idx, wt, n in (("w", iw, ww, Wo), ("h", ih, wh, Ho)):
-            for t, dt in ((idx, torch.int32), (wt, torch.float32)):
-                if not torch.is_tensor(t) or t.device != x.device or t.dtype != dt or tuple(t.shape) != (n, 4) or not t.is_contiguous():
-                    raise _lib.FFError(f"resize_cv_cubic: the {name} tables must be contiguous int32 / float32 [{n}, 4] tensors on x's device")
-    if out is None:
-        out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "resize_cv_cubic.out")
-        if tuple(out.shape) != (N, C, Ho, Wo) or not out.is_contiguous() or out.device != x.device:
-            raise _lib.FFError(f"resize_cv_cubic: out must be a contiguous [{N},{C},{Ho},{Wo}] tensor on x's device, got {list(out.shape)}")
-    _lib.check(_L().ff_resize_cv_cubic(x.data_ptr(), out.data_ptr(), N * C, Hi, Wi, Ho, Wo, tw[0].data_ptr(), tw[1].data_ptr(),
-                                       th[0].data_ptr(), th[1].data_ptr(), _stream()))
+        for t in (iw, ww, ih, wh):
+            if torch.is_tensor(t) and t.device != x.device:
+                raise _lib.FFError("resize_cv_cubic: the tables must be contiguous int32 / float32 [n, 4] tensors on x's device")
+    tabs = (_dense(tw[0], "resize_cv_cubic.tables.idx_w", _I32, shape=(Wo, 4)), _dense(tw[1], "resize_cv_cubic.tables.wt_w", shape=(Wo, 4)),
+            _dense(th[0], "resize_cv_cubic.tables.idx_h", _I32, shape=(Ho, 4)), _dense(th[1], "resize_cv_cubic.tables.wt_h", shape=(Ho, 4)))
+    if out is not None and isinstance(out, torch.Tensor) and out.device != x.device:
+        raise _lib.FFError(f"resize_cv_cubic: out must be a contiguous [{N},{C},{Ho},{Wo}] tensor on x's device, got {list(out.shape)}")
+    out, op, _ = _out(out, "resize_cv_cubic.out", (N, C, Ho, Wo), x.device, kind="dense")
+    _lib.check(_L().ff_resize_cv_cubic(xp, op, N * C, Hi, Wi, Ho, Wo, *tabs, _stream()))
     _note(0.0, 4.0 * N * C * (Hi * Wi + Ho * Wo))
     return out
-
-
-for _n in ("conv2d", "cab_fused", "sgfn_tail", "ocab_attn", "ocab_attn_rows16", "token_linear_rows16", "linear", "win_attn_fused", "token_projmlp", "hab_link", "token_linear_gated", "token_mlp", "token_linear", "pixel_mlp", "dwconv3_gate_pool", "naf_front", "naf_ffn", "naf_tail", "window_attn", "layernorm", "pool_mean", "vec_mlp", "dwconv2d", "dwconv3x3_ln", "mix2", "fma3", "affine",
-           "nchw_to_nhwc", "nhwc_to_nchw", "resize", "avgpool2", "dct8_bands", "dwt_pass", "fft_bands", "chan_attn_weights", "chan_qkv_attn",
-           "band_mha_core", "band_weight", "freq_guidance", "dynamic_gates", "fuse_blend", "tile_accum", "tile_normalize"):
-    globals()[_n] = _instrument(globals()[_n])
